@@ -1,6 +1,6 @@
 """Benchmark of the NeRF volume-rendering hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" is one complete optimisation step of the reference's training loop
 (ray_caster.py:319-329) on one batch of synthetic rays: stratified t-sampling -> fused
@@ -80,7 +80,13 @@ def parse_args():
     ap.add_argument("--model", default="tiny", choices=["tiny", "nerf", "gaussian512"],
                     help="tiny = BASELINE configs[1] (the metric's config); nerf = configs[2]-shaped "
                          "full NeRF (8x256, skip, view branch), use with --samples 128")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its loss, its "
+                         "gradients and the model state it left) as DIR/<name>.npy, for comparing builds")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def synthetic_rig(num_cameras, size, fov_deg=40.0, distance=4.0, seed=20080524):
@@ -353,6 +359,26 @@ class KernelTimer:
             out[key] = {"avg_ms": round(avg, 4), "launches": len(ms), "achieved": round(tf, 2),
                         "frac": round(tf / F32_MFMA_PEAK_TFLOPS, 4), "flop_per_sample": flops[key]}
         return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes `arrays` (name -> tensor) as out_dir/<name>.npy: float64 stays float64, everything
+    else becomes float32.  The files hold DUMP_LIMIT_BYTES in all at most: an array larger than
+    its equal share of that is replaced by a fixed, seeded sample of its flattened elements (in
+    index order), so that two runs with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, value in arrays.items():
+        a = value.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            pick = np.sort(np.random.RandomState(20080524).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def git_head():
@@ -1303,6 +1329,11 @@ def main():
     timer.on = False
     timer.close()
     engine.check_finite()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss, its (all-reduced) gradients and the weights its optimiser
+        # update left; the model's other state (fixed encodings) rides along
+        dump_outputs(args.dump_outputs, dict({"loss": loss, "gradients": engine.grads},
+                                             **{"model." + k: v for k, v in model.state_dict().items()}))
     # (a batch above TrainEngine's launch bound -- 2^22 samples -- runs as several launches)
     launches_per_step = max(1, len(next(iter(timer.spans.values()))) // max(args.steps, 1)) if timer.spans else 1
     n_samples //= launches_per_step
