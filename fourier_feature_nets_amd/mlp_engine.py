@@ -982,19 +982,38 @@ class MlpProgram:
         """The output of hidden layer ``layer`` (an index into ``self.layers``) as an ``(n, out)``
         tensor, read back from the activation slab a training forward left in ``saved`` -- a copy
         for `FourierFeatureMLP.keep_activations` (fourier_feature_models.py:74-75), off the hot
-        path.  Slab layout (section 3 of DESIGN.md): per 32-sample block ``C * 32`` floats as
-        float4 ``[cq][pos]``, ``cq = channel / 4``, ``pos = sample ^ (cq & 15)``."""
+        path."""
         slot = self.slot_of.get(layer) if isinstance(self.slot_of, dict) else None
         if slot is None:
             raise ValueError("layer %d leaves no activation slab" % layer)
-        blocks = (n + 31) // 32
         acts, _ = self._split_saved(saved, n)
+        return self.slot_rows(acts, n, slot)[:n, :self.layers[layer].out].contiguous()
+
+    def slot_rows(self, region: torch.Tensor, n: int, slot: int, first_block: int = 0,
+                  num_blocks: Optional[int] = None) -> torch.Tensor:
+        """Slot ``slot`` (a hidden layer's or an encoding's) of a slab region -- the activations
+        part of ``saved`` or the dZ workspace -- as ``(32 * num_blocks, slot channels)`` rows from
+        block ``first_block`` on: every row of the last block and every padded channel included.
+        Slab layout (section 3 of DESIGN.md): per 32-sample block ``C * 32`` floats as float4
+        ``[cq][pos]``, ``cq = channel / 4``, ``pos = sample ^ (cq & 15)``.  Off the hot path."""
+        blocks = (n + 31) // 32
+        if num_blocks is None:
+            num_blocks = blocks - first_block
         ch, off = int(self.fwd.slot_channels[slot]), int(self.fwd.slot_offset[slot])
-        region = acts[off * blocks * 32:(off + ch) * blocks * 32].view(blocks, ch // 4, 32, 4)
-        cq = torch.arange(ch // 4, device=saved.device)
-        pos = torch.arange(32, device=saved.device)[None, :] ^ (cq[:, None] & 15)      # where sample s sits
-        rows = region[:, cq[:, None], pos, :]                                          # (blocks, cq, s, 4)
-        return rows.permute(0, 2, 1, 3).reshape(blocks * 32, ch)[:n, :self.layers[layer].out].contiguous()
+        area = region[off * blocks * 32:(off + ch) * blocks * 32].view(blocks, ch // 4, 32, 4)
+        area = area[first_block:first_block + num_blocks]
+        cq = torch.arange(ch // 4, device=region.device)
+        pos = torch.arange(32, device=region.device)[None, :] ^ (cq[:, None] & 15)   # where sample s sits
+        rows = area[:, cq[:, None], pos, :]                                          # (blocks, cq, s, 4)
+        return rows.permute(0, 2, 1, 3).reshape(-1, ch)
+
+    def dz_rows(self, dz: torch.Tensor, n: int, layer: int) -> torch.Tensor:
+        """dZ of hidden layer ``layer`` as the backward pass of ``n`` samples left it in ``dz``
+        (``Workspace.dz``): ``(32 * blocks, padded width)`` rows, the same slab layout."""
+        slot = self.slot_of.get(layer)
+        if slot is None or slot >= self.fwd.num_slots:
+            raise ValueError("layer %d has no dZ slab" % layer)
+        return self.slot_rows(dz, n, slot)
 
     # ------------------------------------------------------------------ tail on wave pairs
     def _resident_waves(self) -> int:
