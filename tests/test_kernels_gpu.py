@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import ffn_oracle as orc
+from tests import composite_reference as cr
 from tests.helpers import formula_fill, look_at_camera
 
 pytestmark = pytest.mark.gpu
@@ -214,6 +215,9 @@ def test_composite_ragged_sample_counts(ops, S):
     np.testing.assert_allclose(alpha.cpu().numpy(), a.detach().numpy(), rtol=1e-5, atol=2e-6)
     same = depth.cpu().numpy() == d.numpy()
     assert same.mean() > 0.99       # argmax ties under 1-ulp weight differences
+    # every ray: the t of a sample whose float64 weight is within budget of the largest
+    cand = cr.depth_candidates(cr.composite_forward(logits, t)) & (t.double() == depth.cpu().double()[:, None])
+    assert bool(cand.any(1).all())
     gc, ga = torch.rand(R, 3), torch.rand(R)
     orc.mse_loss(c, a, gc, ga, 0.1).backward()
     dc = (2 * (color.cpu() - gc) / (3 * R)).to(dev())
