@@ -28,12 +28,12 @@ from .utils import (
     load_model,
 )
 from .visualizers import ActivationVisualizer, EvaluationVisualizer, OrbitVideoVisualizer, Visualizer
-from .voxels import Voxels
+from .voxels import VoxelProgram, Voxels
 
 __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
            "OccupancyGrid", "OrbitVideoVisualizer", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster",
-           "RenderResult", "Resolution", "TrainEngine", "Visualizer", "Voxels", "calculate_blend_weights",
+           "RenderResult", "Resolution", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "linspace", "load_model", "orbit"]

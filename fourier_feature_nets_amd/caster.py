@@ -22,6 +22,7 @@ from .dataset import RayDataset
 from .occupancy import OccupancyGrid
 from .sampler import RaySampler, RaySamples
 from .utils import RenderResult, check_color_space, learning_rate_at
+from .voxels import VoxelProgram, Voxels
 
 LogEntry = NamedTuple("LogEntry", [("step", int), ("timestamp", float),
                                    ("state", OrderedDict[str, torch.Tensor]),
@@ -105,7 +106,14 @@ class TrainEngine:
         self._saved = {}
         self.loss_history = None          # set to [] to record every step's loss (device scalars)
         model.invalidate_packed()
-        assert model.program().num_grad_floats == total
+        assert self._program().num_grad_floats == total
+
+    def _program(self):
+        """The kernel program of a step: the fused MLP's ``MlpProgram``, or a ``VoxelProgram`` for a
+        ``Voxels`` model (which has no ``program`` attribute of its own, see voxels.py)."""
+        if isinstance(self.model, Voxels):
+            return VoxelProgram(self.model)
+        return self.model.program()
 
     # ------------------------------------------------------------------ pieces
     def _saved_buffer(self, prog, n):
@@ -180,7 +188,10 @@ class TrainEngine:
         count = int(rays.numel())
         alphas = dataset._gt_alphas()
         aw = float(dataset.alpha_weight) if alphas is not None else 0.0
-        prog = self.model.program()
+        if self.occupancy is not None and isinstance(self.model, Voxels):
+            raise NotImplementedError("empty-space skipping during training is not implemented "
+                                      "for Voxels models")
+        prog = self._program()
         sums = self.loss_sums
         per_launch = max(1, self.max_samples // sampler.num_samples)
         if count == 0:
@@ -330,7 +341,7 @@ class TrainEngine:
         mode = getattr(self.model, "precision", "f32")
         if hasattr(self.model, "effective_precision"):
             mode = self.model.effective_precision(mode)
-        prog = self.model.program()
+        prog = self._program()
         logits = prog.forward16(pos, views) if mode == "bf16x3" else prog.forward(pos, views, None, precision=mode)
         color, alpha, _ = ops.composite_fwd(logits, t, False, self.nan_flag)
         sums, _, _ = ops.mse_loss(color, alpha, dataset.colors, alphas, rays, 1.0, 1.0,
@@ -570,6 +581,9 @@ class Raycaster(nn.Module):
             decay_rate: float, decay_steps: int, weight_decay: float, visualizers: List,
             disable_aml=False) -> List[LogEntry]:
         """Trains the model; same arguments, schedule and log lines as ray_caster.py:248-377."""
+        if self.train_occupancy_schedule is not None and isinstance(self.model, Voxels):
+            raise NotImplementedError("train_occupancy_schedule (empty-space skipping during "
+                                      "training) is not implemented for Voxels models")
         trainval_dataset = train_dataset.sample_cameras(val_dataset.num_cameras,
                                                         val_dataset.num_samples, False)
         engine = TrainEngine(self.model, weight_decay, self.process_group)

@@ -337,3 +337,37 @@ def voxels_forward(volume: torch.Tensor, bias: torch.Tensor, positions: torch.Te
     _call("ffn_voxels_forward", _dev(volume), _dev(bias), _dev(positions, name="positions"),
               c_i64(n), c_i(side), c_f(scale), _dev(out))
     return out
+
+
+def voxels_backward_workspace_bytes(n: int, side: int) -> int:
+    """Bytes of workspace ``voxels_backward`` needs for ``n`` samples of a side-``side`` volume."""
+    fn = _lib.load().ffn_voxels_backward_workspace
+    fn.restype = ctypes.c_int64
+    size = fn(c_i64(n), c_i(side))
+    if size < 0:
+        raise _lib.FfnError("ffn_voxels_backward_workspace failed: %s"
+                            % _lib.load().ffn_last_error_string().decode())
+    return int(size)
+
+
+def voxels_backward(positions: torch.Tensor, d_logits: torch.Tensor, side: int, scale: float,
+                    workspace: Optional[torch.Tensor] = None, d_volume: Optional[torch.Tensor] = None,
+                    d_bias: Optional[torch.Tensor] = None):
+    """K10b, the adjoint of K10.  positions (N,3), d_logits (N,4) -> d_volume (4,S,S,S) and
+    d_bias (4), both overwritten (no zeroing needed); deterministic (no float atomics).
+    ``workspace``: any float32 device tensor of at least ``voxels_backward_workspace_bytes``."""
+    n = positions.shape[0]
+    dev = positions.device
+    need = voxels_backward_workspace_bytes(n, side)
+    if workspace is None:
+        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    if d_volume is None:
+        d_volume = torch.empty((4, side, side, side), dtype=torch.float32, device=dev)
+    if d_bias is None:
+        d_bias = torch.empty((4,), dtype=torch.float32, device=dev)
+    if d_volume.numel() != 4 * side ** 3 or d_bias.numel() != 4:
+        raise ValueError("voxels_backward: d_volume must hold 4*side^3 floats and d_bias 4")
+    _call("ffn_voxels_backward", _dev(positions, name="positions"), _dev(d_logits, name="d_logits"),
+          c_i64(n), c_i(side), c_f(scale), _dev(workspace), c_i64(workspace.numel() * 4),
+          _dev(d_volume), _dev(d_bias))
+    return d_volume, d_bias

@@ -653,10 +653,26 @@ int ffn_gather_logits(const float* full, const int32_t* index, int64_t m, float*
 
 /* ---- K10: dense voxel radiance field (voxels_model.py:35-45): trilinear lookup of a
  * (4,S,S,S) volume at positions/scale in [-1,1]^3 (grid_sample semantics: x = fastest axis,
- * border padding, align_corners = false) + bias (4) -> logits (N,4).  Inference only; it is
- * the opacity model the README workflows hand to the focus sampler. */
+ * border padding, align_corners = false) + bias (4) -> logits (N,4).  It is the opacity model
+ * the README workflows hand to the focus sampler, and the forward pass of voxel training. */
 int ffn_voxels_forward(const float* volume, const float* bias, const float* positions, int64_t n,
                        int side, float scale, float* out, void* stream);
+
+/* ---- K10b: the adjoint of K10 -- the backward of Voxels.forward (voxels_model.py:35-45 of the
+ * reference: grid_sample(padding_mode="border", align_corners=False) + bias, under autograd).
+ *   positions (N,3), d_logits (N,4) (16-byte aligned), side S in [1, 1024], 0 <= N <= 2^30,
+ *   finite scale > 0
+ *   d_volume (4,S,S,S) out: EVERY entry written (no zeroing by the caller);
+ *   d_bias (4) out: the column sums of d_logits
+ *   workspace: ffn_voxels_backward_workspace(N, S) bytes (-1 for an invalid shape)
+ * Same coordinate formula, clamp, corners and weight products as ffn_voxels_forward; a corner
+ * clamped onto lo carries weight 0 and receives nothing.  No float atomics: the same inputs give
+ * bit-identical outputs on every call (store-and-sum: per-cell lists in sample-id order, summed
+ * per voxel over its 8 cells in a fixed order; lists longer than 16 in chunks of 16). */
+int64_t ffn_voxels_backward_workspace(int64_t n, int side);
+int ffn_voxels_backward(const float* positions, const float* d_logits, int64_t n, int side,
+                        float scale, void* workspace, int64_t workspace_bytes, float* d_volume,
+                        float* d_bias, void* stream);
 
 #ifdef __cplusplus
 }

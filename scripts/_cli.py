@@ -65,6 +65,30 @@ TINY_ONLY = [
     ("--make-activations", dict(action="store_true")),
     ("--decay-steps", dict(type=int, default=25000)),
 ]
+# train_voxels.py:11-49 of the reference (positionals data_path side results_dir; --num-cameras is
+# parsed but unused there too)
+VOXELS = [
+    ("data_path", dict(help="Path to the data NPZ")),
+    ("side", dict(type=int, help="One side of the voxel volume")),
+    ("results_dir", dict(help="Path to output results")),
+    ("--mode", dict(choices=["rgba", "rgb", "dilate"], default="rgba")),
+    ("--num-samples", dict(type=int, default=256)),
+    ("--num-cameras", dict(type=int, default=100)),
+    ("--batch-size", dict(type=int, default=1024)),
+    ("--learning-rate", dict(type=float, default=0.01)),
+    ("--num-steps", dict(type=int, default=10000)),
+    ("--report-interval", dict(type=int, default=1000)),
+    ("--image-interval", dict(type=int, default=2000)),
+    ("--seed", dict(type=int, default=20080524)),
+    ("--decay-rate", dict(type=float, default=0.9)),
+    ("--decay-steps", dict(type=int, default=25000)),
+    ("--make-video", dict(action="store_true")),
+    ("--color-space", dict(choices=["YCrCb", "RGB"], default="RGB")),
+    ("--num-frames", dict(type=int, default=200)),
+    ("--device", dict(default="cuda")),
+    ("--anneal-start", dict(type=float, default=0.2)),
+    ("--num-anneal-steps", dict(type=int, default=2000)),
+]
 ORBIT = [
     ("model_path", dict(help="trained checkpoint")),
     ("resolution", dict(type=int, help="frame size in pixels")),
