@@ -10,6 +10,8 @@ from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
+from .pixel_dataset import PixelData, PixelDataset
+from .regression import RegressionEngine
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -34,6 +36,6 @@ __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OccupancyGrid", "OrbitVideoVisualizer", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster",
+           "OccupancyGrid", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
            "RenderResult", "Resolution", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "linspace", "load_model", "orbit"]

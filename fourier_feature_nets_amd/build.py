@@ -39,6 +39,7 @@ SOURCES = {
     "wgrad_bf16x6.hip": [],
     "occupancy.hip": [],
     "voxels.hip": [],
+    "regression.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -154,14 +154,28 @@ def _struct_array_to_device(items, device):
 
 
 class EncodingSpec:
-    """A sin/cos feature map of a 3-vector: [a cos(s x B), a sin(s x B)] (+ x)."""
+    """A sin/cos feature map of a 3-vector: [a cos(s x B), a sin(s x B)] (+ x).
+
+    ``num_inputs`` D < 3 (image and signal regression) is lifted on the host: B (D,F) is
+    zero-padded to (3,F) and the positions to (N,3) with zero columns, so the kernels still see a
+    3-input chain -- with b_d = 0 and x_d = 0 the feature's mul / fma / fma adds exact zeros, the
+    same bits as a D-term dot product -- and the raw channels 2F+d, d >= D, have no natural
+    column: the operand packs put zero weights there and the gradient reducer drops them."""
 
     def __init__(self, b: Optional[torch.Tensor], a: Optional[torch.Tensor], scale: float,
-                 include_input: bool, device: Optional[torch.device] = None):
+                 include_input: bool, device: Optional[torch.device] = None, num_inputs: int = 3):
+        if num_inputs not in (1, 2, 3):
+            raise NotImplementedError("encodings of 1, 2 or 3 inputs (got %d)" % num_inputs)
+        self.num_inputs = int(num_inputs)
         self.num_freq = 0 if b is None else int(b.shape[1])
         dev = device if device is not None else (b.device if b is not None else None)
         if b is None:
             b = torch.zeros((3, 1), dtype=torch.float32, device=dev)
+        elif b.shape[0] != num_inputs:
+            raise ValueError("B has %d rows for %d inputs" % (b.shape[0], num_inputs))
+        elif num_inputs < 3:
+            b = torch.cat([b, torch.zeros((3 - num_inputs, b.shape[1]), dtype=b.dtype,
+                                          device=b.device)])
         if a is None:
             a = torch.ones((max(self.num_freq, 1),), dtype=torch.float32, device=dev)
         self.b = b.contiguous()
@@ -170,17 +184,17 @@ class EncodingSpec:
         self.include_input = bool(include_input) or self.num_freq == 0
         if self.num_freq > 256:
             raise NotImplementedError("encodings with more than 256 frequencies")
-        natural = 2 * self.num_freq + (3 if self.include_input else 0)
+        natural = 2 * self.num_freq + (self.num_inputs if self.include_input else 0)
         self.natural_width = natural
         self.width = ((natural + 31) // 32) * 32
 
     def natural_index(self, internal: int) -> int:
-        """Natural column ([cos F][sin F][x 3]) of internal channel 2k+trig / 2F+d, or -1."""
+        """Natural column ([cos F][sin F][x D]) of internal channel 2k+trig / 2F+d, or -1."""
         freq = self.num_freq
         if internal < 2 * freq:
             k = internal >> 1
             return k if (internal & 1) == 0 else freq + k
-        if self.include_input and internal < 2 * freq + 3:
+        if self.include_input and internal < 2 * freq + self.num_inputs:
             return internal
         return -1
 

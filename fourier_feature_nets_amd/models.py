@@ -216,12 +216,15 @@ class FourierFeatureMLP(_FusedModel):
         return out
 
     def _chain(self, device):
-        if self.num_inputs != 3 or self.num_outputs > 4:
-            raise NotImplementedError("the fused kernels cover the volume-rendering case "
-                                      "(3 inputs, <= 4 outputs)")
+        if self.num_inputs not in (1, 2, 3) or self.num_outputs > 4:
+            raise NotImplementedError("the fused kernels cover 1, 2 or 3 inputs and <= 4 outputs "
+                                      "(got %d inputs, %d outputs)"
+                                      % (self.num_inputs, self.num_outputs))
+        # (fewer than 3 inputs: a 3-input chain with zero rows of B / zero raw-input weight
+        # columns, see EncodingSpec; forward pads the positions to match)
         enc = EncodingSpec(None if self.b_values is None else self.b_values.data,
                            None if self.a_values is None else self.a_values.data,
-                           math.pi, False, device)
+                           math.pi, False, device, num_inputs=self.num_inputs)
         specs = []
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
@@ -231,10 +234,18 @@ class FourierFeatureMLP(_FusedModel):
         return [enc], specs
 
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:
-        """(N,3) positions -> (N,num_outputs) raw outputs."""
+        """(..., num_inputs) positions -> (..., num_outputs) raw outputs (any leading shape, as
+        the reference's matmul-based forward accepts: ``(H, W, 2)`` uv grids in image regression)."""
         self.activations.clear()
         self._kept_slabs = None
-        out = _FusedChainFunction.apply(self, torch.is_grad_enabled(), inputs, None,
+        if inputs.dim() < 1 or inputs.shape[-1] != self.num_inputs:
+            raise ValueError("%s expects (..., %d) inputs, got %s"
+                             % (type(self).__name__, self.num_inputs, tuple(inputs.shape)))
+        lead = tuple(inputs.shape[:-1])
+        flat = inputs.reshape(-1, self.num_inputs)
+        if self.num_inputs < 3:      # lifted to the kernels' (N,3) positions with zero columns
+            flat = torch.nn.functional.pad(flat, (0, 3 - self.num_inputs))
+        out = _FusedChainFunction.apply(self, torch.is_grad_enabled(), flat, None,
                                         *self._dense_params())
         if self.keep_activations:
             # fourier_feature_models.py:70-75: the output of the last hidden layer, as a numpy
@@ -243,14 +254,15 @@ class FourierFeatureMLP(_FusedModel):
             hidden = len(self.layers) - 2
             if hidden < 0:
                 raise NotImplementedError("keep_activations needs at least one hidden layer")
-            n = inputs.shape[0]
+            n = flat.shape[0]
             if n == 0:
                 rows = torch.zeros((0, self.layers[hidden].out_features))
             else:
                 rows = self.program().slab_rows(self._kept_slabs, n, hidden)
             self._kept_slabs = None
-            self.activations.append(rows.detach().cpu().numpy())
-        return out if self.num_outputs == 4 else out[:, :self.num_outputs]
+            self.activations.append(rows.detach().cpu().numpy().reshape(lead + (rows.shape[-1],)))
+        out = out if self.num_outputs == 4 else out[:, :self.num_outputs]
+        return out if len(lead) == 1 else out.reshape(lead + (self.num_outputs,))
 
     def save(self, path: str):
         """Checkpoint in the reference format: state dict + "type" + "params"."""

@@ -259,6 +259,38 @@ def loss_value(sums: torch.Tensor, rays: int, alpha_weight: float) -> torch.Tens
     return out
 
 
+# --------------------------------------------------------------------------------- regression
+def regression_blocks(n: int) -> int:
+    """Workgroups (= partial sums) of K11 for ``n`` pixels."""
+    return int(_lib.load().ffn_regression_blocks(c_i64(n)))
+
+
+def regression_train(logits: torch.Tensor, target: torch.Tensor, d_logits: torch.Tensor,
+                     partials: torch.Tensor):
+    """K11 training: logits (n,4), target (n,c) -> d_logits (n,4) of 0.5 * mean((sigmoid - y)^2)
+    (columns >= c exactly 0) and one sum of squares per workgroup in ``partials``."""
+    n, c = target.shape
+    _call("ffn_regression_train", _dev(logits, name="logits"), _dev(target, name="target"),
+          c_i64(n), c_i(c), c_f(1.0 / (n * c)), _dev(d_logits, name="d_logits"),
+          _dev(partials, name="partials"))
+
+
+def regression_eval(logits: torch.Tensor, target: Optional[torch.Tensor], c: int,
+                    partials: Optional[torch.Tensor], image: Optional[torch.Tensor] = None):
+    """K11 validation: sums of (sigmoid - y)^2 per workgroup into ``partials`` and / or the
+    (sigmoid * 255) u8 pixels (n,c) into ``image``."""
+    n = logits.shape[0]
+    _call("ffn_regression_eval", _dev(logits, name="logits"), _dev(target, name="target"),
+          c_i64(n), c_i(c), _dev(partials, name="partials"), _dev(image, torch.uint8, "image"))
+
+
+def regression_loss(partials: torch.Tensor, count: int, sse_out: Optional[torch.Tensor] = None,
+                    loss_out: Optional[torch.Tensor] = None):
+    """Fixed-order sum of K11's partials: sse into ``sse_out``, 0.5 * sse / count into ``loss_out``."""
+    _call("ffn_regression_loss", _dev(partials), c_i(partials.shape[0]), c_f(float(count)),
+          _dev(sse_out), _dev(loss_out))
+
+
 # --------------------------------------------------------------------------------- optimiser
 def clip_adam(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, weight_decay=0.0,
               clip_value=0.1, max_norm=0.1, beta1=0.9, beta2=0.999, eps=1e-8,

@@ -674,6 +674,33 @@ int ffn_voxels_backward(const float* positions, const float* d_logits, int64_t n
                         float scale, void* workspace, int64_t workspace_bytes, float* d_volume,
                         float* d_bias, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K11  per-pixel regression loss of 2-D image regression (csrc/regression.hip).
+ * Replaces torch.sigmoid(model(uv)), 0.5 * torch.square(out - y).mean() and their autograd
+ * (train_image_regression.py:183-185), and the validation path sigmoid -> PixelDataset.psnr ->
+ * PixelDataset.to_image (train_image_regression.py:141-142, pixel_dataset.py:168,189-198).
+ *   logits (n,4) of the fused MLP, the first c columns used; target (n,c); 1 <= c <= 4, n >= 1.
+ *   partials: ffn_regression_blocks(n) floats, one sum((sigmoid - y)^2) per workgroup.
+ * No float atomics: the same inputs give the same bits.  Bad shapes / null pointers are refused
+ * before any launch. */
+int ffn_regression_blocks(int64_t n);
+
+/* d_logits (n,4) out: ((sigmoid - y) * inv_count) * (1 - sigmoid) * sigmoid in f32 (ATen's
+ * autograd order, inv_count = 1 / (n c)) for the first c columns, exactly 0 in the others. */
+int ffn_regression_train(const float* logits, const float* target, int64_t n, int c,
+                         float inv_count, float* d_logits, float* partials, void* stream);
+
+/* Validation: partials (may be NULL; then target may be NULL) for the PSNR, and / or image
+ * (n,c) u8 (may be NULL): (sigmoid * 255) truncated, as to_image's astype(np.uint8).  YCrCb
+ * frames go on to ffn_ycrcb_to_rgb_u8. */
+int ffn_regression_eval(const float* logits, const float* target, int64_t n, int c,
+                        float* partials, uint8_t* image, void* stream);
+
+/* Fixed-order sum of K11's partials: sse_out = sum (may be NULL), loss_out = 0.5 * (sum / count)
+ * (may be NULL; count = n c). */
+int ffn_regression_loss(const float* partials, int num_blocks, float count, float* sse_out,
+                        float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

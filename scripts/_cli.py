@@ -89,6 +89,28 @@ VOXELS = [
     ("--anneal-start", dict(type=float, default=0.2)),
     ("--num-anneal-steps", dict(type=int, default=2000)),
 ]
+# train_image_regression.py:21-59 of the reference (positionals image_path nerf_model results_dir)
+IMAGE_REGRESSION = [
+    ("image_path", dict(help="Path to an image file")),
+    ("nerf_model", dict(choices=["mlp", "basic", "positional", "gaussian"])),
+    ("results_dir", dict(help="Path to the results directory")),
+    ("--activations", dict(action="store_true", help="Produce activation visualizations")),
+    ("--vertical", dict(action="store_true", help="Whether to stack the images vertically")),
+    ("--omit-gt", dict(action="store_true", help="whether to omit the GT image from the display")),
+    ("--image-size", dict(type=int, default=512, help="Size of the square input image")),
+    ("--color-space", dict(choices=["YCrCb", "RGB"], default="RGB")),
+    ("--num-channels", dict(type=int, default=256)),
+    ("--embedding_size", dict(type=int, default=256)),
+    ("--pos-max-log-scale", dict(type=float, default=6)),
+    ("--gauss-sigma", dict(type=float, default=10)),
+    ("--num-steps", dict(type=int, default=2000)),
+    ("--learning-rate", dict(type=float, default=1e-3)),
+    ("--report-interval", dict(type=int, default=50)),
+    ("--make-video", dict(action="store_true")),
+    ("--decay-rate", dict(type=float, default=0.1)),
+    ("--decay-steps", dict(type=int, default=2500)),
+    ("--device", dict(default="cuda")),
+]
 ORBIT = [
     ("model_path", dict(help="trained checkpoint")),
     ("resolution", dict(type=int, help="frame size in pixels")),
