@@ -21,7 +21,8 @@ _SUBMODULES = {
     "utils": "utils", "visualizers": "visualizers", "camera_info": "cameras",
     "ray_sampler": "sampler", "ray_caster": "caster", "ray_dataset": "dataset",
     "image_dataset": "dataset", "fourier_feature_models": "models", "nerf_model": "models",
-    "voxels_model": "voxels", "pixel_dataset": "pixel_dataset", "version": None,
+    "voxels_model": "voxels", "pixel_dataset": "pixel_dataset",
+    "signal_dataset": "signal_dataset", "version": None,
 }
 for _ref_name, _ours in _SUBMODULES.items():
     _mod = _impl if _ours is None else _sys.modules[_impl.__name__ + "." + _ours]

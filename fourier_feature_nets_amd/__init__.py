@@ -12,6 +12,7 @@ from .frames import FrameSink
 from .occupancy import OccupancyGrid
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
+from .signal_dataset import SignalData, SignalDataset
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -37,5 +38,5 @@ __version__ = "0.1.0"
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
            "OccupancyGrid", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
-           "RenderResult", "Resolution", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "linspace", "load_model", "orbit"]

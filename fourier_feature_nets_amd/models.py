@@ -78,7 +78,8 @@ class _FusedChainFunction(torch.autograd.Function):
             w0 = prog.grad_w_off[i]
             outs.append(grads[w0:w0 + spec.out * spec.ld].view(spec.out, spec.ld))
             b0 = prog.grad_b_off[i]
-            outs.append(grads[b0:b0 + spec.out])
+            # (a 0-d bias -- train_signal_regression.py:126 assigns one -- gets a 0-d gradient)
+            outs.append(grads[b0:b0 + spec.out].view(spec.bias.shape))
         return (None, None, None, None) + tuple(outs)
 
 
@@ -143,6 +144,31 @@ class _FusedModel(nn.Module):
         self.invalidate_packed()
         return out
 
+    def check_params(self, device: torch.device):
+        """Every dense weight / bias is a float32 tensor on ``device`` of its layer's size (a bias
+        may be 0-d when its layer has one output, as train_signal_regression.py:126 makes it).
+        Runs before the pack table is built: that table copies from the raw data pointers, so a
+        host tensor assigned to ``layer.bias.data`` of a GPU model would hand a host pointer to a
+        device copy."""
+        params = self._dense_params()
+        for k in range(0, len(params), 2):
+            w, b = params[k], params[k + 1]
+            for name, t in (("weight", w), ("bias", b)):
+                if t.device != device:
+                    raise RuntimeError("%s: a dense %s lives on %s, the model on %s; move it with "
+                                       "the model (.to(device)) before calling it"
+                                       % (type(self).__name__, name, t.device, device))
+                if t.dtype != torch.float32:
+                    raise TypeError("%s: a dense %s is %s; the kernels take float32"
+                                    % (type(self).__name__, name, t.dtype))
+            if w.dim() != 2 or w.stride(1) != 1:
+                raise ValueError("%s: a dense weight must be a row-major (out, in) matrix, got "
+                                 "shape %s" % (type(self).__name__, tuple(w.shape)))
+            if b.dim() > 1 or b.numel() != w.shape[0] or not b.is_contiguous():
+                raise ValueError("%s: a bias of shape %s for a layer of %d outputs (a (%d,) or, "
+                                 "for one output, a 0-d tensor)"
+                                 % (type(self).__name__, tuple(b.shape), w.shape[0], w.shape[0]))
+
     def program(self) -> MlpProgram:
         params = self._dense_params()
         device = params[0].device
@@ -152,6 +178,9 @@ class _FusedModel(nn.Module):
                 "is no CPU fallback" % type(self).__name__)
         ptrs = tuple(p.data_ptr() for p in params)
         if self._prog is None or self._prog.device != device or self._prog_ptrs != ptrs:
+            # (a tensor assigned to a parameter's .data always changes its pointer: the checks run
+            # whenever the pack table is rebuilt, off the per-step path)
+            self.check_params(device)
             encodings, specs = self._chain(device)
             self._prog = MlpProgram(encodings, specs, device)
             self._prog_ptrs = ptrs

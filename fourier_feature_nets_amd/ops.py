@@ -6,6 +6,7 @@ import ctypes
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -288,6 +289,36 @@ def regression_loss(partials: torch.Tensor, count: int, sse_out: Optional[torch.
                     loss_out: Optional[torch.Tensor] = None):
     """Fixed-order sum of K11's partials: sse into ``sse_out``, 0.5 * sse / count into ``loss_out``."""
     _call("ffn_regression_loss", _dev(partials), c_i(partials.shape[0]), c_f(float(count)),
+          _dev(sse_out), _dev(loss_out))
+
+
+def inv_count(count: int) -> float:
+    """fl32(1 / count), divided in float32 as ATen's mean backward does (not rounded from a
+    float64 quotient)."""
+    return float(np.float32(1.0) / np.float32(count))
+
+
+def regression_mse_train(logits: torch.Tensor, target: torch.Tensor, d_logits: torch.Tensor,
+                         partials: torch.Tensor):
+    """K11b training: logits (n,4), target (n,c) -> d_logits (n,4) of mean((z - y)^2) (columns
+    >= c exactly 0) and one sum of squares per workgroup in ``partials``."""
+    n, c = target.shape
+    _call("ffn_regression_mse_train", _dev(logits, name="logits"), _dev(target, name="target"),
+          c_i64(n), c_i(c), c_f(inv_count(n * c)), _dev(d_logits, name="d_logits"),
+          _dev(partials, name="partials"))
+
+
+def regression_mse_eval(logits: torch.Tensor, target: torch.Tensor, partials: torch.Tensor):
+    """K11b validation: sums of (z - y)^2 per workgroup into ``partials``."""
+    n, c = target.shape
+    _call("ffn_regression_mse_eval", _dev(logits, name="logits"), _dev(target, name="target"),
+          c_i64(n), c_i(c), _dev(partials, name="partials"))
+
+
+def regression_mse_loss(partials: torch.Tensor, count: int, sse_out: Optional[torch.Tensor] = None,
+                        loss_out: Optional[torch.Tensor] = None):
+    """Fixed-order sum of K11b's partials: sse into ``sse_out``, sse / count into ``loss_out``."""
+    _call("ffn_regression_mse_loss", _dev(partials), c_i(partials.shape[0]), c_f(float(count)),
           _dev(sse_out), _dev(loss_out))
 
 

@@ -701,6 +701,29 @@ int ffn_regression_eval(const float* logits, const float* target, int64_t n, int
 int ffn_regression_loss(const float* partials, int num_blocks, float count, float* sse_out,
                         float* loss_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K11b  linear-output MSE of 1-D signal regression (csrc/regression.hip).
+ * Replaces (model(x) - y).square().mean() and its autograd (train_signal_regression.py:81-85,
+ * run over the full training set every step at :155-157) and the validation loss (:88-95).
+ * No sigmoid and no 0.5 factor.  Same grid, partial layout (ffn_regression_blocks(n) floats) and
+ * fixed-order sum as K11; logits (n,4) with the first c columns used, target (n,c), 1 <= c <= 4,
+ * n >= 1.  No float atomics; bad shapes / null pointers are refused before any launch. */
+
+/* d_logits (n,4) out: inv_count * (2 * (z - y)) in f32 (ATen's autograd order: MeanBackward's
+ * 1 / count, then PowBackward's grad * (2 * r); inv_count = fl(1 / (n c))) for the first c
+ * columns, exactly 0 in the others; partials: one sum((z - y)^2) per workgroup. */
+int ffn_regression_mse_train(const float* logits, const float* target, int64_t n, int c,
+                             float inv_count, float* d_logits, float* partials, void* stream);
+
+/* Validation: partials only, bit-identical to ffn_regression_mse_train's. */
+int ffn_regression_mse_eval(const float* logits, const float* target, int64_t n, int c,
+                            float* partials, void* stream);
+
+/* Fixed-order sum of the partials: sse_out = sum (may be NULL), loss_out = sum / count (may be
+ * NULL; count = n c) -- not K11's 0.5 * (sum / count). */
+int ffn_regression_mse_loss(const float* partials, int num_blocks, float count, float* sse_out,
+                            float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

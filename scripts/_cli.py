@@ -111,6 +111,29 @@ IMAGE_REGRESSION = [
     ("--decay-steps", dict(type=int, default=2500)),
     ("--device", dict(default="cuda")),
 ]
+# train_signal_regression.py:48-78 of the reference (positionals signal results_dir; --num_plot is
+# spelled with an underscore there too), then --device as in the other drivers
+SIGNAL_REGRESSION = [
+    ("signal", dict(choices=["multifreq", "sawtooth", "triangle"],
+                    help="the 1-D signal to fit")),
+    ("results_dir", dict(help="directory for log.txt and the frames")),
+    ("--num-channels", dict(type=int, default=64, help="hidden channels")),
+    ("--num-layers", dict(type=int, default=1, help="hidden layers")),
+    ("--num-samples", dict(type=int, default=32, help="training samples")),
+    ("--sample-rate", dict(type=int, default=8,
+                           help="validation points per training sample")),
+    ("--num_plot", dict(type=int, default=48,
+                        help="points in the plots")),
+    ("--max-hidden", dict(type=int, default=10,
+                          help="hidden units drawn")),
+    ("--fourier", dict(action="store_true", help="Fourier-feature input encoding")),
+    ("--resolution", dict(default="1280x720", help="frame size WIDTHxHEIGHT")),
+    ("--num-steps", dict(type=int, default=10000, help="training steps")),
+    ("--make-video", dict(action="store_true", help="(no MP4 writer here: PNG frames instead)")),
+    ("--framerate", dict(type=int, default=5, help="video frame rate (unused)")),
+    ("--no-plot", dict(action="store_true", help="no frames")),
+    ("--device", dict(default="cuda")),
+]
 ORBIT = [
     ("model_path", dict(help="trained checkpoint")),
     ("resolution", dict(type=int, help="frame size in pixels")),
