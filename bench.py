@@ -1,6 +1,6 @@
 """Benchmark of the NeRF volume-rendering hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" is one complete optimisation step of the reference's training loop
 (ray_caster.py:319-329) on one batch of synthetic rays: stratified t-sampling -> fused
@@ -11,11 +11,15 @@ Fourier-MLP forward -> alpha compositing -> loss -> backward (composite, dgrad, 
 weights) are resident in HBM before the timed region.
 
 ``--gpus N`` without a launcher spawns its own N ranks (torch.distributed.run, one per GPU).
-Rank 0 prints ONE JSON line: the metric, the roofline of the dominant kernel, per-kernel
-timings, the all-reduce cost (N > 1), and -- at N = 1 -- the reporting-only legs: frames/sec of
-the fused render (with and without frame I/O), the MLP kernels at the north-star launch shape,
-a full optimisation step of BASELINE configs[2] (full NeRF, 64 uniform + 64 opacity-guided
-samples with a live coarse model) and the CPU baseline.
+Rank 0 prints ONE JSON line: the metric, the roofline of the dominant kernel and per-kernel
+timings (both from HIP events inside the timed steps) and the all-reduce cost (N > 1).  A plain
+run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  ``--full``
+adds the reporting-only legs, each timed in runs of its own after the timed steps: frames/sec of
+the fused render (with and without frame I/O), the CPU baseline and -- at N = 1 -- the MLP
+kernels at the north-star launch shape, a full optimisation step of BASELINE configs[2] (full
+NeRF, 64 uniform + 64 opacity-guided samples with a live coarse model), configs[3] and [4], the
+reference drivers' default batch, empty-space skipping and the opt-in split-bf16 modes.  In a
+plain line the fields of those legs are null.
 """
 
 import argparse
@@ -65,6 +69,9 @@ def parse_args():
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--cameras", type=int, default=100)
     ap.add_argument("--size", type=int, default=400)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the reporting-only legs (render, CPU baseline, "
+                         "other configurations and precisions); the --no-* options below skip single legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-render", action="store_true", help="skip the frames/sec leg")
     ap.add_argument("--no-target-shape", action="store_true",
@@ -360,6 +367,11 @@ class KernelTimer:
                         "frac": round(tf / F32_MFMA_PEAK_TFLOPS, 4), "flop_per_sample": flops[key]}
         return out
 
+
+# fields of the line that only --full fills (null in a plain run; "render" is set where it runs)
+REPORTING_LEGS = ("north_star_shape", "config3_step", "config4_step", "default_batch_step",
+                  "empty_space_skipping", "split_bf16_inference", "split_bf16_training",
+                  "f32_accurate_split", "config5_step", "cpu_baseline")
 
 DUMP_LIMIT_BYTES = 64 << 20
 
@@ -1342,7 +1354,7 @@ def main():
     # ---- render leg: 400x400 frames of the first cameras (replicas only: frame f -> rank f%world)
     caster = ffn.Raycaster(model)
     render = None
-    if not args.no_render:
+    if args.full and not args.no_render:
         # like orbit_video.py:76-78: a plain (non-stratified) sampler over the frames' cameras
         with contextlib.redirect_stdout(io.StringIO()):
             frame_sampler = ffn.RaySampler(bounds, cams[:8 * world], args.samples, False, device=device)
@@ -1442,35 +1454,39 @@ def main():
                 "rank_step_ms": rank_ms, "placement": placement}
         else:
             result["collective"] = None
-        solo = world == 1 and args.model == "tiny"
-        state = {k: v.detach().clone() for k, v in model.state_dict().items()}
-        # free the headline leg's buffers before the large reporting-only legs
-        del engine, caster
-        prog.release_workspaces()
-        torch.cuda.empty_cache()
-        result["north_star_shape"] = target_shape_leg(device) if solo and not args.no_target_shape else None
-        result["config3_step"] = (config3_leg(device, cams, images, bounds)
-                                  if solo and not args.no_config3 and args.size == 400 else None)
-        result["config4_step"] = (config4_leg(device, bounds)
-                                  if solo and not args.no_config3 and args.size == 400 else None)
-        result["default_batch_step"] = (default_batch_leg(device, cams, images, bounds)
-                                        if solo and not args.no_config3 and args.size == 400 else None)
-        result["empty_space_skipping"] = (skip_leg(device, dataset, bounds, args.rays)
-                                          if solo and not args.no_skip_leg else None)
-        result["split_bf16_inference"] = (bf16_leg(device, bounds, cams, args.samples)
-                                          if solo and not args.no_bf16_leg else None)
-        result["split_bf16_training"] = (bf16_train_leg(device, dataset, args.rays, args.samples)
-                                         if solo and not args.no_bf16_leg else None)
-        result["f32_accurate_split"] = (bf16_train_leg(device, dataset, args.rays, args.samples, mode="bf16x6")
-                                        if solo and not args.no_bf16_leg else None)
-        if result["f32_accurate_split"] is not None:
-            result["f32_accurate_split"]["inference"] = split_render(device, bounds, cams, args.samples, "bf16x6")
-        del dataset
-        torch.cuda.empty_cache()
-        result["config5_step"] = (config5_leg(device, bounds)
-                                  if solo and not args.no_config5 and args.size == 400 else None)
-        result["cpu_baseline"] = (cpu_baseline_for(args, state, world)
-                                  if args.model == "tiny" and not args.no_cpu_baseline else None)
+        result["full"] = args.full
+        # the reporting-only legs (--full only): each times runs of its own after the headline's steps
+        result.update(dict.fromkeys(REPORTING_LEGS))
+        if args.full:
+            solo = world == 1 and args.model == "tiny"
+            state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+            # free the headline leg's buffers before the large reporting-only legs
+            del engine, caster
+            prog.release_workspaces()
+            torch.cuda.empty_cache()
+            result["north_star_shape"] = target_shape_leg(device) if solo and not args.no_target_shape else None
+            result["config3_step"] = (config3_leg(device, cams, images, bounds)
+                                      if solo and not args.no_config3 and args.size == 400 else None)
+            result["config4_step"] = (config4_leg(device, bounds)
+                                      if solo and not args.no_config3 and args.size == 400 else None)
+            result["default_batch_step"] = (default_batch_leg(device, cams, images, bounds)
+                                            if solo and not args.no_config3 and args.size == 400 else None)
+            result["empty_space_skipping"] = (skip_leg(device, dataset, bounds, args.rays)
+                                              if solo and not args.no_skip_leg else None)
+            result["split_bf16_inference"] = (bf16_leg(device, bounds, cams, args.samples)
+                                              if solo and not args.no_bf16_leg else None)
+            result["split_bf16_training"] = (bf16_train_leg(device, dataset, args.rays, args.samples)
+                                             if solo and not args.no_bf16_leg else None)
+            result["f32_accurate_split"] = (bf16_train_leg(device, dataset, args.rays, args.samples, mode="bf16x6")
+                                            if solo and not args.no_bf16_leg else None)
+            if result["f32_accurate_split"] is not None:
+                result["f32_accurate_split"]["inference"] = split_render(device, bounds, cams, args.samples, "bf16x6")
+            del dataset
+            torch.cuda.empty_cache()
+            result["config5_step"] = (config5_leg(device, bounds)
+                                      if solo and not args.no_config5 and args.size == 400 else None)
+            result["cpu_baseline"] = (cpu_baseline_for(args, state, world)
+                                      if args.model == "tiny" and not args.no_cpu_baseline else None)
         print(json.dumps(result), flush=True)
     if group is not None:
         import torch.distributed as dist

@@ -2,7 +2,7 @@
 # every -m gpu test in exact f32 and again with --precision bf16x6, kernel stats of the bench workload
 # and of the training kernels in the three arithmetic modes side by side (exact f32, bf16x3, bf16x6),
 # FETCH / WRITE traffic of those kernels (separate passes), SQ counters, the HBM-bound kernels against
-# fill / copy, then the default bench line.  --pmc passes carry --kernel-trace only.
+# fill / copy, then the bench line with every leg (--full).  --pmc passes carry --kernel-trace only.
 #   ROUND=r06 bash scripts/gpu/profile.sh      -> gpurun_out/prof/${ROUND}_*  (copy what is judged into profiles/)
 ROUND=${ROUND:-r06}
 OUT=gpurun_out/prof
@@ -31,7 +31,7 @@ for n in stats train; do python scripts/kernel_stats_csv.py $OUT/${n}_kernel_sta
 python scripts/pmc_traffic_summary.py $OUT $OUT/${ROUND}_hbm_traffic_train_kernels.json $HEAD "$M"
 python scripts/pmc_counter_summary.py $OUT/sq_counter_collection.csv $OUT/${ROUND}_sq_counters_train_kernels.json "rocprofv3 --kernel-trace --pmc (8 SQ counters, one pass) on: $M" $HEAD
 python scripts/microbench_hbm.py > $OUT/${ROUND}_hbm_microbench.json 2> $OUT/hbm.err
-S=$(date +%s); python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - S ))s"
+S=$(date +%s); python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall=$(( $(date +%s) - S ))s"
 rm -f $OUT/*_kernel_trace.csv $OUT/*counter_collection.csv $OUT/*agent_info.csv
 export ROUND
 python - <<'PY'

@@ -19,7 +19,7 @@ for N in $NS; do
   if [ "$N" = 1 ] && [ "$MODE" = strong ] && [ -f gpurun_out/scale/bench_weak_1.json ]; then
     cp gpurun_out/scale/bench_weak_1.json gpurun_out/scale/bench_strong_1.json; continue   # (N = 1: the same run)
   fi
-  python bench.py --gpus $N --steps $STEPS --warmup $WARMUP --rays $RAYS --scaling $MODE --no-target-shape --no-config3 \
+  python bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP --rays $RAYS --scaling $MODE --no-target-shape --no-config3 \
       --no-config5 --no-bf16-leg --no-skip-leg $EXTRA > gpurun_out/scale/bench_${MODE}_$N.json 2> gpurun_out/scale/bench_${MODE}_$N.err
   echo "$MODE N=$N rc=$? wall=$(( $(date +%s) - S ))s"
 done
