@@ -29,7 +29,7 @@ __device__ __forceinline__ float scan_add(float v, int lane) {
 // sigma = F.softplus(logit), beta = 1, threshold = 20 (ray_sampler.py:261-265)
 __device__ __forceinline__ float softplus_probe(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 
-// cdf = [0, cumsum(w[1:-1] + 1e-5) / sum], w = blend weights of a probe of n samples held as
+// cdf = [0, cumsum(w[1:-1] + 1e-5) / cumsum[-1]], w = blend weights of a probe of n samples held as
 // ROWS x 64 lanes (sample s on lane s & 63 of row s >> 6): sigma[row] and delta[row] =
 // t[s+1] - t[s] (anything for s >= n-1: the last delta is 1e10).  Writes n-1 floats to `out`
 // (LDS or global).
@@ -66,7 +66,14 @@ __device__ __forceinline__ void cdf_of_probe(const float (&sigma)[ROWS], const f
         run[row] = base + incl;
         base += __shfl(incl, 63, 64);
     }
-    const float total = base;
+    // divide by the LAST ENTRY's own running sum, as the reference divides by cdf[:, -1:], so that
+    // the row ends at exactly 1.0f: the scan's lane-63 total adds the same terms on another tree
+    // and can differ from it by a few ulps
+    const int last = n - 2;
+    float total = 0.0f;
+#pragma unroll
+    for (int row = 0; row < ROWS; ++row)
+        if (row == (last >> 6)) total = __shfl(run[row], last & 63, 64);
     if (lane == 0) out[0] = 0.0f;
 #pragma unroll
     for (int row = 0; row < ROWS; ++row) {

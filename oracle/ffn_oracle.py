@@ -120,12 +120,16 @@ def sampler_state(bounds: np.ndarray, intrinsics: Sequence[np.ndarray],
 #  a4 / a5: t sampling
 # --------------------------------------------------------------------------- #
 
-def linspace_rows(start: torch.Tensor, stop: torch.Tensor, count: int) -> torch.Tensor:
+def linspace_rows(start: torch.Tensor, stop: torch.Tensor, count: int,
+                  unit: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-row linspace incl. both ends.  Restates utils.py:179-194.
 
-    A multiply then an add (two roundings, no fused multiply-add).
+    A multiply then an add (two roundings, no fused multiply-add).  ``unit``: the
+    (count,) fractions to use instead of ``torch.linspace(0, 1, count)`` (a kernel's
+    own input, when its outputs are checked).
     """
-    unit = torch.linspace(0, 1, count)
+    if unit is None:
+        unit = torch.linspace(0, 1, count)
     return start.unsqueeze(-1) + unit.unsqueeze(0) * (stop - start).unsqueeze(-1)
 
 
@@ -144,14 +148,14 @@ def anneal_range(near: torch.Tensor, far: torch.Tensor, step: Optional[int],
 
 
 def uniform_t(near: torch.Tensor, far: torch.Tensor, count: int,
-              noise: Optional[torch.Tensor]) -> torch.Tensor:
+              noise: Optional[torch.Tensor], unit: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Evenly spaced (optionally jittered) t.  Restates ray_sampler.py:380-386.
 
     ``noise`` is the (R, count) block the reference draws with ``torch.rand``;
     passing it in keeps the oracle deterministic and lets the device path be
     compared bit for bit.
     """
-    t = linspace_rows(near, far, count)
+    t = linspace_rows(near, far, count, unit)
     if noise is not None:
         scale = (far - near) / count
         t = t + noise * scale.unsqueeze(-1)
@@ -167,7 +171,7 @@ def determine_cdf(t_values: torch.Tensor, opacity: torch.Tensor) -> torch.Tensor
 
 
 def focus_t(near: torch.Tensor, far: torch.Tensor, cdf: torch.Tensor,
-            u: torch.Tensor) -> torch.Tensor:
+            u: torch.Tensor, unit: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Inverse-transform samples from the CDF.  Restates ray_sampler.py:301-357.
 
     Bin locations are the mid-points of linspace(near, far, n); ``u`` is the
@@ -175,7 +179,7 @@ def focus_t(near: torch.Tensor, far: torch.Tensor, cdf: torch.Tensor,
     repeated otherwise).
     """
     n = u.shape[1]
-    grid = linspace_rows(near, far, n)
+    grid = linspace_rows(near, far, n, unit)
     mids = 0.5 * (grid[..., :-1] + grid[..., 1:])
     k = torch.searchsorted(cdf, u, right=True)
     lo = torch.clamp(k - 1, min=0)

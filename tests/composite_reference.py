@@ -428,7 +428,9 @@ def loss_of(sums, rays, alpha_weight):
 class Report:
     """Worst ratio per output, failures, and the teeth."""
 
-    def __init__(self):
+    def __init__(self, kappa=None, teeth_doc=None):
+        self.kappa = KAPPA if kappa is None else kappa
+        self.teeth_doc = TEETH_DOC if teeth_doc is None else teeth_doc
         self.worst = {}
         self.failures = []
         self.teeth = {}      # tooth -> dict(touched, exceeds, ratio (|got - alt| / bound, worst), out)
@@ -441,7 +443,7 @@ class Report:
             return
         err = (got - rv).abs()
         scale = U * rb
-        ok = err <= KAPPA[out] * scale                      # (NaN fails)
+        ok = err <= self.kappa[out] * scale                      # (NaN fails)
         ratio = torch.where(err == 0, torch.zeros_like(err), err / scale)
         ratio = torch.nan_to_num(ratio, nan=float("inf"))
         self.worst[out] = max(self.worst.get(out, 0.0), float(ratio.max()))
@@ -449,7 +451,7 @@ class Report:
             bad = int((~ok).nonzero()[0, 0])
             self.failures.append("%s %s: %d of %d elements out of bound, first at flat index %d: got %r want %r "
                                  "(bound %.3g)" % (out, key, int((~ok).sum()), ok.numel(), bad, float(got[bad]),
-                                                   float(rv[bad]), float(KAPPA[out] * scale[bad])))
+                                                   float(rv[bad]), float(self.kappa[out] * scale[bad])))
 
     def tooth(self, out, name, got, ref, alt):
         """Records how far the kernel's ``got`` is from the changed reference ``alt``, in units of the
@@ -459,7 +461,7 @@ class Report:
         touched = ~(av == rv)
         if not bool(touched.any()):
             return
-        bound = KAPPA[out] * U * rb[touched]
+        bound = self.kappa[out] * U * rb[touched]
         shift = (av - rv).abs()[touched]
         exceeds = bool(((shift > bound) | torch.isnan(shift)).any())
         far = torch.nan_to_num((got[touched] - av[touched]).abs() / bound, nan=float("inf"))
@@ -473,7 +475,7 @@ class Report:
         p = list(self.failures)
         for name in required_teeth:
             if name not in self.teeth:
-                p.append("tooth %s (%s): the data has no element it changes" % (name, TEETH_DOC[name]))
+                p.append("tooth %s (%s): the data has no element it changes" % (name, self.teeth_doc.get(name, "")))
         for name, t in self.teeth.items():
             if not t["exceeds"]:
                 p.append("tooth %s: the changed reference stays within the bound everywhere" % name)

@@ -85,7 +85,9 @@ def test_raygen_full_size_properties(ops):
     assert float(nf[0][v].min()) >= 0.1
     bad_cpu = set(st["invalid"].tolist())
     bad_gpu = set(np.nonzero(valid[:160000].cpu().numpy() == 0)[0].tolist())
-    assert len(bad_cpu ^ bad_gpu) <= 4      # grazing rays may flip on a 1-ulp direction change
+    # grazing rays may flip on a 1-ulp direction change (the oracle's numpy matmul / norm round otherwise);
+    # test_sampling_reference_gpu.py holds every flag to the float64 slab test within its error budget
+    assert len(bad_cpu ^ bad_gpu) <= 4
 
 
 # ----------------------------------------------------------------------------------- K2
