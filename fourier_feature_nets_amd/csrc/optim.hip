@@ -45,8 +45,13 @@ norm_adam_kernel(float* __restrict__ params, float* __restrict__ grads, float* _
     float acc = 0.0f;
     for (int i = threadIdx.x; i < num_partials; i += 256) acc += partial[i];
     const float norm = sqrtf(block_sum_256(acc, red));
-    float coef = max_norm / (norm + 1e-6f);
-    coef = coef > 1.0f ? 1.0f : coef;
+    // max_norm = +inf (no norm clip): coef is 1 whatever the norm -- inf / (inf + 1e-6f) would be
+    // NaN once the f32 sum of squares overflows
+    float coef = 1.0f;
+    if (max_norm != INFINITY) {
+        coef = max_norm / (norm + 1e-6f);
+        coef = coef > 1.0f ? 1.0f : coef;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0 && grad_norm_out != nullptr) grad_norm_out[0] = norm;
     const int64_t base = (int64_t)blockIdx.x * 1024;
 #pragma unroll

@@ -107,8 +107,8 @@ class RegressionEngine:
             ops.regression_loss(partials, n * c, loss_out=loss)
         prog.backward(d_logits, inputs3, None, saved, self.grads, precision=precision)
         self.count += 1
-        # the reference's loop does not clip: with both bounds at +inf K7's clamp and its norm
-        # coefficient min(1, inf / (norm + 1e-6)) are the identity, bit for bit
+        # the reference's loop does not clip: with both bounds at +inf K7's clamp is the identity
+        # and its norm coefficient exactly 1 (even where the f32 sum of squares overflows)
         ops.clip_adam(self.flat, self.grads, self.exp_avg, self.exp_avg_sq, self.count, lr,
                       weight_decay=self.weight_decay, clip_value=math.inf, max_norm=math.inf, beta1=self.beta1, beta2=self.beta2,
                       eps=self.eps, scratch=self.scratch)

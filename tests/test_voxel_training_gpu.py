@@ -1,8 +1,8 @@
 """Voxel radiance-field training on the GPU: the K10b backward (csrc/voxels.hip) against ATen's
 grid_sample backward in float64, its adjoint identity with K10, its determinism and argument
 refusals; `Voxels` through `TrainEngine` / `Raycaster.fit` replayed against the reference's own
-`fit` (tests/golden/fit_schedule_voxels.npz); and the README workflow train_voxels.py ->
---opacity-model end to end.
+`fit` (tests/golden/fit_schedule_voxels.npz); the K10 forward against grid_sample in float64
+(``check_forward``); and the README workflow train_voxels.py -> --opacity-model end to end.
 
 Error budgets follow tests/composite_reference.py: every element is held to
 kappa * 2^-24 * budget, the budget being a first-order f32 error bound of that element:
@@ -317,6 +317,125 @@ def test_occupancy_schedule_with_voxels_raises():
     engine.occupancy = object()
     with pytest.raises(NotImplementedError):
         engine.train_step(ds, torch.arange(0, 64, device=dev()), 0, 0.01)
+
+
+# ----------------------------------------------------------------------------------- K10 forward
+# K10's forward against float64: element budget (units of 2^-24) per output channel
+#     summation    12 (sum_k |v_k w_k| + |bias|)     weights 1 - f and two products, eight products,
+#                                                   seven additions, the bias
+#     coordinates  sum_d D_d delta_d                delta_d: the f32 coordinate's error bound
+#                                                   (1/scale rounded on the host, the kernel's
+#                                                   fma((p, inv, 1)) * S - 1), D_d: the largest corner
+#                                                   difference along axis d over the cell and its
+#                                                   neighbours (the f32 coordinate may sit in the next
+#                                                   cell where the exact one lies within delta_d of an
+#                                                   integer)
+KAPPA_FORWARD = 0.4      # about twice the worst ratio measured on an MI355X over the cases below [0.201, S=2]
+FORWARD_TEETH = ("align_corners", "zeros_padding", "xz_swapped", "no_bias")
+
+
+def _forward64(vol, bias, pos, scale, variant=None):
+    """grid_sample of p / scale (border, align_corners=False) + bias in float64 on vol's device; (N,4)."""
+    grid = pos.double() / scale
+    if variant == "xz_swapped":
+        grid = grid[:, [2, 1, 0]]
+    out = F.grid_sample(vol.double()[None], grid.reshape(1, -1, 1, 1, 3),
+                        padding_mode="zeros" if variant == "zeros_padding" else "border",
+                        align_corners=variant == "align_corners")
+    out = out.reshape(4, -1).t()
+    return out if variant == "no_bias" else out + bias.double()
+
+
+def forward_budget(vol, bias, pos, side, scale):
+    """(N,4) budget in units of 2^-24 of K10 at ``pos`` (see the block comment)."""
+    v = vol.double()
+    x = pos.double() / scale
+    c = (((x + 1) * side - 1) / 2).clamp(0, side - 1)
+    lo = c.floor().long().clamp(max=side - 1)
+    f = c - lo
+    hi = (lo + 1).clamp(max=side - 1)
+    u = 2.0 ** -24
+    # |c32 - c| / u: inv = 1/scale (1 + e), fma(p, inv, 1), * S, - 1, * 0.5 (exact)
+    delta = (side * (x.abs() + (x + 1).abs()) + ((x + 1) * side).abs() + ((x + 1) * side - 1).abs()) / 2 + 1
+    flat = lambda z, y, xx: (z * side + y) * side + xx            # noqa: E731
+    vf = v.reshape(4, -1)
+    sum_abs = torch.zeros((pos.shape[0], 4), dtype=torch.float64, device=pos.device)
+    for cz in (0, 1):
+        for cy in (0, 1):
+            for cx in (0, 1):
+                w = ((f[:, 0] if cx else 1 - f[:, 0]) * (f[:, 1] if cy else 1 - f[:, 1])
+                     * (f[:, 2] if cz else 1 - f[:, 2]))
+                idx = flat((hi if cz else lo)[:, 2], (hi if cy else lo)[:, 1], (hi if cx else lo)[:, 0])
+                sum_abs += (vf[:, idx].t() * w[:, None]).abs()
+    budget = 12 * (sum_abs + bias.double().abs())
+    for d in range(3):                      # x is the last volume axis
+        axis = 3 - d
+        if side > 1:                        # |v[i + 1] - v[i]| along the axis, 0 at the last voxel
+            diff = (v.narrow(axis, 1, side - 1) - v.narrow(axis, 0, side - 1)).abs()
+            diff = F.pad(diff, [0, int(axis == 3), 0, int(axis == 2), 0, int(axis == 1)])
+        else:
+            diff = torch.zeros_like(v)
+        near = F.max_pool3d(diff[None], 3, 1, 1)[0].reshape(4, -1)    # the cell's neighbours
+        dmax = torch.zeros((pos.shape[0], 4), dtype=torch.float64, device=pos.device)
+        for cz in (lo, hi):
+            for cy in (lo, hi):
+                for cx in (lo, hi):
+                    dmax = torch.maximum(dmax, near[:, flat(cz[:, 2], cy[:, 1], cx[:, 0])].t())
+        budget += dmax * delta[:, d:d + 1]
+    return budget
+
+
+def check_forward(vol, bias, pos, side, scale, label=""):
+    """K10 from NaN-filled outputs against ``_forward64`` within KAPPA_FORWARD * 2^-24 * budget; the
+    teeth (changed references) must each be failed somewhere.  Returns the worst ratio and the
+    teeth's smallest multiples of the bound."""
+    from fourier_feature_nets_amd import ops
+    n = pos.shape[0]
+    out = torch.full((n, 4), float("nan"), device=dev())
+    ops._call("ffn_voxels_forward", ops._dev(vol), ops._dev(bias), ops._dev(pos, name="positions"),
+              ops._lib.c_i64(n), ops._lib.c_i(side), ops._lib.c_f(scale), ops._dev(out))
+    got = out.double()
+    ref = _forward64(vol, bias, pos, scale)
+    bound = KAPPA_FORWARD * U * forward_budget(vol, bias, pos, side, scale)
+    err = (got - ref).abs()
+    ratio = float((err / bound).max())
+    assert bool(torch.isfinite(got).all()), label
+    assert bool((err <= bound).all()), (label, ratio, int((err > bound).sum()))
+    teeth = {}
+    for name in FORWARD_TEETH:
+        alt = _forward64(vol, bias, pos, scale, name)
+        touched = (alt - ref).abs() > bound
+        if bool(touched.any()):
+            teeth[name] = float(((got - alt).abs() / bound)[touched].max())
+    return ratio, teeth
+
+
+@pytest.mark.parametrize("side,scale", [(1, 1.0), (2, 0.8), (5, 1.5), (8, 1.0), (32, 0.7), (128, 1.0),
+                                        (256, 1.3)])
+def test_forward_against_grid_sample_float64(side, scale):
+    """K10 against float64 grid_sample + bias on _positions (faces, the S-1 clamp, voxel centres,
+    corners, outside the cube); every tooth must touch the data and be failed."""
+    gen = torch.Generator().manual_seed(side)
+    vol = torch.randn((4, side, side, side), generator=gen).to(dev())
+    bias = torch.randn((4,), generator=gen).to(dev())
+    pos = _positions(20000, side, scale, seed=side + 1).to(dev())
+    ratio, teeth = check_forward(vol, bias, pos, side, scale, "S=%d" % side)
+    print("K10 forward S=%d worst error / budget %.3g, teeth %s" % (side, ratio, teeth))
+    want = [t for t in FORWARD_TEETH if side > 1 or t in ("zeros_padding", "no_bias")]   # (S = 1: constant)
+    for name in want:
+        assert name in teeth and teeth[name] > 1.0, (name, teeth)
+
+
+def test_forward_past_the_grid_stride_cap():
+    """More samples than 8192 workgroups x 256 threads: every thread loops; all written."""
+    side, scale = 8, 1.0
+    gen = torch.Generator().manual_seed(3)
+    vol = torch.randn((4, side, side, side), generator=gen).to(dev())
+    bias = torch.randn((4,), generator=gen).to(dev())
+    n = 8192 * 256 + 4099
+    pos = ((torch.rand((n, 3), generator=gen) * 2 - 1) * 1.1).to(dev())
+    ratio, teeth = check_forward(vol, bias, pos, side, scale, "cap")
+    print("K10 forward cap worst error / budget %.3g, teeth %s" % (ratio, teeth))
 
 
 # ----------------------------------------------------------------------------------- the reference's fit replayed
