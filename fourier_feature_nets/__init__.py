@@ -22,7 +22,7 @@ _SUBMODULES = {
     "ray_sampler": "sampler", "ray_caster": "caster", "ray_dataset": "dataset",
     "image_dataset": "dataset", "fourier_feature_models": "models", "nerf_model": "models",
     "voxels_model": "voxels", "pixel_dataset": "pixel_dataset",
-    "signal_dataset": "signal_dataset", "version": None,
+    "signal_dataset": "signal_dataset", "octree": "octree", "version": None,
 }
 for _ref_name, _ours in _SUBMODULES.items():
     _mod = _impl if _ours is None else _sys.modules[_impl.__name__ + "." + _ours]

@@ -10,6 +10,7 @@ from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
+from .octree import OcTree
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
@@ -37,6 +38,6 @@ __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OccupancyGrid", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
+           "OcTree", "OccupancyGrid", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "linspace", "load_model", "orbit"]

@@ -1,0 +1,510 @@
+// K12  Sparse octree from a point cloud, and the surface points that feed it.
+//
+// Replaces the host-side (Python / Numba, one point at a time) octree of the reference:
+// voxelize_model.py:71-77 (surface points of a render batch), octree.py:274-286 (child index of
+// a point), octree.py:733-806 (build_from_samples), octree.py:513-541 (point query) and the
+// node-by-node walk behind leaf_centers / leaf_depths (octree.py:564-582, 605-613).
+//
+// Node ids are the reference's: root 0, children of i are 8 i + 1 .. 8 i + 8, child index
+// 4 [x >= cx] + 2 [y >= cy] + [z >= cz].  A node centre is reached from the root by adding
+// +-scale / 2^k level by level, every add rounded to f32 (the reference's Node arithmetic on an
+// np.float32 scale); the kernels replay exactly that chain, so a point on or next to a splitting
+// plane takes the reference's side.
+//
+// The build counts by SORTING: a point's path code is its D-1 child indices, 3 bits each, root
+// first.  With the codes sorted (a stable key sort done by the caller), the points of any node
+// are one contiguous range and the ranges of its children nest inside it, so "how many points
+// does this node hold" is two binary searches inside the parent's range -- integer work only,
+// no atomics, no per-level histogram whose size grows as 8^D.
+//
+//   K12a surface_flags / K12d surface_scatter   alpha > threshold, stable compaction
+//   K12b/c scan_*            exclusive scan of u8 flags (tile counts, one-workgroup scan, offsets)
+//   K12e path_codes          per point: shift by the cube centre, descend D-1 levels
+//   K12f assign              per sorted point: walk down the nested ranges, stop at the first
+//                            node with < min_leaf_size points; leaf id or -1
+//   K12g leaf_heads / leaf_gather    first point of every leaf -> (id, start, count), code order
+//   K12h ancestor_flags / ancestor_gather   interior nodes = proper ancestors of the leaves
+//   K12i leaf_means          one wave per leaf, lanes stride the leaf's points in sorted order,
+//                            fixed butterfly: the same input gives the same bits
+//   K12j query               containment, descent, binary search in the sorted id arrays
+//   K12k leaf_geometry       centre and depth of a leaf from its id alone
+#include "common.h"
+
+namespace ffn {
+
+constexpr int kOctThreads = 256;
+constexpr int kScanItems = 8;
+constexpr int kScanTile = kOctThreads * kScanItems;
+constexpr int kOctMaxDepth = 11;      // 3 (D - 1) code bits in an int32
+constexpr int kOctMaxLevels = 21;     // 8^21 < 2^63: the deepest id an int64 holds
+
+static inline int oct_blocks(int64_t n) { return (int)((n + kOctThreads - 1) / kOctThreads); }
+static inline int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+
+// inclusive scan of one int per thread over the workgroup; *total = sum over the workgroup
+__device__ __forceinline__ int block_inclusive_scan(int v, int* wave_sums, int* total) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int up = __shfl_up(v, off, kWave);
+        if (lane >= off) v += up;
+    }
+    __syncthreads();   // wave_sums may still be read from the previous call
+    if (lane == kWave - 1) wave_sums[wave] = v;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kOctThreads / kWave; ++w) {
+        const int s = wave_sums[w];
+        if (w < wave) before += s;
+        all += s;
+    }
+    *total = all;
+    return v + before;
+}
+
+// ------------------------------------------------------------------------------- K12b/c
+__global__ void __launch_bounds__(kOctThreads)
+scan_tile_counts_kernel(const uint8_t* __restrict__ flags, int64_t n, int* __restrict__ tile_sums) {
+    __shared__ int wave_sums[kOctThreads / kWave];
+    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < kScanItems; ++j)
+        if (base + j < n) c += flags[base + j] != 0;
+    int total;
+    block_inclusive_scan(c, wave_sums, &total);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// one workgroup: tile_sums -> exclusive prefix in place, *total = sum
+__global__ void __launch_bounds__(kOctThreads)
+scan_tile_sums_kernel(int* __restrict__ tile_sums, int64_t tiles, int* __restrict__ total_out) {
+    __shared__ int wave_sums[kOctThreads / kWave];
+    int carry = 0;
+    for (int64_t base = 0; base < tiles; base += kOctThreads) {
+        const int64_t i = base + threadIdx.x;
+        const int v = i < tiles ? tile_sums[i] : 0;
+        int total;
+        const int incl = block_inclusive_scan(v, wave_sums, &total);
+        if (i < tiles) tile_sums[i] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *total_out = carry;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+scan_offsets_kernel(const uint8_t* __restrict__ flags, int64_t n, const int* __restrict__ tile_sums,
+                    int* __restrict__ offsets) {
+    __shared__ int wave_sums[kOctThreads / kWave];
+    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    bool f[kScanItems];
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < kScanItems; ++j) {
+        f[j] = base + j < n && flags[base + j] != 0;
+        c += f[j];
+    }
+    int total;
+    int rank = tile_sums[blockIdx.x] + block_inclusive_scan(c, wave_sums, &total) - c;
+#pragma unroll
+    for (int j = 0; j < kScanItems; ++j) {
+        if (base + j < n) offsets[base + j] = rank;
+        rank += f[j];
+    }
+}
+
+// flags (n) -> offsets (n) exclusive, *total; tile_sums holds scan_tiles(n) ints
+static int scan_flags(const uint8_t* flags, int64_t n, int* tile_sums, int* offsets, int* total,
+                      hipStream_t s) {
+    const int64_t tiles = scan_tiles(n);
+    hipLaunchKernelGGL(scan_tile_counts_kernel, dim3((unsigned)tiles), dim3(kOctThreads), 0, s,
+                       flags, n, tile_sums);
+    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(1), dim3(kOctThreads), 0, s, tile_sums, tiles,
+                       total);
+    hipLaunchKernelGGL(scan_offsets_kernel, dim3((unsigned)tiles), dim3(kOctThreads), 0, s, flags,
+                       n, tile_sums, offsets);
+    return check_launch("ffn_octree: flag scan");
+}
+
+// ------------------------------------------------------------------------------- K12a/d
+__global__ void __launch_bounds__(kOctThreads)
+surface_flags_kernel(const float* __restrict__ alpha, int64_t n, float threshold,
+                     uint8_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i < n) flags[i] = alpha[i] > threshold;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+surface_scatter_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ offsets,
+                       const float* __restrict__ starts, const float* __restrict__ directions,
+                       const float* __restrict__ depth, const float* __restrict__ color,
+                       int64_t n, int channels, float* __restrict__ out_positions,
+                       float* __restrict__ out_colors) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const int64_t o = offsets[i];   // < number of set flags <= n: inside the (n, .) outputs
+    const float d = depth[i];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        out_positions[o * 3 + a] = mul_add_rn(directions[i * 3 + a], d, starts[i * 3 + a]);
+    for (int c = 0; c < channels; ++c) out_colors[o * channels + c] = color[i * channels + c];
+}
+
+// ------------------------------------------------------------------------------- K12e
+// child index of p in the node centred at c (octree.py:274-286), and the child's centre
+__device__ __forceinline__ int descend(float x, float y, float z, float& cx, float& cy, float& cz,
+                                       float half) {
+#pragma clang fp contract(off)
+    const bool px = x >= cx, py = y >= cy, pz = z >= cz;
+    cx = px ? cx + half : cx - half;
+    cy = py ? cy + half : cy - half;
+    cz = pz ? cz + half : cz - half;
+    return (px ? 4 : 0) + (py ? 2 : 0) + (pz ? 1 : 0);
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+path_codes_kernel(const float* __restrict__ positions, int64_t n, float ox, float oy, float oz,
+                  float scale, int depth, int* __restrict__ codes) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const float x = sub_rn(positions[i * 3 + 0], ox);
+    const float y = sub_rn(positions[i * 3 + 1], oy);
+    const float z = sub_rn(positions[i * 3 + 2], oz);
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
+    uint32_t code = 0u;
+    for (int level = 1; level < depth; ++level) {
+        half *= 0.5f;
+        code = (code << 3) | (uint32_t)descend(x, y, z, cx, cy, cz, half);
+    }
+    codes[i] = (int)code;
+}
+
+// ------------------------------------------------------------------------------- K12f
+// first index in [lo, hi) whose code is >= key
+__device__ __forceinline__ int64_t lower_bound_code(const int* __restrict__ codes, int64_t lo,
+                                                    int64_t hi, uint32_t key) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((uint32_t)codes[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+assign_kernel(const int* __restrict__ codes, const int64_t* __restrict__ perm, int64_t n, int depth,
+              int64_t min_leaf, int64_t* __restrict__ leaf_sorted, int* __restrict__ count_sorted,
+              int64_t* __restrict__ leaf_of_point) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t code = (uint32_t)codes[i];
+    int64_t lo = 0, hi = n, id = 0, leaf = -1;
+    bool done = false;
+    if (depth == 1) {
+        leaf = n >= min_leaf ? 0 : -1;
+        done = true;
+    }
+    for (int level = 1; level < depth && !done; ++level) {
+        const int shift = 3 * (depth - 1 - level);
+        const uint32_t prefix = code >> shift;
+        const int64_t clo = lower_bound_code(codes, lo, hi, prefix << shift);
+        const int64_t chi = lower_bound_code(codes, clo, hi, (prefix + 1u) << shift);
+        if (chi - clo < min_leaf) {
+            // this child is not visited: its parent is a leaf iff no sibling is visited either,
+            // otherwise the point is dropped (octree.py:780-797)
+            const uint32_t first = prefix & ~7u;
+            bool any = false;
+            int64_t b = lo;
+            for (uint32_t j = 1; j <= 8u; ++j) {
+                const int64_t e = j == 8u ? hi : lower_bound_code(codes, b, hi, (first + j) << shift);
+                any = any || e - b >= min_leaf;
+                b = e;
+            }
+            if (!any) leaf = id;
+            done = true;
+        } else {
+            id = 8 * id + 1 + (prefix & 7u);
+            lo = clo;
+            hi = chi;
+        }
+    }
+    if (!done) leaf = id;   // visited at depth D-1 with >= min_leaf points
+    leaf_sorted[i] = leaf;
+    count_sorted[i] = (int)(hi - lo);
+    leaf_of_point[perm[i]] = leaf;   // perm is a permutation of [0, n)
+}
+
+// ------------------------------------------------------------------------------- K12g
+__global__ void __launch_bounds__(kOctThreads)
+leaf_heads_kernel(const int64_t* __restrict__ leaf_sorted, int64_t n, uint8_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t leaf = leaf_sorted[i];
+    flags[i] = leaf >= 0 && (i == 0 || leaf_sorted[i - 1] != leaf);
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+leaf_gather_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ offsets,
+                   const int64_t* __restrict__ leaf_sorted, const int* __restrict__ count_sorted,
+                   int64_t n, int64_t* __restrict__ leaf_ids, int64_t* __restrict__ leaf_start,
+                   int* __restrict__ leaf_count) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const int o = offsets[i];
+    leaf_ids[o] = leaf_sorted[i];
+    leaf_start[o] = i;
+    leaf_count[o] = count_sorted[i];
+}
+
+// ------------------------------------------------------------------------------- K12h
+__device__ __forceinline__ int id_depth(int64_t id) {
+    int d = 0;
+    while (id > 0) { id = (id - 1) >> 3; ++d; }
+    return d;
+}
+__device__ __forceinline__ int64_t ancestor_at(int64_t id, int from_depth, int level) {
+    for (int d = from_depth; d > level; --d) id = (id - 1) >> 3;
+    return id;
+}
+
+// leaves in code (depth-first) order: the leaves below one node are consecutive, so ancestor
+// (leaf j, level L) is new iff leaf j-1 does not have the same one.  flags (num_leaves, levels).
+__global__ void __launch_bounds__(kOctThreads)
+ancestor_flags_kernel(const int64_t* __restrict__ leaf_ids, int64_t num_leaves, int levels,
+                      uint8_t* __restrict__ flags) {
+    const int64_t t = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (t >= num_leaves * levels) return;
+    const int64_t j = t / levels;
+    const int level = (int)(t % levels);
+    const int64_t id = leaf_ids[j];
+    const int d = id_depth(id);
+    bool flag = false;
+    if (level < d) {
+        flag = true;
+        if (j > 0) {
+            const int64_t prev = leaf_ids[j - 1];
+            const int pd = id_depth(prev);
+            if (level < pd && ancestor_at(prev, pd, level) == ancestor_at(id, d, level)) flag = false;
+        }
+    }
+    flags[t] = flag;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+ancestor_gather_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ offsets,
+                       const int64_t* __restrict__ leaf_ids, int64_t num_leaves, int levels,
+                       int64_t* __restrict__ node_ids) {
+    const int64_t t = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (t >= num_leaves * levels || !flags[t]) return;
+    const int64_t id = leaf_ids[t / levels];
+    node_ids[offsets[t]] = ancestor_at(id, id_depth(id), (int)(t % levels));
+}
+
+// ------------------------------------------------------------------------------- K12i
+__global__ void __launch_bounds__(kOctThreads)
+leaf_means_kernel(const float* __restrict__ data, int channels, const int64_t* __restrict__ perm,
+                  const int64_t* __restrict__ leaf_start, const int* __restrict__ leaf_count,
+                  int64_t num_leaves, float* __restrict__ out) {
+    const int64_t leaf = (int64_t)blockIdx.x * (kOctThreads / kWave) + (threadIdx.x >> 6);
+    if (leaf >= num_leaves) return;   // whole waves leave together
+    const int lane = lane_id();
+    const int64_t start = leaf_start[leaf];
+    const int count = leaf_count[leaf];
+    for (int c = 0; c < channels; ++c) {
+        float acc = 0.0f;
+        for (int j = lane; j < count; j += kWave) acc += data[perm[start + j] * channels + c];
+#pragma unroll
+        for (int off = kWave / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+        if (lane == 0) out[leaf * channels + c] = acc / (float)count;
+    }
+}
+
+// ------------------------------------------------------------------------------- K12j
+__device__ __forceinline__ int64_t lower_bound_id(const int64_t* __restrict__ ids, int64_t n,
+                                                  int64_t key) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (ids[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+query_kernel(const float* __restrict__ positions, int64_t n, float scale,
+             const int64_t* __restrict__ node_index, int64_t num_nodes,
+             const int64_t* __restrict__ leaf_index, int64_t num_leaves, int64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const float x = positions[i * 3 + 0], y = positions[i * 3 + 1], z = positions[i * 3 + 2];
+    int64_t result = -1;
+    // _node_contains (octree.py:262-267): the faces belong to the cube
+    const bool outside = fabsf(x) > scale || fabsf(y) > scale || fabsf(z) > scale;
+    if (!outside) {
+        if (leaf_index[0] == 0) {
+            result = 0;   // the root is the only leaf
+        } else {
+            const int64_t max_id = leaf_index[num_leaves - 1];
+            float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
+            int64_t id = 0;
+            for (int level = 0; level < kOctMaxLevels && id <= max_id; ++level) {
+                half *= 0.5f;
+                id = 8 * id + 1 + descend(x, y, z, cx, cy, cz, half);
+                int64_t j = lower_bound_id(leaf_index, num_leaves, id);
+                if (j < num_leaves && leaf_index[j] == id) { result = j; break; }
+                j = lower_bound_id(node_index, num_nodes, id);
+                if (j == num_nodes || node_index[j] != id) break;
+            }
+        }
+    }
+    out[i] = result;
+}
+
+// ------------------------------------------------------------------------------- K12k
+__global__ void __launch_bounds__(kOctThreads)
+leaf_geometry_kernel(const int64_t* __restrict__ leaf_index, int64_t num_leaves, float scale,
+                     float* __restrict__ centers, int* __restrict__ depths) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= num_leaves) return;
+    int64_t id = leaf_index[i];
+    uint64_t digits = 0u;   // child indices, the leaf's own in the low bits
+    int d = 0;
+    while (id > 0 && d < kOctMaxLevels) {
+        digits |= (uint64_t)((id - 1) & 7) << (3 * d);
+        id = (id - 1) >> 3;
+        ++d;
+    }
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
+    for (int k = d - 1; k >= 0; --k) {
+        const int child = (int)((digits >> (3 * k)) & 7u);
+        half *= 0.5f;
+        cx = (child & 4) ? cx + half : cx - half;
+        cy = (child & 2) ? cy + half : cy - half;
+        cz = (child & 1) ? cz + half : cz - half;
+    }
+    centers[i * 3 + 0] = cx;
+    centers[i * 3 + 1] = cy;
+    centers[i * 3 + 2] = cz;
+    depths[i] = d;
+}
+
+}  // namespace ffn
+
+using namespace ffn;
+
+static const int64_t kOctMaxPoints = ((int64_t)1 << 31) - kScanTile;
+
+extern "C" int64_t ffn_octree_scan_tiles(int64_t n) { return n < 0 ? -1 : scan_tiles(n); }
+
+extern "C" int ffn_octree_max_depth(void) { return kOctMaxDepth; }
+
+extern "C" int ffn_octree_surface_points(const float* alpha, const float* depth, const float* starts,
+                                         const float* directions, const float* color, int64_t n,
+                                         int channels, float threshold, uint8_t* flags,
+                                         int* offsets, int* tile_sums, float* out_positions,
+                                         float* out_colors, int* count, void* stream) {
+    if (n < 1 || n > kOctMaxPoints || channels < 0)
+        return fail_arg("ffn_octree_surface_points: shape (1 <= n < 2^31, channels >= 0)");
+    if (!alpha || !depth || !starts || !directions || !flags || !offsets || !tile_sums ||
+        !out_positions || !count || (channels > 0 && (!color || !out_colors)))
+        return fail_arg("ffn_octree_surface_points: null argument");
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(surface_flags_kernel, dim3(oct_blocks(n)), dim3(kOctThreads), 0, s, alpha, n,
+                       threshold, flags);
+    if (int err = scan_flags(flags, n, tile_sums, offsets, count, s)) return err;
+    hipLaunchKernelGGL(surface_scatter_kernel, dim3(oct_blocks(n)), dim3(kOctThreads), 0, s, flags,
+                       offsets, starts, directions, depth, color, n, channels, out_positions,
+                       out_colors);
+    return check_launch("ffn_octree_surface_points");
+}
+
+extern "C" int ffn_octree_path_codes(const float* positions, int64_t n, float center_x,
+                                     float center_y, float center_z, float scale, int depth,
+                                     int* codes, void* stream) {
+    if (n < 1 || n > kOctMaxPoints || depth < 1 || depth > kOctMaxDepth)
+        return fail_arg("ffn_octree_path_codes: shape (1 <= n < 2^31, 1 <= depth <= 11)");
+    if (!positions || !codes) return fail_arg("ffn_octree_path_codes: null argument");
+    hipLaunchKernelGGL(path_codes_kernel, dim3(oct_blocks(n)), dim3(kOctThreads), 0,
+                       (hipStream_t)stream, positions, n, center_x, center_y, center_z, scale,
+                       depth, codes);
+    return check_launch("ffn_octree_path_codes");
+}
+
+extern "C" int ffn_octree_structure(const int* sorted_codes, const int64_t* perm, int64_t n,
+                                    int depth, int64_t min_leaf_size, int64_t* leaf_sorted,
+                                    int* count_sorted, int64_t* leaf_of_point, uint8_t* flags,
+                                    int* offsets, int* tile_sums, int64_t* leaf_ids,
+                                    int64_t* leaf_start, int* leaf_count, int* num_leaves,
+                                    void* stream) {
+    if (n < 1 || n > kOctMaxPoints || depth < 1 || depth > kOctMaxDepth)
+        return fail_arg("ffn_octree_structure: shape (1 <= n < 2^31, 1 <= depth <= 11)");
+    if (!sorted_codes || !perm || !leaf_sorted || !count_sorted || !leaf_of_point || !flags ||
+        !offsets || !tile_sums || !leaf_ids || !leaf_start || !leaf_count || !num_leaves)
+        return fail_arg("ffn_octree_structure: null argument");
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(oct_blocks(n)), block(kOctThreads);
+    hipLaunchKernelGGL(assign_kernel, grid, block, 0, s, sorted_codes, perm, n, depth,
+                       min_leaf_size, leaf_sorted, count_sorted, leaf_of_point);
+    hipLaunchKernelGGL(leaf_heads_kernel, grid, block, 0, s, leaf_sorted, n, flags);
+    if (int err = scan_flags(flags, n, tile_sums, offsets, num_leaves, s)) return err;
+    hipLaunchKernelGGL(leaf_gather_kernel, grid, block, 0, s, flags, offsets, leaf_sorted,
+                       count_sorted, n, leaf_ids, leaf_start, leaf_count);
+    return check_launch("ffn_octree_structure");
+}
+
+extern "C" int ffn_octree_interior_nodes(const int64_t* leaf_ids, int64_t num_leaves, int depth,
+                                         uint8_t* flags, int* offsets, int* tile_sums,
+                                         int64_t* node_ids, int* num_nodes, void* stream) {
+    const int levels = depth - 1;
+    if (num_leaves < 1 || depth < 2 || depth > kOctMaxDepth ||
+        num_leaves * levels > kOctMaxPoints)
+        return fail_arg("ffn_octree_interior_nodes: shape (num_leaves >= 1, 2 <= depth <= 11)");
+    if (!leaf_ids || !flags || !offsets || !tile_sums || !node_ids || !num_nodes)
+        return fail_arg("ffn_octree_interior_nodes: null argument");
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t m = num_leaves * levels;
+    hipLaunchKernelGGL(ancestor_flags_kernel, dim3(oct_blocks(m)), dim3(kOctThreads), 0, s,
+                       leaf_ids, num_leaves, levels, flags);
+    if (int err = scan_flags(flags, m, tile_sums, offsets, num_nodes, s)) return err;
+    hipLaunchKernelGGL(ancestor_gather_kernel, dim3(oct_blocks(m)), dim3(kOctThreads), 0, s, flags,
+                       offsets, leaf_ids, num_leaves, levels, node_ids);
+    return check_launch("ffn_octree_interior_nodes");
+}
+
+extern "C" int ffn_octree_leaf_means(const float* data, int64_t n, int channels, const int64_t* perm,
+                                     const int64_t* leaf_start, const int* leaf_count,
+                                     int64_t num_leaves, float* leaf_data, void* stream) {
+    if (n < 1 || channels < 1 || num_leaves < 1 || num_leaves > kOctMaxPoints)
+        return fail_arg("ffn_octree_leaf_means: shape");
+    if (!data || !perm || !leaf_start || !leaf_count || !leaf_data)
+        return fail_arg("ffn_octree_leaf_means: null argument");
+    const int per_block = kOctThreads / kWave;
+    hipLaunchKernelGGL(leaf_means_kernel, dim3((unsigned)((num_leaves + per_block - 1) / per_block)),
+                       dim3(kOctThreads), 0, (hipStream_t)stream, data, channels, perm, leaf_start,
+                       leaf_count, num_leaves, leaf_data);
+    return check_launch("ffn_octree_leaf_means");
+}
+
+extern "C" int ffn_octree_query(const float* positions, int64_t n, float scale,
+                                const int64_t* node_index, int64_t num_nodes,
+                                const int64_t* leaf_index, int64_t num_leaves, int64_t* result,
+                                void* stream) {
+    if (n < 1 || n > kOctMaxPoints || num_leaves < 1 || num_nodes < 0)
+        return fail_arg("ffn_octree_query: shape (n >= 1, num_leaves >= 1)");
+    if (!positions || !leaf_index || !result || (num_nodes > 0 && !node_index))
+        return fail_arg("ffn_octree_query: null argument");
+    hipLaunchKernelGGL(query_kernel, dim3(oct_blocks(n)), dim3(kOctThreads), 0, (hipStream_t)stream,
+                       positions, n, scale, node_index, num_nodes, leaf_index, num_leaves, result);
+    return check_launch("ffn_octree_query");
+}
+
+extern "C" int ffn_octree_leaf_geometry(const int64_t* leaf_index, int64_t num_leaves, float scale,
+                                        float* centers, int* depths, void* stream) {
+    if (num_leaves < 1 || num_leaves > kOctMaxPoints)
+        return fail_arg("ffn_octree_leaf_geometry: num_leaves >= 1");
+    if (!leaf_index || !centers || !depths) return fail_arg("ffn_octree_leaf_geometry: null argument");
+    hipLaunchKernelGGL(leaf_geometry_kernel, dim3(oct_blocks(num_leaves)), dim3(kOctThreads), 0,
+                       (hipStream_t)stream, leaf_index, num_leaves, scale, centers, depths);
+    return check_launch("ffn_octree_leaf_geometry");
+}

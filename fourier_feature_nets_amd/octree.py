@@ -1,0 +1,262 @@
+"""Sparse octree over a point cloud (the reference's ``OcTree``, octree.py:584-927), built and
+queried by the K12 kernels of ``csrc/octree.hip``.
+
+Node ids, the ``.npz`` keys (``node_index``, ``leaf_index``, ``scale``, ``leaf_data``) and the
+public signatures are the reference's, so files and calling code go both ways.  What differs:
+
+* ``build_from_samples`` does not shift the caller's array in place (octree.py:760 does); the
+  root cube's centre is used for the build and, like the reference, not stored: ``query`` takes
+  positions relative to that centre.
+* a tree whose only leaf is the root reports that leaf with the real ``scale`` (the reference
+  substitutes a stand-in leaf of scale 1, octree.py:864-866, and its ``query`` fails on such a
+  tree); ``query`` answers 0 inside the cube.
+* inputs the reference fails on raise ``ValueError``: no leaf at all (``depth == 1`` with fewer
+  than ``min_leaf_size`` points), an empty cloud, a depth the path codes cannot hold.
+* node centres are always the f32 chain ``c +- scale / 2^k`` of a freshly built reference tree.
+  (A tree the reference has *loaded* carries a Python-float scale and descends in f64; the two
+  can differ for a position within an f32 rounding of a splitting plane.)
+* ``intersect`` and ``build_from_mesh`` are not part of this path.
+
+The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
+``save`` / ``prune`` need no GPU.  Building, ``query``, ``leaf_centers`` and ``leaf_depths`` run on
+the GPU and raise without one.
+"""
+
+import os
+from typing import Dict, Optional, Union
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+def _as_index(ids) -> np.ndarray:
+    if isinstance(ids, (set, frozenset)):
+        ids = sorted(ids)
+    return np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+
+
+def _id_depths(ids: np.ndarray) -> np.ndarray:
+    depth = np.zeros(ids.shape, np.int32)
+    ids = ids.copy()
+    while (ids > 0).any():
+        live = ids > 0
+        depth[live] += 1
+        ids[live] = (ids[live] - 1) >> 3
+    return depth
+
+
+class OcTree:
+    """Class representing an OcTree datastructure."""
+
+    def __init__(self, scale: float, node_ids, leaf_ids, leaf_data: np.ndarray = None):
+        """``node_ids`` / ``leaf_ids``: sets (as the reference takes) or arrays of node ids; the
+        children of node i have the ids 8 i + 1 .. 8 i + 8."""
+        self._device = None
+        self._point_leaf = None
+        self._update(node_ids, leaf_ids, scale)
+        self._leaf_data = leaf_data
+
+    # ------------------------------------------------------------------ host-side state
+    def _update(self, node_ids, leaf_ids, scale: float):
+        self._scale = float(np.float32(scale))
+        self._leaf_index = _as_index(leaf_ids)
+        if len(self._leaf_index) == 0:
+            raise ValueError("OcTree: a tree needs at least one leaf")
+        self._node_index = np.setdiff1d(_as_index(node_ids), self._leaf_index)
+        self._cache = {}
+
+    @property
+    def _leaf_ids(self):
+        return set(self._leaf_index.tolist())
+
+    @property
+    def _node_ids(self):
+        return set(self._node_index.tolist())
+
+    def __len__(self):
+        """Counts all the nodes in the tree."""
+        return len(self._node_index) + len(self._leaf_index)
+
+    @property
+    def num_leaves(self) -> int:
+        """Counts the number of leaves in the tree."""
+        return len(self._leaf_index)
+
+    @property
+    def scale(self) -> float:
+        """Scale of the cube (side is 2 * scale)."""
+        return self._scale
+
+    @property
+    def depth(self) -> int:
+        """The maximum depth of the tree."""
+        return int(_id_depths(self._leaf_index[-1:])[0]) + 1
+
+    @property
+    def point_leaf_ids(self) -> Optional[torch.Tensor]:
+        """After ``build_from_samples``: per input point the id of the leaf it ended in, -1 for
+        a dropped point (device tensor).  ``None`` for a loaded tree."""
+        return self._point_leaf
+
+    def leaf_data(self) -> np.ndarray:
+        """The data stored in each leaf."""
+        return self._leaf_data
+
+    @property
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """The state needed to reconstruct the OcTree."""
+        state = {"node_index": self._node_index, "leaf_index": self._leaf_index,
+                 "scale": np.float32(self._scale)}
+        if self._leaf_data is not None:
+            state["leaf_data"] = self._leaf_data
+        return state
+
+    def save(self, path: str):
+        """Saves the OcTree to the provided path."""
+        np.savez(path, **self.state_dict)
+
+    @staticmethod
+    def load(path_or_data: Union[str, Dict[str, np.ndarray]]) -> "OcTree":
+        """Loads an OcTree from a ``.npz`` path or a state dict (ours or the reference's).
+        Returns ``None`` (with a message) when the file does not exist; no download."""
+        if isinstance(path_or_data, str):
+            path = path_or_data
+            if not os.path.exists(path):
+                path = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "data",
+                                                    path_or_data))
+                if not os.path.exists(path):
+                    print("Unable to find octree", path_or_data)
+                    return None
+            with np.load(path) as data:
+                data = {key: data[key] for key in data.files}
+        else:
+            data = path_or_data
+        leaf_data = np.asarray(data["leaf_data"]) if "leaf_data" in data else None
+        return OcTree(float(data["scale"]), data["node_index"], data["leaf_index"], leaf_data)
+
+    def load_state(self, state_dict: Dict[str, np.ndarray]):
+        """Loads the information from the state dictionary."""
+        self._update(state_dict["node_index"], state_dict["leaf_index"],
+                     float(state_dict["scale"]))
+
+    def prune(self) -> "OcTree":
+        """Prunes all leaves at the maximum depth: they merge into their parents, which become
+        leaves holding the mean of the merged leaves' data (octree.py:629-665)."""
+        depths = _id_depths(self._leaf_index)
+        max_depth = self.depth - 1
+        if max_depth == 0:
+            raise ValueError("OcTree.prune: the root is the only leaf")
+        deep = depths >= max_depth
+        new_ids = np.where(deep, (self._leaf_index - 1) >> 3, self._leaf_index)
+        leaf_ids, inverse = np.unique(new_ids, return_inverse=True)
+        node_ids = np.setdiff1d(self._node_index, leaf_ids)
+        leaf_data = None
+        if self._leaf_data is not None:
+            data = self._leaf_data
+            sums = np.zeros((len(leaf_ids),) + data.shape[1:], data.dtype)
+            np.add.at(sums, inverse, data)      # in leaf order, as the reference accumulates
+            counts = np.bincount(inverse, minlength=len(leaf_ids))
+            merged = np.isin(leaf_ids, new_ids[deep])
+            means = sums / counts[:, None].astype(data.dtype)
+            leaf_data = np.where(merged[:, None], means, sums).astype(data.dtype)
+        return OcTree(self._scale, node_ids, leaf_ids, leaf_data)
+
+    # ------------------------------------------------------------------ GPU side
+    def _dev(self):
+        return torch.device(self._device if self._device is not None else "cuda")
+
+    def _on_device(self, name: str) -> torch.Tensor:
+        dev = self._dev()
+        key = (name, str(dev))
+        if key not in self._cache:
+            self._cache[key] = torch.from_numpy(getattr(self, "_" + name)).to(dev)
+        return self._cache[key]
+
+    def _geometry(self):
+        if "geometry" not in self._cache:
+            centers, depths = ops.octree_leaf_geometry(self._on_device("leaf_index"), self._scale)
+            self._cache["geometry"] = (centers.cpu().numpy(), depths.cpu().numpy())
+        return self._cache["geometry"]
+
+    def leaf_centers(self) -> np.ndarray:
+        """The Nx3 center coordinates of all leaves."""
+        return self._geometry()[0]
+
+    def leaf_depths(self) -> np.ndarray:
+        """The N depths for all leaves."""
+        return self._geometry()[1]
+
+    def query(self, positions):
+        """Index into the sorted leaf ids of the leaf containing each position, -1 outside the
+        cube or in an empty region.  positions: (N,3) or (3,), numpy (-> numpy int64) or a
+        device tensor (-> device tensor)."""
+        assert positions.shape[-1] == 3
+        assert len(positions.shape) <= 2
+        as_numpy = not torch.is_tensor(positions)
+        if as_numpy:
+            positions = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))
+            positions = positions.to(self._dev())
+        elif self._device is None:
+            self._device = positions.device
+        positions = positions.reshape(-1, 3).to(torch.float32).contiguous()
+        result = ops.octree_query(positions, self._scale, self._on_device("node_index"),
+                                  self._on_device("leaf_index"))
+        return result.cpu().numpy() if as_numpy else result
+
+    def intersect(self, starts, directions, max_length: int):
+        raise NotImplementedError("OcTree.intersect (the ray walker of the lecture animations) "
+                                  "is not part of the HIP path")
+
+    @staticmethod
+    def build_from_mesh(mesh_path: str, voxel_depth: int, min_leaf_size: int,
+                        up_dir=(0, 1, 0)) -> "OcTree":
+        raise NotImplementedError("OcTree.build_from_mesh needs trimesh and is not part of the "
+                                  "HIP path; sample the mesh and call build_from_samples")
+
+    @staticmethod
+    def build_from_samples(positions, depth: int, min_leaf_size: int, data=None) -> "OcTree":
+        """Builds a sparse OcTree from position samples (octree.py:733-806) on the GPU.
+
+        positions (N,3) and data (N,C): numpy arrays or device tensors.  The leaves hold the
+        mean of their points' data.  The caller's positions are left as they are."""
+        depth = int(depth)
+        limit = ops.octree_max_depth()
+        if depth < 1 or depth > limit:
+            raise ValueError("OcTree.build_from_samples: depth %d is outside what the path codes "
+                             "hold (1 .. %d)" % (depth, limit))
+
+        def to_device(x, device):
+            if torch.is_tensor(x):
+                return x.to(torch.float32).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+
+        device = positions.device if torch.is_tensor(positions) else torch.device("cuda")
+        pos = to_device(positions, device).reshape(-1, 3)
+        n = pos.shape[0]
+        if n == 0:
+            raise ValueError("OcTree.build_from_samples: empty point cloud")
+        # the root cube in the reference's f32 arithmetic (octree.py:756-759)
+        min_pos, max_pos = pos.amin(0), pos.amax(0)
+        cube = torch.cat([0.5 * (min_pos + max_pos), ((max_pos - min_pos).max() * 0.5)[None]])
+        cx, cy, cz, scale = [float(v) for v in cube.cpu()]
+
+        codes = ops.octree_path_codes(pos, (cx, cy, cz), scale, depth)
+        codes, perm = torch.sort(codes, stable=True)     # key sort: plumbing
+        point_leaf, leaf_ids, leaf_start, leaf_count = ops.octree_structure(
+            codes, perm, depth, int(min_leaf_size))
+        if leaf_ids.shape[0] == 0:
+            raise ValueError("OcTree.build_from_samples: no leaf (%d points, min_leaf_size %d, "
+                             "depth %d)" % (n, min_leaf_size, depth))
+        node_ids = ops.octree_interior_nodes(leaf_ids, depth)
+        leaf_ids, order = torch.sort(leaf_ids)            # code order -> id order
+        leaf_data = None
+        if data is not None:
+            values = to_device(data, device).reshape(n, -1)
+            leaf_data = ops.octree_leaf_means(values, perm, leaf_start[order].contiguous(),
+                                              leaf_count[order].contiguous()).cpu().numpy()
+        tree = OcTree(scale, node_ids.cpu().numpy(), leaf_ids.cpu().numpy(), leaf_data)
+        tree._device = device
+        tree._point_leaf = point_leaf
+        return tree

@@ -434,3 +434,134 @@ def voxels_backward(positions: torch.Tensor, d_logits: torch.Tensor, side: int, 
           c_i64(n), c_i(side), c_f(scale), _dev(workspace), c_i64(workspace.numel() * 4),
           _dev(d_volume), _dev(d_bias))
     return d_volume, d_bias
+
+
+# --------------------------------------------------------------------------------- octree
+def octree_max_depth() -> int:
+    """The deepest ``voxel_depth`` the K12 path codes hold."""
+    fn = _lib.load().ffn_octree_max_depth
+    fn.restype = ctypes.c_int
+    return int(fn())
+
+
+def _scan_scratch(elements: int, device):
+    """flags, offsets, tile_sums for a K12 flag scan over ``elements`` flags."""
+    fn = _lib.load().ffn_octree_scan_tiles
+    fn.restype = ctypes.c_int64
+    tiles = int(fn(c_i64(elements)))
+    return (torch.empty((elements,), dtype=torch.uint8, device=device),
+            torch.empty((elements,), dtype=torch.int32, device=device),
+            torch.empty((max(tiles, 1),), dtype=torch.int32, device=device))
+
+
+def octree_surface_points(alpha: torch.Tensor, depth: torch.Tensor, starts: torch.Tensor,
+                          directions: torch.Tensor, threshold: float,
+                          color: Optional[torch.Tensor] = None):
+    """K12a-d.  alpha (N), depth (N), starts (N,3), directions (N,3), color (N,C) or None ->
+    positions (N,3), colors (N,C) or None, count (int32 scalar on the device): the first
+    ``count`` rows hold ``starts + directions * depth`` / ``color`` of the rays with
+    ``alpha > threshold``, in ray order."""
+    n = alpha.shape[0]
+    dev = alpha.device
+    channels = 0 if color is None else color.shape[1]
+    out_pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out_col = None if color is None else torch.empty((n, channels), dtype=torch.float32, device=dev)
+    count = torch.zeros((), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out_pos, out_col, count
+    if depth.shape[0] != n or starts.shape != (n, 3) or directions.shape != (n, 3):
+        raise ValueError("octree_surface_points: alpha, depth, starts, directions disagree on N")
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_surface_points", _dev(alpha, name="alpha"), _dev(depth, name="depth"),
+          _dev(starts, name="starts"), _dev(directions, name="directions"),
+          _dev(color, name="color"), c_i64(n), c_i(channels), c_f(threshold),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
+          _dev(out_pos), _dev(out_col), _dev(count, torch.int32))
+    return out_pos, out_col, count
+
+
+def octree_path_codes(positions: torch.Tensor, center, scale: float, depth: int) -> torch.Tensor:
+    """K12e.  positions (N,3), the cube's centre (3 floats) and half side -> int32 codes (N)."""
+    n = positions.shape[0]
+    codes = torch.empty((n,), dtype=torch.int32, device=positions.device)
+    _call("ffn_octree_path_codes", _dev(positions, name="positions"), c_i64(n), c_f(center[0]),
+          c_f(center[1]), c_f(center[2]), c_f(scale), c_i(depth), _dev(codes, torch.int32))
+    return codes
+
+
+def octree_structure(sorted_codes: torch.Tensor, perm: torch.Tensor, depth: int,
+                     min_leaf_size: int):
+    """K12f-g on stably sorted codes.  -> leaf_of_point (N) int64 (leaf id or -1, in the caller's
+    point order), and per leaf in code order: leaf_ids (L) int64, leaf_start (L) int64,
+    leaf_count (L) int32.  Reads the leaf count back once."""
+    n = sorted_codes.shape[0]
+    dev = sorted_codes.device
+    leaf_sorted = torch.empty((n,), dtype=torch.int64, device=dev)
+    count_sorted = torch.empty((n,), dtype=torch.int32, device=dev)
+    leaf_of_point = torch.empty((n,), dtype=torch.int64, device=dev)
+    leaf_ids = torch.empty((n,), dtype=torch.int64, device=dev)
+    leaf_start = torch.empty((n,), dtype=torch.int64, device=dev)
+    leaf_count = torch.empty((n,), dtype=torch.int32, device=dev)
+    num = torch.zeros((), dtype=torch.int32, device=dev)
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_structure", _dev(sorted_codes, torch.int32, "sorted_codes"),
+          _dev(perm, torch.int64, "perm"), c_i64(n), c_i(depth), c_i64(min_leaf_size),
+          _dev(leaf_sorted, torch.int64), _dev(count_sorted, torch.int32),
+          _dev(leaf_of_point, torch.int64), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          _dev(tiles, torch.int32), _dev(leaf_ids, torch.int64), _dev(leaf_start, torch.int64),
+          _dev(leaf_count, torch.int32), _dev(num, torch.int32))
+    k = int(num.item())
+    return leaf_of_point, leaf_ids[:k].clone(), leaf_start[:k].clone(), leaf_count[:k].clone()
+
+
+def octree_interior_nodes(leaf_ids: torch.Tensor, depth: int) -> torch.Tensor:
+    """K12h.  leaf ids in code order -> the ids of the interior nodes (int64, unsorted)."""
+    k = leaf_ids.shape[0]
+    dev = leaf_ids.device
+    if depth < 2 or k == 0:
+        return torch.empty((0,), dtype=torch.int64, device=dev)
+    m = k * (depth - 1)
+    flags, offsets, tiles = _scan_scratch(m, dev)
+    nodes = torch.empty((m,), dtype=torch.int64, device=dev)
+    num = torch.zeros((), dtype=torch.int32, device=dev)
+    _call("ffn_octree_interior_nodes", _dev(leaf_ids, torch.int64, "leaf_ids"), c_i64(k),
+          c_i(depth), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          _dev(tiles, torch.int32), _dev(nodes, torch.int64), _dev(num, torch.int32))
+    return nodes[:int(num.item())].clone()
+
+
+def octree_leaf_means(data: torch.Tensor, perm: torch.Tensor, leaf_start: torch.Tensor,
+                      leaf_count: torch.Tensor) -> torch.Tensor:
+    """K12i.  data (N,C), perm (N) int64, per leaf start / count into perm -> (L,C) means."""
+    k = leaf_start.shape[0]
+    n, channels = data.shape
+    out = torch.empty((k, channels), dtype=torch.float32, device=data.device)
+    if k > 0:
+        _call("ffn_octree_leaf_means", _dev(data, name="data"), c_i64(n), c_i(channels),
+              _dev(perm, torch.int64, "perm"), _dev(leaf_start, torch.int64, "leaf_start"),
+              _dev(leaf_count, torch.int32, "leaf_count"), c_i64(k), _dev(out))
+    return out
+
+
+def octree_query(positions: torch.Tensor, scale: float, node_index: torch.Tensor,
+                 leaf_index: torch.Tensor) -> torch.Tensor:
+    """K12j.  positions (N,3), sorted int64 id arrays -> (N) int64 index into leaf_index or -1."""
+    n = positions.shape[0]
+    out = torch.empty((n,), dtype=torch.int64, device=positions.device)
+    if n > 0:
+        _call("ffn_octree_query", _dev(positions, name="positions"), c_i64(n), c_f(scale),
+              _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+              c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),
+              c_i64(leaf_index.numel()), _dev(out, torch.int64))
+    return out
+
+
+def octree_leaf_geometry(leaf_index: torch.Tensor, scale: float):
+    """K12k.  sorted leaf ids -> centres (L,3) float32 and depths (L) int32."""
+    k = leaf_index.shape[0]
+    centers = torch.empty((k, 3), dtype=torch.float32, device=leaf_index.device)
+    depths = torch.empty((k,), dtype=torch.int32, device=leaf_index.device)
+    if k > 0:
+        _call("ffn_octree_leaf_geometry", _dev(leaf_index, torch.int64, "leaf_index"), c_i64(k),
+              c_f(scale), _dev(centers), _dev(depths, torch.int32))
+    return centers, depths

@@ -724,6 +724,74 @@ int ffn_regression_mse_eval(const float* logits, const float* target, int64_t n,
 int ffn_regression_mse_loss(const float* partials, int num_blocks, float count, float* sse_out,
                             float* loss_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K12  sparse octree from a point cloud (csrc/octree.hip).  Node ids as the reference's: root 0,
+ * children of i are 8 i + 1 .. 8 i + 8, child index 4 [x >= cx] + 2 [y >= cy] + [z >= cz]; node
+ * centres are reached by f32 adds of +-scale / 2^k from the root, as the reference's Node
+ * arithmetic does.  Integer decisions only, no float atomics, every result is the same bits on
+ * every run.  Flag scans need three scratch arrays: flags (u8, one per element), offsets (i32,
+ * one per element) and tile_sums (i32, ffn_octree_scan_tiles(elements)).  Element counts are
+ * below 2^31; bad shapes / null pointers are refused before any launch. */
+int64_t ffn_octree_scan_tiles(int64_t n);
+/* the deepest voxel_depth the int32 path codes hold (3 bits per level below the root) */
+int ffn_octree_max_depth(void);
+
+/* Surface points of one render batch (voxelize_model.py:71-77): ray i is kept iff
+ * alpha[i] > threshold; out_positions[k] = starts[i] + directions[i] * depth[i] (product and sum
+ * rounded separately, as numpy), out_colors[k] = color[i] (channels floats per ray; 0 = none),
+ * k = the number of kept rays before i (stable).  Outputs hold n rows; *count (device) = kept. */
+int ffn_octree_surface_points(const float* alpha, const float* depth, const float* starts,
+                              const float* directions, const float* color, int64_t n,
+                              int channels, float threshold, uint8_t* flags, int* offsets,
+                              int* tile_sums, float* out_positions, float* out_colors, int* count,
+                              void* stream);
+
+/* Path code of every point (octree.py:274-286 applied from the root down, replacing
+ * _batch_assign at octree.py:502-508 level by level): p - center rounded to f32
+ * (octree.py:760), then depth - 1 child indices, 3 bits each, the root's child in the highest. */
+int ffn_octree_path_codes(const float* positions, int64_t n, float center_x, float center_y,
+                          float center_z, float scale, int depth, int* codes, void* stream);
+
+/* Tree structure by counting on the SORTED codes (octree.py:762-803): perm[i] = index of the
+ * point at sorted position i (a stable sort).  A node is visited iff it is the root or its
+ * parent is visited and it holds >= min_leaf_size points; a visited node at depth - 1 is a leaf
+ * (the root too when depth == 1 and n >= min_leaf_size); a visited node above with no visited
+ * child is a leaf holding all its points.  Out, per sorted position: leaf_sorted (leaf id or
+ * -1), count_sorted (points of the node the walk stopped in); per point: leaf_of_point.  Out,
+ * per leaf in code (depth-first) order, *num_leaves (device) of them in arrays of n entries:
+ * leaf_ids, leaf_start (first sorted position), leaf_count. */
+int ffn_octree_structure(const int* sorted_codes, const int64_t* perm, int64_t n, int depth,
+                         int64_t min_leaf_size, int64_t* leaf_sorted, int* count_sorted,
+                         int64_t* leaf_of_point, uint8_t* flags, int* offsets, int* tile_sums,
+                         int64_t* leaf_ids, int64_t* leaf_start, int* leaf_count, int* num_leaves,
+                         void* stream);
+
+/* Interior nodes = the distinct proper ancestors of the leaves (the node_ids set of
+ * octree.py:778 minus the leaves, octree.py:887).  leaf_ids in code order as K12's structure
+ * step leaves them; scratch arrays sized for num_leaves * (depth - 1) elements; node_ids holds as
+ * many; unsorted, *num_nodes (device) of them.  depth >= 2. */
+int ffn_octree_interior_nodes(const int64_t* leaf_ids, int64_t num_leaves, int depth,
+                              uint8_t* flags, int* offsets, int* tile_sums, int64_t* node_ids,
+                              int* num_nodes, void* stream);
+
+/* leaf_data[k] = mean of data[perm[leaf_start[k] + j]], j < leaf_count[k] (data[index].mean(0),
+ * octree.py:775,802): one wave per leaf, a fixed summation order. */
+int ffn_octree_leaf_means(const float* data, int64_t n, int channels, const int64_t* perm,
+                          const int64_t* leaf_start, const int* leaf_count, int64_t num_leaves,
+                          float* leaf_data, void* stream);
+
+/* OcTree.query (octree.py:513-541): index into the sorted leaf_index of the leaf containing each
+ * position, -1 outside the root cube (faces inclusive) or in an empty region.  A tree whose only
+ * leaf is the root answers 0 inside the cube. */
+int ffn_octree_query(const float* positions, int64_t n, float scale, const int64_t* node_index,
+                     int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+                     int64_t* result, void* stream);
+
+/* Centre (num_leaves,3) and depth of every leaf from its id alone (replaces the breadth-first
+ * walk of octree.py:564-582 behind leaf_centers / leaf_depths, octree.py:605-613). */
+int ffn_octree_leaf_geometry(const int64_t* leaf_index, int64_t num_leaves, float scale,
+                             float* centers, int* depths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,23 @@ SIGNAL_REGRESSION = [
     ("--no-plot", dict(action="store_true", help="no frames")),
     ("--device", dict(default="cuda")),
 ]
+# voxelize_model.py:11-33 of the reference (positionals model_path data_path output_path;
+# --num-cameras is a float there too)
+VOXELIZE = [
+    ("model_path", dict(help="Path to the saved model")),
+    ("data_path", dict(help="Path to the data used to train the model")),
+    ("output_path", dict(help="Path to the output octree")),
+    ("--scenepic-path", dict()),
+    ("--voxel-depth", dict(type=int, default=8, help="Depth of the octree to use")),
+    ("--num-cameras", dict(type=float, default=100,
+                           help="Number of cameras to use for sampling the volume")),
+    ("--batch-size", dict(type=int, default=4096, help="Number of rays to process in a batch")),
+    ("--min-leaf-size", dict(type=int, default=4, help="Minimum number of samples in a leaf")),
+    ("--alpha-threshold", dict(type=float, default=0.3,
+                               help="Threshold to use when filtering samples")),
+    ("--opacity-model-path", dict(help="Path to an optional opacity model")),
+    ("--device", dict(default="cuda", help="Pytorch compute device")),
+]
 ORBIT = [
     ("model_path", dict(help="trained checkpoint")),
     ("resolution", dict(type=int, help="frame size in pixels")),
