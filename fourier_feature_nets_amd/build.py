@@ -42,6 +42,8 @@ SOURCES = {
     "regression.hip": [],
     # numpy rounds the product and the sum of start + direction * depth separately
     "octree.hip": ["-ffp-contract=off"],
+    # plane crossings (plane - o) / d on the f32 chain of node centres, every operation rounded
+    "octree_walk.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

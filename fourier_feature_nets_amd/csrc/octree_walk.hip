@@ -1,0 +1,265 @@
+// K13  Ray walk through the sparse octree of K12: the regions a ray crosses, in order.
+//
+// Replaces the host-side (Python / Numba, one ray at a time) walker of the reference:
+// octree.py:418-482 (_trace_ray_path), octree.py:485-501 (_batch_intersect) behind
+// OcTree.intersect (octree.py:707-731).
+//
+// A REGION is a leaf, or a maximal empty cell: a child slot of an interior node that is in
+// neither index.  The regions tile the root cube, so a ray that hits the cube crosses a sequence
+// of them; stop k of a ray is the t at which it enters its k-th region and that region's index
+// into leaf_index (-1 for an empty cell).
+//
+// Where the ray is, and where it goes next, is decided on INTEGERS: the ray owns a cell
+// (ix, iy, iz) of the finest grid, 2^(depth-1) cells per axis.  The region of a cell is found by
+// descending from the root along the cell's bits (binary searches in the two sorted id arrays,
+// as K12j).  Leaving a region, the cell steps across the exit face on the exit axis -- to the
+// first cell beyond the region, an integer operation that cannot land inside the region again --
+// and on the other two axes takes the cell of the exit point inside the region's own range,
+// never moving against the ray's direction.  There is no epsilon nudge and no re-test of a
+// moved point (the reference advances by t += 1e-5 until a containment test fails; its own
+// comment asks for integers).
+//
+// Floating point only produces the t-values: the entry of a region is the crossing of its
+// bounding plane, (plane - o) / d in f32, with plane = c +- scale / 2^k from the f32 chain of
+// node centres that K12e / K12j / K12k replay (this file is compiled with -ffp-contract=off).
+//
+// One lane per ray, no stack and no per-lane array: the state is the node id, its level, its
+// centre and the three cell coordinates.  After a step the descent starts again at the root, but
+// the levels above the deepest common ancestor of the old and the new cell are known to be
+// interior and are replayed in registers without a lookup.  Rays of one wave diverge in trip
+// count (the wave runs as long as its longest ray), so a workgroup is ONE wave: a long ray holds
+// back 63 neighbours, not 255, and a finished wave frees its slot at once.  The kernel is bound
+// by the latency of dependent L2 reads (the binary searches); neighbouring rays search the same
+// ids, so the top of both arrays stays in cache.
+#include "common.h"
+
+namespace ffn {
+
+constexpr int kWalkThreads = 64;
+constexpr int kWalkMaxDepth = 11;     // as K12's path codes: at most 10 levels below the root
+static const int64_t kWalkMaxRays = (int64_t)1 << 31;
+
+// is key in the sorted ids?  *at = its position
+__device__ __forceinline__ bool find_id(const int64_t* __restrict__ ids, int64_t n, int64_t key,
+                                        int64_t* at) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (ids[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    *at = lo;
+    return lo < n && ids[lo] == key;
+}
+
+// `count` levels of the one-axis centre chain below centre c (half = the half side at c): the
+// bits of p's cell, highest first.  The octree.py:274-286 comparison, one axis of K12e's descend.
+__device__ __forceinline__ int chain_bits(float p, float c, float half, int count) {
+    int bits = 0;
+    for (int k = 0; k < count; ++k) {
+        half *= 0.5f;
+        const bool up = p >= c;
+        c = up ? c + half : c - half;
+        bits = (bits << 1) | (up ? 1 : 0);
+    }
+    return bits;
+}
+
+// one axis of the root cube [-scale, scale] against o + t d.  A zero component constrains
+// nothing when o lies in the slab and misses otherwise.
+__device__ __forceinline__ void root_slab(float o, float d, float scale, int axis, float& t_in,
+                                          float& t_out, int& axis_in, bool& miss) {
+    if (d == 0.0f) {
+        miss = miss || !(fabsf(o) <= scale);
+        return;
+    }
+    const float near = ((d > 0.0f ? -scale : scale) - o) / d;
+    const float far = ((d > 0.0f ? scale : -scale) - o) / d;
+    miss = miss || near != near || far != far;
+    if (near > t_in) { t_in = near; axis_in = axis; }
+    if (far < t_out) t_out = far;
+}
+
+// t at which o + t d leaves the slab c +- half on one axis (+inf: never, on this axis)
+__device__ __forceinline__ float exit_t(float o, float d, float c, float half) {
+    if (d == 0.0f || d != d) return __builtin_inff();
+    return ((d > 0.0f ? c + half : c - half) - o) / d;
+}
+
+// The cell coordinate on one axis after leaving a region that spans 2^span cells from
+// (i >> span) << span.  On the exit axis: the first cell beyond the region.  Elsewhere: the cell
+// of the exit point p inside the region's range, not behind the cell the ray already owns.
+__device__ __forceinline__ int step_axis(int i, bool is_exit_axis, float d, float p, float c,
+                                         float half, int span) {
+    const int base = (i >> span) << span;
+    if (is_exit_axis) return d > 0.0f ? base + (1 << span) : base - 1;
+    if (d == 0.0f || d != d) return i;
+    const int at = base | chain_bits(p, c, half, span);
+    return d > 0.0f ? max(i, at) : min(i, at);
+}
+
+// kSpans == false: Path rows (t_stops, leaves), max_length entries per ray.
+// kSpans == true:  per ray t_in / t_out / hit over the leaves that end after t_min.
+template <bool kSpans>
+__global__ void __launch_bounds__(kWalkThreads)
+octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
+                   int64_t n, float scale, int depth, const int64_t* __restrict__ node_index,
+                   int64_t num_nodes, const int64_t* __restrict__ leaf_index, int64_t num_leaves,
+                   int max_length, float* __restrict__ t_stops, int64_t* __restrict__ leaves,
+                   float t_min, float pad, float* __restrict__ span_in,
+                   float* __restrict__ span_out, uint8_t* __restrict__ span_hit) {
+    const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (r >= n) return;
+    const float ox = starts[r * 3 + 0], oy = starts[r * 3 + 1], oz = starts[r * 3 + 2];
+    const float dx = directions[r * 3 + 0], dy = directions[r * 3 + 1], dz = directions[r * 3 + 2];
+    const int levels = depth - 1;
+    const int cells = 1 << levels;
+
+    float root_in = -__builtin_inff(), root_out = __builtin_inff();
+    int axis_in = 0;
+    bool miss = false;
+    root_slab(ox, dx, scale, 0, root_in, root_out, axis_in, miss);
+    root_slab(oy, dy, scale, 1, root_in, root_out, axis_in, miss);
+    root_slab(oz, dz, scale, 2, root_in, root_out, axis_in, miss);
+    // a chord of positive, finite length (three zero components: a point, not a ray)
+    const bool hit = !miss && root_in < root_out && fabsf(root_in) < __builtin_inff() &&
+                     fabsf(root_out) < __builtin_inff();
+
+    // the cell the ray enters the cube in: on the entry axis the face's own layer
+    int ix = axis_in == 0 ? (dx > 0.0f ? 0 : cells - 1) : chain_bits(ox + root_in * dx, 0.0f, scale, levels);
+    int iy = axis_in == 1 ? (dy > 0.0f ? 0 : cells - 1) : chain_bits(oy + root_in * dy, 0.0f, scale, levels);
+    int iz = axis_in == 2 ? (dz > 0.0f ? 0 : cells - 1) : chain_bits(oz + root_in * dz, 0.0f, scale, levels);
+
+    // A walk writes at most max_length - 1 stops (the reference's stop == max_length - 1 rule,
+    // octree.py:460); a span walk has no such cap, but every step moves one cell coordinate
+    // forward for good, so a chord has at most 3 * cells + 1 regions.
+    const int max_stops = kSpans ? 3 * cells + 1 : max_length - 1;
+    // Every region costs at most `depth` trips: depth - 1 descents and the region itself.  The
+    // loop condition holds the trip count to max_stops * depth for ANY input (NaNs, a tree
+    // whose two indices contradict each other): nothing below can extend it.
+    const int max_trips = max_stops * depth;
+
+    int64_t id = 0;
+    int level = 0, known = 0, stop = 0;
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale, t = root_in;
+    bool inside = hit, any_leaf = false;
+    float first_in = 0.0f, last_out = 0.0f;
+    for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
+        int64_t at;
+        const bool interior = level < known ||
+                              (level < levels && find_id(node_index, num_nodes, id, &at));
+        if (interior) {
+            const int shift = levels - 1 - level;
+            const int bx = (ix >> shift) & 1, by = (iy >> shift) & 1, bz = (iz >> shift) & 1;
+            half *= 0.5f;
+            cx = bx ? cx + half : cx - half;
+            cy = by ? cy + half : cy - half;
+            cz = bz ? cz + half : cz - half;
+            id = 8 * id + 1 + (4 * bx + 2 * by + bz);
+            ++level;
+            continue;
+        }
+        // a region: a leaf or an empty cell
+        const int64_t leaf = find_id(leaf_index, num_leaves, id, &at) ? at : -1;
+        const float tx = exit_t(ox, dx, cx, half), ty = exit_t(oy, dy, cy, half),
+                    tz = exit_t(oz, dz, cz, half);
+        int axis_out = 0;
+        float t_exit = tx;
+        if (ty < t_exit) { t_exit = ty; axis_out = 1; }
+        if (tz < t_exit) { t_exit = tz; axis_out = 2; }
+        if (kSpans) {
+            if (leaf >= 0 && t_exit > t_min) {
+                if (!any_leaf) first_in = t > t_min ? t : t_min;
+                any_leaf = true;
+                last_out = t_exit;
+            }
+        } else {
+            t_stops[r * max_length + stop] = t;      // stop < max_length - 1
+            leaves[r * max_length + stop] = leaf;
+        }
+        ++stop;
+        // step to the next cell
+        const int span = levels - level;
+        const int nx = step_axis(ix, axis_out == 0, dx, ox + t_exit * dx, cx, half, span);
+        const int ny = step_axis(iy, axis_out == 1, dy, oy + t_exit * dy, cy, half, span);
+        const int nz = step_axis(iz, axis_out == 2, dz, oz + t_exit * dz, cz, half, span);
+        inside = ((nx | ny | nz) >= 0) && nx < cells && ny < cells && nz < cells;
+        // the levels above the deepest common ancestor of the two cells were interior on the
+        // way down to this region (the new cell lies outside it)
+        const int differ = (ix ^ nx) | (iy ^ ny) | (iz ^ nz);
+        known = inside ? min(level, levels - (32 - __clz(differ)) + 1) : 0;
+        ix = nx; iy = ny; iz = nz;
+        t = t_exit;
+        id = 0; level = 0;
+        cx = 0.0f; cy = 0.0f; cz = 0.0f; half = scale;
+    }
+    if (kSpans) {
+        // pad finest-cell sides along the ray, in t
+        const float side = 2.0f * scale / (float)cells;
+        const float widen = pad * side / sqrtf(dx * dx + dy * dy + dz * dz);
+        span_hit[r] = any_leaf ? 1 : 0;
+        span_in[r] = any_leaf ? first_in - widen : 0.0f;
+        span_out[r] = any_leaf ? last_out + widen : 0.0f;
+    } else {
+        // unwritten entries: the cube's exit t and -1 (octree.py:429-430); a miss has no stop
+        const float fill = hit ? root_out : 0.0f;
+        for (int k = stop; k < max_length; ++k) {
+            t_stops[r * max_length + k] = fill;
+            leaves[r * max_length + k] = -1;
+        }
+    }
+}
+
+static int check_walk_args(const char* who, const float* starts, const float* directions,
+                           int64_t n, int depth, const int64_t* node_index, int64_t num_nodes,
+                           const int64_t* leaf_index, int64_t num_leaves) {
+    char text[160];
+    if (n < 1 || n >= kWalkMaxRays || depth < 1 || depth > kWalkMaxDepth || num_leaves < 1 ||
+        num_nodes < 0) {
+        snprintf(text, sizeof text, "%s: shape (1 <= n < 2^31, 1 <= depth <= 11, num_leaves >= 1)", who);
+        return fail_arg(text);
+    }
+    if (!starts || !directions || !leaf_index || (num_nodes > 0 && !node_index)) {
+        snprintf(text, sizeof text, "%s: null argument", who);
+        return fail_arg(text);
+    }
+    return 0;
+}
+
+}  // namespace ffn
+
+using namespace ffn;
+
+extern "C" int ffn_octree_walk(const float* starts, const float* directions, int64_t n, float scale,
+                               int depth, const int64_t* node_index, int64_t num_nodes,
+                               const int64_t* leaf_index, int64_t num_leaves, int max_length,
+                               float* t_stops, int64_t* leaves, void* stream) {
+    if (int err = check_walk_args("ffn_octree_walk", starts, directions, n, depth, node_index,
+                                  num_nodes, leaf_index, num_leaves))
+        return err;
+    if (max_length < 2 || max_length > (1 << 16))
+        return fail_arg("ffn_octree_walk: 2 <= max_length <= 65536");
+    if (!t_stops || !leaves) return fail_arg("ffn_octree_walk: null argument");
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<false>, dim3(blocks), dim3(kWalkThreads), 0,
+                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                       num_nodes, leaf_index, num_leaves, max_length, t_stops, leaves, 0.0f, 0.0f,
+                       (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr);
+    return check_launch("ffn_octree_walk");
+}
+
+extern "C" int ffn_octree_spans(const float* starts, const float* directions, int64_t n, float scale,
+                                int depth, const int64_t* node_index, int64_t num_nodes,
+                                const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                                float pad, float* t_in, float* t_out, uint8_t* hit, void* stream) {
+    if (int err = check_walk_args("ffn_octree_spans", starts, directions, n, depth, node_index,
+                                  num_nodes, leaf_index, num_leaves))
+        return err;
+    if (!t_in || !t_out || !hit) return fail_arg("ffn_octree_spans: null argument");
+    if (!(pad >= 0.0f)) return fail_arg("ffn_octree_spans: pad >= 0");
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<true>, dim3(blocks), dim3(kWalkThreads), 0,
+                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
+                       t_min, pad, t_in, t_out, hit);
+    return check_launch("ffn_octree_spans");
+}

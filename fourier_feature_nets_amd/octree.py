@@ -1,5 +1,5 @@
 """Sparse octree over a point cloud (the reference's ``OcTree``, octree.py:584-927), built and
-queried by the K12 kernels of ``csrc/octree.hip``.
+queried by the K12 kernels of ``csrc/octree.hip`` and walked by K13 (``csrc/octree_walk.hip``).
 
 Node ids, the ``.npz`` keys (``node_index``, ``leaf_index``, ``scale``, ``leaf_data``) and the
 public signatures are the reference's, so files and calling code go both ways.  What differs:
@@ -15,15 +15,30 @@ public signatures are the reference's, so files and calling code go both ways.  
 * node centres are always the f32 chain ``c +- scale / 2^k`` of a freshly built reference tree.
   (A tree the reference has *loaded* carries a Python-float scale and descends in f64; the two
   can differ for a position within an f32 rounding of a splitting plane.)
-* ``intersect`` and ``build_from_mesh`` are not part of this path.
+* ``intersect`` and ``build_from_mesh`` are not part of this path.  ``walk`` is the GPU
+  counterpart of ``intersect`` (same arguments, same ``Path`` layout); against the reference's
+  ``_trace_ray_path`` (octree.py:418-482) it differs in three ways:
+
+  - no nudge: the reference advances by ``t += 1e-5`` steps and records the nudged ``t``, so
+    its stops lie one or more such steps above the plane crossings that ``walk`` records, and
+    it can step over a region whose chord is a few nudges long.  ``walk`` moves from region to
+    region on integer cell coordinates and records the crossing itself.
+  - zero direction components: the reference replaces them by 1e-8 (octree.py:728).  Here such a
+    component constrains nothing when the start lies inside that slab of the root cube, and
+    the ray misses otherwise.
+  - misses: every leaf is -1 and the ``t_stops`` row is not meaningful (the reference fills it
+    with the far crossing of a cube the ray never enters).  NaN rays and an all-zero direction
+    are misses.
+
+* ``spans`` and ``center`` have no counterpart in the reference.
 
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
-``save`` / ``prune`` need no GPU.  Building, ``query``, ``leaf_centers`` and ``leaf_depths`` run on
-the GPU and raise without one.
+``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``leaf_centers`` and
+``leaf_depths`` run on the GPU and raise without one.
 """
 
 import os
-from typing import Dict, Optional, Union
+from typing import Dict, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -47,6 +62,9 @@ def _id_depths(ids: np.ndarray) -> np.ndarray:
     return depth
 
 
+Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
+
+
 class OcTree:
     """Class representing an OcTree datastructure."""
 
@@ -55,6 +73,7 @@ class OcTree:
         children of node i have the ids 8 i + 1 .. 8 i + 8."""
         self._device = None
         self._point_leaf = None
+        self._center = None
         self._update(node_ids, leaf_ids, scale)
         self._leaf_data = leaf_data
 
@@ -99,6 +118,13 @@ class OcTree:
         """After ``build_from_samples``: per input point the id of the leaf it ended in, -1 for
         a dropped point (device tensor).  ``None`` for a loaded tree."""
         return self._point_leaf
+
+    @property
+    def center(self) -> Optional[Tuple[float, float, float]]:
+        """After ``build_from_samples``: the root cube's centre in the frame of the build's
+        positions (``query`` / ``walk`` take positions relative to it).  ``None`` for a loaded
+        tree: like the reference, the file does not hold it."""
+        return self._center
 
     def leaf_data(self) -> np.ndarray:
         """The data stored in each leaf."""
@@ -205,6 +231,68 @@ class OcTree:
                                   self._on_device("leaf_index"))
         return result.cpu().numpy() if as_numpy else result
 
+    def _rays(self, starts, directions):
+        """The shape rules of the reference's ``intersect`` (octree.py:718-726); -> float32 (N,3)
+        device tensors and whether the caller passed numpy."""
+        assert starts.shape[-1] == 3
+        assert directions.shape[-1] == 3
+        assert len(starts.shape) <= 2
+        assert len(directions.shape) <= 2
+        assert len(starts.shape) == len(directions.shape)
+        as_numpy = not torch.is_tensor(starts)
+        if torch.is_tensor(directions) == as_numpy:
+            raise TypeError("OcTree: starts and directions must both be numpy arrays or both be "
+                            "tensors")
+        if self.depth > ops.octree_max_depth():
+            raise ValueError("OcTree: a tree of depth %d is deeper than the ray walk's cell "
+                             "coordinates hold (%d)" % (self.depth, ops.octree_max_depth()))
+        if as_numpy:
+            dev = self._dev()
+            starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.float32)).to(dev)
+            directions = torch.from_numpy(np.ascontiguousarray(directions,
+                                                               dtype=np.float32)).to(dev)
+        else:
+            if self._device is None:
+                self._device = starts.device
+            directions = directions.to(starts.device)
+        starts = starts.reshape(-1, 3).to(torch.float32).contiguous()
+        directions = directions.reshape(-1, 3).to(torch.float32).contiguous()
+        assert starts.shape == directions.shape
+        return starts, directions, as_numpy
+
+    def walk(self, starts, directions, max_length: int) -> Path:
+        """The regions every ray crosses, in order: the GPU counterpart of the reference's
+        ``intersect`` (octree.py:707-731), in its ``Path`` layout.
+
+        starts, directions: (N,3) or (3,), relative to the root cube's centre; numpy (-> numpy)
+        or device tensors (-> device tensors).  ``t_stops`` (N,max_length) float32: the t at
+        which the ray enters its k-th region (a leaf or a maximal empty cell) along the whole
+        chord through the cube; ``leaves`` (N,max_length) int64: the region's index into the
+        sorted leaf ids, -1 for empty space.  At most ``max_length - 1`` stops are written; the
+        rest hold the cube's exit t and -1.  A ray that misses the cube has every leaf -1."""
+        starts, directions, as_numpy = self._rays(starts, directions)
+        t_stops, leaves = ops.octree_walk(starts, directions, self._scale, self.depth,
+                                          self._on_device("node_index"),
+                                          self._on_device("leaf_index"), int(max_length))
+        if as_numpy:
+            return Path(t_stops.cpu().numpy(), leaves.cpu().numpy())
+        return Path(t_stops, leaves)
+
+    def spans(self, starts, directions, t_min: float = 0.0, pad: float = 1):
+        """Per ray the span ``[t_in, t_out]`` that holds every leaf the ray crosses after
+        ``t_min``, widened at both ends by ``pad`` sides of a finest cell (measured along the
+        ray), and ``hit``: whether there is such a leaf.  Inputs as for ``walk``; -> (t_in, t_out
+        float32, hit bool), each (N,)."""
+        starts, directions, as_numpy = self._rays(starts, directions)
+        t_in, t_out, hit = ops.octree_spans(starts, directions, self._scale, self.depth,
+                                            self._on_device("node_index"),
+                                            self._on_device("leaf_index"), float(t_min),
+                                            float(pad))
+        hit = hit != 0
+        if as_numpy:
+            return t_in.cpu().numpy(), t_out.cpu().numpy(), hit.cpu().numpy()
+        return t_in, t_out, hit
+
     def intersect(self, starts, directions, max_length: int):
         raise NotImplementedError("OcTree.intersect (the ray walker of the lecture animations) "
                                   "is not part of the HIP path")
@@ -259,4 +347,5 @@ class OcTree:
         tree = OcTree(scale, node_ids.cpu().numpy(), leaf_ids.cpu().numpy(), leaf_data)
         tree._device = device
         tree._point_leaf = point_leaf
+        tree._center = (cx, cy, cz)
         return tree

@@ -565,3 +565,44 @@ def octree_leaf_geometry(leaf_index: torch.Tensor, scale: float):
         _call("ffn_octree_leaf_geometry", _dev(leaf_index, torch.int64, "leaf_index"), c_i64(k),
               c_f(scale), _dev(centers), _dev(depths, torch.int32))
     return centers, depths
+
+
+def _walk_args(starts, directions, scale, depth, node_index, leaf_index):
+    n = starts.shape[0]
+    if starts.shape != (n, 3) or directions.shape != (n, 3):
+        raise ValueError("octree walk: starts and directions must both be (N,3)")
+    return (_dev(starts, name="starts"), _dev(directions, name="directions"), c_i64(n),
+            c_f(scale), c_i(depth),
+            _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+            c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),
+            c_i64(leaf_index.numel()))
+
+
+def octree_walk(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                node_index: torch.Tensor, leaf_index: torch.Tensor, max_length: int):
+    """K13.  starts, directions (N,3) in the tree's frame, sorted int64 id arrays, depth = 1 + the
+    deepest leaf's level -> t_stops (N,max_length) float32, leaves (N,max_length) int64."""
+    n = starts.shape[0]
+    t_stops = torch.empty((n, max_length), dtype=torch.float32, device=starts.device)
+    leaves = torch.empty((n, max_length), dtype=torch.int64, device=starts.device)
+    if n > 0:
+        _call("ffn_octree_walk", *_walk_args(starts, directions, scale, depth, node_index,
+                                             leaf_index),
+              c_i(max_length), _dev(t_stops), _dev(leaves, torch.int64))
+    return t_stops, leaves
+
+
+def octree_spans(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                 node_index: torch.Tensor, leaf_index: torch.Tensor, t_min: float = 0.0,
+                 pad: float = 1.0):
+    """K13, span form.  -> t_in (N), t_out (N) float32 and hit (N) uint8: the span of the leaves
+    that end after ``t_min``, widened by ``pad`` finest-cell sides along the ray."""
+    n = starts.shape[0]
+    t_in = torch.empty((n,), dtype=torch.float32, device=starts.device)
+    t_out = torch.empty((n,), dtype=torch.float32, device=starts.device)
+    hit = torch.empty((n,), dtype=torch.uint8, device=starts.device)
+    if n > 0:
+        _call("ffn_octree_spans", *_walk_args(starts, directions, scale, depth, node_index,
+                                              leaf_index),
+              c_f(t_min), c_f(pad), _dev(t_in), _dev(t_out), _dev(hit, torch.uint8))
+    return t_in, t_out, hit

@@ -792,6 +792,40 @@ int ffn_octree_query(const float* positions, int64_t n, float scale, const int64
 int ffn_octree_leaf_geometry(const int64_t* leaf_index, int64_t num_leaves, float scale,
                              float* centers, int* depths, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K13  ray walk through the octree (csrc/octree_walk.hip), one lane per ray.  starts and
+ * directions (n,3) are in the tree's frame (relative to the root cube's centre, as for
+ * ffn_octree_query); directions need not be unit length.  depth = 1 + the deepest leaf's level
+ * (1 .. 11).  A REGION is a leaf or a maximal empty cell (a child slot of an interior node that is
+ * in neither index).  Entry t of a region = the crossing of its bounding plane, (plane - o) / d in
+ * f32, planes from the f32 chain of node centres; progress from region to region is decided on
+ * integer cell coordinates of the finest grid (2^(depth-1) per axis) -- no epsilon nudge.  A zero
+ * direction component constrains nothing if the start lies inside that slab of the root cube and
+ * makes the ray a miss otherwise; NaNs and an all-zero direction are misses.  At most
+ * (stops) * depth loop trips per ray for any input. */
+
+/* OcTree.intersect (octree.py:418-501 _trace_ray_path / _batch_intersect, 707-731), the reference's
+ * Path layout: t_stops (n,max_length) f32 and leaves (n,max_length) i64.  Stop k = the t at which
+ * the ray enters its k-th region along the whole chord through the root cube (negative t when the
+ * start is inside) and the region's index into leaf_index, -1 for an empty cell.  At most
+ * max_length - 1 stops are written (octree.py:460); the other entries hold the cube's exit t
+ * and -1 (octree.py:429-430).  A ray that misses the cube has every leaf -1 (its t_stops are 0).
+ * max_length >= 2. */
+int ffn_octree_walk(const float* starts, const float* directions, int64_t n, float scale,
+                    int depth, const int64_t* node_index, int64_t num_nodes,
+                    const int64_t* leaf_index, int64_t num_leaves, int max_length, float* t_stops,
+                    int64_t* leaves, void* stream);
+
+/* The same walk (octree.py:418-501) over the whole chord, reduced per ray to the span of the
+ * leaves that end after t_min: hit = there is such a leaf; t_in = max(entry of the first one,
+ * t_min) - w; t_out = exit of the last one + w, with w = pad finest-cell sides
+ * (2 scale / 2^(depth-1)) measured along the ray, pad / |d| in t.  t_in = t_out = 0 without a
+ * hit.  pad >= 0. */
+int ffn_octree_spans(const float* starts, const float* directions, int64_t n, float scale,
+                     int depth, const int64_t* node_index, int64_t num_nodes,
+                     const int64_t* leaf_index, int64_t num_leaves, float t_min, float pad,
+                     float* t_in, float* t_out, uint8_t* hit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
