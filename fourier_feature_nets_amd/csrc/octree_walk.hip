@@ -31,6 +31,13 @@
 // back 63 neighbours, not 255, and a finished wave frees its slot at once.  The kernel is bound
 // by the latency of dependent L2 reads (the binary searches); neighbouring rays search the same
 // ids, so the top of both arrays stays in cache.
+//
+// K14  First hit: the same walk, ended at the first leaf whose exit t is > t_min (the predicate of
+// the span form).  The leaves of a voxelized model are opaque surface cells with one colour each
+// and no density, so the first one a ray meets IS the render: no stop arrays, no compositing.  The
+// hit gives the leaf, its entry t (depth) and the face the ray came in through -- the exit axis of
+// the region before it -- and, in the same launch, the leaf's colour.  Replaces the scenepic view
+// of the leaf cubes (voxelize_model.py:90-110 of the reference) on top of octree.py:418-501.
 #include "common.h"
 
 namespace ffn {
@@ -97,16 +104,43 @@ __device__ __forceinline__ int step_axis(int i, bool is_exit_axis, float d, floa
     return d > 0.0f ? max(i, at) : min(i, at);
 }
 
-// kSpans == false: Path rows (t_stops, leaves), max_length entries per ray.
-// kSpans == true:  per ray t_in / t_out / hit over the leaves that end after t_min.
-template <bool kSpans>
+// one factor per axis pair, 1 for a clamped entry (face 6): FFN_OCTREE_FACE_SHADE without a table
+// in memory (a table indexed per lane would live in scratch)
+__device__ __forceinline__ float face_shade(int face) {
+    const int pair = face >> 1;
+    return pair == 0 ? FFN_OCTREE_SHADE_X
+                     : pair == 1 ? FFN_OCTREE_SHADE_Y : pair == 2 ? FFN_OCTREE_SHADE_Z : 1.0f;
+}
+
+// what only the first-hit mode reads and writes; any of leaf / t_hit / face, and all of
+// color / alpha / depth together, may be null
+struct FirstHit {
+    int64_t* leaf;
+    float* t_hit;
+    int8_t* face;
+    const float* leaf_data;      // (num_leaves, channels), the first three channels are used
+    int channels;
+    int shading;                 // FFN_OCTREE_SHADING_*
+    float bg_r, bg_g, bg_b;
+    float* color;
+    float* alpha;
+    float* depth;
+};
+
+enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2 };
+
+// kPath:     Path rows (t_stops, leaves), max_length entries per ray.
+// kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
+// kFirstHit: the first of those leaves, where the loop ends (K14).
+template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
                    int64_t n, float scale, int depth, const int64_t* __restrict__ node_index,
                    int64_t num_nodes, const int64_t* __restrict__ leaf_index, int64_t num_leaves,
                    int max_length, float* __restrict__ t_stops, int64_t* __restrict__ leaves,
                    float t_min, float pad, float* __restrict__ span_in,
-                   float* __restrict__ span_out, uint8_t* __restrict__ span_hit) {
+                   float* __restrict__ span_out, uint8_t* __restrict__ span_hit, FirstHit first) {
+    constexpr bool kSpans = kMode == kSpan;
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= n) return;
     const float ox = starts[r * 3 + 0], oy = starts[r * 3 + 1], oz = starts[r * 3 + 2];
@@ -132,7 +166,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     // A walk writes at most max_length - 1 stops (the reference's stop == max_length - 1 rule,
     // octree.py:460); a span walk has no such cap, but every step moves one cell coordinate
     // forward for good, so a chord has at most 3 * cells + 1 regions.
-    const int max_stops = kSpans ? 3 * cells + 1 : max_length - 1;
+    const int max_stops = kMode == kPath ? max_length - 1 : 3 * cells + 1;
     // Every region costs at most `depth` trips: depth - 1 descents and the region itself.  The
     // loop condition holds the trip count to max_stops * depth for ANY input (NaNs, a tree
     // whose two indices contradict each other): nothing below can extend it.
@@ -143,6 +177,9 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale, t = root_in;
     bool inside = hit, any_leaf = false;
     float first_in = 0.0f, last_out = 0.0f;
+    // first hit: the axis of the plane the ray crossed into the current region, and the answer
+    int axis_prev = axis_in, hit_face = -1;
+    int64_t hit_leaf = -1;
     for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
         int64_t at;
         const bool interior = level < known ||
@@ -166,7 +203,16 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         float t_exit = tx;
         if (ty < t_exit) { t_exit = ty; axis_out = 1; }
         if (tz < t_exit) { t_exit = tz; axis_out = 2; }
-        if (kSpans) {
+        if (kMode == kFirstHit) {
+            if (leaf >= 0 && t_exit > t_min) {
+                const float d_in = axis_prev == 0 ? dx : axis_prev == 1 ? dy : dz;
+                hit_leaf = leaf;
+                first_in = t > t_min ? t : t_min;
+                hit_face = t < t_min ? 6 : 2 * axis_prev + (d_in > 0.0f ? 0 : 1);
+                break;
+            }
+            axis_prev = axis_out;
+        } else if (kSpans) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (!any_leaf) first_in = t > t_min ? t : t_min;
                 any_leaf = true;
@@ -192,7 +238,28 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         id = 0; level = 0;
         cx = 0.0f; cy = 0.0f; cz = 0.0f; half = scale;
     }
-    if (kSpans) {
+    if (kMode == kFirstHit) {
+        const bool found = hit_leaf >= 0;
+        if (first.leaf) first.leaf[r] = hit_leaf;
+        if (first.t_hit) first.t_hit[r] = first_in;
+        if (first.face) first.face[r] = (int8_t)hit_face;
+        if (first.color) {
+            float cr = first.bg_r, cg = first.bg_g, cb = first.bg_b;
+            if (found) {
+                const float* data = first.leaf_data + hit_leaf * first.channels;
+                cr = data[0]; cg = data[1]; cb = data[2];
+                if (first.shading == FFN_OCTREE_SHADING_FACES) {
+                    const float k = face_shade(hit_face);
+                    cr *= k; cg *= k; cb *= k;
+                }
+            }
+            first.color[r * 3 + 0] = cr;
+            first.color[r * 3 + 1] = cg;
+            first.color[r * 3 + 2] = cb;
+            first.alpha[r] = found ? 1.0f : 0.0f;
+            first.depth[r] = first_in;
+        }
+    } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
         const float side = 2.0f * scale / (float)cells;
         const float widen = pad * side / sqrtf(dx * dx + dy * dy + dz * dz);
@@ -240,10 +307,10 @@ extern "C" int ffn_octree_walk(const float* starts, const float* directions, int
         return fail_arg("ffn_octree_walk: 2 <= max_length <= 65536");
     if (!t_stops || !leaves) return fail_arg("ffn_octree_walk: null argument");
     const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<false>, dim3(blocks), dim3(kWalkThreads), 0,
+    hipLaunchKernelGGL(octree_walk_kernel<kPath>, dim3(blocks), dim3(kWalkThreads), 0,
                        (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
                        num_nodes, leaf_index, num_leaves, max_length, t_stops, leaves, 0.0f, 0.0f,
-                       (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr);
+                       (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, FirstHit{});
     return check_launch("ffn_octree_walk");
 }
 
@@ -257,9 +324,68 @@ extern "C" int ffn_octree_spans(const float* starts, const float* directions, in
     if (!t_in || !t_out || !hit) return fail_arg("ffn_octree_spans: null argument");
     if (!(pad >= 0.0f)) return fail_arg("ffn_octree_spans: pad >= 0");
     const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<true>, dim3(blocks), dim3(kWalkThreads), 0,
+    hipLaunchKernelGGL(octree_walk_kernel<kSpan>, dim3(blocks), dim3(kWalkThreads), 0,
                        (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
                        num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
-                       t_min, pad, t_in, t_out, hit);
+                       t_min, pad, t_in, t_out, hit, FirstHit{});
     return check_launch("ffn_octree_spans");
+}
+
+static int launch_first_hit(const char* who, const float* starts, const float* directions,
+                            int64_t n, float scale, int depth, const int64_t* node_index,
+                            int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+                            float t_min, const FirstHit& first, void* stream) {
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<kFirstHit>, dim3(blocks), dim3(kWalkThreads), 0,
+                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
+                       t_min, 0.0f, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
+    return check_launch(who);
+}
+
+extern "C" int ffn_octree_first_hit(const float* starts, const float* directions, int64_t n,
+                                    float scale, int depth, const int64_t* node_index,
+                                    int64_t num_nodes, const int64_t* leaf_index,
+                                    int64_t num_leaves, float t_min, int64_t* leaf, float* t_hit,
+                                    int8_t* face, void* stream) {
+    // scalars first: which check refuses does not depend on the pointers
+    if (t_min != t_min) return fail_arg("ffn_octree_first_hit: t_min is NaN");
+    if (int err = check_walk_args("ffn_octree_first_hit", starts, directions, n, depth, node_index,
+                                  num_nodes, leaf_index, num_leaves))
+        return err;
+    if (!leaf || !t_hit || !face) return fail_arg("ffn_octree_first_hit: null argument");
+    FirstHit first{};
+    first.leaf = leaf; first.t_hit = t_hit; first.face = face;
+    return launch_first_hit("ffn_octree_first_hit", starts, directions, n, scale, depth,
+                            node_index, num_nodes, leaf_index, num_leaves, t_min, first, stream);
+}
+
+extern "C" int ffn_octree_render(const float* starts, const float* directions, int64_t n,
+                                 float scale, int depth, const int64_t* node_index,
+                                 int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+                                 float t_min, const float* leaf_data, int channels, float bg_r,
+                                 float bg_g, float bg_b, int shading, float* color, float* alpha,
+                                 float* depth_out, int64_t* leaf, float* t_hit, int8_t* face,
+                                 void* stream) {
+    if (channels < 3) return fail_arg("ffn_octree_render: channels >= 3");
+    if (shading != FFN_OCTREE_SHADING_FLAT && shading != FFN_OCTREE_SHADING_FACES)
+        return fail_arg("ffn_octree_render: unknown shading mode");
+    if (t_min != t_min) return fail_arg("ffn_octree_render: t_min is NaN");
+    if (int err = check_walk_args("ffn_octree_render", starts, directions, n, depth, node_index,
+                                  num_nodes, leaf_index, num_leaves))
+        return err;
+    if (!leaf_data || !color || !alpha || !depth_out)
+        return fail_arg("ffn_octree_render: null argument");
+    FirstHit first{};
+    first.leaf = leaf; first.t_hit = t_hit; first.face = face;
+    first.leaf_data = leaf_data; first.channels = channels; first.shading = shading;
+    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
+    first.color = color; first.alpha = alpha; first.depth = depth_out;
+    return launch_first_hit("ffn_octree_render", starts, directions, n, scale, depth, node_index,
+                            num_nodes, leaf_index, num_leaves, t_min, first, stream);
+}
+
+extern "C" void ffn_octree_face_shade(float* table) {
+    const float k[7] = FFN_OCTREE_FACE_SHADE;
+    for (int i = 0; i < 7; ++i) table[i] = k[i];
 }

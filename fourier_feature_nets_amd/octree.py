@@ -31,10 +31,14 @@ public signatures are the reference's, so files and calling code go both ways.  
     are misses.
 
 * ``spans`` and ``center`` have no counterpart in the reference.
+* ``first_hit`` / ``render`` / ``render_image`` (K14) have none either: the reference looks at a
+  voxelized model through scenepic (voxelize_model.py:90-110).  The leaves of such a tree are opaque
+  surface cells with one colour each, so the render is the first leaf a ray meets.  The file format
+  has no place for the root cube's centre; a caller that loads a tree passes it (``center=``).
 
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
-``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``leaf_centers`` and
-``leaf_depths`` run on the GPU and raise without one.
+``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
+``leaf_centers`` and ``leaf_depths`` run on the GPU and raise without one.
 """
 
 import os
@@ -44,6 +48,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .utils import RenderResult
 
 
 def _as_index(ids) -> np.ndarray:
@@ -63,6 +68,7 @@ def _id_depths(ids: np.ndarray) -> np.ndarray:
 
 
 Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
+Hit = NamedTuple("Hit", [("leaves", np.ndarray), ("t", np.ndarray), ("faces", np.ndarray)])
 
 
 class OcTree:
@@ -292,6 +298,85 @@ class OcTree:
         if as_numpy:
             return t_in.cpu().numpy(), t_out.cpu().numpy(), hit.cpu().numpy()
         return t_in, t_out, hit
+
+    def first_hit(self, starts, directions, t_min: float = 0.0) -> Hit:
+        """Per ray the first leaf that ends after ``t_min`` (K14; the walk stops there).  Inputs
+        as for ``walk``.  -> ``Hit``: ``leaves`` (N,) int64 index into the sorted leaf ids, -1
+        without a hit; ``t`` (N,) float32 ``max(entry t, t_min)``, 0 on a miss; ``faces`` (N,) int8,
+        the face the ray enters the leaf through: ``2 * axis + (d[axis] > 0 ? 0 : 1)`` (0 / 2 / 4:
+        outward normal -x / -y / -z, 1 / 3 / 5: +x / +y / +z), 6 when the entry lies before
+        ``t_min`` (the ray starts inside the leaf), -1 on a miss."""
+        starts, directions, as_numpy = self._rays(starts, directions)
+        hit = ops.octree_first_hit(starts, directions, self._scale, self.depth,
+                                   self._on_device("node_index"), self._on_device("leaf_index"),
+                                   float(t_min))
+        if as_numpy:
+            return Hit(*[x.cpu().numpy() for x in hit])
+        return Hit(*hit)
+
+    def _check_colors(self):
+        data = self._leaf_data
+        if data is None:
+            raise ValueError("OcTree.render: the tree has no leaf_data to show")
+        if np.ndim(data) != 2 or np.shape(data)[1] < 3:
+            raise ValueError("OcTree.render: leaf_data must be (num_leaves, C >= 3) to hold a "
+                             "colour, got %s" % (np.shape(data),))
+
+    def _colors_on_device(self) -> torch.Tensor:
+        """``leaf_data`` as float32 on the device, cast once (a tree the reference saved, or a
+        pruned one, holds float64); ``_update`` drops it with the rest of the cache."""
+        self._check_colors()
+        data = self._leaf_data
+        dev = self._dev()
+        key = ("leaf_data_f32", str(dev))
+        if key not in self._cache:
+            self._cache[key] = torch.from_numpy(
+                np.ascontiguousarray(data, dtype=np.float32)).to(dev)
+        return self._cache[key]
+
+    def render(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
+               shading: str = "flat") -> RenderResult:
+        """The tree as ``first_hit`` sees it, shaded in the same launch.  -> ``RenderResult``:
+        ``color`` (N,3) the hit leaf's first three ``leaf_data`` channels (``shading="faces"``:
+        times one factor per axis pair of the entry face, cube shading) or ``background``;
+        ``alpha`` (N,) 1 on a hit, 0 otherwise; ``depth`` (N,) the hit's t.  Inputs as for
+        ``walk``; numpy in gives numpy out."""
+        if shading not in ops.OCTREE_SHADING:
+            raise ValueError("OcTree.render: shading is 'flat' or 'faces', got %r" % (shading,))
+        self._check_colors()                     # before any device is needed
+        starts, directions, as_numpy = self._rays(starts, directions)
+        out = RenderResult(*ops.octree_render(
+            starts, directions, self._scale, self.depth, self._on_device("node_index"),
+            self._on_device("leaf_index"), self._colors_on_device(), float(t_min), background,
+            shading))
+        return out.numpy() if as_numpy else out
+
+    def render_image(self, sampler, index: int, center=None, t_min: float = 0.0,
+                     background=(0, 0, 0), shading: str = "flat", include_depth: bool = False):
+        """(H,W,3) uint8 frame of the sampler's camera ``index % num_cameras``, as
+        ``Raycaster.render_image`` returns it; with ``include_depth`` also the (H,W) float32
+        alpha and depth maps.  Every ray of the camera is used -- the octree is the geometry, the
+        sampler's validity mask is not applied.  ``center``: the root cube's centre in the
+        sampler's frame; defaults to ``tree.center``, which a loaded tree does not have."""
+        if center is None:
+            center = self._center
+        if center is None:
+            raise ValueError("OcTree.render_image: a loaded tree does not know the centre of its "
+                             "root cube (the file has no place for it); pass center=")
+        camera = index % sampler.num_cameras
+        first = camera * sampler.rays_per_camera
+        rays = slice(first, first + sampler.rays_per_camera)
+        shift = torch.tensor([float(c) for c in center], dtype=torch.float32,
+                             device=sampler.starts.device)
+        color, alpha, depth = self.render(sampler.starts[rays] - shift, sampler.directions[rays],
+                                          t_min, background, shading)
+        pixels = torch.arange(sampler.rays_per_camera, dtype=torch.int64, device=color.device)
+        image = ops.to_image(color, pixels, sampler.image_width, sampler.image_height)
+        image = image.cpu().numpy()
+        if not include_depth:
+            return image
+        shape = (sampler.image_height, sampler.image_width)
+        return image, alpha.reshape(shape).cpu().numpy(), depth.reshape(shape).cpu().numpy()
 
     def intersect(self, starts, directions, max_length: int):
         raise NotImplementedError("OcTree.intersect (the ray walker of the lecture animations) "

@@ -606,3 +606,68 @@ def octree_spans(starts: torch.Tensor, directions: torch.Tensor, scale: float, d
                                               leaf_index),
               c_f(t_min), c_f(pad), _dev(t_in), _dev(t_out), _dev(hit, torch.uint8))
     return t_in, t_out, hit
+
+
+OCTREE_SHADING = {"flat": 0, "faces": 1}      # FFN_OCTREE_SHADING_* of include/ffn_hip.h
+
+
+def octree_face_shade():
+    """The seven factors of ``"faces"`` shading (FFN_OCTREE_FACE_SHADE), as the library holds
+    them: one per entry face 0 .. 5 and 1.0 for face 6 -> numpy float32 (7,)."""
+    table = (ctypes.c_float * 7)()
+    fn = _lib.load().ffn_octree_face_shade
+    fn.restype = None
+    fn(table)
+    return np.array(list(table), dtype=np.float32)
+
+
+def octree_first_hit(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                     node_index: torch.Tensor, leaf_index: torch.Tensor, t_min: float = 0.0):
+    """K14.  Arguments as for ``octree_spans`` -> per ray the first leaf that ends after ``t_min``:
+    leaf (N) int64 index into leaf_index or -1, t_hit (N) float32 = max(entry t, t_min) or 0,
+    face (N) int8: the entry face 0 .. 5, 6 for an entry before ``t_min``, -1 for a miss."""
+    n = starts.shape[0]
+    leaf = torch.empty((n,), dtype=torch.int64, device=starts.device)
+    t_hit = torch.empty((n,), dtype=torch.float32, device=starts.device)
+    face = torch.empty((n,), dtype=torch.int8, device=starts.device)
+    if n > 0:
+        _call("ffn_octree_first_hit", *_walk_args(starts, directions, scale, depth, node_index,
+                                                  leaf_index),
+              c_f(t_min), _dev(leaf, torch.int64), _dev(t_hit), _dev(face, torch.int8))
+    return leaf, t_hit, face
+
+
+def octree_render(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                  node_index: torch.Tensor, leaf_index: torch.Tensor, leaf_data: torch.Tensor,
+                  t_min: float = 0.0, background=(0.0, 0.0, 0.0), shading: str = "flat",
+                  want_hit: bool = False):
+    """K14, shaded in the same launch.  leaf_data (L,C) float32 with C >= 3 -> color (N,3),
+    alpha (N) (1 on a hit, 0 otherwise), depth (N) = t_hit; misses carry ``background``.
+    ``shading``: "flat" or "faces".  With ``want_hit`` also the (leaf, t_hit, face) of
+    ``octree_first_hit``."""
+    if shading not in OCTREE_SHADING:
+        raise ValueError("octree render: shading is 'flat' or 'faces', got %r" % (shading,))
+    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 3:
+        raise ValueError("octree render: leaf_data must be (num_leaves, C >= 3), got %s for %d "
+                         "leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
+    n = starts.shape[0]
+    dev = starts.device
+    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
+    hit = None
+    if want_hit:
+        hit = (torch.empty((n,), dtype=torch.int64, device=dev),
+               torch.empty((n,), dtype=torch.float32, device=dev),
+               torch.empty((n,), dtype=torch.int8, device=dev))
+    if n > 0:
+        r, g, b = [float(v) for v in background]
+        _call("ffn_octree_render", *_walk_args(starts, directions, scale, depth, node_index,
+                                               leaf_index),
+              c_f(t_min), _dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1]), c_f(r),
+              c_f(g), c_f(b), c_i(OCTREE_SHADING[shading]), _dev(color), _dev(alpha),
+              _dev(depth_out), _dev(hit[0] if hit else None, torch.int64),
+              _dev(hit[1] if hit else None), _dev(hit[2] if hit else None, torch.int8))
+    if want_hit:
+        return color, alpha, depth_out, hit
+    return color, alpha, depth_out

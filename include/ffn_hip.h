@@ -826,6 +826,54 @@ int ffn_octree_spans(const float* starts, const float* directions, int64_t n, fl
                      const int64_t* leaf_index, int64_t num_leaves, float t_min, float pad,
                      float* t_in, float* t_out, uint8_t* hit, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K14  first hit of the K13 walk (csrc/octree_walk.hip, a third mode of the same kernel): the render
+ * of a voxelized model, whose leaves are opaque surface cells with one colour each.  Replaces the
+ * walker of octree.py:418-501 cut at the first leaf, and the leaf-cube view the reference hands to
+ * scenepic (voxelize_model.py:90-110).  Arguments up to num_leaves as for K13.
+ *
+ * The ray's regions are walked in order; the hit is the first LEAF whose exit t is > t_min (the
+ * predicate of ffn_octree_spans), and the walk ends there.  Per ray:
+ *   leaf   index into leaf_index, -1 without a hit;
+ *   t_hit  max(entry t, t_min) -- t_min itself, bit for bit, when it is the larger; 0 on a miss;
+ *   face   the face the ray enters the leaf through: 2 * axis + (d[axis] > 0 ? 0 : 1), so that
+ *          0 / 2 / 4 have the outward normal -x / -y / -z and 1 / 3 / 5 have +x / +y / +z; axis is
+ *          the root cube's entry axis for the chord's first region and the exit axis of the region
+ *          before otherwise.  6: the entry lies before t_min (the ray starts inside the leaf, or
+ *          t_min lies inside it).  -1: a miss.
+ * Rays K13 cannot follow (NaN or infinite components, an all-zero direction, a zero component
+ * outside its slab) are misses.  t_min must not be NaN. */
+
+#define FFN_OCTREE_SHADING_FLAT 0   /* color = leaf_data[leaf, :3] */
+#define FFN_OCTREE_SHADING_FACES 1  /* color = leaf_data[leaf, :3] * k[face], one f32 multiply */
+/* k: one factor per axis pair (x, y, z faces) and 1 for face 6 */
+#define FFN_OCTREE_SHADE_X 0.8f
+#define FFN_OCTREE_SHADE_Y 1.0f
+#define FFN_OCTREE_SHADE_Z 0.6f
+#define FFN_OCTREE_FACE_SHADE                                                                 \
+    {FFN_OCTREE_SHADE_X, FFN_OCTREE_SHADE_X, FFN_OCTREE_SHADE_Y, FFN_OCTREE_SHADE_Y,          \
+     FFN_OCTREE_SHADE_Z, FFN_OCTREE_SHADE_Z, 1.0f}
+
+int ffn_octree_first_hit(const float* starts, const float* directions, int64_t n, float scale,
+                         int depth, const int64_t* node_index, int64_t num_nodes,
+                         const int64_t* leaf_index, int64_t num_leaves, float t_min, int64_t* leaf,
+                         float* t_hit, int8_t* face, void* stream);
+
+/* The same launch, shaded: leaf_data (num_leaves, channels) f32 with channels >= 3, of which the
+ * first three are the colour.  color (n,3) = the hit leaf's colour (times k[face] with
+ * FFN_OCTREE_SHADING_FACES), the background (bg_r, bg_g, bg_b) on a miss, both bit for bit;
+ * alpha (n) = 1 on a hit and 0 otherwise; depth (n) = t_hit.  leaf, t_hit and face are written
+ * too where they are not null. */
+int ffn_octree_render(const float* starts, const float* directions, int64_t n, float scale,
+                      int depth, const int64_t* node_index, int64_t num_nodes,
+                      const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                      const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+                      int shading, float* color, float* alpha, float* depth_out, int64_t* leaf,
+                      float* t_hit, int8_t* face, void* stream);
+
+/* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
+void ffn_octree_face_shade(float* table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ octree from the cloud (K12e-i).  The cloud never leaves the GPU."""
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -53,6 +54,9 @@ def main():
     colors = torch.cat(colors)
     print(len(positions), "points in cloud")
     voxels = ffn.OcTree.build_from_samples(positions, args.voxel_depth, args.min_leaf_size, colors)
+    # the file format is the reference's and has no place for the root cube's centre
+    print("root cube centre (for render_octree.py): --center",
+          " ".join(np.format_float_positional(np.float32(c), trim="0") for c in voxels.center))
     voxels.save(args.output_path)
     if args.scenepic_path:
         # (voxelize_model.py:90-110 of the reference writes a scenepic HTML of the leaf cubes)
