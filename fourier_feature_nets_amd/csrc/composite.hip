@@ -344,6 +344,18 @@ mse_final_kernel(const float* __restrict__ scratch, int blocks, float* __restric
     if (threadIdx.x == 0) { sums[0] = ec; sums[1] = ea; }
 }
 
+// ---------------------------------------------------------------------------------- octree bake
+// raw model logits [r, g, b, sigma] of one leaf -> what make_terms makes of them: the leaf data of
+// a baked octree (K15 of octree_walk.hip composites over it).  Here, not in octree_walk.hip, so
+// that the activations are compiled as the render kernels' own.
+__global__ void __launch_bounds__(256)
+octree_bake_kernel(const float4* __restrict__ logits, int64_t count, float4* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float4 l = logits[i];
+    out[i] = make_float4(sigmoid_f(l.x), sigmoid_f(l.y), sigmoid_f(l.z), softplus_torch(l.w));
+}
+
 }  // namespace ffn
 
 using namespace ffn;
@@ -469,4 +481,17 @@ extern "C" int ffn_loss_from_partials(const float* partials, int num_blocks, flo
     hipLaunchKernelGGL(loss_from_partials_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials,
                        num_blocks, colour_count, alpha_count, alpha_weight, sums, loss_out);
     return check_launch("ffn_loss_from_partials");
+}
+
+extern "C" int ffn_octree_bake(const float* logits, int64_t num_leaves, float* leaf_data,
+                               void* stream) {
+    if (num_leaves < 1 || num_leaves >= ((int64_t)1 << 31))
+        return fail_arg("ffn_octree_bake: shape (1 <= num_leaves < 2^31)");
+    if (!logits || !leaf_data) return fail_arg("ffn_octree_bake: null argument");
+    if ((((uintptr_t)logits | (uintptr_t)leaf_data) & 15) != 0)
+        return fail_arg("ffn_octree_bake: logits and leaf_data must be 16-byte aligned");
+    const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
+    hipLaunchKernelGGL(octree_bake_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const float4*)logits, num_leaves, (float4*)leaf_data);
+    return check_launch("ffn_octree_bake");
 }

@@ -38,6 +38,13 @@
 // hit gives the leaf, its entry t (depth) and the face the ray came in through -- the exit axis of
 // the region before it -- and, in the same launch, the leaf's colour.  Replaces the scenepic view
 // of the leaf cubes (voxelize_model.py:90-110 of the reference) on top of octree.py:418-501.
+//
+// K15  Volume: the same walk, composited front to back.  A baked tree (ffn_octree_bake) holds the
+// model's own colour and density in every leaf; the walk has the entry and the exit t of a leaf in
+// registers, so the chord, its opacity 1 - exp(-sigma * length) and the running transmittance are
+// a handful of VALU operations per leaf on top of one 16-byte load, and nothing is written per
+// stop.  The walk ends early once the transmittance is at or below a threshold.  No counterpart in
+// the reference.
 #include "common.h"
 
 namespace ffn {
@@ -112,8 +119,9 @@ __device__ __forceinline__ float face_shade(int face) {
                      : pair == 1 ? FFN_OCTREE_SHADE_Y : pair == 2 ? FFN_OCTREE_SHADE_Z : 1.0f;
 }
 
-// what only the first-hit mode reads and writes; any of leaf / t_hit / face, and all of
-// color / alpha / depth together, may be null
+// what only the first-hit and the volume mode read and write; any of leaf / t_hit / face, and all
+// of color / alpha / depth together, may be null in the first-hit mode.  The volume mode reads
+// four channels (colour and density) and writes color / alpha / depth only.
 struct FirstHit {
     int64_t* leaf;
     float* t_hit;
@@ -122,16 +130,18 @@ struct FirstHit {
     int channels;
     int shading;                 // FFN_OCTREE_SHADING_*
     float bg_r, bg_g, bg_b;
+    float min_transmittance;     // kVolume: the walk ends once T <= this
     float* color;
     float* alpha;
     float* depth;
 };
 
-enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2 };
+enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
 // kFirstHit: the first of those leaves, where the loop ends (K14).
+// kVolume:   colour, opacity and depth composited front to back over those leaves (K15).
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -180,6 +190,9 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     // first hit: the axis of the plane the ray crossed into the current region, and the answer
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
+    // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
+    const float norm = kMode == kVolume ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
+    float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
         int64_t at;
         const bool interior = level < known ||
@@ -212,6 +225,26 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 break;
             }
             axis_prev = axis_out;
+        } else if (kMode == kVolume) {
+            if (leaf >= 0 && t_exit > t_min) {
+                float lr, lg, lb, ls;
+                if (first.channels == 4) {
+                    const float4 v = reinterpret_cast<const float4*>(first.leaf_data)[leaf];
+                    lr = v.x; lg = v.y; lb = v.z; ls = v.w;
+                } else {
+                    const float* data = first.leaf_data + leaf * first.channels;
+                    lr = data[0]; lg = data[1]; lb = data[2]; ls = data[3];
+                }
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                acc_r += w * lr; acc_g += w * lg; acc_b += w * lb;
+                if (w > w_best) { w_best = w; t_best = t0; }
+                trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
         } else if (kSpans) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (!any_leaf) first_in = t > t_min ? t : t_min;
@@ -259,6 +292,12 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
             first.alpha[r] = found ? 1.0f : 0.0f;
             first.depth[r] = first_in;
         }
+    } else if (kMode == kVolume) {
+        first.color[r * 3 + 0] = acc_r + trans * first.bg_r;
+        first.color[r * 3 + 1] = acc_g + trans * first.bg_g;
+        first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
+        first.alpha[r] = 1.0f - trans;
+        first.depth[r] = t_best;
     } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
         const float side = 2.0f * scale / (float)cells;
@@ -383,6 +422,38 @@ extern "C" int ffn_octree_render(const float* starts, const float* directions, i
     first.color = color; first.alpha = alpha; first.depth = depth_out;
     return launch_first_hit("ffn_octree_render", starts, directions, n, scale, depth, node_index,
                             num_nodes, leaf_index, num_leaves, t_min, first, stream);
+}
+
+extern "C" int ffn_octree_render_volume(const float* starts, const float* directions, int64_t n,
+                                        float scale, int depth, const int64_t* node_index,
+                                        int64_t num_nodes, const int64_t* leaf_index,
+                                        int64_t num_leaves, float t_min, const float* leaf_data,
+                                        int channels, float bg_r, float bg_g, float bg_b,
+                                        float min_transmittance, float* color, float* alpha,
+                                        float* depth_out, void* stream) {
+    if (channels < 4) return fail_arg("ffn_octree_render_volume: channels >= 4");
+    if (t_min != t_min) return fail_arg("ffn_octree_render_volume: t_min is NaN");
+    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
+        return fail_arg("ffn_octree_render_volume: 0 <= min_transmittance < 1");
+    if (!leaf_data || !color || !alpha || !depth_out)
+        return fail_arg("ffn_octree_render_volume: null argument");
+    if (int err = check_walk_args("ffn_octree_render_volume", starts, directions, n, depth,
+                                  node_index, num_nodes, leaf_index, num_leaves))
+        return err;
+    // four channels are read as one 16-byte load per leaf
+    if (channels == 4 && ((uintptr_t)leaf_data & 15) != 0)
+        return fail_arg("ffn_octree_render_volume: leaf_data with 4 channels must be 16-byte aligned");
+    FirstHit first{};
+    first.leaf_data = leaf_data; first.channels = channels;
+    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
+    first.min_transmittance = min_transmittance;
+    first.color = color; first.alpha = alpha; first.depth = depth_out;
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<kVolume>, dim3(blocks), dim3(kWalkThreads), 0,
+                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
+                       t_min, 0.0f, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
+    return check_launch("ffn_octree_render_volume");
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

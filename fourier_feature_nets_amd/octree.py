@@ -35,10 +35,18 @@ public signatures are the reference's, so files and calling code go both ways.  
   voxelized model through scenepic (voxelize_model.py:90-110).  The leaves of such a tree are opaque
   surface cells with one colour each, so the render is the first leaf a ray meets.  The file format
   has no place for the root cube's centre; a caller that loads a tree passes it (``center=``).
+* ``bake`` / ``render_volume`` / ``render_image(mode="volume")`` (K15) have none either.  ``bake``
+  evaluates a trained model at the leaf centres and stores its own colour and density
+  (``[sigmoid(rgb), softplus(sigma)]``, as ``Raycaster.render`` activates them) in every leaf;
+  ``render_volume`` composites them front to back along the ray's whole chord through the tree, so
+  soft edges, thin structure and the transmittance left for the background survive.  A leaf holds
+  one colour: the view dependence of a model with ``use_view`` is lost (it is baked for one fixed
+  view direction).
 
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
-``leaf_centers`` and ``leaf_depths`` run on the GPU and raise without one.
+``bake``, ``render_volume``, ``leaf_centers`` and ``leaf_depths`` run on the GPU and raise without
+one.
 """
 
 import os
@@ -322,6 +330,19 @@ class OcTree:
             raise ValueError("OcTree.render: leaf_data must be (num_leaves, C >= 3) to hold a "
                              "colour, got %s" % (np.shape(data),))
 
+    def _check_volume(self, min_transmittance):
+        data = self._leaf_data
+        if data is None:
+            raise ValueError("OcTree.render_volume: the tree has no leaf_data to composite "
+                             "(see OcTree.bake)")
+        if np.ndim(data) != 2 or np.shape(data)[1] < 4:
+            raise ValueError("OcTree.render_volume: leaf_data must be (num_leaves, C >= 4) to "
+                             "hold a colour and a density, got %s (see OcTree.bake)"
+                             % (np.shape(data),))
+        if not 0.0 <= float(min_transmittance) < 1.0:        # NaN fails too
+            raise ValueError("OcTree.render_volume: min_transmittance must lie in [0, 1), got %r"
+                             % (min_transmittance,))
+
     def _colors_on_device(self) -> torch.Tensor:
         """``leaf_data`` as float32 on the device, cast once (a tree the reference saved, or a
         pruned one, holds float64); ``_update`` drops it with the rest of the cache."""
@@ -351,13 +372,90 @@ class OcTree:
             shading))
         return out.numpy() if as_numpy else out
 
+    def render_volume(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
+                      min_transmittance: float = 0.0) -> RenderResult:
+        """A baked tree (``bake``) composited front to back (K15).  ``leaf_data`` holds
+        ``[r, g, b, sigma]`` per leaf, ``sigma`` per unit of world length.  Over the leaves a ray
+        crosses after ``t_min``, in order: ``a = 1 - exp(-sigma * chord)``, ``w = T * a``,
+        ``T *= 1 - a``.  -> ``RenderResult``: ``color`` (N,3) ``sum(w * rgb) + T * background``;
+        ``alpha`` (N,) ``1 - T``; ``depth`` (N,) the ``max(entry t, t_min)`` of the leaf with the
+        largest ``w`` (the first of equals), 0 when nothing is in the way.  The walk of a ray ends
+        once ``T <= min_transmittance``.  Rescaling ``directions`` does not change the result.
+        Inputs as for ``walk``; numpy in gives numpy out."""
+        self._check_volume(min_transmittance)         # before any device is needed
+        starts, directions, as_numpy = self._rays(starts, directions)
+        out = RenderResult(*ops.octree_render_volume(
+            starts, directions, self._scale, self.depth, self._on_device("node_index"),
+            self._on_device("leaf_index"), self._colors_on_device(), float(t_min), background,
+            float(min_transmittance)))
+        return out.numpy() if as_numpy else out
+
+    def bake(self, model, center=None, view=(0, 0, 1), batch_size: int = 1 << 20) -> "OcTree":
+        """A NEW tree of the same structure and centre whose ``leaf_data`` (L,4) float32 holds the
+        model's own colour and density at every leaf's centre: ``[sigmoid(r), sigmoid(g),
+        sigmoid(b), softplus(sigma)]`` of the model's logits, bit for bit what ``Raycaster.render``
+        makes of them.  This tree is not modified.
+
+        ``model`` is evaluated in eval mode without gradients, ``batch_size`` leaves at a time, at
+        ``leaf_centers() + center``; ``center`` defaults to ``tree.center``, which a loaded tree
+        does not have.  A model with ``use_view`` is given the fixed direction ``view`` for every
+        leaf: a leaf holds one colour, so the view dependence of such a model is lost."""
+        if center is None:
+            center = self._center
+        if center is None:
+            raise ValueError("OcTree.bake: a loaded tree does not know the centre of its root "
+                             "cube (the file has no place for it); pass center=")
+        center = tuple(float(c) for c in center)
+        batch_size = int(batch_size)
+        if len(center) != 3 or batch_size < 1:
+            raise ValueError("OcTree.bake: center has three components and batch_size is >= 1")
+        device = next(model.parameters()).device
+        if self._device is None:
+            self._device = device
+        points = torch.from_numpy(self.leaf_centers()).to(device)
+        points = points + torch.tensor(center, dtype=torch.float32, device=device)
+        use_view = bool(getattr(model, "use_view", False))
+        if use_view:
+            direction = torch.tensor([float(v) for v in view], dtype=torch.float32, device=device)
+        was_training = model.training
+        model.eval()
+        baked = []
+        try:
+            with torch.no_grad():
+                for start in range(0, points.shape[0], batch_size):
+                    batch = points[start:start + batch_size].contiguous()
+                    if use_view:
+                        logits = model(batch, direction.expand(batch.shape[0], 3).contiguous())
+                    else:
+                        logits = model(batch)
+                    baked.append(ops.octree_bake(logits.reshape(-1, 4).to(torch.float32)
+                                                 .contiguous()))
+        finally:
+            model.train(was_training)
+        tree = OcTree(self._scale, self._node_index, self._leaf_index,
+                      torch.cat(baked).cpu().numpy())
+        tree._device = self._device
+        tree._center = center
+        return tree
+
     def render_image(self, sampler, index: int, center=None, t_min: float = 0.0,
-                     background=(0, 0, 0), shading: str = "flat", include_depth: bool = False):
+                     background=(0, 0, 0), shading: str = "flat", include_depth: bool = False,
+                     mode: str = "first_hit", min_transmittance: float = 0.0):
         """(H,W,3) uint8 frame of the sampler's camera ``index % num_cameras``, as
         ``Raycaster.render_image`` returns it; with ``include_depth`` also the (H,W) float32
         alpha and depth maps.  Every ray of the camera is used -- the octree is the geometry, the
         sampler's validity mask is not applied.  ``center``: the root cube's centre in the
-        sampler's frame; defaults to ``tree.center``, which a loaded tree does not have."""
+        sampler's frame; defaults to ``tree.center``, which a loaded tree does not have.
+        ``mode``: ``"first_hit"`` (``render``) or ``"volume"`` (``render_volume`` of a baked tree,
+        with ``min_transmittance``; its shading is ``"flat"``)."""
+        if mode not in ("first_hit", "volume"):
+            raise ValueError("OcTree.render_image: mode is 'first_hit' or 'volume', got %r"
+                             % (mode,))
+        if mode == "volume":
+            if shading != "flat":
+                raise ValueError("OcTree.render_image: mode='volume' has no face shading; "
+                                 "shading must be 'flat', got %r" % (shading,))
+            self._check_volume(min_transmittance)
         if center is None:
             center = self._center
         if center is None:
@@ -368,8 +466,13 @@ class OcTree:
         rays = slice(first, first + sampler.rays_per_camera)
         shift = torch.tensor([float(c) for c in center], dtype=torch.float32,
                              device=sampler.starts.device)
-        color, alpha, depth = self.render(sampler.starts[rays] - shift, sampler.directions[rays],
-                                          t_min, background, shading)
+        if mode == "volume":
+            color, alpha, depth = self.render_volume(sampler.starts[rays] - shift,
+                                                     sampler.directions[rays], t_min, background,
+                                                     min_transmittance)
+        else:
+            color, alpha, depth = self.render(sampler.starts[rays] - shift,
+                                              sampler.directions[rays], t_min, background, shading)
         pixels = torch.arange(sampler.rays_per_camera, dtype=torch.int64, device=color.device)
         image = ops.to_image(color, pixels, sampler.image_width, sampler.image_height)
         image = image.cpu().numpy()

@@ -671,3 +671,42 @@ def octree_render(starts: torch.Tensor, directions: torch.Tensor, scale: float, 
     if want_hit:
         return color, alpha, depth_out, hit
     return color, alpha, depth_out
+
+
+def octree_render_volume(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                         node_index: torch.Tensor, leaf_index: torch.Tensor,
+                         leaf_data: torch.Tensor, t_min: float = 0.0,
+                         background=(0.0, 0.0, 0.0), min_transmittance: float = 0.0):
+    """K15.  leaf_data (L,C) float32 with C >= 4, [r, g, b, sigma, ...] as ``octree_bake`` makes
+    them -> color (N,3), alpha (N), depth (N), composited front to back over the leaves every ray
+    crosses after ``t_min``; the walk of a ray ends once its transmittance is at or below
+    ``min_transmittance``."""
+    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
+        raise ValueError("octree render_volume: leaf_data must be (num_leaves, C >= 4), got %s "
+                         "for %d leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
+    if not 0.0 <= min_transmittance < 1.0:
+        raise ValueError("octree render_volume: min_transmittance must lie in [0, 1), got %r"
+                         % (min_transmittance,))
+    n = starts.shape[0]
+    dev = starts.device
+    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n > 0:
+        r, g, b = [float(v) for v in background]
+        _call("ffn_octree_render_volume", *_walk_args(starts, directions, scale, depth,
+                                                      node_index, leaf_index),
+              c_f(t_min), _dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1]), c_f(r),
+              c_f(g), c_f(b), c_f(min_transmittance), _dev(color), _dev(alpha), _dev(depth_out))
+    return color, alpha, depth_out
+
+
+def octree_bake(logits: torch.Tensor) -> torch.Tensor:
+    """Raw model logits (L,4) [r, g, b, sigma] -> (L,4) float32 [sigmoid(r), sigmoid(g),
+    sigmoid(b), softplus(sigma)], the activations of the compositing kernels bit for bit."""
+    if logits.dim() != 2 or logits.shape[1] != 4:
+        raise ValueError("octree bake: logits must be (L,4), got %s" % (tuple(logits.shape),))
+    out = torch.empty_like(logits)
+    if logits.shape[0] > 0:
+        _call("ffn_octree_bake", _dev(logits, name="logits"), c_i64(logits.shape[0]), _dev(out))
+    return out

@@ -871,6 +871,43 @@ int ffn_octree_render(const float* starts, const float* directions, int64_t n, f
                       int shading, float* color, float* alpha, float* depth_out, int64_t* leaf,
                       float* t_hit, int8_t* face, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K15  volume render of the K13 walk (csrc/octree_walk.hip, a fourth mode of the same kernel): the
+ * render of a BAKED tree, whose leaves hold a colour and a density (ffn_octree_bake).  No
+ * counterpart in the reference.  Arguments up to num_leaves as for K13; leaf_data
+ * (num_leaves, channels) f32 with channels >= 4: [r, g, b, sigma, ...], sigma per unit of world
+ * length.  With channels == 4 a leaf is one aligned 16-byte load (leaf_data 16-byte aligned).
+ *
+ * Per ray, in f32, every operation rounded on its own (no fused multiply-add):
+ *   norm = sqrtf(dx*dx + dy*dy + dz*dz);  T = 1, C = 0, w_best = 0, depth = 0
+ *   for every region of the walk that is a leaf with t_exit > t_min (the predicate of
+ *   ffn_octree_spans and K14), in walk order:
+ *     t0    = max(t, t_min)                      t = the region's entry
+ *     L     = (t_exit - t0) * norm
+ *     sigma = fmaxf(leaf_data[leaf, 3], 0)       a NaN density counts as 0
+ *     a     = 1 - expf(-(sigma * L))
+ *     w     = T * a
+ *     C    += w * leaf_data[leaf, 0..2]
+ *     if w > w_best: w_best = w, depth = t0      strict: the first leaf wins a tie
+ *     T     = T * (1 - a)
+ *     the walk ends when T <= min_transmittance
+ *   color = C + T * (bg_r, bg_g, bg_b);  alpha = 1 - T;  depth (0 when no leaf had w > 0)
+ * The density is per world length, so the result does not depend on the length of the directions.
+ * A ray that misses the cube, or that K13 cannot follow, gives the background, alpha 0 and depth 0,
+ * as K14 does.  t_min must not be NaN; 0 <= min_transmittance < 1.  The trip bound of K13 holds. */
+int ffn_octree_render_volume(const float* starts, const float* directions, int64_t n, float scale,
+                             int depth, const int64_t* node_index, int64_t num_nodes,
+                             const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                             const float* leaf_data, int channels, float bg_r, float bg_g,
+                             float bg_b, float min_transmittance, float* color, float* alpha,
+                             float* depth_out, void* stream);
+
+/* Raw model logits (num_leaves,4) [r, g, b, sigma] -> leaf_data (num_leaves,4) f32
+ * [sigmoid(r), sigmoid(g), sigmoid(b), softplus(sigma)] (softplus: beta 1, threshold 20): the
+ * activations of the compositing kernels (ray_caster.py:66-74), bit for bit.  Both arrays are
+ * 16-byte aligned. */
+int ffn_octree_bake(const float* logits, int64_t num_leaves, float* leaf_data, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

@@ -1,7 +1,8 @@
 """Renders a voxelized model (the ``.npz`` octree of ``scripts/voxelize_model.py``) from a
 dataset's cameras with the first-hit walk (kernel K14): one PNG per camera and its PSNR against
 the camera's ground-truth image.  No counterpart in the reference, which shows the leaf cubes
-through scenepic (voxelize_model.py:90-110).
+through scenepic (voxelize_model.py:90-110).  ``--mode volume`` composites a tree that
+``scripts/bake_octree.py`` has baked along the whole ray instead (kernel K15).
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.
@@ -31,6 +32,10 @@ RENDER_OCTREE = [
     ("--shading", dict(choices=["flat", "faces"], default="flat")),
     ("--background", dict(type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("R", "G", "B"))),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
+    ("--mode", dict(choices=["first-hit", "volume"], default="first-hit",
+                    help="first-hit: one opaque colour per cell; volume: composite a baked tree")),
+    ("--min-transmittance", dict(type=float, default=0.0,
+                                 help="volume: a ray ends once its transmittance is at or below")),
 ]
 
 
@@ -85,7 +90,9 @@ def main():
     values = []
     for camera in range(sampler.num_cameras):
         image = tree.render_image(sampler, camera, center=args.center,
-                                  background=args.background, shading=args.shading)
+                                  background=args.background, shading=args.shading,
+                                  mode=args.mode.replace("-", "_"),
+                                  min_transmittance=args.min_transmittance)
         _cli.save_png(os.path.join(args.output_dir, "frame_{:05d}.png".format(camera)), image)
         truth = ground_truth(dataset.images[camera], resolution, args.background)
         values.append(psnr(image, truth))
