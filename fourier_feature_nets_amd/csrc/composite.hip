@@ -356,6 +356,30 @@ octree_bake_kernel(const float4* __restrict__ logits, int64_t count, float4* __r
     out[i] = make_float4(sigmoid_f(l.x), sigmoid_f(l.y), sigmoid_f(l.z), softplus_torch(l.w));
 }
 
+// K16b, first half (the rest is in octree.hip): the logits of one chunk of finest cells -> the
+// same activations, and per cell whether sigma * side > tau.  Here for the reason above: the
+// data of a density tree has to be what ffn_octree_bake makes of the same logits, bit for bit.
+// A NaN density fails the comparison: the cell is not kept.
+__global__ void __launch_bounds__(256)
+octree_density_flags_kernel(const float4* __restrict__ logits, int64_t count, float tau, float side,
+                            float4* __restrict__ activated, uint8_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float4 l = logits[i];
+    const float sigma = softplus_torch(l.w);
+    activated[i] = make_float4(sigmoid_f(l.x), sigmoid_f(l.y), sigmoid_f(l.z), sigma);
+    flags[i] = sigma * side > tau;
+}
+
+// called by ffn_octree_density_select (octree.hip), which has checked the arguments
+__attribute__((visibility("hidden")))
+void launch_octree_density_flags(const float* logits, int64_t count, float tau, float side,
+                                 float* activated, uint8_t* flags, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((count + 255) / 256);
+    hipLaunchKernelGGL(octree_density_flags_kernel, dim3(blocks), dim3(256), 0, stream,
+                       (const float4*)logits, count, tau, side, (float4*)activated, flags);
+}
+
 }  // namespace ffn
 
 using namespace ffn;

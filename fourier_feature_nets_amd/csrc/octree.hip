@@ -389,6 +389,116 @@ leaf_geometry_kernel(const int64_t* __restrict__ leaf_index, int64_t num_leaves,
     depths[i] = d;
 }
 
+// ------------------------------------------------------------------------------- K16
+// Density octree from a trained model: the finest grid is evaluated densely, chunk by chunk, in
+// path-code order.  No reference counterpart (voxelize_model.py builds from depth renders only).
+//
+//   K16a cell_centers     code -> centre of the finest cell, the chain of K12k plus the cube centre
+//   K16b density_scatter  stable compaction of the cells octree_density_flags_kernel
+//                         (composite.hip, where the activations live) has flagged
+//   K16c merge_*          one bottom-up coarsening pass over the code-sorted leaf list
+__global__ void __launch_bounds__(kOctThreads)
+cell_centers_kernel(int64_t first_code, int64_t count, float ox, float oy, float oz, float scale,
+                    int depth, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= count) return;
+    const int64_t code = first_code + i;
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
+    for (int level = 1; level < depth; ++level) {
+        const int child = (int)((code >> (3 * (depth - 1 - level))) & 7);
+        half *= 0.5f;
+        cx = (child & 4) ? cx + half : cx - half;
+        cy = (child & 2) ? cy + half : cy - half;
+        cz = (child & 1) ? cz + half : cz - half;
+    }
+    out[i * 3 + 0] = cx + ox;
+    out[i * 3 + 1] = cy + oy;
+    out[i * 3 + 2] = cz + oz;
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+density_scatter_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ offsets,
+                       const float4* __restrict__ activated, int64_t first_code, int64_t count,
+                       int* __restrict__ codes_out, float4* __restrict__ data_out) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= count || !flags[i]) return;
+    const int64_t o = offsets[i];   // < number of set flags <= count: inside the (count, .) outputs
+    codes_out[o] = (int)(first_code + i);
+    data_out[o] = activated[i];
+}
+
+// mean of eight siblings: the f32 sum of children 0 .. 7 in that order, times 1/8
+__device__ __forceinline__ float4 sibling_mean(const float4* __restrict__ d) {
+#pragma clang fp contract(off)
+    float4 s = d[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        const float4 v = d[k];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    return make_float4(s.x * 0.125f, s.y * 0.125f, s.z * 0.125f, s.w * 0.125f);
+}
+
+// merge[i] = entry i heads eight siblings, all leaves of `level`, that lie within the tolerances
+// of their mean.  A NaN in the group fails a comparison: no merge.
+__global__ void __launch_bounds__(kOctThreads)
+merge_heads_kernel(const int* __restrict__ codes, const int* __restrict__ levels,
+                   const float4* __restrict__ data, int64_t n, int level, int depth, float rgb_tol,
+                   float sigma_tol, uint8_t* __restrict__ merge) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const int shift = 3 * (depth - 1 - level);
+    bool ok = false;
+    if (i + 7 < n && levels[i] == level && (((uint32_t)codes[i] >> shift) & 7u) == 0u) {
+        bool all = true;
+#pragma unroll
+        for (int k = 1; k < 8; ++k) all = all && levels[i + k] == level;
+        if (all && ((uint32_t)codes[i + 7] >> shift) == ((uint32_t)codes[i] >> shift) + 7u) {
+            const float4 m = sibling_mean(data + i);
+            ok = true;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float4 v = data[i + k];
+                ok = ok && fabsf(v.x - m.x) <= rgb_tol && fabsf(v.y - m.y) <= rgb_tol &&
+                     fabsf(v.z - m.z) <= rgb_tol && fabsf(v.w - m.w) <= sigma_tol;
+            }
+        }
+    }
+    merge[i] = ok;
+}
+
+// an entry stays unless it is child 1 .. 7 of a merging group; its head is then j entries before
+__global__ void __launch_bounds__(kOctThreads)
+merge_flags_kernel(const int* __restrict__ codes, const int* __restrict__ levels,
+                   const uint8_t* __restrict__ merge, int64_t n, int level, int depth,
+                   uint8_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n) return;
+    const int j = (int)(((uint32_t)codes[i] >> (3 * (depth - 1 - level))) & 7u);
+    flags[i] = !(levels[i] == level && j > 0 && i >= j && merge[i - j]);
+}
+
+__global__ void __launch_bounds__(kOctThreads)
+merge_scatter_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ offsets,
+                     const uint8_t* __restrict__ merge, const int* __restrict__ codes,
+                     const int* __restrict__ levels, const float4* __restrict__ data, int64_t n,
+                     int* __restrict__ codes_out, int* __restrict__ levels_out,
+                     float4* __restrict__ data_out) {
+    const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const int64_t o = offsets[i];   // < number of set flags <= n
+    const bool head = merge[i];     // then i + 7 < n
+    codes_out[o] = codes[i];        // child 0 of its parent: the parent's left-aligned code
+    levels_out[o] = head ? levels[i] - 1 : levels[i];
+    data_out[o] = head ? sibling_mean(data + i) : data[i];
+}
+
+// composite.hip: activations and sigma * side > tau of one chunk
+void launch_octree_density_flags(const float* logits, int64_t count, float tau, float side,
+                                 float* activated, uint8_t* flags, hipStream_t stream);
+
 }  // namespace ffn
 
 using namespace ffn;
@@ -507,4 +617,77 @@ extern "C" int ffn_octree_leaf_geometry(const int64_t* leaf_index, int64_t num_l
     hipLaunchKernelGGL(leaf_geometry_kernel, dim3(oct_blocks(num_leaves)), dim3(kOctThreads), 0,
                        (hipStream_t)stream, leaf_index, num_leaves, scale, centers, depths);
     return check_launch("ffn_octree_leaf_geometry");
+}
+
+static inline bool misaligned16(const void* a, const void* b) {
+    return (((uintptr_t)a | (uintptr_t)b) & 15) != 0;
+}
+
+extern "C" int ffn_octree_cell_centers(int64_t first_code, int64_t count, float center_x,
+                                       float center_y, float center_z, float scale, int depth,
+                                       float* out, void* stream) {
+    if (depth < 1 || depth > kOctMaxDepth)
+        return fail_arg("ffn_octree_cell_centers: shape (1 <= depth <= 11)");
+    if (count < 1 || count > kOctMaxPoints || first_code < 0 ||
+        first_code + count > ((int64_t)1 << (3 * (depth - 1))))
+        return fail_arg("ffn_octree_cell_centers: shape (count >= 1, codes inside "
+                        "[0, 8^(depth-1)))");
+    if (!out) return fail_arg("ffn_octree_cell_centers: null argument");
+    hipLaunchKernelGGL(cell_centers_kernel, dim3(oct_blocks(count)), dim3(kOctThreads), 0,
+                       (hipStream_t)stream, first_code, count, center_x, center_y, center_z, scale,
+                       depth, out);
+    return check_launch("ffn_octree_cell_centers");
+}
+
+extern "C" int ffn_octree_density_select(const float* logits, int64_t first_code, int64_t count,
+                                         float tau, float side, int depth, uint8_t* flags,
+                                         int* offsets, int* tile_sums, float* activated,
+                                         int* codes_out, float* data_out, int* total,
+                                         void* stream) {
+    if (depth < 1 || depth > kOctMaxDepth)
+        return fail_arg("ffn_octree_density_select: shape (1 <= depth <= 11)");
+    if (count < 1 || count > kOctMaxPoints || first_code < 0 ||
+        first_code + count > ((int64_t)1 << (3 * (depth - 1))))
+        return fail_arg("ffn_octree_density_select: shape (count >= 1, codes inside "
+                        "[0, 8^(depth-1)))");
+    if (!logits || !flags || !offsets || !tile_sums || !activated || !codes_out || !data_out ||
+        !total)
+        return fail_arg("ffn_octree_density_select: null argument");
+    if (misaligned16(logits, activated) || misaligned16(data_out, nullptr))
+        return fail_arg("ffn_octree_density_select: logits, activated and data_out must be "
+                        "16-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    launch_octree_density_flags(logits, count, tau, side, activated, flags, s);
+    if (int err = scan_flags(flags, count, tile_sums, offsets, total, s)) return err;
+    hipLaunchKernelGGL(density_scatter_kernel, dim3(oct_blocks(count)), dim3(kOctThreads), 0, s,
+                       flags, offsets, (const float4*)activated, first_code, count, codes_out,
+                       (float4*)data_out);
+    return check_launch("ffn_octree_density_select");
+}
+
+extern "C" int ffn_octree_merge_level(const int* codes, const int* levels, const float* data,
+                                      int64_t n, int level, int depth, float rgb_tol,
+                                      float sigma_tol, uint8_t* merge, uint8_t* flags, int* offsets,
+                                      int* tile_sums, int* codes_out, int* levels_out,
+                                      float* data_out, int* total, void* stream) {
+    if (depth < 2 || depth > kOctMaxDepth || level < 1 || level > depth - 1)
+        return fail_arg("ffn_octree_merge_level: shape (2 <= depth <= 11, 1 <= level < depth)");
+    if (n < 1 || n > kOctMaxPoints) return fail_arg("ffn_octree_merge_level: shape (1 <= n < 2^31)");
+    if (!(rgb_tol >= 0.0f) || !(sigma_tol >= 0.0f))   // NaN fails too
+        return fail_arg("ffn_octree_merge_level: tolerances must be >= 0");
+    if (!codes || !levels || !data || !merge || !flags || !offsets || !tile_sums || !codes_out ||
+        !levels_out || !data_out || !total)
+        return fail_arg("ffn_octree_merge_level: null argument");
+    if (misaligned16(data, data_out))
+        return fail_arg("ffn_octree_merge_level: data and data_out must be 16-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(oct_blocks(n)), block(kOctThreads);
+    hipLaunchKernelGGL(merge_heads_kernel, grid, block, 0, s, codes, levels, (const float4*)data, n,
+                       level, depth, rgb_tol, sigma_tol, merge);
+    hipLaunchKernelGGL(merge_flags_kernel, grid, block, 0, s, codes, levels, merge, n, level, depth,
+                       flags);
+    if (int err = scan_flags(flags, n, tile_sums, offsets, total, s)) return err;
+    hipLaunchKernelGGL(merge_scatter_kernel, grid, block, 0, s, flags, offsets, merge, codes, levels,
+                       (const float4*)data, n, codes_out, levels_out, (float4*)data_out);
+    return check_launch("ffn_octree_merge_level");
 }

@@ -460,12 +460,14 @@ def octree_surface_points(alpha: torch.Tensor, depth: torch.Tensor, starts: torc
     """K12a-d.  alpha (N), depth (N), starts (N,3), directions (N,3), color (N,C) or None ->
     positions (N,3), colors (N,C) or None, count (int32 scalar on the device): the first
     ``count`` rows hold ``starts + directions * depth`` / ``color`` of the rays with
-    ``alpha > threshold``, in ray order."""
+    ``alpha > threshold``, in ray order; the other rows are zero."""
     n = alpha.shape[0]
     dev = alpha.device
     channels = 0 if color is None else color.shape[1]
-    out_pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    out_col = None if color is None else torch.empty((n, channels), dtype=torch.float32, device=dev)
+    # zeros, not empty: the rows past ``count`` are returned too, and whatever an earlier tensor
+    # left in recycled memory (a NaN, say) must not show up in them
+    out_pos = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    out_col = None if color is None else torch.zeros((n, channels), dtype=torch.float32, device=dev)
     count = torch.zeros((), dtype=torch.int32, device=dev)
     if n == 0:
         return out_pos, out_col, count
@@ -710,3 +712,62 @@ def octree_bake(logits: torch.Tensor) -> torch.Tensor:
     if logits.shape[0] > 0:
         _call("ffn_octree_bake", _dev(logits, name="logits"), c_i64(logits.shape[0]), _dev(out))
     return out
+
+
+def octree_cell_centers(first_code: int, count: int, center, scale: float, depth: int,
+                        device) -> torch.Tensor:
+    """K16a.  -> (count,3) float32 on ``device``: the centres of the finest cells (level
+    ``depth - 1``) with the path codes ``first_code .. first_code + count - 1``, shifted by the
+    cube's ``center``."""
+    out = torch.empty((count, 3), dtype=torch.float32, device=device)
+    _call("ffn_octree_cell_centers", c_i64(first_code), c_i64(count), c_f(center[0]),
+          c_f(center[1]), c_f(center[2]), c_f(scale), c_i(depth), _dev(out))
+    return out
+
+
+def octree_density_select(logits: torch.Tensor, first_code: int, tau: float, side: float,
+                          depth: int):
+    """K16b.  logits (N,4) of the cells ``first_code .. first_code + N - 1`` -> codes (K) int32 and
+    data (K,4) float32 of the cells with ``softplus(sigma) * side > tau``, in code order; data is
+    what ``octree_bake`` makes of the kept rows.  Reads the count back once."""
+    if logits.dim() != 2 or logits.shape[1] != 4:
+        raise ValueError("octree density select: logits must be (N,4), got %s"
+                         % (tuple(logits.shape),))
+    n = logits.shape[0]
+    dev = logits.device
+    activated = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    codes = torch.empty((n,), dtype=torch.int32, device=dev)
+    data = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_density_select", _dev(logits, name="logits"), c_i64(first_code), c_i64(n),
+          c_f(tau), c_f(side), c_i(depth), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          _dev(tiles, torch.int32), _dev(activated), _dev(codes, torch.int32), _dev(data),
+          _dev(total, torch.int32))
+    k = int(total.item())
+    return codes[:k].clone(), data[:k].clone()
+
+
+def octree_merge_level(codes: torch.Tensor, levels: torch.Tensor, data: torch.Tensor, level: int,
+                       depth: int, rgb_tol: float, sigma_tol: float):
+    """K16c.  One coarsening pass over the code-sorted leaf list (codes (N) int32 left-aligned to
+    the finest level, levels (N) int32, data (N,4) float32): eight sibling leaves of ``level``
+    within the tolerances of their mean become their parent.  -> the new (codes, levels, data).
+    Reads the count back once."""
+    n = codes.shape[0]
+    dev = codes.device
+    if levels.shape != (n,) or data.shape != (n, 4):
+        raise ValueError("octree merge level: codes (N), levels (N) and data (N,4) disagree")
+    merge = torch.empty((n,), dtype=torch.uint8, device=dev)
+    codes_out, levels_out, data_out = (torch.empty_like(codes), torch.empty_like(levels),
+                                       torch.empty_like(data))
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_merge_level", _dev(codes, torch.int32, "codes"),
+          _dev(levels, torch.int32, "levels"), _dev(data, name="data"), c_i64(n), c_i(level),
+          c_i(depth), c_f(rgb_tol), c_f(sigma_tol), _dev(merge, torch.uint8),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
+          _dev(codes_out, torch.int32), _dev(levels_out, torch.int32), _dev(data_out),
+          _dev(total, torch.int32))
+    k = int(total.item())
+    return codes_out[:k].clone(), levels_out[:k].clone(), data_out[:k].clone()

@@ -908,6 +908,47 @@ int ffn_octree_render_volume(const float* starts, const float* directions, int64
  * 16-byte aligned. */
 int ffn_octree_bake(const float* logits, int64_t num_leaves, float* leaf_data, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K16  density octree from a trained model (csrc/octree.hip; the activations of K16b in
+ * csrc/composite.hip).  The finest grid (level depth - 1, 2^(depth-1) cells per axis) is evaluated
+ * densely in chunks of consecutive path codes (the codes of ffn_octree_path_codes), the cells with
+ * sigma * side > tau become leaves, and siblings that agree are merged bottom-up.  No reference
+ * counterpart: voxelize_model.py builds the one-cell shell of the depth renders only. */
+
+/* K16a.  out (count,3): centre of the finest cell of code first_code + i, the f32 chain
+ * +-scale / 2^k from 0 as ffn_octree_leaf_geometry makes it for the cell's id, then one f32 add of
+ * the cube centre.  0 <= first_code, first_code + count <= 8^(depth-1).  No reference
+ * counterpart. */
+int ffn_octree_cell_centers(int64_t first_code, int64_t count, float center_x, float center_y,
+                            float center_z, float scale, int depth, float* out, void* stream);
+
+/* K16b.  logits (count,4): the model at the centres of K16a.  activated (count,4) = what
+ * ffn_octree_bake makes of them (the same device functions, bit for bit); a cell is kept iff
+ * activated[i, 3] * side > tau in f32 (strict; a NaN density is not kept).  The kept cells, in code
+ * order (stable): codes_out (int32) and data_out (count,4), *total (device) of them in arrays of
+ * count entries.  flags / offsets / tile_sums as for ffn_octree_surface_points
+ * (ffn_octree_scan_tiles(count) tile sums).  logits, activated and data_out are 16-byte aligned.
+ * No reference counterpart. */
+int ffn_octree_density_select(const float* logits, int64_t first_code, int64_t count, float tau,
+                              float side, int depth, uint8_t* flags, int* offsets, int* tile_sums,
+                              float* activated, int* codes_out, float* data_out, int* total,
+                              void* stream);
+
+/* K16c.  One coarsening pass over a leaf list sorted by code: codes (n) left-aligned to the finest
+ * level (a leaf of level l has zeros below its 3 l bits), levels (n), data (n,4).  Entry i heads a
+ * group when its child index at `level` is 0, entries i .. i+7 are all leaves of `level` and entry
+ * i+7 is child 7 of the same parent.  The group becomes its parent (level - 1, the head's code,
+ * the mean) when |x - mean| <= rgb_tol for the first three channels and <= sigma_tol for the
+ * fourth, for all eight; mean = the f32 sum of children 0 .. 7 in that order, times 0.125f, no
+ * fused multiply-add.  A NaN in the group: no merge.  Everything else is copied; the output stays
+ * sorted; *total (device) entries.  merge and flags hold n bytes; offsets / tile_sums as above.
+ * 1 <= level <= depth - 1; tolerances >= 0; data and data_out 16-byte aligned.  Related to, but no
+ * replacement of, OcTree.prune (octree.py:629-665), which merges unconditionally. */
+int ffn_octree_merge_level(const int* codes, const int* levels, const float* data, int64_t n,
+                           int level, int depth, float rgb_tol, float sigma_tol, uint8_t* merge,
+                           uint8_t* flags, int* offsets, int* tile_sums, int* codes_out,
+                           int* levels_out, float* data_out, int* total, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 
