@@ -11,6 +11,7 @@ from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
 from .octree import OcTree
+from .octree_fit import FitLogEntry, OctreeField, fit_octree
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
@@ -36,8 +37,8 @@ from .voxels import VoxelProgram, Voxels
 
 __version__ = "0.1.0"
 
-__all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FourierFeatureMLP", "FrameSink",
+__all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OcTree", "OccupancyGrid", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
+           "OcTree", "OccupancyGrid", "OctreeField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
-           "exponential_lr_decay", "linspace", "load_model", "orbit"]
+           "exponential_lr_decay", "fit_octree", "linspace", "load_model", "orbit"]

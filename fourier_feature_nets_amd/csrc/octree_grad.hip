@@ -1,0 +1,423 @@
+// K17b  Per-leaf sums of the gradient walk's entries (K17a, csrc/octree_walk.hip) without float
+// atomics, and K17c, the projection after the optimiser step.
+//
+// K17a leaves one entry per (ray, taken leaf): a float4 (d rgb, d sigma) and the leaf's number,
+// ray-major at offsets[ray] + k -- a place that depends on the inputs only.  d_leaf_data[l] is the
+// sum of the entries of leaf l.  As K10b (csrc/voxels.hip) this is the store-and-sum form: the
+// entries are brought into a fixed order, leaf by leaf, and added in a fixed tree, so that the
+// same inputs give the same bits on every call.  Unlike K10b-4, which ranks an entry by reading
+// its whole list, nothing here reads a list longer than a fixed chunk -- one leaf may be taken by
+// every ray (a root-only tree):
+//
+//   K17b-1 grad_scan_*      exclusive scan of the per-ray counts (the three kernels of K10b-2);
+//                           the total E is read back once, to hold it against the caller's
+//                           workspace and to size the launches below
+//   K17b-2 grad_sort_*      stable LSD radix sort of (leaf, entry) by leaf, 8 bits a pass,
+//                           ceil(bits(L - 1) / 8) passes: per tile of 1024 entries a digit histogram
+//                           (integer LDS atomics), a scan of the digit-major (digit, tile) table,
+//                           and a scatter in which an entry's place among its tile's equal digits
+//                           comes from wave ballots and a 16 x 256 table of per-wave counts.  Stable,
+//                           so the entries of a leaf stay in ray order.
+//   K17b-3 grad_bounds      first and one-past-last sorted position of every leaf that has entries
+//   K17b-4 grad_reduce      level j: every run of kGradChunk consecutive partial sums of a leaf
+//                           into one, at the leaf's own range of the other buffer; ceil(log16 n)
+//                           levels, since a ray takes a leaf once
+//   K17b-5 grad_finish      every row of d_leaf_data: the leaf's sum, or zeros
+//
+// Integer atomics appear in the tile histogram only, where their order does not matter.
+#include "common.h"
+#include "octree_grad.h"
+
+namespace ffn {
+
+constexpr int kGradChunk = 16;          // partial sums added by one thread
+constexpr int kGradScanBlock = 4096;    // elements per workgroup of the scan (256 x 16)
+constexpr int kSortThreads = 256;
+constexpr int kSortItems = 4;
+constexpr int kSortTile = kSortThreads * kSortItems;
+constexpr int kSortGroups = kSortItems * (kSortThreads / 64);   // (item, wave) pairs of a tile
+static const int64_t kGradMaxEntries = ((int64_t)1 << 31) - 1;
+
+// ---------------------------------------------------------------------------------- K17b-1
+__global__ void __launch_bounds__(256)
+grad_scan_sums_kernel(const int32_t* __restrict__ values, int64_t m,
+                      int32_t* __restrict__ block_sums) {
+    __shared__ int lds[4];
+    const int64_t first = (int64_t)blockIdx.x * kGradScanBlock + threadIdx.x * 16;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (first + k < m) s += values[first + k];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane_id() == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// one workgroup: exclusive scan of the block sums in place, and the total
+__global__ void __launch_bounds__(1024)
+grad_scan_top_kernel(int32_t* __restrict__ block_sums, int blocks, int32_t* __restrict__ total) {
+    __shared__ int part[1024];
+    int carry = 0;
+    for (int t0 = 0; t0 < blocks; t0 += 1024) {
+        const int t = t0 + threadIdx.x;
+        const int v = t < blocks ? block_sums[t] : 0;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (int off = 1; off < 1024; off <<= 1) {
+            const int add = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (t < blocks) block_sums[t] = carry + part[threadIdx.x] - v;
+        carry += part[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && total != nullptr) *total = carry;
+}
+
+// in place: values[i] becomes the sum of everything before it
+__global__ void __launch_bounds__(256)
+grad_scan_apply_kernel(int32_t* values, int64_t m, const int32_t* __restrict__ block_sums) {
+    __shared__ int wave_tot[4];
+    const int64_t first = (int64_t)blockIdx.x * kGradScanBlock + threadIdx.x * 16;
+    int local[16];
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        local[k] = first + k < m ? values[first + k] : 0;
+        s += local[k];
+    }
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    int inc = s;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    int run = block_sums[blockIdx.x] + inc - s;
+    for (int w = 0; w < wave; ++w) run += wave_tot[w];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (first + k < m) values[first + k] = run;
+        run += local[k];
+    }
+}
+
+static void exclusive_scan(int32_t* values, int64_t m, int32_t* block_sums, int32_t* total,
+                           hipStream_t st) {
+    const int blocks = (int)((m + kGradScanBlock - 1) / kGradScanBlock);
+    hipLaunchKernelGGL(grad_scan_sums_kernel, dim3(blocks), dim3(256), 0, st, values, m, block_sums);
+    hipLaunchKernelGGL(grad_scan_top_kernel, dim3(1), dim3(1024), 0, st, block_sums, blocks, total);
+    hipLaunchKernelGGL(grad_scan_apply_kernel, dim3(blocks), dim3(256), 0, st, values, m, block_sums);
+}
+
+// ---------------------------------------------------------------------------------- K17b-2
+// table[digit * tiles + tile]: how many entries of the tile have that digit
+__global__ void __launch_bounds__(kSortThreads)
+grad_sort_hist_kernel(const int32_t* __restrict__ keys, int32_t e, int shift, int32_t tiles,
+                      int32_t* __restrict__ table) {
+    __shared__ int hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kSortItems; ++j) {
+        const int64_t i = (int64_t)blockIdx.x * kSortTile + j * kSortThreads + threadIdx.x;
+        if (i < e) atomicAdd(&hist[(keys[i] >> shift) & 255], 1);
+    }
+    __syncthreads();
+    table[(int64_t)threadIdx.x * tiles + blockIdx.x] = hist[threadIdx.x];
+}
+
+// table: scanned.  The order inside a tile is (item, wave, lane), which is the entry order.
+// order_in null: the entries are still where K17a put them (the first pass).
+__global__ void __launch_bounds__(kSortThreads)
+grad_sort_scatter_kernel(const int32_t* __restrict__ keys_in, const int32_t* __restrict__ order_in,
+                         int32_t e, int shift, int32_t tiles, const int32_t* __restrict__ table,
+                         int32_t* __restrict__ keys_out, int32_t* __restrict__ order_out) {
+    __shared__ int groups[kSortGroups][256];
+    for (int g = 0; g < kSortGroups; ++g) groups[g][threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint64_t below = (1ull << lane) - 1ull;
+    int key[kSortItems], rank[kSortItems];
+#pragma unroll
+    for (int j = 0; j < kSortItems; ++j) {
+        const int64_t i = (int64_t)blockIdx.x * kSortTile + j * kSortThreads + threadIdx.x;
+        const bool valid = i < e;
+        key[j] = valid ? keys_in[i] : 0;
+        const int digit = (key[j] >> shift) & 255;
+        // the lanes of this wave that hold the same digit
+        uint64_t peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (digit >> b) & 1;
+            const uint64_t set = __ballot(valid && bit);
+            peers &= bit ? set : ~set;
+        }
+        rank[j] = __popcll(peers & below);
+        if (valid && rank[j] == 0) groups[j * 4 + wave][digit] = __popcll(peers);
+    }
+    __syncthreads();
+    // per digit: the groups' counts into the groups' starts
+    int run = 0;
+    for (int g = 0; g < kSortGroups; ++g) {
+        const int c = groups[g][threadIdx.x];
+        groups[g][threadIdx.x] = run;
+        run += c;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kSortItems; ++j) {
+        const int64_t i = (int64_t)blockIdx.x * kSortTile + j * kSortThreads + threadIdx.x;
+        if (i < e) {
+            const int digit = (key[j] >> shift) & 255;
+            const int32_t at = table[(int64_t)digit * tiles + blockIdx.x] +
+                               groups[j * 4 + wave][digit] + rank[j];
+            if (at >= 0 && at < e) {          // always, for a table made from these keys
+                keys_out[at] = key[j];
+                order_out[at] = order_in != nullptr ? order_in[i] : (int32_t)i;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------- K17b-3
+__global__ void __launch_bounds__(256)
+grad_bounds_kernel(const int32_t* __restrict__ keys, int32_t e, int32_t num_leaves,
+                   int32_t* __restrict__ seg_lo, int32_t* __restrict__ seg_hi) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= e) return;
+    const int32_t l = keys[p];
+    if (l < 0 || l >= num_leaves) return;
+    if (p == 0 || keys[p - 1] != l) seg_lo[l] = (int32_t)p;
+    if (p == e - 1 || keys[p + 1] != l) seg_hi[l] = (int32_t)p + 1;
+}
+
+// ---------------------------------------------------------------------------------- K17b-4
+// order: level 0 only, where src is K17a's ray-major values
+__global__ void __launch_bounds__(256)
+grad_reduce_kernel(const int32_t* __restrict__ keys, const int32_t* __restrict__ order,
+                   const float4* __restrict__ src, float4* __restrict__ dst, int32_t e,
+                   int32_t num_leaves, const int32_t* __restrict__ seg_lo,
+                   const int32_t* __restrict__ seg_hi, int level) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= e) return;
+    const int32_t l = keys[p];
+    if (l < 0 || l >= num_leaves) return;
+    const int lo = seg_lo[l];
+    int len = seg_hi[l] - lo;
+    for (int j = 0; j < level; ++j) len = (len + kGradChunk - 1) / kGradChunk;
+    const int q = (int)p - lo;
+    if (q < 0 || q >= (len + kGradChunk - 1) / kGradChunk) return;
+    const int first = lo + q * kGradChunk;
+    const int end = min(first + kGradChunk, lo + len);
+    float4 acc = order != nullptr ? src[order[first]] : src[first];
+    for (int i = first + 1; i < end; ++i) {
+        const float4 v = order != nullptr ? src[order[i]] : src[i];
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    dst[lo + q] = acc;
+}
+
+// ---------------------------------------------------------------------------------- K17b-5
+__global__ void __launch_bounds__(256)
+grad_finish_kernel(const float4* __restrict__ sums, const int32_t* __restrict__ seg_lo,
+                   const int32_t* __restrict__ seg_hi, int64_t num_leaves,
+                   float4* __restrict__ d_leaf_data) {
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= num_leaves) return;
+    const int lo = seg_lo[l];
+    d_leaf_data[l] = seg_hi[l] > lo ? sums[lo] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// ---------------------------------------------------------------------------------- K17c
+__global__ void __launch_bounds__(256)
+octree_project_kernel(float4* __restrict__ leaf_data, int64_t num_leaves) {
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= num_leaves) return;
+    float4 v = leaf_data[l];
+    // fmaxf / fminf return the other operand for a NaN: NaN -> 0
+    v.x = fminf(fmaxf(v.x, 0.0f), 1.0f);
+    v.y = fminf(fmaxf(v.y, 0.0f), 1.0f);
+    v.z = fminf(fmaxf(v.z, 0.0f), 1.0f);
+    v.w = fmaxf(v.w, 0.0f);
+    leaf_data[l] = v;
+}
+
+struct GradWorkspace {
+    int32_t* ray_slots;     // n + 1
+    float* ray_color;       // 3n
+    float* ray_trans;       // n
+    int32_t* block_sums;    // of the longer of the two scans
+    float4* values;         // capacity, ray-major; then the odd reduce levels' target
+    float4* sums;           // capacity
+    int32_t* keys[2];       // capacity each
+    int32_t* order[2];      // capacity each
+    int32_t* table;         // 256 * tiles
+    int32_t* seg_lo;        // num_leaves
+    int32_t* seg_hi;        // num_leaves
+};
+
+static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
+static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, GradWorkspace* ws,
+                           char* base) {
+    const int64_t tiles = (capacity + kSortTile - 1) / kSortTile;
+    const int64_t longest = 256 * tiles > n ? 256 * tiles : n;
+    const int64_t blocks = (longest + kGradScanBlock - 1) / kGradScanBlock + 1;
+    const int64_t sizes[13] = {4 * (n + 1), 12 * n, 4 * n, 4 * blocks, 16 * capacity, 16 * capacity,
+                               4 * capacity, 4 * capacity, 4 * capacity, 4 * capacity,
+                               4 * 256 * tiles, 4 * num_leaves, 4 * num_leaves};
+    GradWorkspace scratch;
+    GradWorkspace* w = ws != nullptr ? ws : &scratch;
+    void** slots[13] = {(void**)&w->ray_slots, (void**)&w->ray_color, (void**)&w->ray_trans,
+                        (void**)&w->block_sums, (void**)&w->values, (void**)&w->sums,
+                        (void**)&w->keys[0], (void**)&w->keys[1], (void**)&w->order[0],
+                        (void**)&w->order[1], (void**)&w->table, (void**)&w->seg_lo,
+                        (void**)&w->seg_hi};
+    int64_t off = 0;
+    for (int r = 0; r < 13; ++r) {
+        *slots[r] = base != nullptr ? base + off : nullptr;
+        off += align256(sizes[r]);
+    }
+    return off;
+}
+
+static inline bool grad_shape(int64_t n, int64_t num_leaves, int64_t max_entries) {
+    return n >= 1 && n < ((int64_t)1 << 31) && num_leaves >= 1 && num_leaves < ((int64_t)1 << 31) &&
+           max_entries >= 0 && max_entries <= kGradMaxEntries;
+}
+
+}  // namespace ffn
+
+using namespace ffn;
+
+extern "C" int64_t ffn_octree_grad_workspace_bytes(int64_t n, int64_t num_leaves,
+                                                   int64_t max_entries) {
+    if (!grad_shape(n, num_leaves, max_entries)) {
+        fail_arg("ffn_octree_grad_workspace_bytes: shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, "
+                 "0 <= max_entries < 2^31)");
+        return -1;
+    }
+    return grad_layout(n, num_leaves, max_entries, nullptr, nullptr);
+}
+
+extern "C" int ffn_octree_render_volume_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    void* stream) {
+    const char* who = "ffn_octree_render_volume_backward";
+    if (entries != nullptr) *entries = -1;
+    if (channels < 4) return fail_arg("ffn_octree_render_volume_backward: channels >= 4");
+    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_backward: t_min is NaN");
+    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
+        return fail_arg("ffn_octree_render_volume_backward: 0 <= min_transmittance < 1");
+    if (!leaf_data || !d_color || !d_alpha || !d_leaf_data || !workspace)
+        return fail_arg("ffn_octree_render_volume_backward: null argument");
+    if (int err = octree_check_walk_args(who, starts, directions, n, depth, node_index, num_nodes,
+                                         leaf_index, num_leaves))
+        return err;
+    if (channels == 4 && ((uintptr_t)leaf_data & 15) != 0)
+        return fail_arg("ffn_octree_render_volume_backward: leaf_data with 4 channels must be "
+                        "16-byte aligned");
+    if (((uintptr_t)d_leaf_data & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+        return fail_arg("ffn_octree_render_volume_backward: d_leaf_data and workspace must be "
+                        "16-byte aligned");
+    // a ray crosses at most 3 * 2^(depth-1) + 1 regions: the entry offsets stay below 2^31
+    if (!grad_shape(n, num_leaves, max_entries) ||
+        n * (3 * ((int64_t)1 << (depth - 1)) + 1) > kGradMaxEntries)
+        return fail_arg("ffn_octree_render_volume_backward: shape (n * (3 * 2^(depth-1) + 1) < 2^31: "
+                        "split the rays)");
+    if (workspace_bytes < grad_layout(n, num_leaves, max_entries, nullptr, nullptr))
+        return fail_arg("ffn_octree_render_volume_backward: workspace too small for max_entries");
+    hipStream_t st = (hipStream_t)stream;
+    GradWorkspace ws;
+    grad_layout(n, num_leaves, max_entries, &ws, (char*)workspace);
+
+    // K17a, first walk: counts, C and T_{n+1} per ray
+    if (int err = octree_grad_walk(who, starts, directions, n, scale, depth, node_index, num_nodes,
+                                   leaf_index, num_leaves, t_min, leaf_data, channels, bg_r, bg_g,
+                                   bg_b, min_transmittance, d_color, d_alpha, ws.ray_slots,
+                                   ws.ray_color, ws.ray_trans, ws.values, ws.keys[0], 0, st))
+        return err;
+    exclusive_scan(ws.ray_slots, n, ws.block_sums, ws.ray_slots + n, st);
+    int32_t total = 0;
+    hipError_t copied = hipMemcpyAsync(&total, ws.ray_slots + n, 4, hipMemcpyDeviceToHost, st);
+    if (copied == hipSuccess) copied = hipStreamSynchronize(st);
+    if (copied != hipSuccess) {
+        set_error(who, copied);
+        return (int)copied;
+    }
+    if (entries != nullptr) *entries = total;
+    if (total < 0 || total > max_entries) {
+        char text[160];
+        snprintf(text, sizeof text, "%s: the rays take %lld leaves, the workspace holds %lld entries",
+                 who, (long long)total, (long long)max_entries);
+        return fail_arg(text);
+    }
+    const int32_t e = total;
+    if (e == 0) {
+        (void)hipMemsetAsync(d_leaf_data, 0, 16 * num_leaves, st);
+        return check_launch(who);
+    }
+    // K17a, second walk: the entries
+    if (int err = octree_grad_walk(who, starts, directions, n, scale, depth, node_index, num_nodes,
+                                   leaf_index, num_leaves, t_min, leaf_data, channels, bg_r, bg_g,
+                                   bg_b, min_transmittance, d_color, d_alpha, ws.ray_slots,
+                                   ws.ray_color, ws.ray_trans, ws.values, ws.keys[0], 1, st))
+        return err;
+
+    int bits = 0;
+    while (bits < 31 && ((int64_t)1 << bits) < num_leaves) ++bits;
+    const int passes = (bits + 7) / 8;
+    const int32_t tiles = (e + kSortTile - 1) / kSortTile;
+    const int32_t* keys = ws.keys[0];
+    const int32_t* order = nullptr;
+    for (int pass = 0; pass < passes; ++pass) {
+        int32_t* keys_out = ws.keys[(pass + 1) & 1];
+        int32_t* order_out = ws.order[(pass + 1) & 1];
+        hipLaunchKernelGGL(grad_sort_hist_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys, e,
+                           8 * pass, tiles, ws.table);
+        exclusive_scan(ws.table, (int64_t)256 * tiles, ws.block_sums, nullptr, st);
+        hipLaunchKernelGGL(grad_sort_scatter_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys,
+                           order, e, 8 * pass, tiles, ws.table, keys_out, order_out);
+        keys = keys_out;
+        order = order_out;
+    }
+    const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
+    (void)hipMemsetAsync(ws.seg_lo, 0, 4 * num_leaves, st);
+    (void)hipMemsetAsync(ws.seg_hi, 0, 4 * num_leaves, st);
+    hipLaunchKernelGGL(grad_bounds_kernel, dim3(over_entries), dim3(256), 0, st, keys, e,
+                       (int32_t)num_leaves, ws.seg_lo, ws.seg_hi);
+    // a ray takes a leaf once: no list is longer than min(n, e)
+    const int64_t longest = n < e ? n : e;
+    int levels = 1;
+    for (int64_t reach = kGradChunk; reach < longest; reach *= kGradChunk) ++levels;
+    const float4* src = ws.values;
+    for (int level = 0; level < levels; ++level) {
+        float4* dst = (level & 1) ? ws.values : ws.sums;
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3(over_entries), dim3(256), 0, st, keys,
+                           level == 0 ? order : (const int32_t*)nullptr, src, dst, e,
+                           (int32_t)num_leaves, ws.seg_lo, ws.seg_hi, level);
+        src = dst;
+    }
+    hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0,
+                       st, src, ws.seg_lo, ws.seg_hi, num_leaves, (float4*)d_leaf_data);
+    return check_launch(who);
+}
+
+extern "C" int ffn_octree_project(float* leaf_data, int64_t num_leaves, void* stream) {
+    if (!leaf_data) return fail_arg("ffn_octree_project: null argument");
+    if (num_leaves < 1) return fail_arg("ffn_octree_project: num_leaves >= 1");
+    if (((uintptr_t)leaf_data & 15) != 0)
+        return fail_arg("ffn_octree_project: leaf_data must be 16-byte aligned");
+    hipLaunchKernelGGL(octree_project_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256),
+                       0, (hipStream_t)stream, (float4*)leaf_data, num_leaves);
+    return check_launch("ffn_octree_project");
+}

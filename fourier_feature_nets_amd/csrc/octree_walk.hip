@@ -45,7 +45,30 @@
 // a handful of VALU operations per leaf on top of one 16-byte load, and nothing is written per
 // stop.  The walk ends early once the transmittance is at or below a threshold.  No counterpart in
 // the reference.
+//
+// K17a  Gradient walk: the backward of K15, a fifth mode of the same kernel (same integer stepping,
+// same t0, chord, sigma = max(data[leaf,3], 0) and early end, same f32 operations in the same
+// order, so the colour it accumulates has the forward's bits).  With x_k = sigma_k L_k,
+// a_k = 1 - exp(-x_k), T_k = prod_{j<k}(1 - a_j), w_k = T_k a_k, C = sum w_k c_k + T_{n+1} bg and
+// upstream gradients g_C, g_A, taken leaf k of a ray gets ONE entry
+//     d c_k     = w_k g_C
+//     d sigma_k = L_k [ g_C . (T_{k+1} c_k - S_k) + g_A T_{n+1} ],   S_k = C - sum_{j<=k} w_j c_j
+// (0 where the stored density is negative or NaN; it passes at exactly 0).  C and T_{n+1} come from
+// a FIRST WALK of this same mode, not from the forward's outputs: the entries of a ray need a
+// place in the entry list, so its taken leaves have to be counted before anything is written, and
+// the walk that counts them composites on the way (phase 0: count, C, T_{n+1} per ray; phase 1,
+// after a scan of the counts: the entries, ray-major at offsets[ray] + k).  T_{n+1} is then the
+// transmittance itself and not 1 - alpha.  The per-leaf sums are K17b (csrc/octree_grad.hip).
+// The mode reuses the parameters the other modes leave idle (see grad_walk below) so that their
+// instantiations are compiled from unchanged code.
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), kGrad: 61 VGPRs, 99 SGPRs,
+// 0 bytes of scratch, 0 spills, 0 bytes of LDS, occupancy 8 waves/SIMD; the other four instantiations
+// compile to the instructions they had before the mode existed (38 / 40 / 50 / 53 VGPRs).
+// Divergence and dependent reads: as K15, a wave runs as long as its longest ray (one wave per
+// workgroup) and waits on the binary searches; the entry stores are one 16-byte and one 4-byte
+// store per lane and leaf into the lane's own run of the list, off the dependent chain.
 #include "common.h"
+#include "octree_grad.h"
 
 namespace ffn {
 
@@ -136,12 +159,17 @@ struct FirstHit {
     float* depth;
 };
 
-enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3 };
+enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
 // kFirstHit: the first of those leaves, where the loop ends (K14).
 // kVolume:   colour, opacity and depth composited front to back over those leaves (K15).
+// kGrad:     K17a.  The idle parameters carry its buffers: max_length the phase (0 count, 1 emit),
+//            span_hit the int32 ray counts (phase 0, written) / offsets (phase 1, n + 1 read),
+//            first.color / first.alpha the per-ray C and T_{n+1} (written in phase 0, read in
+//            phase 1), span_in / span_out the upstream d_color / d_alpha, t_stops the entries'
+//            float4 values and leaves their int32 leaf numbers.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -191,8 +219,26 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
+    const float norm = kMode == kVolume || kMode == kGrad ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
+    // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
+    const bool emit = kMode == kGrad && max_length != 0;
+    int32_t* ray_slots = reinterpret_cast<int32_t*>(span_hit);
+    float4* entry_values = reinterpret_cast<float4*>(t_stops);
+    int32_t* entry_leaves = reinterpret_cast<int32_t*>(leaves);
+    int taken = 0, base = 0, mine = 0;
+    float c_r = 0.0f, c_g = 0.0f, c_b = 0.0f, t_end = 0.0f, g_r = 0.0f, g_g = 0.0f, g_b = 0.0f,
+          g_a = 0.0f;
+    if (emit) {
+        base = ray_slots[r];
+        mine = ray_slots[r + 1] - base;
+        // a ray without entries has nothing to walk for
+        if (mine <= 0) return;
+        c_r = first.color[r * 3 + 0]; c_g = first.color[r * 3 + 1]; c_b = first.color[r * 3 + 2];
+        t_end = first.alpha[r];
+        g_r = span_in[r * 3 + 0]; g_g = span_in[r * 3 + 1]; g_b = span_in[r * 3 + 2];
+        g_a = span_out[r];
+    }
     for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
         int64_t at;
         const bool interior = level < known ||
@@ -243,6 +289,34 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 acc_r += w * lr; acc_g += w * lg; acc_b += w * lb;
                 if (w > w_best) { w_best = w; t_best = t0; }
                 trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
+        } else if (kMode == kGrad) {
+            if (leaf >= 0 && t_exit > t_min) {
+                float lr, lg, lb, ls;
+                if (first.channels == 4) {
+                    const float4 v = reinterpret_cast<const float4*>(first.leaf_data)[leaf];
+                    lr = v.x; lg = v.y; lb = v.z; ls = v.w;
+                } else {
+                    const float* data = first.leaf_data + leaf * first.channels;
+                    lr = data[0]; lg = data[1]; lb = data[2]; ls = data[3];
+                }
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                acc_r += w * lr; acc_g += w * lg; acc_b += w * lb;
+                trans = trans * (1.0f - a);                    // T_{k+1}
+                if (emit && taken < mine) {
+                    const float behind = g_r * (trans * lr - (c_r - acc_r)) +
+                                         g_g * (trans * lg - (c_g - acc_g)) +
+                                         g_b * (trans * lb - (c_b - acc_b));
+                    const float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    entry_values[base + taken] = make_float4(w * g_r, w * g_g, w * g_b, ds);
+                    entry_leaves[base + taken] = (int32_t)leaf;
+                }
+                ++taken;
                 if (trans <= first.min_transmittance) break;
             }
         } else if (kSpans) {
@@ -298,6 +372,14 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
         first.alpha[r] = 1.0f - trans;
         first.depth[r] = t_best;
+    } else if (kMode == kGrad) {
+        if (!emit) {
+            ray_slots[r] = taken;
+            first.color[r * 3 + 0] = acc_r + trans * first.bg_r;
+            first.color[r * 3 + 1] = acc_g + trans * first.bg_g;
+            first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
+            first.alpha[r] = trans;
+        }
     } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
         const float side = 2.0f * scale / (float)cells;
@@ -329,6 +411,35 @@ static int check_walk_args(const char* who, const float* starts, const float* di
         return fail_arg(text);
     }
     return 0;
+}
+
+// K17a, launched by ffn_octree_render_volume_backward (csrc/octree_grad.hip), which has checked
+// the arguments
+int octree_grad_walk(const char* who, const float* starts, const float* directions, int64_t n,
+                     float scale, int depth, const int64_t* node_index, int64_t num_nodes,
+                     const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                     const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+                     float min_transmittance, const float* d_color, const float* d_alpha,
+                     int32_t* ray_slots, float* ray_color, float* ray_trans, float4* entry_values,
+                     int32_t* entry_leaves, int phase, hipStream_t stream) {
+    FirstHit first{};
+    first.leaf_data = leaf_data; first.channels = channels;
+    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
+    first.min_transmittance = min_transmittance;
+    first.color = ray_color; first.alpha = ray_trans;
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<kGrad>, dim3(blocks), dim3(kWalkThreads), 0, stream,
+                       starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                       num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min, 0.0f,
+                       (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
+    return check_launch(who);
+}
+
+int octree_check_walk_args(const char* who, const float* starts, const float* directions,
+                           int64_t n, int depth, const int64_t* node_index, int64_t num_nodes,
+                           const int64_t* leaf_index, int64_t num_leaves) {
+    return check_walk_args(who, starts, directions, n, depth, node_index, num_nodes, leaf_index,
+                           num_leaves);
 }
 
 }  // namespace ffn

@@ -56,6 +56,11 @@ public signatures are the reference's, so files and calling code go both ways.  
   sample (width 1e10, opacity 1) and an octree frame shows the background.  Kernel times under
   rocprofv3 and ``--precision bf16x6`` are unmeasured.
 
+* fitting lives in ``octree_fit.py`` (K17): ``OctreeField`` makes the leaf values of a baked tree a
+  parameter whose forward is ``render_volume`` bit for bit and whose backward is the gradient walk
+  plus deterministic per-leaf sums; ``fit_octree`` optimises them against a dataset's images.  The
+  structure of the tree is not changed.  No counterpart in the reference.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
 ``bake``, ``build_from_model``, ``render_volume``, ``leaf_centers`` and ``leaf_depths`` run on the

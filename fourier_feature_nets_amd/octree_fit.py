@@ -1,0 +1,215 @@
+"""Fitting a baked octree to the training images through its own volume renderer (K17).
+
+A density tree (``OcTree.build_from_model`` / ``bake``) holds the model's value at one point per
+leaf.  ``OctreeField`` makes the leaf values a parameter: its forward is ``OcTree.render_volume``
+(K15) bit for bit, its backward the gradient walk K17a and the per-leaf sums K17b
+(``csrc/octree_walk.hip``, ``csrc/octree_grad.hip``), deterministic and without float atomics.
+``fit_octree`` is the training loop on the kernels of the NeRF path: K6 (loss and its gradient),
+K17a + K17b, K7 (clip and Adam) on the flat ``(4 L,)`` buffer, K17c (projection onto
+``0 <= rgb <= 1``, ``sigma >= 0``).  The structure of the tree does not change.  No counterpart in
+the reference.
+"""
+
+import time
+from typing import List, NamedTuple, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .octree import OcTree
+from .utils import RenderResult
+
+FitLogEntry = NamedTuple("FitLogEntry", [("step", int), ("loss", float), ("val_psnr", float)])
+
+# Raycaster.fit's clipping (ops.clip_adam's defaults)
+CLIP_VALUE = 0.1
+MAX_NORM = 0.1
+# of 1e-3, 1e-2 and 1e-1 tried on the depth-8 density tree of the opaque-ball model, the fastest
+# descent of the training loss; 1e-1 diverges (README, profiles/r15_octree_fit_microbench.json)
+LEARNING_RATE = 1e-2
+
+
+class _RenderVolume(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, field, starts, directions, t_min, background, min_transmittance):
+        tree = field._tree
+        color, alpha, depth = ops.octree_render_volume(
+            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
+            tree._on_device("leaf_index"), data, t_min, background, min_transmittance)
+        ctx.field = field
+        ctx.args = (t_min, background, min_transmittance)
+        ctx.save_for_backward(data, starts, directions)
+        ctx.mark_non_differentiable(depth)
+        return color, alpha, depth
+
+    @staticmethod
+    def backward(ctx, d_color, d_alpha, _):
+        data, starts, directions = ctx.saved_tensors
+        n = starts.shape[0]
+        if d_color is None:
+            d_color = torch.zeros((n, 3), dtype=torch.float32, device=starts.device)
+        if d_alpha is None:
+            d_alpha = torch.zeros((n,), dtype=torch.float32, device=starts.device)
+        grad = ctx.field.backward(starts, directions, d_color.contiguous(), d_alpha.contiguous(),
+                                  *ctx.args, data=data)
+        return grad, None, None, None, None, None, None
+
+
+class OctreeField(torch.nn.Module):
+    """The leaf values of a baked tree as a parameter.  ``data`` (L,4) float32 ``[r, g, b, sigma]``
+    on the device, initialised from ``tree.leaf_data()``."""
+
+    def __init__(self, tree: OcTree, center=None, device=None):
+        super().__init__()
+        tree._check_volume(0.0)
+        values = np.asarray(tree.leaf_data())[:, :4]      # further channels are never rendered
+        if center is None:
+            center = tree.center
+        self.center = None if center is None else tuple(float(c) for c in center)
+        if self.center is not None and len(self.center) != 3:
+            raise ValueError("OctreeField: center has three components")
+        if device is not None:
+            tree._device = torch.device(device)
+        self._tree = tree
+        self.data = torch.nn.Parameter(torch.from_numpy(
+            np.ascontiguousarray(values, dtype=np.float32)).to(tree._dev()))
+        self.workspace = ops.OctreeGradWorkspace()
+
+    def forward(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
+                min_transmittance: float = 0.0) -> RenderResult:
+        """``tree.render_volume`` of the current data, bit for bit, as device tensors;
+        differentiable with respect to ``data`` (colour and alpha; depth has no gradient).
+        starts, directions: (N,3) float32 device tensors relative to the root cube's centre."""
+        self._tree._check_volume(min_transmittance)
+        starts, directions, _ = self._tree._rays(starts, directions)
+        background = tuple(float(v) for v in background)
+        return RenderResult(*_RenderVolume.apply(self.data, self, starts, directions, float(t_min),
+                                                 background, float(min_transmittance)))
+
+    def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
+                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
+        """K17a + K17b: d(data) (L,4) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
+        tree = self._tree
+        return ops.octree_render_volume_backward(
+            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
+            tree._on_device("leaf_index"), self.data.detach() if data is None else data, d_color,
+            d_alpha, float(t_min), background, float(min_transmittance), self.workspace, out)
+
+    def tree(self) -> OcTree:
+        """A new ``OcTree`` with the same structure and centre and the current data."""
+        old = self._tree
+        new = OcTree(old._scale, old._node_index, old._leaf_index,
+                     self.data.detach().cpu().numpy().copy())
+        new._device = old._device
+        new._center = self.center
+        return new
+
+
+def _validation_psnr(field: OctreeField, dataset, t_min, min_transmittance) -> float:
+    """-10 log10 of the mean colour-MSE + alpha_weight * alpha-MSE over every ray of the
+    dataset's cameras, camera by camera."""
+    sampler = dataset.sampler
+    shift = torch.tensor(field.center, dtype=torch.float32, device=sampler.starts.device)
+    alphas = dataset._gt_alphas()
+    aw = float(dataset.alpha_weight) if alphas is not None else 0.0
+    per = sampler.rays_per_camera
+    total = torch.zeros((2,), dtype=torch.float32, device=sampler.starts.device)
+    with torch.no_grad():
+        for camera in range(sampler.num_cameras):
+            rays = torch.arange(camera * per, (camera + 1) * per, dtype=torch.int64,
+                                device=sampler.starts.device)
+            out = field(sampler.starts[rays] - shift, sampler.directions[rays], t_min, (0, 0, 0),
+                        min_transmittance)
+            sums, _, _ = ops.mse_loss(out.color, out.alpha, dataset.colors, alphas, rays, 0.0, 0.0,
+                                      want_grad=False)
+            total += sums
+    count = per * sampler.num_cameras
+    total = total.cpu().numpy().astype(np.float64)
+    mean = total[0] / (3 * count) + aw * total[1] / count
+    return float(-10.0 * np.log10(max(mean, 1e-12)))
+
+
+def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 4096,
+               learning_rate: float = LEARNING_RATE, num_steps: int = 2000,
+               report_interval: int = 500, center=None, t_min: float = 0.0,
+               min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
+               max_norm: float = MAX_NORM, seed: int = 20080524,
+               verbose: bool = True) -> Tuple[OcTree, List[FitLogEntry]]:
+    """Optimises the leaf values of a baked ``tree`` against the images of ``train_dataset`` (an
+    ``ImageDataset``) through ``render_volume`` with a black background; -> (a new ``OcTree`` of the
+    same structure, log).  One step: a batch of ray ids from a seeded shuffle of EVERY ray of every
+    camera (as ``render_image``, the sampler's validity mask is not applied), the forward on
+    ``sampler.starts - center``, K6 with the dataset's colours, alphas and ``alpha_weight``, K17a +
+    K17b, K7 with ``clip_value`` / ``max_norm`` (defaults: those of ``Raycaster.fit``), K17c.  The
+    log holds ``(step, loss, val_psnr)`` -- every step's training loss, ``val_psnr`` (over all rays
+    of ``val_dataset``'s cameras) at steps below 10 and multiples of ``report_interval``, else NaN
+    -- and report steps are printed as ``Raycaster.fit`` prints them.  The only host
+    synchronisation of a step is the read-back inside K17b; the losses are fetched at the end."""
+    batch_size, num_steps = int(batch_size), int(num_steps)
+    if batch_size < 1 or num_steps < 0 or int(report_interval) < 1:
+        raise ValueError("fit_octree: batch_size >= 1, num_steps >= 0, report_interval >= 1")
+    if not learning_rate > 0:
+        raise ValueError("fit_octree: learning_rate must be positive, got %r" % (learning_rate,))
+    tree._check_volume(min_transmittance)
+    if center is None:
+        center = tree.center
+    if center is None:
+        raise ValueError("fit_octree: a loaded tree does not know the centre of its root cube "
+                         "(the file has no place for it); pass center=")
+    sampler = train_dataset.sampler
+    dev = sampler.starts.device
+    field = OctreeField(tree, center, dev)
+    data = field.data.detach()
+    flat = data.view(-1)
+    grads = torch.empty_like(data)
+    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
+    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=dev)
+    shift = torch.tensor(field.center, dtype=torch.float32, device=dev)
+    alphas = train_dataset._gt_alphas()
+    aw = float(train_dataset.alpha_weight) if alphas is not None else 0.0
+    num_rays = sampler.num_cameras * sampler.rays_per_camera
+    generator = torch.Generator(device=dev)
+    generator.manual_seed(int(seed))
+    tr = tree
+    node_index, leaf_index = tr._on_device("node_index"), tr._on_device("leaf_index")
+    losses, reports = [], {}
+    start_time = time.time()
+    step = 0
+    while step < num_steps:
+        order = torch.randperm(num_rays, generator=generator, device=dev)
+        for start in range(0, num_rays, batch_size):
+            if step >= num_steps:
+                break
+            rays = order[start:start + batch_size]
+            count = int(rays.numel())
+            starts = (sampler.starts[rays] - shift).contiguous()
+            directions = sampler.directions[rays].contiguous()
+            color, alpha, _ = ops.octree_render_volume(
+                starts, directions, tr._scale, tr.depth, node_index, leaf_index, data,
+                float(t_min), (0.0, 0.0, 0.0), float(min_transmittance))
+            sums, d_color, d_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas, rays,
+                                                  1.0 / (3 * count), aw / count)
+            losses.append(ops.loss_value(sums, count, aw))
+            field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
+                           min_transmittance, data=data, out=grads)
+            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
+                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
+            ops.octree_project(data)
+            if val_dataset is not None and (step < 10 or step % report_interval == 0):
+                reports[step] = _validation_psnr(field, val_dataset, t_min, min_transmittance)
+                if verbose:
+                    now = time.time()
+                    per_step = (now - start_time) / step if step >= report_interval else 0
+                    eta = "N/A" if not per_step else time.strftime(
+                        "%a, %d %b %Y %H:%M:%S +0000",
+                        time.gmtime(now + (num_steps - step) * per_step))
+                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
+                          "loss: {:2f}".format(float(losses[-1].item())),
+                          "val_psnr: {:2f}".format(reports[step]),
+                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
+            step += 1
+    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
+    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
+           for k in range(len(values))]
+    return field.tree(), log

@@ -703,6 +703,104 @@ def octree_render_volume(starts: torch.Tensor, directions: torch.Tensor, scale: 
     return color, alpha, depth_out
 
 
+def octree_grad_workspace_bytes(n: int, num_leaves: int, max_entries: int) -> int:
+    """Bytes of workspace ``octree_render_volume_backward`` needs for ``n`` rays, ``num_leaves``
+    leaves and up to ``max_entries`` (ray, taken leaf) pairs."""
+    fn = _lib.load().ffn_octree_grad_workspace_bytes
+    fn.restype = ctypes.c_int64
+    size = fn(c_i64(n), c_i64(num_leaves), c_i64(max_entries))
+    if size < 0:
+        raise _lib.FfnError("ffn_octree_grad_workspace_bytes failed: %s"
+                            % _lib.load().ffn_last_error_string().decode())
+    return int(size)
+
+
+class OctreeGradWorkspace:
+    """The workspace of K17b, kept between calls and grown when the rays take more leaves than
+    it holds (``entries_per_ray`` is the first guess)."""
+
+    def __init__(self, entries_per_ray: int = 32):
+        self.entries_per_ray = int(entries_per_ray)
+        self.max_entries = 0
+        self.buffer = None
+        self.shape = None
+        self.entries = 0            # of the last call
+
+    def fit(self, n: int, num_leaves: int, device, at_least: int = 0):
+        same = (self.buffer is not None and self.shape == (n, num_leaves)
+                and self.buffer.device == device)
+        if same and self.max_entries >= max(at_least, 1):
+            return
+        if at_least > 0:
+            self.entries_per_ray = max(self.entries_per_ray, -(-at_least // n))
+        want = max(at_least, n * self.entries_per_ray, 1024)
+        need = octree_grad_workspace_bytes(n, num_leaves, want)
+        if self.buffer is None or self.buffer.numel() * 4 < need or self.buffer.device != device:
+            self.buffer = None              # release before the larger one is taken
+            self.buffer = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=device)
+        self.max_entries = want
+        self.shape = (n, num_leaves)
+
+
+def octree_render_volume_backward(starts: torch.Tensor, directions: torch.Tensor, scale: float,
+                                  depth: int, node_index: torch.Tensor, leaf_index: torch.Tensor,
+                                  leaf_data: torch.Tensor, d_color: torch.Tensor,
+                                  d_alpha: torch.Tensor, t_min: float = 0.0,
+                                  background=(0.0, 0.0, 0.0), min_transmittance: float = 0.0,
+                                  workspace: Optional[OctreeGradWorkspace] = None,
+                                  d_leaf_data: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K17a + K17b, the backward of ``octree_render_volume``: d_color (N,3), d_alpha (N) ->
+    d_leaf_data (L,4) float32 [d r, d g, d b, d sigma], every row written, deterministic (no float
+    atomics).  One read-back (the number of (ray, taken leaf) pairs) per call; when the workspace
+    turns out too small for them it is grown and the call repeated."""
+    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
+        raise ValueError("octree render_volume_backward: leaf_data must be (num_leaves, C >= 4), "
+                         "got %s for %d leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
+    if not 0.0 <= min_transmittance < 1.0:
+        raise ValueError("octree render_volume_backward: min_transmittance must lie in [0, 1), "
+                         "got %r" % (min_transmittance,))
+    n, leaves = starts.shape[0], leaf_index.numel()
+    if d_color.shape != (n, 3) or d_alpha.shape != (n,):
+        raise ValueError("octree render_volume_backward: d_color must be (N,3) and d_alpha (N,)")
+    dev = starts.device
+    if d_leaf_data is None:
+        d_leaf_data = torch.empty((leaves, 4), dtype=torch.float32, device=dev)
+    if d_leaf_data.shape != (leaves, 4):
+        raise ValueError("octree render_volume_backward: d_leaf_data must be (num_leaves, 4)")
+    if n == 0:
+        return d_leaf_data.zero_()
+    if workspace is None:
+        workspace = OctreeGradWorkspace()
+    r, g, b = [float(v) for v in background]
+    entries = c_i64(-1)
+    workspace.fit(n, leaves, dev)
+    for attempt in range(2):
+        try:
+            _call("ffn_octree_render_volume_backward",
+                  *_walk_args(starts, directions, scale, depth, node_index, leaf_index),
+                  c_f(t_min), _dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1]), c_f(r),
+                  c_f(g), c_f(b), c_f(min_transmittance), _dev(d_color, name="d_color"),
+                  _dev(d_alpha, name="d_alpha"), _dev(workspace.buffer),
+                  c_i64(workspace.buffer.numel() * 4), c_i64(workspace.max_entries),
+                  _dev(d_leaf_data), ctypes.byref(entries))
+            break
+        except _lib.FfnError:
+            if attempt == 1 or entries.value <= workspace.max_entries:
+                raise
+            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
+    workspace.entries = int(entries.value)
+    return d_leaf_data
+
+
+def octree_project(leaf_data: torch.Tensor) -> torch.Tensor:
+    """K17c, in place on leaf_data (L,4): rgb clamped to [0, 1], sigma to [0, inf), NaN -> 0."""
+    if leaf_data.dim() != 2 or leaf_data.shape[1] != 4:
+        raise ValueError("octree project: leaf_data must be (L,4), got %s" % (tuple(leaf_data.shape),))
+    if leaf_data.shape[0] > 0:
+        _call("ffn_octree_project", _dev(leaf_data, name="leaf_data"), c_i64(leaf_data.shape[0]))
+    return leaf_data
+
+
 def octree_bake(logits: torch.Tensor) -> torch.Tensor:
     """Raw model logits (L,4) [r, g, b, sigma] -> (L,4) float32 [sigmoid(r), sigmoid(g),
     sigmoid(b), softplus(sigma)], the activations of the compositing kernels bit for bit."""

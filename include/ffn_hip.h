@@ -949,6 +949,41 @@ int ffn_octree_merge_level(const int* codes, const int* levels, const float* dat
                            uint8_t* flags, int* offsets, int* tile_sums, int* codes_out,
                            int* levels_out, float* data_out, int* total, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K17  backward of the K15 volume render, for fitting a baked tree to images (K17a: a fifth mode
+ * of the K13 kernel in csrc/octree_walk.hip; K17b, K17c: csrc/octree_grad.hip).  No counterpart in
+ * the reference.  Arguments up to min_transmittance as for ffn_octree_render_volume, with the
+ * same taken leaves, t0, L, sigma, a, w and T (the same f32 operations in the same order).  With
+ * T_k the transmittance in front of taken leaf k = 1..n, w_k = T_k a_k, C = sum w_k c_k +
+ * T_{n+1} bg, and the upstream gradients g_C = d_color[ray] (n,3), g_A = d_alpha[ray] (n):
+ *   d c_k     = w_k g_C
+ *   d sigma_k = L_k [ g_C . (T_{k+1} c_k - S_k) + g_A T_{n+1} ],   S_k = C - sum_{j<=k} w_j c_j
+ * d sigma_k is 0 where the stored density is negative or NaN (it passes where it is exactly 0).
+ * Depth has no gradient, leaves after an early end get nothing, and neither do the background,
+ * the rays or rays that K13 cannot follow.  d_leaf_data (num_leaves,4) f32, 16-byte aligned:
+ * every row is written, the sum of the leaf's contributions in a fixed order without float
+ * atomics (the same inputs give the same bits on every call), zeros for a leaf no ray took.
+ *
+ * C and T_{n+1} come from a first walk (which also counts the taken leaves of every ray), not
+ * from the forward's outputs.  The call reads the total number of (ray, taken leaf) entries back
+ * ONCE (it synchronises the stream) and stores it in *entries (host, may be null).  The
+ * workspace (16-byte aligned, ffn_octree_grad_workspace_bytes(n, num_leaves, max_entries) bytes)
+ * holds max_entries of them: with more the call fails, *entries says how many there are, and
+ * nothing has been written to d_leaf_data.  n * (3 * 2^(depth-1) + 1) < 2^31. */
+int64_t ffn_octree_grad_workspace_bytes(int64_t n, int64_t num_leaves, int64_t max_entries);
+
+int ffn_octree_render_volume_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    void* stream);
+
+/* K17c.  The projection after an optimiser step, in place on leaf_data (num_leaves,4) f32,
+ * 16-byte aligned: r, g, b = min(max(x, 0), 1), sigma = max(x, 0); a NaN becomes 0. */
+int ffn_octree_project(float* leaf_data, int64_t num_leaves, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

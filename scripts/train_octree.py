@@ -1,0 +1,65 @@
+"""Fits the leaf values of a baked octree (``scripts/bake_octree.py``, or a density tree of
+``OcTree.build_from_model``) to the training images through the tree's own volume renderer
+(``fit_octree``: kernels K15, K6, K17a-c, K7), and writes the fitted tree in the reference's file
+format, ready for ``scripts/render_octree.py --mode volume``.  The structure of the tree does not
+change.  No counterpart in the reference.
+
+The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
+form ``--center`` takes.
+
+    python scripts/train_octree.py tree.npz data.npz out.npz --center X Y Z
+"""
+
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scripts import _cli  # noqa: E402
+
+# (flag, kwargs), as the tables of scripts/_cli.py
+TRAIN_OCTREE = [
+    ("tree_path", dict(help="Path to the baked octree NPZ")),
+    ("data_path", dict(help="Path to the dataset NPZ")),
+    ("output_path", dict(help="Path to the fitted octree NPZ")),
+    ("--center", dict(type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"),
+                      help="Centre of the tree's root cube, as voxelize_model.py prints it")),
+    ("--steps", dict(type=int, default=2000, help="Number of optimiser steps")),
+    ("--lr", dict(type=float, default=None, help="Learning rate (default: fit_octree's)")),
+    ("--batch-size", dict(type=int, default=4096, help="Rays per step")),
+    ("--min-transmittance", dict(type=float, default=0.0,
+                                 help="End a ray's walk once its transmittance is at or below this")),
+    ("--report-interval", dict(type=int, default=500, help="Steps between validation reports")),
+    ("--seed", dict(type=int, default=20080524, help="Seed of the ray shuffle")),
+    ("--device", dict(default="cuda", help="Pytorch compute device")),
+]
+
+
+def build_parser():
+    return _cli.build_parser("Octree Trainer", TRAIN_OCTREE)
+
+
+def main():
+    args = build_parser().parse_args()
+    device, _, _, _ = _cli.setup_device(args.device, False)
+    import fourier_feature_nets_amd as ffn
+    from fourier_feature_nets_amd import octree_fit
+    tree = ffn.OcTree.load(args.tree_path)
+    if tree is None:
+        return 1
+    train = ffn.ImageDataset.load(args.data_path, "train", 1, True, False, None, device=device)
+    val = ffn.ImageDataset.load(args.data_path, "val", 1, True, False, None, device=device)
+    if train is None or val is None:
+        return 1
+    lr = octree_fit.LEARNING_RATE if args.lr is None else args.lr
+    fitted, log = ffn.fit_octree(tree, train, val, args.batch_size, lr, args.steps,
+                                 args.report_interval, center=args.center,
+                                 min_transmittance=args.min_transmittance, seed=args.seed)
+    if log:
+        print("loss first %.6g last %.6g over %d steps" % (log[0].loss, log[-1].loss, len(log)))
+    fitted.save(args.output_path)
+    print(fitted.num_leaves, "leaves fitted")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
