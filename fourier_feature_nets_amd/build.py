@@ -44,7 +44,8 @@ SOURCES = {
     "octree.hip": ["-ffp-contract=off"],
     # plane crossings (plane - o) / d on the f32 chain of node centres, every operation rounded
     "octree_walk.hip": ["-ffp-contract=off"],
-    # sums of stored entries in a fixed order: plain adds
+    # sums of stored entries in a fixed order: plain adds.  K17b-5 turns a sum of -0 into +0 by
+    # adding 0.0f, which -ffast-math or -fno-signed-zeros would fold away: never add those here
     "octree_grad.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,

@@ -230,7 +230,11 @@ grad_finish_kernel(const float4* __restrict__ sums, const int32_t* __restrict__ 
     const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (l >= num_leaves) return;
     const int lo = seg_lo[l];
-    d_leaf_data[l] = seg_hi[l] > lo ? sums[lo] : make_float4(0.f, 0.f, 0.f, 0.f);
+    // + 0: a leaf whose only entries are those of rays that touch it (a chord of length 0, terms
+    // of -0 under a negative upstream gradient) ends at +0 like a leaf without entries
+    float4 v = seg_hi[l] > lo ? sums[lo] : make_float4(0.f, 0.f, 0.f, 0.f);
+    v.x += 0.0f; v.y += 0.0f; v.z += 0.0f; v.w += 0.0f;
+    d_leaf_data[l] = v;
 }
 
 // ---------------------------------------------------------------------------------- K17c

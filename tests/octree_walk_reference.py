@@ -46,21 +46,29 @@ def regions(scale, node_index, leaf_index):
     return ids, slot, centers.astype(np.float64), half
 
 
-def _slab(o, d, lo, hi, top):
-    """Per row: entry t, exit t, and per axis the near / far crossing.  o, d, lo, hi: (K,3)."""
+def _slab(o, d, lo, hi, top, zero_rule="lower"):
+    """Per row: entry t, exit t, and per axis the near / far crossing.  o, d, lo, hi: (K,3).
+    ``zero_rule``: see ``walk``."""
     with np.errstate(divide="ignore", invalid="ignore"):
         t0 = (lo - o) / d
         t1 = (hi - o) / d
     near, far = np.minimum(t0, t1), np.maximum(t0, t1)
     zero = d == 0
-    inside = (o >= lo) & ((o < hi) | ((o == top) & (hi >= top * (1 - 1e-6))))
+    if zero_rule == "lower":
+        inside = (o >= lo) & ((o < hi) | ((o == top) & (hi >= top * (1 - 1e-6))))
+    else:
+        inside = ((o > lo) | ((o == -top) & (lo <= -top * (1 - 1e-6)))) & (o <= hi)
     near = np.where(zero, np.where(inside, -np.inf, np.inf), near)
     far = np.where(zero, np.where(inside, np.inf, -np.inf), far)
     return near, far
 
 
-def walk(scale, node_index, leaf_index, starts, directions, chunk=8192):
-    """-> dict with, per ray (R,): ``hit`` (crosses the cube with a chord of positive length),
+def walk(scale, node_index, leaf_index, starts, directions, chunk=8192, zero_rule="lower"):
+    """``zero_rule``: which side of a plane a zero direction component belongs to.  "lower" is the
+    contract (``lo <= o < hi``); "upper" (``lo < o <= hi``) is a deliberately WRONG restatement
+    that tests/test_octree_lattice_gpu.py holds its checkers against.
+
+    -> dict with, per ray (R,): ``hit`` (crosses the cube with a chord of positive length),
     ``root_in`` / ``root_out`` (the cube's entry / exit t), ``margin``, ``offsets`` (R+1,) into
     the flat per-crossing arrays, sorted by ray and entry t: ``t_in``, ``t_out``, ``leaf`` (slot
     or -1), ``axis_in`` / ``axis_out`` (the axes whose planes give the entry / exit)."""
@@ -72,7 +80,7 @@ def walk(scale, node_index, leaf_index, starts, directions, chunk=8192):
     directions = np.asarray(directions, np.float32).reshape(-1, 3).astype(np.float64)
     count = len(starts)
     near, far = _slab(starts, directions, np.full_like(starts, -scale), np.full_like(starts, scale),
-                      scale)
+                      scale, zero_rule)
     root_in, root_out = near.max(1), far.min(1)
     finite = np.isfinite(starts).all(1) & np.isfinite(directions).all(1)
     with np.errstate(invalid="ignore"):
@@ -91,7 +99,7 @@ def walk(scale, node_index, leaf_index, starts, directions, chunk=8192):
             r, c = rays[~interior], centers[~interior].astype(np.float64)
             if len(r):
                 near, far = _slab(starts[r], directions[r], c - np.float64(half32),
-                                  c + np.float64(half32), scale)
+                                  c + np.float64(half32), scale, zero_rule)
                 t_in, t_out = near.max(1), far.min(1)
                 with np.errstate(invalid="ignore"):
                     chord = t_out - t_in
@@ -115,7 +123,8 @@ def walk(scale, node_index, leaf_index, starts, directions, chunk=8192):
             child_r = np.repeat(r, 8)
             grow = np.float64(child_half) + PRUNE * scale
             c64 = child_c.astype(np.float64)
-            near, far = _slab(starts[child_r], directions[child_r], c64 - grow, c64 + grow, np.inf)
+            near, far = _slab(starts[child_r], directions[child_r], c64 - grow, c64 + grow, np.inf,
+                              zero_rule)
             with np.errstate(invalid="ignore"):
                 keep = near.max(1) <= far.min(1)
             rays, ids, centers = child_r[keep], child_i[keep], child_c[keep]

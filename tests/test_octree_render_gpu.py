@@ -37,8 +37,10 @@ def bits(x):
     return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
-def check_first_hit(what, state, starts, directions, t_min, got, w=None):
-    """Asserts ``got`` (a ``Hit`` of numpy arrays) against the restatement; -> (w, want, ok)."""
+def check_first_hit(what, state, starts, directions, t_min, got, w=None, every_ray=False):
+    """Asserts ``got`` (a ``Hit`` of numpy arrays) against the restatement; -> (w, want, ok).
+    ``every_ray``: rays whose crossings are exact in f32 (tests/octree_lattice_helpers.py) and that
+    the caller has found free of ties, where no budget is needed to have a single right answer."""
     scale, nodes, leaves = state["scale"], state["node_index"], state["leaf_index"]
     if w is None:
         w = wref.walk(scale, nodes, leaves, starts, directions)
@@ -51,6 +53,9 @@ def check_first_hit(what, state, starts, directions, t_min, got, w=None):
     near_t_min[w["ray"][close]] = True
     ok = (~w["hit"] | (w["margin"] > budget)) & ~near_t_min
     edge = want["edge_gap"] <= budget
+    if every_ray:
+        ok[:] = True
+        edge[:] = False
     left_out = 1.0 - (ok & ~edge).mean()
     same_leaf = got.leaves == want["leaf"]
     same_face = got.faces == want["face"]
