@@ -486,6 +486,8 @@ def octree_path_codes(positions: torch.Tensor, center, scale: float, depth: int)
     """K12e.  positions (N,3), the cube's centre (3 floats) and half side -> int32 codes (N)."""
     n = positions.shape[0]
     codes = torch.empty((n,), dtype=torch.int32, device=positions.device)
+    if n == 0:
+        return codes
     _call("ffn_octree_path_codes", _dev(positions, name="positions"), c_i64(n), c_f(center[0]),
           c_f(center[1]), c_f(center[2]), c_f(scale), c_i(depth), _dev(codes, torch.int32))
     return codes
@@ -505,6 +507,8 @@ def octree_structure(sorted_codes: torch.Tensor, perm: torch.Tensor, depth: int,
     leaf_start = torch.empty((n,), dtype=torch.int64, device=dev)
     leaf_count = torch.empty((n,), dtype=torch.int32, device=dev)
     num = torch.zeros((), dtype=torch.int32, device=dev)
+    if n == 0:
+        return leaf_of_point, leaf_ids, leaf_start, leaf_count
     flags, offsets, tiles = _scan_scratch(n, dev)
     _call("ffn_octree_structure", _dev(sorted_codes, torch.int32, "sorted_codes"),
           _dev(perm, torch.int64, "perm"), c_i64(n), c_i(depth), c_i64(min_leaf_size),

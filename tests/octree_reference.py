@@ -12,7 +12,13 @@ reference.  It restates, level by level over whole arrays, what the reference do
 * query: octree.py:513-530; leaf centres / depths: octree.py:564-582.
 
 ``tests/test_octree_cpu.py`` checks it against trees the reference itself built
-(tests/golden/octree.npz)."""
+(tests/golden/octree.npz).
+
+The second half restates the build OP BY OP, as ``csrc/octree.hip`` splits it (surface points, path
+codes, structure from sorted codes, interior nodes), so that every K12 kernel can be compared on
+inputs of the test's choosing.  These use no binary search: they count with ``np.unique`` and compare
+code prefixes.  ``tests/test_octree_build_ops_cpu.py`` checks that chained together they give the
+reference's trees (octree.npz, octree_edges.npz) and ``build``'s ``point_leaf``."""
 
 import numpy as np
 
@@ -138,3 +144,75 @@ def leaf_geometry(scale, leaf_index):
         centers = np.where(live[:, None], moved, centers)
         level += live
     return centers, depths
+
+
+# ---------------------------------------------------------------------------- op by op
+def surface_points(alpha, depth, starts, directions, color, threshold):
+    """voxelize_model.py:71-77 in f32: the rays with ``alpha > threshold``, in ray order, at
+    ``starts + directions * depth`` (product and sum each rounded to f32), and their colours
+    (``None`` without colours)."""
+    alpha, depth = np.asarray(alpha, np.float32), np.asarray(depth, np.float32)
+    starts, directions = np.asarray(starts, np.float32), np.asarray(directions, np.float32)
+    valid = alpha > np.float32(threshold)
+    position = starts + directions * depth[..., np.newaxis]
+    assert position.dtype == np.float32
+    return position[valid], None if color is None else np.asarray(color, np.float32)[valid]
+
+
+def path_codes(positions, center, scale, depth):
+    """The child indices (octree.py:274-286) of every position on its way down a cube the CALLER
+    gives, 3 bits per level, root first -> (N,) int64.  The centre is subtracted in f32 first, as
+    octree.py:760 shifts the cloud; then ``depth - 1`` descents."""
+    positions = np.asarray(positions, np.float32).reshape(-1, 3)
+    points = (positions - np.asarray(center, np.float32)).astype(np.float32)
+    centers = np.zeros_like(points)
+    half = np.float32(scale)
+    codes = np.zeros(len(points), np.int64)
+    for _ in range(1, depth):
+        half = np.float32(half / np.float32(2))
+        index, centers = _descend(points, centers, half)
+        codes = codes * 8 + index
+    return codes
+
+
+def structure_from_codes(sorted_codes, depth, min_leaf_size):
+    """octree.py:762-803 on sorted path codes: the node of level k a point lies in is the first k
+    digits of its code.  -> ``leaf`` (N,) int64, the leaf id per sorted point or -1, and
+    ``leaves`` (L,3) int64 rows ``(id, start, count)`` in code order: a leaf's points are one run of
+    the sorted order."""
+    codes = np.asarray(sorted_codes, np.int64)
+    n = len(codes)
+    assert (np.diff(codes) >= 0).all()
+    leaf = np.full(n, -1, np.int64)
+    ids = np.zeros(n, np.int64)
+    alive = np.full(n, depth > 1 or n >= min_leaf_size)      # the root is always visited
+    for level in range(1, depth):
+        child = codes >> (3 * (depth - 1 - level))           # the level's node: a code prefix
+        _, inverse, counts = np.unique(child[alive], return_inverse=True, return_counts=True)
+        followed = np.zeros(n, bool)
+        followed[alive] = counts[inverse] >= min_leaf_size
+        # a visited node without a followed child is a leaf with all its points; below one
+        # with a followed child, the points of the other children are dropped
+        interior = alive & np.isin(child >> 3, np.unique(child[followed] >> 3))
+        leaf_here = alive & ~interior
+        leaf[leaf_here] = ids[leaf_here]
+        alive = followed
+        ids = np.where(alive, 8 * ids + 1 + (child & 7), ids)
+    leaf[alive] = ids[alive]
+    head = (leaf >= 0) & (np.concatenate([[-2], leaf[:-1]]) != leaf)
+    start = np.flatnonzero(head)
+    run = np.cumsum(head) - 1                                # which run a kept point lies in
+    count = np.bincount(run[leaf >= 0], minlength=len(start))
+    assert (leaf[leaf >= 0] == leaf[start][run[leaf >= 0]]).all()
+    return leaf, np.stack([leaf[start], start, count], 1).astype(np.int64).reshape(-1, 3)
+
+
+def interior_nodes(leaf_ids):
+    """The proper ancestors of the leaves (parent of i is ``(i - 1) >> 3``), sorted, each once:
+    the ``node_index`` of a tree with these leaves."""
+    ids = np.unique(np.asarray(leaf_ids, np.int64))
+    found = []
+    while (ids > 0).any():
+        ids = np.unique((ids[ids > 0] - 1) >> 3)
+        found.append(ids)
+    return np.unique(np.concatenate(found)) if found else np.zeros(0, np.int64)

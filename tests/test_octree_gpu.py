@@ -96,8 +96,8 @@ def test_device_tensors_in_and_the_callers_array_untouched(fixture):
     assert np.array_equal(answers.cpu().numpy(), g["query_result"])
 
 
-@pytest.mark.parametrize("depth", list(range(1, 11)))
-def test_every_depth_from_1_to_10(depth):
+@pytest.mark.parametrize("depth", list(range(1, 12)))
+def test_every_depth_from_1_to_11(depth):
     import fourier_feature_nets as ffn
     rng = np.random.default_rng(depth)
     pos = (rng.normal(size=(30000, 3)) * [1.0, 0.6, 0.3]).astype(np.float32)
@@ -218,11 +218,9 @@ def render_batches(model, batch_size):
 
 
 def numpy_surface(alpha, depth, color, starts, dirs, threshold):
-    """voxelize_model.py:71-77."""
+    """voxelize_model.py:71-77: the old name of ``octree_reference.surface_points``, on tensors."""
     alpha, depth, color, starts, dirs = [t.cpu().numpy() for t in (alpha, depth, color, starts, dirs)]
-    valid = alpha > np.float32(threshold)
-    position = starts + dirs * depth[..., np.newaxis]
-    return position[valid], color[valid]
+    return oref.surface_points(alpha, depth, starts, dirs, color, threshold)
 
 
 def test_surface_points_equal_the_numpy_expression():
