@@ -356,6 +356,36 @@ octree_bake_kernel(const float4* __restrict__ logits, int64_t count, float4* __r
     out[i] = make_float4(sigmoid_f(l.x), sigmoid_f(l.y), sigmoid_f(l.z), softplus_torch(l.w));
 }
 
+// K18b: one view of the SH projection of OcTree.bake_sh.  Row i of `out` (3 kBasis + 1 floats,
+// [k_r0 .. k_r(B-1), k_g0 .., k_b0 .., sigma]) takes k[c B + b] += weight[b] * logit[c], one multiply
+// and one add (contraction is off in this body whatever the file is compiled with, so numpy float32
+// reproduces it), and sigma += softplus(logit[3]) * inv_views.  One thread per leaf, no atomics: a
+// row has one writer, and the views are accumulated in call order.  Here for the reason above: the
+// softplus is ffn_octree_bake's, bit for bit.
+struct ShWeights { float w[9]; };
+
+template <int kBasis>
+__global__ void __launch_bounds__(256)
+octree_sh_accumulate_kernel(const float4* __restrict__ logits, int64_t count, ShWeights weights,
+                            float inv_views, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float4 l = logits[i];
+    const float rgb[3] = {l.x, l.y, l.z};
+    float* row = out + i * (3 * kBasis + 1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int b = 0; b < kBasis; ++b) {
+            const float term = weights.w[b] * rgb[c];
+            row[c * kBasis + b] = row[c * kBasis + b] + term;
+        }
+    }
+    const float share = softplus_torch(l.w) * inv_views;
+    row[3 * kBasis] = row[3 * kBasis] + share;
+}
+
 // K16b, first half (the rest is in octree.hip): the logits of one chunk of finest cells -> the
 // same activations, and per cell whether sigma * side > tau.  Here for the reason above: the
 // data of a density tree has to be what ffn_octree_bake makes of the same logits, bit for bit.
@@ -518,4 +548,29 @@ extern "C" int ffn_octree_bake(const float* logits, int64_t num_leaves, float* l
     hipLaunchKernelGGL(octree_bake_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const float4*)logits, num_leaves, (float4*)leaf_data);
     return check_launch("ffn_octree_bake");
+}
+
+extern "C" int ffn_octree_sh_accumulate(const float* logits, int64_t num_leaves, int degree,
+                                        const float* weights, float inv_views, float* leaf_data,
+                                        void* stream) {
+    if (degree != 1 && degree != 2) return fail_arg("ffn_octree_sh_accumulate: degree is 1 or 2");
+    if (num_leaves < 1 || num_leaves >= ((int64_t)1 << 31))
+        return fail_arg("ffn_octree_sh_accumulate: shape (1 <= num_leaves < 2^31)");
+    if (!logits || !weights || !leaf_data)
+        return fail_arg("ffn_octree_sh_accumulate: null argument");
+    if (((uintptr_t)logits & 15) != 0)
+        return fail_arg("ffn_octree_sh_accumulate: logits must be 16-byte aligned");
+    const int basis = (degree + 1) * (degree + 1);
+    ShWeights host{};
+    for (int b = 0; b < basis; ++b) host.w[b] = weights[b];
+    const unsigned blocks = (unsigned)((num_leaves + 255) / 256);
+    if (degree == 1)
+        hipLaunchKernelGGL(octree_sh_accumulate_kernel<4>, dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, (const float4*)logits, num_leaves, host, inv_views,
+                           leaf_data);
+    else
+        hipLaunchKernelGGL(octree_sh_accumulate_kernel<9>, dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, (const float4*)logits, num_leaves, host, inv_views,
+                           leaf_data);
+    return check_launch("ffn_octree_sh_accumulate");
 }

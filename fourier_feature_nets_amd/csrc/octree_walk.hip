@@ -67,7 +67,23 @@
 // Divergence and dependent reads: as K15, a wave runs as long as its longest ray (one wave per
 // workgroup) and waits on the binary searches; the entry stores are one 16-byte and one 4-byte
 // store per lane and leaf into the lane's own run of the list, off the dependent chain.
+//
+// K18a  SH volume: K15 with a view-dependent leaf colour, two more modes of the same kernel (one per
+// degree, B = (degree + 1)^2 = 4 or 9).  A leaf holds 3 B logit-space coefficients and a density;
+// its colour for the ray's unit direction u is sigmoid(sum_b k_cb Y_b(u)), Y the real SH basis
+// (sh_terms below).  u is constant along a ray: the B basis values are computed once before the
+// loop and stay in registers, and a leaf costs B fused multiply-adds and one sigmoid per channel
+// on top of K15's steps.  t0, the chord, sigma, a, w, T, the depth and the early end are K15's
+// operations in K15's order, so alpha and depth have K15's bits on the same densities.  The device
+// copy of the leaf data is a layout of its own: rows of `stride` floats, a multiple of four and
+// 16-byte aligned, [sigma, k_r0 .. k_r(B-1), k_g0 .., k_b0 .., padding], read as stride / 4
+// 16-byte loads (4 at degree 1, 7 at degree 2) of which the first holds the density.  first.channels
+// carries the stride.  No counterpart in the reference.
+// Resource report, kVolumeSH1 / kVolumeSH2: 56 / 72 VGPRs (occupancy 8 / 7 waves per SIMD), 0 bytes
+// of scratch, 0 spills, 0 bytes of LDS; the five older instantiations compile to the instructions
+// they had before (38 / 40 / 50 / 53 / 61 VGPRs).
 #include "common.h"
+#include "composite_terms.h"
 #include "octree_grad.h"
 
 namespace ffn {
@@ -159,12 +175,33 @@ struct FirstHit {
     float* depth;
 };
 
-enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4 };
+enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
+                kVolumeSH2 = 6 };
+
+// K18a: the real SH basis of bands 0 .. kDegree at the unit vector (x, y, z), in the order and with
+// the signs of include/ffn_hip.h
+template <int kDegree>
+__device__ __forceinline__ void sh_terms(float x, float y, float z,
+                                         float (&basis)[(kDegree + 1) * (kDegree + 1)]) {
+    basis[0] = 0.28209479177387814f;
+    basis[1] = -0.4886025119029199f * y;
+    basis[2] = 0.4886025119029199f * z;
+    basis[3] = -0.4886025119029199f * x;
+    if constexpr (kDegree >= 2) {
+        basis[4] = 1.0925484305920792f * (x * y);
+        basis[5] = -1.0925484305920792f * (y * z);
+        basis[6] = 0.31539156525252005f * (2.0f * (z * z) - x * x - y * y);
+        basis[7] = -1.0925484305920792f * (x * z);
+        basis[8] = 0.5462742152960396f * (x * x - y * y);
+    }
+}
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
 // kFirstHit: the first of those leaves, where the loop ends (K14).
 // kVolume:   colour, opacity and depth composited front to back over those leaves (K15).
+// kVolumeSH1 / kVolumeSH2: kVolume with the leaf colour of K18a, degree 1 / 2; first.leaf_data is the
+//            padded device layout and first.channels its row stride.
 // kGrad:     K17a.  The idle parameters carry its buffers: max_length the phase (0 count, 1 emit),
 //            span_hit the int32 ray counts (phase 0, written) / offsets (phase 1, n + 1 read),
 //            first.color / first.alpha the per-ray C and T_{n+1} (written in phase 0, read in
@@ -179,6 +216,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                    float t_min, float pad, float* __restrict__ span_in,
                    float* __restrict__ span_out, uint8_t* __restrict__ span_hit, FirstHit first) {
     constexpr bool kSpans = kMode == kSpan;
+    constexpr bool kSH = kMode == kVolumeSH1 || kMode == kVolumeSH2;
+    constexpr int kBasis = kMode == kVolumeSH2 ? 9 : 4;
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= n) return;
     const float ox = starts[r * 3 + 0], oy = starts[r * 3 + 1], oz = starts[r * 3 + 2];
@@ -219,7 +258,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume || kMode == kGrad ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
+    const float norm = kMode == kVolume || kMode == kGrad || kSH
+                           ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
     const bool emit = kMode == kGrad && max_length != 0;
@@ -229,6 +269,13 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int taken = 0, base = 0, mine = 0;
     float c_r = 0.0f, c_g = 0.0f, c_b = 0.0f, t_end = 0.0f, g_r = 0.0f, g_g = 0.0f, g_b = 0.0f,
           g_a = 0.0f;
+    // K18a: the basis at the ray's unit direction.  A direction without a length (zero, NaN) is a
+    // miss and takes no leaf; its basis is never read, and is kept finite anyway
+    float basis[kBasis];
+    if (kSH) {
+        const float inv = norm > 0.0f && norm < __builtin_inff() ? 1.0f / norm : 0.0f;
+        sh_terms<kMode == kVolumeSH2 ? 2 : 1>(dx * inv, dy * inv, dz * inv, basis);
+    }
     if (emit) {
         base = ray_slots[r];
         mine = ray_slots[r + 1] - base;
@@ -281,6 +328,39 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                     const float* data = first.leaf_data + leaf * first.channels;
                     lr = data[0]; lg = data[1]; lb = data[2]; ls = data[3];
                 }
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                acc_r += w * lr; acc_g += w * lg; acc_b += w * lb;
+                if (w > w_best) { w_best = w; t_best = t0; }
+                trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
+        } else if (kSH) {
+            if (leaf >= 0 && t_exit > t_min) {
+                constexpr int kQuads = (3 * kBasis + 1 + 3) / 4;
+                const float4* row4 = reinterpret_cast<const float4*>(first.leaf_data +
+                                                                     leaf * first.channels);
+                float row[4 * kQuads];
+#pragma unroll
+                for (int q = 0; q < kQuads; ++q) {
+                    const float4 v = row4[q];
+                    row[4 * q + 0] = v.x; row[4 * q + 1] = v.y; row[4 * q + 2] = v.z;
+                    row[4 * q + 3] = v.w;
+                }
+                const float ls = row[0];
+                float rgb[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float z = row[1 + c * kBasis] * basis[0];
+#pragma unroll
+                    for (int b = 1; b < kBasis; ++b)
+                        z = __builtin_fmaf(row[1 + c * kBasis + b], basis[b], z);
+                    rgb[c] = sigmoid_f(z);
+                }
+                const float lr = rgb[0], lg = rgb[1], lb = rgb[2];
                 const float t0 = t > t_min ? t : t_min;
                 const float length = (t_exit - t0) * norm;
                 const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
@@ -366,7 +446,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
             first.alpha[r] = found ? 1.0f : 0.0f;
             first.depth[r] = first_in;
         }
-    } else if (kMode == kVolume) {
+    } else if (kMode == kVolume || kSH) {
         first.color[r * 3 + 0] = acc_r + trans * first.bg_r;
         first.color[r * 3 + 1] = acc_g + trans * first.bg_g;
         first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
@@ -565,6 +645,52 @@ extern "C" int ffn_octree_render_volume(const float* starts, const float* direct
                        num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
                        t_min, 0.0f, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
     return check_launch("ffn_octree_render_volume");
+}
+
+extern "C" int ffn_octree_render_volume_sh(const float* starts, const float* directions, int64_t n,
+                                           float scale, int depth, const int64_t* node_index,
+                                           int64_t num_nodes, const int64_t* leaf_index,
+                                           int64_t num_leaves, float t_min, const float* leaf_data,
+                                           int channels, float bg_r, float bg_g, float bg_b,
+                                           float min_transmittance, float* color, float* alpha,
+                                           float* depth_out, int degree, int row_stride,
+                                           void* stream) {
+    if (degree != 1 && degree != 2) return fail_arg("ffn_octree_render_volume_sh: degree is 1 or 2");
+    if (channels != 3 * (degree + 1) * (degree + 1) + 1)
+        return fail_arg("ffn_octree_render_volume_sh: channels == 3 * (degree + 1)^2 + 1");
+    if (row_stride < channels || row_stride % 4 != 0 || row_stride > 64)
+        return fail_arg("ffn_octree_render_volume_sh: row_stride is a multiple of 4, channels <= "
+                        "row_stride <= 64");
+    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_sh: t_min is NaN");
+    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
+        return fail_arg("ffn_octree_render_volume_sh: 0 <= min_transmittance < 1");
+    if (!leaf_data || !color || !alpha || !depth_out)
+        return fail_arg("ffn_octree_render_volume_sh: null argument");
+    if (int err = check_walk_args("ffn_octree_render_volume_sh", starts, directions, n, depth,
+                                  node_index, num_nodes, leaf_index, num_leaves))
+        return err;
+    // a row is read as 16-byte loads
+    if (((uintptr_t)leaf_data & 15) != 0)
+        return fail_arg("ffn_octree_render_volume_sh: leaf_data must be 16-byte aligned");
+    FirstHit first{};
+    first.leaf_data = leaf_data; first.channels = row_stride;
+    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
+    first.min_transmittance = min_transmittance;
+    first.color = color; first.alpha = alpha; first.depth = depth_out;
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    if (degree == 1)
+        hipLaunchKernelGGL(octree_walk_kernel<kVolumeSH1>, dim3(blocks), dim3(kWalkThreads), 0,
+                           (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                           num_nodes, leaf_index, num_leaves, 0, (float*)nullptr,
+                           (int64_t*)nullptr, t_min, 0.0f, (float*)nullptr, (float*)nullptr,
+                           (uint8_t*)nullptr, first);
+    else
+        hipLaunchKernelGGL(octree_walk_kernel<kVolumeSH2>, dim3(blocks), dim3(kWalkThreads), 0,
+                           (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
+                           num_nodes, leaf_index, num_leaves, 0, (float*)nullptr,
+                           (int64_t*)nullptr, t_min, 0.0f, (float*)nullptr, (float*)nullptr,
+                           (uint8_t*)nullptr, first);
+    return check_launch("ffn_octree_render_volume_sh");
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

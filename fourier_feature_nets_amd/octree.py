@@ -39,9 +39,17 @@ public signatures are the reference's, so files and calling code go both ways.  
   evaluates a trained model at the leaf centres and stores its own colour and density
   (``[sigmoid(rgb), softplus(sigma)]``, as ``Raycaster.render`` activates them) in every leaf;
   ``render_volume`` composites them front to back along the ray's whole chord through the tree, so
-  soft edges, thin structure and the transmittance left for the background survive.  A leaf holds
-  one colour: the view dependence of a model with ``use_view`` is lost (it is baked for one fixed
-  view direction).
+  soft edges, thin structure and the transmittance left for the background survive.  A leaf of
+  ``bake`` holds one colour: the view dependence of a model with ``use_view`` is baked for one fixed
+  view direction.  ``bake_sh`` keeps it.
+* ``bake_sh`` / ``sh_degree`` (K18) have none either.  A leaf of an SH tree holds ``B = (degree +
+  1)^2`` spherical-harmonic coefficients per colour channel, in logit space, and a density:
+  ``leaf_data`` is ``(L, 3 B + 1)``, ``[k_r0 .. k_r(B-1), k_g0 .., k_b0 .., sigma]``, and the colour a
+  ray sees is ``sigmoid(sum_b k_cb Y_b(u))`` for its unit direction ``u`` (``sh_basis``).
+  ``bake_sh`` projects a model onto the basis from ``num_views`` directions on a Fibonacci sphere;
+  ``render_volume`` of a tree whose ``sh_degree`` is set evaluates the basis once per ray.  The
+  degree travels in the file as one more key, ``sh_degree``, that the reference's ``load`` ignores;
+  it is never inferred from the channel count.  Fitting SH leaves (K17 for them) is not built.
 * ``build_from_model`` (K16) has none either: the reference can only voxelize the depth renders
   of a model (voxelize_model.py), a one-cell shell that is nearly transparent once baked.
   ``build_from_model`` evaluates the model at the centre of every finest cell, chunk by chunk in
@@ -63,7 +71,7 @@ public signatures are the reference's, so files and calling code go both ways.  
 
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
-``bake``, ``build_from_model``, ``render_volume``, ``leaf_centers`` and ``leaf_depths`` run on the
+``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers`` and ``leaf_depths`` run on the
 GPU and raise without one.
 """
 
@@ -93,6 +101,51 @@ def _id_depths(ids: np.ndarray) -> np.ndarray:
     return depth
 
 
+SH_Y0 = 0.28209479177387814
+SH_Y1 = 0.4886025119029199
+SH_Y2 = (1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+
+
+def _sh_bases(degree) -> int:
+    """(degree + 1)^2 for the degrees an SH tree can have."""
+    if isinstance(degree, (bool, float)) or degree not in (1, 2):
+        raise ValueError("OcTree: sh_degree is 1 or 2, got %r" % (degree,))
+    return (int(degree) + 1) ** 2
+
+
+def sh_view_directions(num_views: int) -> np.ndarray:
+    """``num_views`` unit vectors on a Fibonacci sphere, float64 (V,3): ``z`` at the midpoints of V
+    equal slices of [-1, 1], the azimuth advancing by the golden angle.  Deterministic."""
+    num_views = int(num_views)
+    if num_views < 1:
+        raise ValueError("sh_view_directions: num_views >= 1, got %d" % num_views)
+    i = np.arange(num_views, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / num_views
+    radius = np.sqrt(np.maximum(1.0 - z * z, 0.0))
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([radius * np.cos(phi), radius * np.sin(phi), z], 1)
+
+
+def sh_basis(directions, degree: int) -> np.ndarray:
+    """The real SH basis of bands 0 .. degree at unit vectors ``directions`` (V,3) or (3,): float64
+    (V, B), in the order and with the signs K18a uses (include/ffn_hip.h)."""
+    bases = _sh_bases(degree)
+    u = np.asarray(directions, np.float64).reshape(-1, 3)
+    x, y, z = u[:, 0], u[:, 1], u[:, 2]
+    out = np.empty((len(u), bases))
+    out[:, 0] = SH_Y0
+    out[:, 1] = -SH_Y1 * y
+    out[:, 2] = SH_Y1 * z
+    out[:, 3] = -SH_Y1 * x
+    if degree == 2:
+        out[:, 4] = SH_Y2[0] * x * y
+        out[:, 5] = -SH_Y2[0] * y * z
+        out[:, 6] = SH_Y2[1] * (2 * z * z - x * x - y * y)
+        out[:, 7] = -SH_Y2[0] * x * z
+        out[:, 8] = SH_Y2[2] * (x * x - y * y)
+    return out
+
+
 Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
 Hit = NamedTuple("Hit", [("leaves", np.ndarray), ("t", np.ndarray), ("faces", np.ndarray)])
 
@@ -100,14 +153,24 @@ Hit = NamedTuple("Hit", [("leaves", np.ndarray), ("t", np.ndarray), ("faces", np
 class OcTree:
     """Class representing an OcTree datastructure."""
 
-    def __init__(self, scale: float, node_ids, leaf_ids, leaf_data: np.ndarray = None):
+    def __init__(self, scale: float, node_ids, leaf_ids, leaf_data: np.ndarray = None,
+                 sh_degree: Optional[int] = None):
         """``node_ids`` / ``leaf_ids``: sets (as the reference takes) or arrays of node ids; the
-        children of node i have the ids 8 i + 1 .. 8 i + 8."""
+        children of node i have the ids 8 i + 1 .. 8 i + 8.  ``sh_degree``: 1 or 2 when
+        ``leaf_data`` (L, 3 (degree + 1)^2 + 1) holds SH coefficients (see ``bake_sh``)."""
         self._device = None
         self._point_leaf = None
         self._center = None
         self._update(node_ids, leaf_ids, scale)
         self._leaf_data = leaf_data
+        self._sh_degree = None
+        if sh_degree is not None:
+            channels = 3 * _sh_bases(sh_degree) + 1
+            if leaf_data is None or np.ndim(leaf_data) != 2 or np.shape(leaf_data)[1] != channels:
+                raise ValueError("OcTree: sh_degree %d needs leaf_data of shape (num_leaves, %d), "
+                                 "got %s" % (sh_degree, channels,
+                                             None if leaf_data is None else np.shape(leaf_data)))
+            self._sh_degree = int(sh_degree)
 
     # ------------------------------------------------------------------ host-side state
     def _update(self, node_ids, leaf_ids, scale: float):
@@ -158,6 +221,13 @@ class OcTree:
         tree: like the reference, the file does not hold it."""
         return self._center
 
+    @property
+    def sh_degree(self) -> Optional[int]:
+        """1 or 2 when the leaves hold spherical-harmonic coefficients (``bake_sh``): ``leaf_data``
+        is ``[k_r0 .. k_r(B-1), k_g0 .., k_b0 .., sigma]`` with ``B = (sh_degree + 1)^2``.  ``None``
+        otherwise; never inferred from the channel count."""
+        return self._sh_degree
+
     def leaf_data(self) -> np.ndarray:
         """The data stored in each leaf."""
         return self._leaf_data
@@ -169,6 +239,8 @@ class OcTree:
                  "scale": np.float32(self._scale)}
         if self._leaf_data is not None:
             state["leaf_data"] = self._leaf_data
+        if self._sh_degree is not None:
+            state["sh_degree"] = np.int32(self._sh_degree)
         return state
 
     def save(self, path: str):
@@ -192,7 +264,9 @@ class OcTree:
         else:
             data = path_or_data
         leaf_data = np.asarray(data["leaf_data"]) if "leaf_data" in data else None
-        return OcTree(float(data["scale"]), data["node_index"], data["leaf_index"], leaf_data)
+        sh_degree = int(data["sh_degree"]) if "sh_degree" in data else None
+        return OcTree(float(data["scale"]), data["node_index"], data["leaf_index"], leaf_data,
+                      sh_degree)
 
     def load_state(self, state_dict: Dict[str, np.ndarray]):
         """Loads the information from the state dictionary."""
@@ -219,7 +293,9 @@ class OcTree:
             merged = np.isin(leaf_ids, new_ids[deep])
             means = sums / counts[:, None].astype(data.dtype)
             leaf_data = np.where(merged[:, None], means, sums).astype(data.dtype)
-        return OcTree(self._scale, node_ids, leaf_ids, leaf_data)
+        # a mean of SH coefficient vectors is a coefficient vector
+        return OcTree(self._scale, node_ids, leaf_ids, leaf_data,
+                      self._sh_degree if leaf_data is not None else None)
 
     # ------------------------------------------------------------------ GPU side
     def _dev(self):
@@ -360,6 +436,23 @@ class OcTree:
         if not 0.0 <= float(min_transmittance) < 1.0:        # NaN fails too
             raise ValueError("OcTree.render_volume: min_transmittance must lie in [0, 1), got %r"
                              % (min_transmittance,))
+        if self._sh_degree is not None:
+            channels = 3 * _sh_bases(self._sh_degree) + 1
+            if np.shape(data)[1] != channels:
+                raise ValueError("OcTree.render_volume: sh_degree %d needs leaf_data of shape "
+                                 "(num_leaves, %d), got %s" % (self._sh_degree, channels,
+                                                               np.shape(data)))
+
+    def _sh_rows_on_device(self) -> torch.Tensor:
+        """The SH ``leaf_data`` in the layout K18a reads (``ops.octree_sh_device_layout``: density
+        first, rows padded to whole 16-byte loads) on the device, made once, cached like
+        ``leaf_data_f32``."""
+        dev = self._dev()
+        key = ("leaf_data_sh", str(dev))
+        if key not in self._cache:
+            self._cache[key] = torch.from_numpy(
+                ops.octree_sh_device_layout(self._leaf_data, self._sh_degree)).to(dev)
+        return self._cache[key]
 
     def _colors_on_device(self) -> torch.Tensor:
         """``leaf_data`` as float32 on the device, cast once (a tree the reference saved, or a
@@ -399,9 +492,21 @@ class OcTree:
         ``alpha`` (N,) ``1 - T``; ``depth`` (N,) the ``max(entry t, t_min)`` of the leaf with the
         largest ``w`` (the first of equals), 0 when nothing is in the way.  The walk of a ray ends
         once ``T <= min_transmittance``.  Rescaling ``directions`` does not change the result.
-        Inputs as for ``walk``; numpy in gives numpy out."""
+        Inputs as for ``walk``; numpy in gives numpy out.
+
+        A tree whose ``sh_degree`` is set (``bake_sh``) takes the K18a path: the same compositing,
+        with the leaf colour ``sigmoid(sum_b k_cb Y_b(u))`` for the ray's unit direction ``u =
+        direction / |direction|`` (not negated), so ``alpha`` and ``depth`` are those of a plain
+        tree with the same densities, bit for bit.  Without ``sh_degree`` the first four channels
+        are ``[r, g, b, sigma]`` whatever the channel count."""
         self._check_volume(min_transmittance)         # before any device is needed
         starts, directions, as_numpy = self._rays(starts, directions)
+        if self._sh_degree is not None:
+            out = RenderResult(*ops.octree_render_volume_sh(
+                starts, directions, self._scale, self.depth, self._on_device("node_index"),
+                self._on_device("leaf_index"), self._sh_rows_on_device(), self._sh_degree,
+                float(t_min), background, float(min_transmittance)))
+            return out.numpy() if as_numpy else out
         out = RenderResult(*ops.octree_render_volume(
             starts, directions, self._scale, self.depth, self._on_device("node_index"),
             self._on_device("leaf_index"), self._colors_on_device(), float(t_min), background,
@@ -417,7 +522,8 @@ class OcTree:
         ``model`` is evaluated in eval mode without gradients, ``batch_size`` leaves at a time, at
         ``leaf_centers() + center``; ``center`` defaults to ``tree.center``, which a loaded tree
         does not have.  A model with ``use_view`` is given the fixed direction ``view`` for every
-        leaf: a leaf holds one colour, so the view dependence of such a model is lost."""
+        leaf: a leaf holds one colour, so the view dependence of such a model is lost
+        (``bake_sh`` keeps it).  The result is a plain tree (``sh_degree`` is ``None``)."""
         if center is None:
             center = self._center
         if center is None:
@@ -452,6 +558,79 @@ class OcTree:
             model.train(was_training)
         tree = OcTree(self._scale, self._node_index, self._leaf_index,
                       torch.cat(baked).cpu().numpy())
+        tree._device = self._device
+        tree._center = center
+        return tree
+
+    def bake_sh(self, model, degree: int = 2, num_views: int = 64, center=None,
+                batch_size: int = 1 << 20) -> "OcTree":
+        """A NEW tree of the same structure and centre with ``sh_degree = degree`` whose
+        ``leaf_data`` (L, 3 B + 1) float32, ``B = (degree + 1)^2``, holds per leaf and colour channel
+        the SH coefficients of the model's colour LOGIT over the view direction, and the density
+        (K18b).  This tree is not modified.
+
+        A model with ``use_view`` is evaluated as ``bake`` evaluates it, once per direction
+        ``v_j`` of ``sh_view_directions(num_views)`` (every leaf of a batch gets ``v_j``), and
+        view j adds ``P[b, j] * logit[c]`` to coefficient ``k[c B + b]``, ``P`` the float32 cast of
+        the float64 pseudo-inverse of ``sh_basis(views, degree)``: the least-squares fit of the
+        logits over the views.  The density is the mean over the views of ``softplus(sigma)``.
+        ``num_views >= 2 B``.  The (L, V, 4) logits are never held.
+
+        A model without ``use_view`` is evaluated once: band 0 is ``logit / Y_0`` and the other
+        bands are zero, the density what ``bake`` stores."""
+        bases = _sh_bases(degree)
+        degree = int(degree)
+        num_views = int(num_views)
+        if num_views < 2 * bases:
+            raise ValueError("OcTree.bake_sh: degree %d needs num_views >= %d, got %d"
+                             % (degree, 2 * bases, num_views))
+        if center is None:
+            center = self._center
+        if center is None:
+            raise ValueError("OcTree.bake: a loaded tree does not know the centre of its root "
+                             "cube (the file has no place for it); pass center=")
+        center = tuple(float(c) for c in center)
+        batch_size = int(batch_size)
+        if len(center) != 3 or batch_size < 1:
+            raise ValueError("OcTree.bake_sh: center has three components and batch_size is >= 1")
+        device = next(model.parameters()).device
+        if self._device is None:
+            self._device = device
+        points = torch.from_numpy(self.leaf_centers()).to(device)
+        points = points + torch.tensor(center, dtype=torch.float32, device=device)
+        count = points.shape[0]
+        use_view = bool(getattr(model, "use_view", False))
+        views = sh_view_directions(num_views)
+        project = np.linalg.pinv(sh_basis(views, degree)).astype(np.float32)      # (B, V)
+        data = torch.zeros((count, 3 * bases + 1), dtype=torch.float32, device=device)
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                if use_view:
+                    inv_views = float(np.float32(1.0 / num_views))
+                    for j in range(num_views):
+                        direction = torch.tensor(views[j], dtype=torch.float32, device=device)
+                        for start in range(0, count, batch_size):
+                            batch = points[start:start + batch_size].contiguous()
+                            logits = model(batch, direction.expand(batch.shape[0], 3).contiguous())
+                            ops.octree_sh_accumulate(
+                                logits.reshape(-1, 4).to(torch.float32).contiguous(),
+                                data[start:start + batch_size], project[:, j], inv_views, degree)
+                else:
+                    # a device tensor, not a Python number: a true f32 division, not a product
+                    # with the reciprocal
+                    y0 = torch.tensor(SH_Y0, dtype=torch.float32, device=device)
+                    for start in range(0, count, batch_size):
+                        batch = points[start:start + batch_size].contiguous()
+                        logits = model(batch).reshape(-1, 4).to(torch.float32).contiguous()
+                        rows = data[start:start + batch_size]
+                        # layout only: band 0 of a constant is the constant over Y_0
+                        rows[:, 0:3 * bases:bases] = logits[:, :3] / y0
+                        rows[:, 3 * bases] = ops.octree_bake(logits)[:, 3]
+        finally:
+            model.train(was_training)
+        tree = OcTree(self._scale, self._node_index, self._leaf_index, data.cpu().numpy(), degree)
         tree._device = self._device
         tree._center = center
         return tree

@@ -56,12 +56,20 @@ class _RenderVolume(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
+def _refuse_sh(tree: OcTree, who: str):
+    if tree.sh_degree is not None:
+        raise ValueError("%s: fitting SH leaves is not built (the tree has sh_degree %d; the "
+                         "backward of the SH volume render does not exist)"
+                         % (who, tree.sh_degree))
+
+
 class OctreeField(torch.nn.Module):
     """The leaf values of a baked tree as a parameter.  ``data`` (L,4) float32 ``[r, g, b, sigma]``
     on the device, initialised from ``tree.leaf_data()``."""
 
     def __init__(self, tree: OcTree, center=None, device=None):
         super().__init__()
+        _refuse_sh(tree, "OctreeField")
         tree._check_volume(0.0)
         values = np.asarray(tree.leaf_data())[:, :4]      # further channels are never rendered
         if center is None:
@@ -151,6 +159,7 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
         raise ValueError("fit_octree: batch_size >= 1, num_steps >= 0, report_interval >= 1")
     if not learning_rate > 0:
         raise ValueError("fit_octree: learning_rate must be positive, got %r" % (learning_rate,))
+    _refuse_sh(tree, "fit_octree")
     tree._check_volume(min_transmittance)
     if center is None:
         center = tree.center

@@ -707,6 +707,82 @@ def octree_render_volume(starts: torch.Tensor, directions: torch.Tensor, scale: 
     return color, alpha, depth_out
 
 
+def octree_sh_channels(degree: int) -> int:
+    """3 (degree + 1)^2 + 1: the channels of an SH leaf; degree is 1 or 2."""
+    if degree not in (1, 2) or isinstance(degree, bool):
+        raise ValueError("octree SH: degree is 1 or 2, got %r" % (degree,))
+    return 3 * (degree + 1) ** 2 + 1
+
+
+def octree_sh_device_layout(leaf_data: np.ndarray, degree: int) -> np.ndarray:
+    """(L, 3B+1) in the file's order [k_r.., k_g.., k_b.., sigma] -> the float32 rows K18a reads:
+    [sigma, k_r.., k_g.., k_b.., 0 ..], the row stride padded to a multiple of four floats."""
+    channels = octree_sh_channels(degree)
+    if np.ndim(leaf_data) != 2 or np.shape(leaf_data)[1] != channels:
+        raise ValueError("octree SH: leaf_data must be (num_leaves, %d) for degree %d, got %s"
+                         % (channels, degree, np.shape(leaf_data),))
+    stride = (channels + 3) // 4 * 4
+    rows = np.zeros((len(leaf_data), stride), np.float32)
+    rows[:, 0] = leaf_data[:, channels - 1]
+    rows[:, 1:channels] = leaf_data[:, :channels - 1]
+    return rows
+
+
+def octree_render_volume_sh(starts: torch.Tensor, directions: torch.Tensor, scale: float,
+                            depth: int, node_index: torch.Tensor, leaf_index: torch.Tensor,
+                            leaf_rows: torch.Tensor, degree: int, t_min: float = 0.0,
+                            background=(0.0, 0.0, 0.0), min_transmittance: float = 0.0):
+    """K18a.  ``octree_render_volume`` with a view-dependent leaf colour: leaf_rows (L, stride)
+    float32 in the device layout of ``octree_sh_device_layout`` -> color (N,3), alpha (N),
+    depth (N)."""
+    channels = octree_sh_channels(degree)
+    if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
+            or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
+        raise ValueError("octree render_volume_sh: leaf_rows must be (num_leaves, stride) with "
+                         "stride a multiple of 4 and >= %d, got %s for %d leaves"
+                         % (channels, tuple(leaf_rows.shape), leaf_index.numel()))
+    if not 0.0 <= min_transmittance < 1.0:
+        raise ValueError("octree render_volume_sh: min_transmittance must lie in [0, 1), got %r"
+                         % (min_transmittance,))
+    n = starts.shape[0]
+    dev = starts.device
+    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n > 0:
+        r, g, b = [float(v) for v in background]
+        _call("ffn_octree_render_volume_sh", *_walk_args(starts, directions, scale, depth,
+                                                         node_index, leaf_index),
+              c_f(t_min), _dev(leaf_rows, name="leaf_rows"), c_i(channels), c_f(r), c_f(g),
+              c_f(b), c_f(min_transmittance), _dev(color), _dev(alpha), _dev(depth_out),
+              c_i(degree), c_i(leaf_rows.shape[1]))
+    return color, alpha, depth_out
+
+
+def octree_sh_accumulate(logits: torch.Tensor, leaf_data: torch.Tensor, weights, inv_views: float,
+                         degree: int) -> torch.Tensor:
+    """K18b, in place on leaf_data (L, 3B+1) (file layout): one view's logits (L,4) times that
+    view's B projection weights (host floats) into the coefficients, softplus(sigma logit) *
+    inv_views into the density."""
+    channels = octree_sh_channels(degree)
+    basis = (channels - 1) // 3
+    if logits.dim() != 2 or logits.shape[1] != 4:
+        raise ValueError("octree sh_accumulate: logits must be (L,4), got %s"
+                         % (tuple(logits.shape),))
+    if leaf_data.dim() != 2 or tuple(leaf_data.shape) != (logits.shape[0], channels):
+        raise ValueError("octree sh_accumulate: leaf_data must be (%d, %d), got %s"
+                         % (logits.shape[0], channels, tuple(leaf_data.shape)))
+    weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if len(weights) != basis:
+        raise ValueError("octree sh_accumulate: %d weights for degree %d, got %d"
+                         % (basis, degree, len(weights)))
+    if logits.shape[0] > 0:
+        host = (ctypes.c_float * basis)(*[float(v) for v in weights])
+        _call("ffn_octree_sh_accumulate", _dev(logits, name="logits"), c_i64(logits.shape[0]),
+              c_i(degree), host, c_f(inv_views), _dev(leaf_data, name="leaf_data"))
+    return leaf_data
+
+
 def octree_grad_workspace_bytes(n: int, num_leaves: int, max_entries: int) -> int:
     """Bytes of workspace ``octree_render_volume_backward`` needs for ``n`` rays, ``num_leaves``
     leaves and up to ``max_entries`` (ray, taken leaf) pairs."""

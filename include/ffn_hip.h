@@ -984,6 +984,43 @@ int ffn_octree_render_volume_backward(
  * 16-byte aligned: r, g, b = min(max(x, 0), 1), sigma = max(x, 0); a NaN becomes 0. */
 int ffn_octree_project(float* leaf_data, int64_t num_leaves, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K18  view-dependent colour in a baked tree: spherical harmonics per leaf.  No counterpart in the
+ * reference.  B = (degree + 1)^2, degree 1 or 2.  A leaf holds 3 B coefficients k in logit space and
+ * a density; its colour for the unit vector u = (x, y, z) is sigmoid(sum_b k[c B + b] Y_b(u)) with
+ *   Y_0 = 0.28209479177387814
+ *   Y_1 = -0.4886025119029199 y     Y_2 = 0.4886025119029199 z     Y_3 = -0.4886025119029199 x
+ *   Y_4 = 1.0925484305920792 xy     Y_5 = -1.0925484305920792 yz
+ *   Y_6 = 0.31539156525252005 (2zz - xx - yy)
+ *   Y_7 = -1.0925484305920792 xz    Y_8 = 0.5462742152960396 (xx - yy)
+ *
+ * K18a (csrc/octree_walk.hip, two more modes of the K13 kernel).  ffn_octree_render_volume with
+ * that colour: u = direction / norm, not negated, its basis computed once per ray; the dot product
+ * is a chain of fused multiply-adds from b = 0, the sigmoid ffn_octree_bake's.  Everything else (t0,
+ * L, sigma, a, w, T, the depth, the early end, the background, a miss) is K15's, operation for
+ * operation: on the same structure and densities alpha and depth have K15's bits.  A direction of
+ * length 0 is a miss like any other and leaks no NaN.  leaf_data is the DEVICE layout, 16-byte
+ * aligned: rows of row_stride floats [sigma, k_r0 .. k_r(B-1), k_g0 .., k_b0 .., padding];
+ * channels == 3 B + 1 <= row_stride <= 64, row_stride a multiple of 4.  The other arguments as for
+ * ffn_octree_render_volume. */
+int ffn_octree_render_volume_sh(const float* starts, const float* directions, int64_t n,
+                                float scale, int depth, const int64_t* node_index,
+                                int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+                                float t_min, const float* leaf_data, int channels, float bg_r,
+                                float bg_g, float bg_b, float min_transmittance, float* color,
+                                float* alpha, float* depth_out, int degree, int row_stride,
+                                void* stream);
+
+/* K18b (csrc/composite.hip).  One view of the projection of a model onto the basis: logits
+ * (num_leaves,4), 16-byte aligned, the model at the leaves for ONE view direction; weights (B
+ * floats, HOST memory) that view's column of the pseudo-inverse of the basis matrix.  In place on
+ * leaf_data (num_leaves, 3 B + 1) f32 in the FILE layout [k_r0 .. k_r(B-1), k_g0 .., k_b0 .., sigma]:
+ *   k[c B + b] = k[c B + b] + weights[b] * logits[c]     one multiply, one add, no fused multiply-add
+ *   sigma      = sigma + softplus(logits[3]) * inv_views  the softplus of ffn_octree_bake
+ * One thread per leaf, no atomics: the same calls in the same order give the same bits. */
+int ffn_octree_sh_accumulate(const float* logits, int64_t num_leaves, int degree,
+                             const float* weights, float inv_views, float* leaf_data, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

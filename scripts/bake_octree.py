@@ -5,9 +5,12 @@ first-hit render shows one opaque colour per cell.  No counterpart in the refere
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.  A model that takes a view direction is baked for the one fixed direction
-``--view``: its view dependence is lost.
+``--view``: its view dependence is lost, unless ``--sh-degree`` is given.  Then every leaf gets
+spherical-harmonic coefficients of the model's colour over ``--num-views`` view directions
+(``OcTree.bake_sh``, kernel K18b); the file carries ``sh_degree`` and ``render_octree.py --mode
+volume`` renders it per ray direction (kernel K18a) without a flag of its own.
 
-    python scripts/bake_octree.py tree.npz model.pt out.npz --center X Y Z
+    python scripts/bake_octree.py tree.npz model.pt out.npz --center X Y Z [--sh-degree 2]
 """
 
 import os
@@ -30,6 +33,10 @@ BAKE_OCTREE = [
     ("--batch-size", dict(type=int, default=1 << 20,
                           help="Number of leaves to evaluate in a batch")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
+    ("--sh-degree", dict(type=int, choices=[1, 2], default=None,
+                         help="Bake view-dependent colour as spherical harmonics of this degree")),
+    ("--num-views", dict(type=int, default=64,
+                         help="--sh-degree: number of view directions the model is sampled from")),
 ]
 
 
@@ -47,9 +54,14 @@ def main():
     model = ffn.load_model(args.model_path)
     if model is None:
         return 1
-    baked = tree.bake(model.to(device), center=args.center, view=args.view,
-                      batch_size=args.batch_size)
-    density = baked.leaf_data()[:, 3]
+    if args.sh_degree is None:
+        baked = tree.bake(model.to(device), center=args.center, view=args.view,
+                          batch_size=args.batch_size)
+        density = baked.leaf_data()[:, 3]
+    else:
+        baked = tree.bake_sh(model.to(device), args.sh_degree, args.num_views, center=args.center,
+                             batch_size=args.batch_size)
+        density = baked.leaf_data()[:, -1]
     print(baked.num_leaves, "leaves baked")
     print("density min %.6g median %.6g max %.6g" % (float(density.min()),
                                                       float(np.median(density)),

@@ -2,7 +2,8 @@
 dataset's cameras with the first-hit walk (kernel K14): one PNG per camera and its PSNR against
 the camera's ground-truth image.  No counterpart in the reference, which shows the leaf cubes
 through scenepic (voxelize_model.py:90-110).  ``--mode volume`` composites a tree that
-``scripts/bake_octree.py`` has baked along the whole ray instead (kernel K15).
+``scripts/bake_octree.py`` has baked along the whole ray instead (kernel K15); a file baked with
+``--sh-degree`` says so itself and gets its view-dependent colour (kernel K18a).
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.
