@@ -11,7 +11,7 @@ from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
 from .octree import OcTree
-from .octree_fit import FitLogEntry, OctreeField, fit_octree
+from .octree_fit import FitLogEntry, OctreeField, OctreeSHField, fit_octree, fit_octree_sh
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
@@ -39,6 +39,6 @@ __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OcTree", "OccupancyGrid", "OctreeField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
+           "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
-           "exponential_lr_decay", "fit_octree", "linspace", "load_model", "orbit"]
+           "exponential_lr_decay", "fit_octree", "fit_octree_sh", "linspace", "load_model", "orbit"]

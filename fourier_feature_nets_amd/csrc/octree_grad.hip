@@ -27,6 +27,7 @@
 // Integer atomics appear in the tile histogram only, where their order does not matter.
 #include "common.h"
 #include "octree_grad.h"
+#include "sh_terms.h"
 
 namespace ffn {
 
@@ -251,6 +252,159 @@ octree_project_kernel(float4* __restrict__ leaf_data, int64_t num_leaves) {
     leaf_data[l] = v;
 }
 
+// ---------------------------------------------------------------------------------- K19b
+// Per-leaf sums of WIDE rows: the gradient of an SH leaf is [d sigma, d k_cb = sum e_c Y_b(u)], 3 B + 1
+// values, but an entry of K19a stays K17a's float4 (e_r, e_g, e_b, d sigma) plus its ray's number: the
+// rank-one factor Y_b(u) belongs to the ray.  K17b-1/2/3 run unchanged.  The first level of the
+// reduce reads a leaf's entries in sorted order in runs of kGradChunk, rebuilds each entry's basis
+// from its ray's direction (sh_terms.h, the walk's own bits), and writes ONE row of kWidth = 16 / 28
+// floats per run; further levels add runs of kGradChunk rows; the finish writes every row of the
+// output.  The summation tree is K17b's, so the density column has K17b's order.  Wide rows exist per
+// partial sum only: leaf l's run q lands at row seg_lo[l] / 16 + (non-empty leaves before l) + q,
+// which never collides with the next leaf's (ceil(len / 16) <= floor((lo + len) / 16) - floor(lo / 16)
+// + 1), so E / 16 + L + 1 rows hold every level.
+//
+// Thread mapping.  Level 0: one thread per run, with the kWidth accumulators in registers (28 + 9
+// basis values + the entry: no LDS, no scratch).  The cost of level 0 is its dependent gathers --
+// order[i], then the entry's 16 + 4 bytes, then 12 bytes of its ray's direction, all at random
+// places -- and a thread per run does each ONCE per entry; one thread per (run, 16-byte quad) would
+// repeat them seven times at degree 2 to make the row's store coalesced, and the row is 7 bytes per
+// entry against 36 gathered.  Further levels and the finish touch 1/16 of that: a thread per run
+// walks the row quad by quad (16 float4 loads each), a thread per (leaf, quad) finishes.
+constexpr int sh_bases(int degree) { return (degree + 1) * (degree + 1); }
+constexpr int sh_width(int degree) { return (3 * sh_bases(degree) + 1 + 3) / 4 * 4; }
+
+// before[l] = 1 where leaf l has entries; scanned in place to the number of such leaves before l
+__global__ void __launch_bounds__(256)
+grad_sh_nonempty_kernel(const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_hi,
+                        int64_t num_leaves, int32_t* __restrict__ before) {
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= num_leaves) return;
+    before[l] = seg_hi[l] > seg_lo[l] ? 1 : 0;
+}
+
+template <int kDegree>
+__global__ void __launch_bounds__(256)
+grad_sh_reduce_first_kernel(const int32_t* __restrict__ keys, const int32_t* __restrict__ order,
+                            const float4* __restrict__ values, const int32_t* __restrict__ rays,
+                            const float* __restrict__ directions, int64_t n,
+                            float4* __restrict__ rows, int64_t row_capacity, int32_t e,
+                            int32_t num_leaves, const int32_t* __restrict__ seg_lo,
+                            const int32_t* __restrict__ seg_hi,
+                            const int32_t* __restrict__ before) {
+    constexpr int kBasis = sh_bases(kDegree);
+    constexpr int kWidth = sh_width(kDegree);
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= e) return;
+    const int32_t l = keys[p];
+    if (l < 0 || l >= num_leaves) return;
+    const int lo = seg_lo[l];
+    const int len = seg_hi[l] - lo;
+    const int q = (int)p - lo;
+    if (q < 0 || q >= (len + kGradChunk - 1) / kGradChunk) return;
+    const int64_t at = (int64_t)(lo / kGradChunk) + before[l] + q;
+    if (at >= row_capacity) return;           // never, for a workspace laid out for e entries
+    const int first = lo + q * kGradChunk;
+    const int end = min(first + kGradChunk, lo + len);
+    float acc[kWidth];
+#pragma unroll
+    for (int k = 0; k < kWidth; ++k) acc[k] = 0.0f;
+    for (int i = first; i < end; ++i) {
+        const int32_t j = order != nullptr ? order[i] : i;
+        if (j < 0 || j >= e) continue;         // never, for an order made by the sort
+        const float4 v = values[j];
+        const int64_t ray = rays[j];
+        float basis[kBasis];
+        if (ray >= 0 && ray < n) {
+            const float dx = directions[ray * 3 + 0], dy = directions[ray * 3 + 1],
+                        dz = directions[ray * 3 + 2];
+            sh_ray_basis<kDegree>(dx, dy, dz, ray_norm(dx, dy, dz), basis);
+        } else {
+#pragma unroll
+            for (int b = 0; b < kBasis; ++b) basis[b] = 0.0f;
+        }
+        const bool head = i == first;          // K17b starts from the first term, not from 0
+        const float e3[3] = {v.x, v.y, v.z};
+        acc[0] = head ? v.w : acc[0] + v.w;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int b = 0; b < kBasis; ++b) {
+                const float term = e3[c] * basis[b];
+                acc[1 + c * kBasis + b] = head ? term : acc[1 + c * kBasis + b] + term;
+            }
+    }
+    float4* dst = rows + at * (kWidth / 4);
+#pragma unroll
+    for (int k = 0; k < kWidth / 4; ++k)
+        dst[k] = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
+}
+
+// level >= 1: runs of kGradChunk rows of a leaf into one, at the leaf's own rows of the other buffer
+__global__ void __launch_bounds__(256)
+grad_sh_reduce_kernel(const int32_t* __restrict__ keys, const float4* __restrict__ src,
+                      float4* __restrict__ dst, int64_t row_capacity, int quads, int32_t e,
+                      int32_t num_leaves, const int32_t* __restrict__ seg_lo,
+                      const int32_t* __restrict__ seg_hi, const int32_t* __restrict__ before,
+                      int level) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= e) return;
+    const int32_t l = keys[p];
+    if (l < 0 || l >= num_leaves) return;
+    const int lo = seg_lo[l];
+    int len = seg_hi[l] - lo;
+    for (int j = 0; j < level; ++j) len = (len + kGradChunk - 1) / kGradChunk;
+    const int q = (int)p - lo;
+    if (q < 0 || q >= (len + kGradChunk - 1) / kGradChunk) return;
+    const int64_t base = (int64_t)(lo / kGradChunk) + before[l];
+    const int64_t first = base + (int64_t)q * kGradChunk;
+    const int64_t last = min(first + kGradChunk, base + len);
+    if (last > row_capacity) return;          // never, as above
+    for (int k = 0; k < quads; ++k) {
+        float4 acc = src[first * quads + k];
+        for (int64_t i = first + 1; i < last; ++i) {
+            const float4 v = src[i * quads + k];
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        dst[(base + q) * quads + k] = acc;
+    }
+}
+
+// every quad of every row of d_leaf_rows: the leaf's sum, +0 for a leaf without entries and for the
+// columns past the kernel's own width (stride > 4 quads)
+__global__ void __launch_bounds__(256)
+grad_sh_finish_kernel(const float4* __restrict__ sums, int quads, const int32_t* __restrict__ seg_lo,
+                      const int32_t* __restrict__ seg_hi, const int32_t* __restrict__ before,
+                      int64_t num_leaves, int stride_quads, float4* __restrict__ d_leaf_rows) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= num_leaves * stride_quads) return;
+    const int64_t l = idx / stride_quads;
+    const int k = (int)(idx - l * stride_quads);
+    const int lo = seg_lo[l];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (seg_hi[l] > lo && k < quads) v = sums[((int64_t)(lo / kGradChunk) + before[l]) * quads + k];
+    v.x += 0.0f; v.y += 0.0f; v.z += 0.0f; v.w += 0.0f;      // as K17b-5
+    d_leaf_rows[idx] = v;
+}
+
+// ---------------------------------------------------------------------------------- K19c
+__global__ void __launch_bounds__(256)
+octree_project_sh_kernel(float4* __restrict__ rows, int64_t num_leaves, int stride_quads,
+                         int channels) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= num_leaves * stride_quads) return;
+    const int col = 4 * (int)(idx % stride_quads);
+    if (col >= channels) return;              // padding: untouched
+    const float4 v = rows[idx];
+    float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (col + j == 0) x[j] = x[j] > 0.0f ? x[j] : 0.0f;              // density; NaN, -0 -> +0
+        else if (col + j < channels) x[j] = x[j] != x[j] ? 0.0f : x[j];  // a logit: only NaN moves
+    }
+    rows[idx] = make_float4(x[0], x[1], x[2], x[3]);
+}
+
 struct GradWorkspace {
     int32_t* ray_slots;     // n + 1
     float* ray_color;       // 3n
@@ -288,6 +442,76 @@ static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, Grad
         off += align256(sizes[r]);
     }
     return off;
+}
+
+struct GradSHWorkspace {
+    GradWorkspace k;        // K17b's (k.sums is not laid out: the partial sums are rows)
+    int32_t* rays;          // capacity: the ray of every entry
+    int32_t* before;        // num_leaves
+    float4* rows[2];        // row_capacity rows of sh_width(degree) floats each
+    int64_t row_capacity;
+};
+
+// E / 16 + min(E, L) rows hold every level's partial sums; the second term is taken at L so that the
+// size stays affine in max_entries
+static int64_t grad_sh_layout(int64_t n, int64_t num_leaves, int64_t capacity, int degree,
+                              GradSHWorkspace* ws, char* base) {
+    const int64_t tiles = (capacity + kSortTile - 1) / kSortTile;
+    int64_t longest = 256 * tiles > n ? 256 * tiles : n;
+    if (num_leaves > longest) longest = num_leaves;
+    const int64_t blocks = (longest + kGradScanBlock - 1) / kGradScanBlock + 1;
+    const int64_t row_capacity = capacity / kGradChunk + num_leaves + 1;
+    const int64_t row_bytes = 4 * (int64_t)sh_width(degree);
+    const int64_t sizes[16] = {4 * (n + 1), 12 * n, 4 * n, 4 * blocks, 16 * capacity, 4 * capacity,
+                               4 * capacity, 4 * capacity, 4 * capacity, 4 * 256 * tiles,
+                               4 * num_leaves, 4 * num_leaves, 4 * capacity, 4 * num_leaves,
+                               row_bytes * row_capacity, row_bytes * row_capacity};
+    GradSHWorkspace scratch;
+    GradSHWorkspace* w = ws != nullptr ? ws : &scratch;
+    void** slots[16] = {(void**)&w->k.ray_slots, (void**)&w->k.ray_color, (void**)&w->k.ray_trans,
+                        (void**)&w->k.block_sums, (void**)&w->k.values, (void**)&w->k.keys[0],
+                        (void**)&w->k.keys[1], (void**)&w->k.order[0], (void**)&w->k.order[1],
+                        (void**)&w->k.table, (void**)&w->k.seg_lo, (void**)&w->k.seg_hi,
+                        (void**)&w->rays, (void**)&w->before, (void**)&w->rows[0],
+                        (void**)&w->rows[1]};
+    int64_t off = 0;
+    for (int r = 0; r < 16; ++r) {
+        *slots[r] = base != nullptr ? base + off : nullptr;
+        off += align256(sizes[r]);
+    }
+    w->k.sums = nullptr;
+    w->row_capacity = row_capacity;
+    return off;
+}
+
+// K17b-2 and K17b-3 on the e entries whose leaf numbers K17a / K19a left in ws.keys[0]: -> the sorted
+// keys and the entries' order (null when a single leaf needs no pass: the entries are in place)
+static void sort_and_bounds(const GradWorkspace& ws, int32_t e, int64_t num_leaves, hipStream_t st,
+                            const int32_t** keys_out_p, const int32_t** order_out_p) {
+    int bits = 0;
+    while (bits < 31 && ((int64_t)1 << bits) < num_leaves) ++bits;
+    const int passes = (bits + 7) / 8;
+    const int32_t tiles = (e + kSortTile - 1) / kSortTile;
+    const int32_t* keys = ws.keys[0];
+    const int32_t* order = nullptr;
+    for (int pass = 0; pass < passes; ++pass) {
+        int32_t* keys_out = ws.keys[(pass + 1) & 1];
+        int32_t* order_out = ws.order[(pass + 1) & 1];
+        hipLaunchKernelGGL(grad_sort_hist_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys, e,
+                           8 * pass, tiles, ws.table);
+        exclusive_scan(ws.table, (int64_t)256 * tiles, ws.block_sums, nullptr, st);
+        hipLaunchKernelGGL(grad_sort_scatter_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys,
+                           order, e, 8 * pass, tiles, ws.table, keys_out, order_out);
+        keys = keys_out;
+        order = order_out;
+    }
+    const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
+    (void)hipMemsetAsync(ws.seg_lo, 0, 4 * num_leaves, st);
+    (void)hipMemsetAsync(ws.seg_hi, 0, 4 * num_leaves, st);
+    hipLaunchKernelGGL(grad_bounds_kernel, dim3(over_entries), dim3(256), 0, st, keys, e,
+                       (int32_t)num_leaves, ws.seg_lo, ws.seg_hi);
+    *keys_out_p = keys;
+    *order_out_p = order;
 }
 
 static inline bool grad_shape(int64_t n, int64_t num_leaves, int64_t max_entries) {
@@ -377,28 +601,10 @@ extern "C" int ffn_octree_render_volume_backward(
                                    ws.ray_color, ws.ray_trans, ws.values, ws.keys[0], 1, st))
         return err;
 
-    int bits = 0;
-    while (bits < 31 && ((int64_t)1 << bits) < num_leaves) ++bits;
-    const int passes = (bits + 7) / 8;
-    const int32_t tiles = (e + kSortTile - 1) / kSortTile;
-    const int32_t* keys = ws.keys[0];
+    const int32_t* keys = nullptr;
     const int32_t* order = nullptr;
-    for (int pass = 0; pass < passes; ++pass) {
-        int32_t* keys_out = ws.keys[(pass + 1) & 1];
-        int32_t* order_out = ws.order[(pass + 1) & 1];
-        hipLaunchKernelGGL(grad_sort_hist_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys, e,
-                           8 * pass, tiles, ws.table);
-        exclusive_scan(ws.table, (int64_t)256 * tiles, ws.block_sums, nullptr, st);
-        hipLaunchKernelGGL(grad_sort_scatter_kernel, dim3(tiles), dim3(kSortThreads), 0, st, keys,
-                           order, e, 8 * pass, tiles, ws.table, keys_out, order_out);
-        keys = keys_out;
-        order = order_out;
-    }
+    sort_and_bounds(ws, e, num_leaves, st, &keys, &order);
     const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
-    (void)hipMemsetAsync(ws.seg_lo, 0, 4 * num_leaves, st);
-    (void)hipMemsetAsync(ws.seg_hi, 0, 4 * num_leaves, st);
-    hipLaunchKernelGGL(grad_bounds_kernel, dim3(over_entries), dim3(256), 0, st, keys, e,
-                       (int32_t)num_leaves, ws.seg_lo, ws.seg_hi);
     // a ray takes a leaf once: no list is longer than min(n, e)
     const int64_t longest = n < e ? n : e;
     int levels = 1;
@@ -424,4 +630,145 @@ extern "C" int ffn_octree_project(float* leaf_data, int64_t num_leaves, void* st
     hipLaunchKernelGGL(octree_project_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256),
                        0, (hipStream_t)stream, (float4*)leaf_data, num_leaves);
     return check_launch("ffn_octree_project");
+}
+
+extern "C" int64_t ffn_octree_grad_sh_workspace_bytes(int64_t n, int64_t num_leaves,
+                                                      int64_t max_entries, int degree) {
+    if (degree != 1 && degree != 2) {
+        fail_arg("ffn_octree_grad_sh_workspace_bytes: degree is 1 or 2");
+        return -1;
+    }
+    if (!grad_shape(n, num_leaves, max_entries)) {
+        fail_arg("ffn_octree_grad_sh_workspace_bytes: shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, "
+                 "0 <= max_entries < 2^31)");
+        return -1;
+    }
+    return grad_sh_layout(n, num_leaves, max_entries, degree, nullptr, nullptr);
+}
+
+extern "C" int ffn_octree_render_volume_sh_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
+    int row_stride, void* stream) {
+    const char* who = "ffn_octree_render_volume_sh_backward";
+    if (entries != nullptr) *entries = -1;
+    if (degree != 1 && degree != 2)
+        return fail_arg("ffn_octree_render_volume_sh_backward: degree is 1 or 2");
+    if (row_stride < 3 * sh_bases(degree) + 1 || row_stride % 4 != 0 || row_stride > 64)
+        return fail_arg("ffn_octree_render_volume_sh_backward: row_stride is a multiple of 4, "
+                        "3 * (degree + 1)^2 + 1 <= row_stride <= 64");
+    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_sh_backward: t_min is NaN");
+    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
+        return fail_arg("ffn_octree_render_volume_sh_backward: 0 <= min_transmittance < 1");
+    if (!leaf_rows || !d_color || !d_alpha || !d_leaf_rows || !workspace)
+        return fail_arg("ffn_octree_render_volume_sh_backward: null argument");
+    if (int err = octree_check_walk_args(who, starts, directions, n, depth, node_index, num_nodes,
+                                         leaf_index, num_leaves))
+        return err;
+    if (((uintptr_t)leaf_rows & 15) != 0 || ((uintptr_t)d_leaf_rows & 15) != 0 ||
+        ((uintptr_t)workspace & 15) != 0)
+        return fail_arg("ffn_octree_render_volume_sh_backward: leaf_rows, d_leaf_rows and workspace "
+                        "must be 16-byte aligned");
+    // a ray crosses at most 3 * 2^(depth-1) + 1 regions: the entry offsets stay below 2^31
+    if (!grad_shape(n, num_leaves, max_entries) ||
+        n * (3 * ((int64_t)1 << (depth - 1)) + 1) > kGradMaxEntries)
+        return fail_arg("ffn_octree_render_volume_sh_backward: shape (n * (3 * 2^(depth-1) + 1) < "
+                        "2^31: split the rays)");
+    if (workspace_bytes < grad_sh_layout(n, num_leaves, max_entries, degree, nullptr, nullptr))
+        return fail_arg("ffn_octree_render_volume_sh_backward: workspace too small for max_entries");
+    hipStream_t st = (hipStream_t)stream;
+    GradSHWorkspace ws;
+    grad_sh_layout(n, num_leaves, max_entries, degree, &ws, (char*)workspace);
+
+    // K19a, first walk: counts, C and T_{n+1} per ray
+    if (int err = octree_grad_sh_walk(who, starts, directions, n, scale, depth, node_index,
+                                      num_nodes, leaf_index, num_leaves, t_min, leaf_rows,
+                                      row_stride, degree, bg_r, bg_g, bg_b, min_transmittance,
+                                      d_color, d_alpha, ws.k.ray_slots, ws.k.ray_color,
+                                      ws.k.ray_trans, ws.k.values, ws.k.keys[0], ws.rays, 0, st))
+        return err;
+    exclusive_scan(ws.k.ray_slots, n, ws.k.block_sums, ws.k.ray_slots + n, st);
+    int32_t total = 0;
+    hipError_t copied = hipMemcpyAsync(&total, ws.k.ray_slots + n, 4, hipMemcpyDeviceToHost, st);
+    if (copied == hipSuccess) copied = hipStreamSynchronize(st);
+    if (copied != hipSuccess) {
+        set_error(who, copied);
+        return (int)copied;
+    }
+    if (entries != nullptr) *entries = total;
+    if (total < 0 || total > max_entries) {
+        char text[160];
+        snprintf(text, sizeof text, "%s: the rays take %lld leaves, the workspace holds %lld entries",
+                 who, (long long)total, (long long)max_entries);
+        return fail_arg(text);
+    }
+    const int32_t e = total;
+    if (e == 0) {
+        (void)hipMemsetAsync(d_leaf_rows, 0, 4 * (int64_t)row_stride * num_leaves, st);
+        return check_launch(who);
+    }
+    // K19a, second walk: the entries
+    if (int err = octree_grad_sh_walk(who, starts, directions, n, scale, depth, node_index,
+                                      num_nodes, leaf_index, num_leaves, t_min, leaf_rows,
+                                      row_stride, degree, bg_r, bg_g, bg_b, min_transmittance,
+                                      d_color, d_alpha, ws.k.ray_slots, ws.k.ray_color,
+                                      ws.k.ray_trans, ws.k.values, ws.k.keys[0], ws.rays, 1, st))
+        return err;
+    const int32_t* keys = nullptr;
+    const int32_t* order = nullptr;
+    sort_and_bounds(ws.k, e, num_leaves, st, &keys, &order);
+    const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
+    const unsigned over_leaves = (unsigned)((num_leaves + 255) / 256);
+    hipLaunchKernelGGL(grad_sh_nonempty_kernel, dim3(over_leaves), dim3(256), 0, st, ws.k.seg_lo,
+                       ws.k.seg_hi, num_leaves, ws.before);
+    exclusive_scan(ws.before, num_leaves, ws.k.block_sums, nullptr, st);
+    const int quads = sh_width(degree) / 4;
+    if (degree == 1)
+        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<1>, dim3(over_entries), dim3(256), 0, st, keys,
+                           order, ws.k.values, ws.rays, directions, n, ws.rows[0], ws.row_capacity,
+                           e, (int32_t)num_leaves, ws.k.seg_lo, ws.k.seg_hi, ws.before);
+    else
+        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<2>, dim3(over_entries), dim3(256), 0, st, keys,
+                           order, ws.k.values, ws.rays, directions, n, ws.rows[0], ws.row_capacity,
+                           e, (int32_t)num_leaves, ws.k.seg_lo, ws.k.seg_hi, ws.before);
+    // a ray takes a leaf once: no list is longer than min(n, e)
+    const int64_t longest = n < e ? n : e;
+    int levels = 1;
+    for (int64_t reach = kGradChunk; reach < longest; reach *= kGradChunk) ++levels;
+    const float4* src = ws.rows[0];
+    for (int level = 1; level < levels; ++level) {
+        float4* dst = ws.rows[level & 1];
+        hipLaunchKernelGGL(grad_sh_reduce_kernel, dim3(over_entries), dim3(256), 0, st, keys, src,
+                           dst, ws.row_capacity, quads, e, (int32_t)num_leaves, ws.k.seg_lo,
+                           ws.k.seg_hi, ws.before, level);
+        src = dst;
+    }
+    const int stride_quads = row_stride / 4;
+    hipLaunchKernelGGL(grad_sh_finish_kernel,
+                       dim3((unsigned)((num_leaves * stride_quads + 255) / 256)), dim3(256), 0, st,
+                       src, quads, ws.k.seg_lo, ws.k.seg_hi, ws.before, num_leaves, stride_quads,
+                       (float4*)d_leaf_rows);
+    return check_launch(who);
+}
+
+extern "C" int ffn_octree_project_sh(float* leaf_rows, int64_t num_leaves, int row_stride,
+                                     int degree, void* stream) {
+    if (degree != 1 && degree != 2) return fail_arg("ffn_octree_project_sh: degree is 1 or 2");
+    if (row_stride < 3 * sh_bases(degree) + 1 || row_stride % 4 != 0 || row_stride > 64)
+        return fail_arg("ffn_octree_project_sh: row_stride is a multiple of 4, "
+                        "3 * (degree + 1)^2 + 1 <= row_stride <= 64");
+    if (!leaf_rows) return fail_arg("ffn_octree_project_sh: null argument");
+    if (num_leaves < 1 || num_leaves >= ((int64_t)1 << 31))
+        return fail_arg("ffn_octree_project_sh: 1 <= num_leaves < 2^31");
+    if (((uintptr_t)leaf_rows & 15) != 0)
+        return fail_arg("ffn_octree_project_sh: leaf_rows must be 16-byte aligned");
+    const int stride_quads = row_stride / 4;
+    hipLaunchKernelGGL(octree_project_sh_kernel,
+                       dim3((unsigned)((num_leaves * stride_quads + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (float4*)leaf_rows, num_leaves, stride_quads,
+                       3 * sh_bases(degree) + 1);
+    return check_launch("ffn_octree_project_sh");
 }

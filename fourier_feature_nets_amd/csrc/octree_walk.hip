@@ -82,9 +82,24 @@
 // Resource report, kVolumeSH1 / kVolumeSH2: 56 / 72 VGPRs (occupancy 8 / 7 waves per SIMD), 0 bytes
 // of scratch, 0 spills, 0 bytes of LDS; the five older instantiations compile to the instructions
 // they had before (38 / 40 / 50 / 53 / 61 VGPRs).
+//
+// K19a  Gradient walk through SH leaves: the backward of K18a, two more modes (kGradSH1 / kGradSH2),
+// to K18a what K17a is to K15: the same two phases (0 counts and composites, 1 emits), the same reuse
+// of idle parameters (first.leaf carries the entries' ray numbers), and K18a's arithmetic operation
+// for operation for t0, the chord, sigma, a, w, T, the basis Y(u) (csrc/sh_terms.h) and the colour
+// c = sigmoid(k . Y(u)), so phase 0 reproduces the forward's C and T_{n+1} bit for bit.  Taken leaf k
+// of a ray leaves ONE narrow entry, as K17a:
+//     (e_r, e_g, e_b) with e_c = (w_k g_c) (c_kc (1 - c_kc)),   d sigma_k as K17a with the sigmoid colour
+// plus the leaf's and the ray's number; d k_cb = e_c Y_b(u) is formed where the entries are summed
+// (K19b, csrc/octree_grad.hip): the rank-one factor belongs to the ray, not to the entry.
+// Resource report, kGradSH1 / kGradSH2: 64 / 82 VGPRs, 102 / 102 SGPRs, 0 bytes of scratch, 0 spills,
+// 0 bytes of LDS, occupancy 7 / 5 waves per SIMD (kGradSH1 is held to 7 by its 102 SGPRs; the whole row is held as in K18a: 7 16-byte loads at
+// degree 2; it did not need to be consumed channel by channel).  The seven older instantiations
+// compile to the instructions they had before (38 / 40 / 50 / 53 / 61 / 56 / 72 VGPRs).
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
+#include "sh_terms.h"
 
 namespace ffn {
 
@@ -176,25 +191,7 @@ struct FirstHit {
 };
 
 enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
-                kVolumeSH2 = 6 };
-
-// K18a: the real SH basis of bands 0 .. kDegree at the unit vector (x, y, z), in the order and with
-// the signs of include/ffn_hip.h
-template <int kDegree>
-__device__ __forceinline__ void sh_terms(float x, float y, float z,
-                                         float (&basis)[(kDegree + 1) * (kDegree + 1)]) {
-    basis[0] = 0.28209479177387814f;
-    basis[1] = -0.4886025119029199f * y;
-    basis[2] = 0.4886025119029199f * z;
-    basis[3] = -0.4886025119029199f * x;
-    if constexpr (kDegree >= 2) {
-        basis[4] = 1.0925484305920792f * (x * y);
-        basis[5] = -1.0925484305920792f * (y * z);
-        basis[6] = 0.31539156525252005f * (2.0f * (z * z) - x * x - y * y);
-        basis[7] = -1.0925484305920792f * (x * z);
-        basis[8] = 0.5462742152960396f * (x * x - y * y);
-    }
-}
+                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
@@ -207,6 +204,8 @@ __device__ __forceinline__ void sh_terms(float x, float y, float z,
 //            first.color / first.alpha the per-ray C and T_{n+1} (written in phase 0, read in
 //            phase 1), span_in / span_out the upstream d_color / d_alpha, t_stops the entries'
 //            float4 values and leaves their int32 leaf numbers.
+// kGradSH1 / kGradSH2: K19a, kGrad with the leaf colour of K18a.  As kGrad, and first.leaf carries
+//            the entries' int32 ray numbers; first.leaf_data / first.channels as kVolumeSH*.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -217,7 +216,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                    float* __restrict__ span_out, uint8_t* __restrict__ span_hit, FirstHit first) {
     constexpr bool kSpans = kMode == kSpan;
     constexpr bool kSH = kMode == kVolumeSH1 || kMode == kVolumeSH2;
-    constexpr int kBasis = kMode == kVolumeSH2 ? 9 : 4;
+    constexpr bool kSHGrad = kMode == kGradSH1 || kMode == kGradSH2;
+    constexpr int kBasis = kMode == kVolumeSH2 || kMode == kGradSH2 ? 9 : 4;
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= n) return;
     const float ox = starts[r * 3 + 0], oy = starts[r * 3 + 1], oz = starts[r * 3 + 2];
@@ -258,24 +258,21 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume || kMode == kGrad || kSH
+    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad
                            ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
-    const bool emit = kMode == kGrad && max_length != 0;
+    const bool emit = (kMode == kGrad || kSHGrad) && max_length != 0;
     int32_t* ray_slots = reinterpret_cast<int32_t*>(span_hit);
     float4* entry_values = reinterpret_cast<float4*>(t_stops);
     int32_t* entry_leaves = reinterpret_cast<int32_t*>(leaves);
+    int32_t* entry_rays = reinterpret_cast<int32_t*>(first.leaf);        // K19a
     int taken = 0, base = 0, mine = 0;
     float c_r = 0.0f, c_g = 0.0f, c_b = 0.0f, t_end = 0.0f, g_r = 0.0f, g_g = 0.0f, g_b = 0.0f,
           g_a = 0.0f;
-    // K18a: the basis at the ray's unit direction.  A direction without a length (zero, NaN) is a
-    // miss and takes no leaf; its basis is never read, and is kept finite anyway
+    // K18a, K19a: the basis at the ray's unit direction (sh_terms.h)
     float basis[kBasis];
-    if (kSH) {
-        const float inv = norm > 0.0f && norm < __builtin_inff() ? 1.0f / norm : 0.0f;
-        sh_terms<kMode == kVolumeSH2 ? 2 : 1>(dx * inv, dy * inv, dz * inv, basis);
-    }
+    if (kSH || kSHGrad) sh_ray_basis<kBasis == 9 ? 2 : 1>(dx, dy, dz, norm, basis);
     if (emit) {
         base = ray_slots[r];
         mine = ray_slots[r + 1] - base;
@@ -399,6 +396,55 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 ++taken;
                 if (trans <= first.min_transmittance) break;
             }
+        } else if (kSHGrad) {
+            if (leaf >= 0 && t_exit > t_min) {
+                // the row, the dot product and the sigmoid are the kSH branch's, line for line.  They
+                // are not shared through a device function: with one (forced inline, with or without
+                // __restrict__) kVolumeSH1 / kVolumeSH2 compile to different instructions, and those
+                // two must keep the ones they have
+                constexpr int kQuads = (3 * kBasis + 1 + 3) / 4;
+                const float4* row4 = reinterpret_cast<const float4*>(first.leaf_data +
+                                                                     leaf * first.channels);
+                float row[4 * kQuads];
+#pragma unroll
+                for (int q = 0; q < kQuads; ++q) {
+                    const float4 v = row4[q];
+                    row[4 * q + 0] = v.x; row[4 * q + 1] = v.y; row[4 * q + 2] = v.z;
+                    row[4 * q + 3] = v.w;
+                }
+                const float ls = row[0];
+                float rgb[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float z = row[1 + c * kBasis] * basis[0];
+#pragma unroll
+                    for (int b = 1; b < kBasis; ++b)
+                        z = __builtin_fmaf(row[1 + c * kBasis + b], basis[b], z);
+                    rgb[c] = sigmoid_f(z);
+                }
+                const float lr = rgb[0], lg = rgb[1], lb = rgb[2];
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                acc_r += w * lr; acc_g += w * lg; acc_b += w * lb;
+                trans = trans * (1.0f - a);                    // T_{k+1}
+                if (emit && taken < mine) {
+                    const float behind = g_r * (trans * lr - (c_r - acc_r)) +
+                                         g_g * (trans * lg - (c_g - acc_g)) +
+                                         g_b * (trans * lb - (c_b - acc_b));
+                    const float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    // e_kc = w g_c (c (1 - c)): the factor of Y_b(u) in d k_cb
+                    entry_values[base + taken] = make_float4((w * g_r) * (lr * (1.0f - lr)),
+                                                             (w * g_g) * (lg * (1.0f - lg)),
+                                                             (w * g_b) * (lb * (1.0f - lb)), ds);
+                    entry_leaves[base + taken] = (int32_t)leaf;
+                    entry_rays[base + taken] = (int32_t)r;
+                }
+                ++taken;
+                if (trans <= first.min_transmittance) break;
+            }
         } else if (kSpans) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (!any_leaf) first_in = t > t_min ? t : t_min;
@@ -452,7 +498,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
         first.alpha[r] = 1.0f - trans;
         first.depth[r] = t_best;
-    } else if (kMode == kGrad) {
+    } else if (kMode == kGrad || kSHGrad) {
         if (!emit) {
             ray_slots[r] = taken;
             first.color[r * 3 + 0] = acc_r + trans * first.bg_r;
@@ -512,6 +558,36 @@ int octree_grad_walk(const char* who, const float* starts, const float* directio
                        starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
                        num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min, 0.0f,
                        (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
+    return check_launch(who);
+}
+
+// K19a, launched by ffn_octree_render_volume_sh_backward (csrc/octree_grad.hip), which has checked
+// the arguments
+int octree_grad_sh_walk(const char* who, const float* starts, const float* directions, int64_t n,
+                        float scale, int depth, const int64_t* node_index, int64_t num_nodes,
+                        const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                        const float* leaf_rows, int row_stride, int degree, float bg_r, float bg_g,
+                        float bg_b, float min_transmittance, const float* d_color,
+                        const float* d_alpha, int32_t* ray_slots, float* ray_color,
+                        float* ray_trans, float4* entry_values, int32_t* entry_leaves,
+                        int32_t* entry_rays, int phase, hipStream_t stream) {
+    FirstHit first{};
+    first.leaf = (int64_t*)entry_rays;
+    first.leaf_data = leaf_rows; first.channels = row_stride;
+    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
+    first.min_transmittance = min_transmittance;
+    first.color = ray_color; first.alpha = ray_trans;
+    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
+    if (degree == 1)
+        hipLaunchKernelGGL(octree_walk_kernel<kGradSH1>, dim3(blocks), dim3(kWalkThreads), 0, stream,
+                           starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                           num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min,
+                           0.0f, (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
+    else
+        hipLaunchKernelGGL(octree_walk_kernel<kGradSH2>, dim3(blocks), dim3(kWalkThreads), 0, stream,
+                           starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                           num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min,
+                           0.0f, (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
     return check_launch(who);
 }
 

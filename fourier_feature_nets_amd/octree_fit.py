@@ -8,6 +8,11 @@ leaf.  ``OctreeField`` makes the leaf values a parameter: its forward is ``OcTre
 K17a + K17b, K7 (clip and Adam) on the flat ``(4 L,)`` buffer, K17c (projection onto
 ``0 <= rgb <= 1``, ``sigma >= 0``).  The structure of the tree does not change.  No counterpart in
 the reference.
+
+``OctreeSHField`` and ``fit_octree_sh`` (K19) are the same for a tree with spherical-harmonic leaves
+(``OcTree.bake_sh``): the parameter is the ``(L, stride)`` buffer in the device layout K18a reads,
+the forward K18a, the backward K19a + K19b, the projection K19c (density ``>= 0``; the coefficients
+live in logit space and are not clamped).
 """
 
 import time
@@ -33,10 +38,9 @@ LEARNING_RATE = 1e-2
 class _RenderVolume(torch.autograd.Function):
     @staticmethod
     def forward(ctx, data, field, starts, directions, t_min, background, min_transmittance):
-        tree = field._tree
-        color, alpha, depth = ops.octree_render_volume(
-            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
-            tree._on_device("leaf_index"), data, t_min, background, min_transmittance)
+        # the field's own render: K15 for an OctreeField, K18a for an OctreeSHField
+        color, alpha, depth = field._render(data, starts, directions, t_min, background,
+                                            min_transmittance)
         ctx.field = field
         ctx.args = (t_min, background, min_transmittance)
         ctx.save_for_backward(data, starts, directions)
@@ -58,9 +62,8 @@ class _RenderVolume(torch.autograd.Function):
 
 def _refuse_sh(tree: OcTree, who: str):
     if tree.sh_degree is not None:
-        raise ValueError("%s: fitting SH leaves is not built (the tree has sh_degree %d; the "
-                         "backward of the SH volume render does not exist)"
-                         % (who, tree.sh_degree))
+        raise ValueError("%s: fitting SH leaves is not built into this entry (the tree has sh_degree %d); "
+                         "use OctreeSHField / fit_octree_sh" % (who, tree.sh_degree))
 
 
 class OctreeField(torch.nn.Module):
@@ -104,6 +107,15 @@ class OctreeField(torch.nn.Module):
             tree._on_device("leaf_index"), self.data.detach() if data is None else data, d_color,
             d_alpha, float(t_min), background, float(min_transmittance), self.workspace, out)
 
+    def _render(self, data, starts, directions, t_min, background, min_transmittance):
+        tree = self._tree
+        return ops.octree_render_volume(
+            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
+            tree._on_device("leaf_index"), data, t_min, background, min_transmittance)
+
+    def _project(self, data):
+        return ops.octree_project(data)
+
     def tree(self) -> OcTree:
         """A new ``OcTree`` with the same structure and centre and the current data."""
         old = self._tree
@@ -114,7 +126,75 @@ class OctreeField(torch.nn.Module):
         return new
 
 
-def _validation_psnr(field: OctreeField, dataset, t_min, min_transmittance) -> float:
+class OctreeSHField(torch.nn.Module):
+    """The leaf values of an SH tree (``OcTree.bake_sh``) as a parameter.  ``data`` (L, stride)
+    float32 on the device in the layout K18a reads (``ops.octree_sh_device_layout``:
+    ``[sigma, k_r.., k_g.., k_b.., 0 ..]``), so that a step never repacks and Adam runs on the flat
+    buffer; the padding has a zero gradient and stays zero."""
+
+    def __init__(self, tree: OcTree, center=None, device=None):
+        super().__init__()
+        if not isinstance(tree, OcTree) or tree.sh_degree is None:
+            raise ValueError("OctreeSHField: the tree has no SH leaves (sh_degree is None); a plain "
+                             "baked tree is fitted by OctreeField / fit_octree")
+        tree._check_volume(0.0)
+        self.sh_degree = int(tree.sh_degree)
+        rows = ops.octree_sh_device_layout(np.asarray(tree.leaf_data()), self.sh_degree)
+        if center is None:
+            center = tree.center
+        self.center = None if center is None else tuple(float(c) for c in center)
+        if self.center is not None and len(self.center) != 3:
+            raise ValueError("OctreeSHField: center has three components")
+        if device is not None:
+            tree._device = torch.device(device)
+        self._tree = tree
+        self.data = torch.nn.Parameter(torch.from_numpy(rows).to(tree._dev()))
+        self.workspace = ops.OctreeGradSHWorkspace(self.sh_degree)
+
+    def _render(self, data, starts, directions, t_min, background, min_transmittance):
+        tree = self._tree
+        return ops.octree_render_volume_sh(
+            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
+            tree._on_device("leaf_index"), data, self.sh_degree, t_min, background,
+            min_transmittance)
+
+    def _project(self, data):
+        return ops.octree_project_sh(data, self.sh_degree)
+
+    def forward(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
+                min_transmittance: float = 0.0) -> RenderResult:
+        """``tree.render_volume`` of the current data, bit for bit, as device tensors;
+        differentiable with respect to ``data`` (colour and alpha; depth has no gradient)."""
+        self._tree._check_volume(min_transmittance)
+        starts, directions, _ = self._tree._rays(starts, directions)
+        background = tuple(float(v) for v in background)
+        return RenderResult(*_RenderVolume.apply(self.data, self, starts, directions,
+                                                   float(t_min), background,
+                                                   float(min_transmittance)))
+
+    def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
+                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
+        """K19a + K19b: d(data) (L, stride) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
+        tree = self._tree
+        return ops.octree_render_volume_sh_backward(
+            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
+            tree._on_device("leaf_index"), self.data.detach() if data is None else data,
+            self.sh_degree, d_color, d_alpha, float(t_min), background, float(min_transmittance),
+            self.workspace, out)
+
+    def tree(self) -> OcTree:
+        """A new SH ``OcTree`` (file layout) with the same ``sh_degree``, structure and centre and
+        the current data."""
+        old = self._tree
+        new = OcTree(old._scale, old._node_index, old._leaf_index,
+                     ops.octree_sh_file_layout(self.data.detach().cpu().numpy(), self.sh_degree),
+                     self.sh_degree)
+        new._device = old._device
+        new._center = self.center
+        return new
+
+
+def _validation_psnr(field, dataset, t_min, min_transmittance) -> float:
     """-10 log10 of the mean colour-MSE + alpha_weight * alpha-MSE over every ray of the
     dataset's cameras, camera by camera."""
     sampler = dataset.sampler
@@ -154,21 +234,50 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
     of ``val_dataset``'s cameras) at steps below 10 and multiples of ``report_interval``, else NaN
     -- and report steps are printed as ``Raycaster.fit`` prints them.  The only host
     synchronisation of a step is the read-back inside K17b; the losses are fetched at the end."""
+    return _fit("fit_octree", OctreeField, tree, train_dataset, val_dataset, batch_size,
+                learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
+                clip_value, max_norm, seed, verbose)
+
+
+def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 4096,
+                  learning_rate: float = LEARNING_RATE, num_steps: int = 2000,
+                  report_interval: int = 500, center=None, t_min: float = 0.0,
+                  min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
+                  max_norm: float = MAX_NORM, seed: int = 20080524,
+                  verbose: bool = True) -> Tuple[OcTree, List[FitLogEntry]]:
+    """``fit_octree`` for a tree with SH leaves (``OcTree.bake_sh``): the same arguments, defaults,
+    seeded shuffle, log and report lines; -> (a new SH ``OcTree`` of the same structure and
+    ``sh_degree``, log).  One step: K18a, K6, K19a + K19b, K7 on the flat ``(L stride,)`` buffer in
+    the device layout, K19c (density ``>= 0``, NaN -> 0; the logit-space coefficients are not
+    clamped).  The default learning rate is ``fit_octree``'s."""
+    return _fit("fit_octree_sh", OctreeSHField, tree, train_dataset, val_dataset, batch_size,
+                learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
+                clip_value, max_norm, seed, verbose)
+
+
+def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning_rate, num_steps,
+         report_interval, center, t_min, min_transmittance, clip_value, max_norm, seed, verbose):
+    """The loop of ``fit_octree`` / ``fit_octree_sh``; the field supplies the render, the backward
+    and the projection."""
     batch_size, num_steps = int(batch_size), int(num_steps)
     if batch_size < 1 or num_steps < 0 or int(report_interval) < 1:
-        raise ValueError("fit_octree: batch_size >= 1, num_steps >= 0, report_interval >= 1")
+        raise ValueError("%s: batch_size >= 1, num_steps >= 0, report_interval >= 1" % who)
     if not learning_rate > 0:
-        raise ValueError("fit_octree: learning_rate must be positive, got %r" % (learning_rate,))
-    _refuse_sh(tree, "fit_octree")
+        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
+    if field_type is OctreeField:
+        _refuse_sh(tree, who)
+    elif not isinstance(tree, OcTree) or tree.sh_degree is None:
+        raise ValueError("%s: the tree has no SH leaves (sh_degree is None); a plain baked tree is "
+                         "fitted by fit_octree" % who)
     tree._check_volume(min_transmittance)
     if center is None:
         center = tree.center
     if center is None:
-        raise ValueError("fit_octree: a loaded tree does not know the centre of its root cube "
-                         "(the file has no place for it); pass center=")
+        raise ValueError("%s: a loaded tree does not know the centre of its root cube "
+                         "(the file has no place for it); pass center=" % who)
     sampler = train_dataset.sampler
     dev = sampler.starts.device
-    field = OctreeField(tree, center, dev)
+    field = field_type(tree, center, dev)
     data = field.data.detach()
     flat = data.view(-1)
     grads = torch.empty_like(data)
@@ -180,8 +289,6 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
     num_rays = sampler.num_cameras * sampler.rays_per_camera
     generator = torch.Generator(device=dev)
     generator.manual_seed(int(seed))
-    tr = tree
-    node_index, leaf_index = tr._on_device("node_index"), tr._on_device("leaf_index")
     losses, reports = [], {}
     start_time = time.time()
     step = 0
@@ -194,9 +301,8 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
             count = int(rays.numel())
             starts = (sampler.starts[rays] - shift).contiguous()
             directions = sampler.directions[rays].contiguous()
-            color, alpha, _ = ops.octree_render_volume(
-                starts, directions, tr._scale, tr.depth, node_index, leaf_index, data,
-                float(t_min), (0.0, 0.0, 0.0), float(min_transmittance))
+            color, alpha, _ = field._render(data, starts, directions, float(t_min),
+                                            (0.0, 0.0, 0.0), float(min_transmittance))
             sums, d_color, d_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas, rays,
                                                   1.0 / (3 * count), aw / count)
             losses.append(ops.loss_value(sums, count, aw))
@@ -204,7 +310,7 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
                            min_transmittance, data=data, out=grads)
             ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
                           clip_value=clip_value, max_norm=max_norm, scratch=scratch)
-            ops.octree_project(data)
+            field._project(data)
             if val_dataset is not None and (step < 10 or step % report_interval == 0):
                 reports[step] = _validation_psnr(field, val_dataset, t_min, min_transmittance)
                 if verbose:

@@ -806,6 +806,9 @@ class OctreeGradWorkspace:
         self.shape = None
         self.entries = 0            # of the last call
 
+    def _bytes(self, n, num_leaves, want):
+        return octree_grad_workspace_bytes(n, num_leaves, want)
+
     def fit(self, n: int, num_leaves: int, device, at_least: int = 0):
         same = (self.buffer is not None and self.shape == (n, num_leaves)
                 and self.buffer.device == device)
@@ -814,7 +817,7 @@ class OctreeGradWorkspace:
         if at_least > 0:
             self.entries_per_ray = max(self.entries_per_ray, -(-at_least // n))
         want = max(at_least, n * self.entries_per_ray, 1024)
-        need = octree_grad_workspace_bytes(n, num_leaves, want)
+        need = self._bytes(n, num_leaves, want)
         if self.buffer is None or self.buffer.numel() * 4 < need or self.buffer.device != device:
             self.buffer = None              # release before the larger one is taken
             self.buffer = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=device)
@@ -879,6 +882,116 @@ def octree_project(leaf_data: torch.Tensor) -> torch.Tensor:
     if leaf_data.shape[0] > 0:
         _call("ffn_octree_project", _dev(leaf_data, name="leaf_data"), c_i64(leaf_data.shape[0]))
     return leaf_data
+
+
+def octree_sh_file_layout(leaf_rows: np.ndarray, degree: int) -> np.ndarray:
+    """The inverse of ``octree_sh_device_layout``: (L, stride >= 3B+1) device rows
+    [sigma, k_r.., k_g.., k_b.., padding] -> (L, 3B+1) float32 in the file's order
+    [k_r.., k_g.., k_b.., sigma]; the padding is dropped."""
+    channels = octree_sh_channels(degree)
+    if np.ndim(leaf_rows) != 2 or np.shape(leaf_rows)[1] < channels or np.shape(leaf_rows)[1] % 4:
+        raise ValueError("octree SH: leaf_rows must be (num_leaves, stride) with stride a multiple "
+                         "of 4 and >= %d for degree %d, got %s"
+                         % (channels, degree, np.shape(leaf_rows),))
+    data = np.empty((len(leaf_rows), channels), np.float32)
+    data[:, :channels - 1] = leaf_rows[:, 1:channels]
+    data[:, channels - 1] = leaf_rows[:, 0]
+    return data
+
+
+def octree_grad_sh_workspace_bytes(n: int, num_leaves: int, max_entries: int, degree: int) -> int:
+    """Bytes of workspace ``octree_render_volume_sh_backward`` needs for ``n`` rays, ``num_leaves``
+    leaves and up to ``max_entries`` (ray, taken leaf) pairs at ``degree``."""
+    fn = _lib.load().ffn_octree_grad_sh_workspace_bytes
+    fn.restype = ctypes.c_int64
+    size = fn(c_i64(n), c_i64(num_leaves), c_i64(max_entries), c_i(degree))
+    if size < 0:
+        raise _lib.FfnError("ffn_octree_grad_sh_workspace_bytes failed: %s"
+                            % _lib.load().ffn_last_error_string().decode())
+    return int(size)
+
+
+class OctreeGradSHWorkspace(OctreeGradWorkspace):
+    """The workspace of K19b: ``OctreeGradWorkspace`` sized for the wide rows of ``degree``."""
+
+    def __init__(self, degree: int, entries_per_ray: int = 32):
+        super().__init__(entries_per_ray)
+        octree_sh_channels(degree)
+        self.degree = int(degree)
+
+    def _bytes(self, n, num_leaves, want):
+        return octree_grad_sh_workspace_bytes(n, num_leaves, want, self.degree)
+
+
+def octree_render_volume_sh_backward(starts: torch.Tensor, directions: torch.Tensor, scale: float,
+                                     depth: int, node_index: torch.Tensor,
+                                     leaf_index: torch.Tensor, leaf_rows: torch.Tensor, degree: int,
+                                     d_color: torch.Tensor, d_alpha: torch.Tensor,
+                                     t_min: float = 0.0, background=(0.0, 0.0, 0.0),
+                                     min_transmittance: float = 0.0,
+                                     workspace: Optional[OctreeGradSHWorkspace] = None,
+                                     d_leaf_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K19a + K19b, the backward of ``octree_render_volume_sh``: d_color (N,3), d_alpha (N) ->
+    d_leaf_rows (L, stride) float32 in the device layout of ``leaf_rows`` [d sigma, d k_r..,
+    d k_g.., d k_b.., 0 ..], every row written, deterministic (no float atomics).  The read-back and
+    the grow-and-repeat of the workspace are those of ``octree_render_volume_backward``."""
+    channels = octree_sh_channels(degree)
+    if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
+            or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
+        raise ValueError("octree render_volume_sh_backward: leaf_rows must be (num_leaves, stride) "
+                         "with stride a multiple of 4 and >= %d, got %s for %d leaves"
+                         % (channels, tuple(leaf_rows.shape), leaf_index.numel()))
+    if not 0.0 <= min_transmittance < 1.0:
+        raise ValueError("octree render_volume_sh_backward: min_transmittance must lie in [0, 1), "
+                         "got %r" % (min_transmittance,))
+    n, leaves, stride = starts.shape[0], leaf_index.numel(), leaf_rows.shape[1]
+    if d_color.shape != (n, 3) or d_alpha.shape != (n,):
+        raise ValueError("octree render_volume_sh_backward: d_color must be (N,3) and d_alpha (N,)")
+    dev = starts.device
+    if d_leaf_rows is None:
+        d_leaf_rows = torch.empty((leaves, stride), dtype=torch.float32, device=dev)
+    if d_leaf_rows.shape != (leaves, stride):
+        raise ValueError("octree render_volume_sh_backward: d_leaf_rows must be (num_leaves, %d)"
+                         % stride)
+    if n == 0:
+        return d_leaf_rows.zero_()
+    if workspace is None:
+        workspace = OctreeGradSHWorkspace(degree)
+    if getattr(workspace, "degree", None) != degree:
+        raise ValueError("octree render_volume_sh_backward: the workspace is not one of degree %d"
+                         % degree)
+    r, g, b = [float(v) for v in background]
+    entries = c_i64(-1)
+    workspace.fit(n, leaves, dev)
+    for attempt in range(2):
+        try:
+            _call("ffn_octree_render_volume_sh_backward",
+                  *_walk_args(starts, directions, scale, depth, node_index, leaf_index),
+                  c_f(t_min), _dev(leaf_rows, name="leaf_rows"), c_f(r), c_f(g), c_f(b),
+                  c_f(min_transmittance), _dev(d_color, name="d_color"),
+                  _dev(d_alpha, name="d_alpha"), _dev(workspace.buffer),
+                  c_i64(workspace.buffer.numel() * 4), c_i64(workspace.max_entries),
+                  _dev(d_leaf_rows), ctypes.byref(entries), c_i(degree), c_i(stride))
+            break
+        except _lib.FfnError:
+            if attempt == 1 or entries.value <= workspace.max_entries:
+                raise
+            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
+    workspace.entries = int(entries.value)
+    return d_leaf_rows
+
+
+def octree_project_sh(leaf_rows: torch.Tensor, degree: int) -> torch.Tensor:
+    """K19c, in place on leaf_rows (L, stride) in the device layout: density to [0, inf), NaN -> 0
+    for density and coefficients; the coefficients are otherwise untouched, the padding too."""
+    channels = octree_sh_channels(degree)
+    if leaf_rows.dim() != 2 or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0:
+        raise ValueError("octree project_sh: leaf_rows must be (L, stride) with stride a multiple "
+                         "of 4 and >= %d, got %s" % (channels, tuple(leaf_rows.shape),))
+    if leaf_rows.shape[0] > 0:
+        _call("ffn_octree_project_sh", _dev(leaf_rows, name="leaf_rows"),
+              c_i64(leaf_rows.shape[0]), c_i(leaf_rows.shape[1]), c_i(degree))
+    return leaf_rows
 
 
 def octree_bake(logits: torch.Tensor) -> torch.Tensor:

@@ -1021,6 +1021,45 @@ int ffn_octree_render_volume_sh(const float* starts, const float* directions, in
 int ffn_octree_sh_accumulate(const float* logits, int64_t num_leaves, int degree,
                              const float* weights, float inv_views, float* leaf_data, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K19  backward of the K18a SH volume render, for fitting SH leaves to images (K19a: two more modes
+ * of the K13 kernel in csrc/octree_walk.hip; K19b, K19c: csrc/octree_grad.hip).  No counterpart in
+ * the reference.  Arguments up to min_transmittance as for ffn_octree_render_volume_sh (leaf_rows is
+ * its DEVICE layout, row_stride floats per row), with the same taken leaves, t0, L, sigma, a, w, T,
+ * basis Y(u) and colour c_k = sigmoid(k . Y(u)), operation for operation.  With K17's notation
+ * (T_k, w_k, C = sum w_k c_k + T_{n+1} bg, S_k = C - sum_{j<=k} w_j c_j, upstream g_C, g_A), taken
+ * leaf k of a ray contributes
+ *   d k_cb    = e_kc Y_b(u),   e_kc = (w_k g_c) (c_kc (1 - c_kc))    each product rounded, in f32
+ *   d sigma_k = L_k [ g_C . (T_{k+1} c_k - S_k) + g_A T_{n+1} ]      K17's expression and order
+ * d sigma_k is 0 where the stored density is negative or NaN (it passes where it is exactly 0);
+ * depth, the background and the rays get no gradient.  d_leaf_rows (num_leaves, row_stride) f32,
+ * 16-byte aligned, in the layout of leaf_rows [d sigma, d k_r0 .., d k_g0 .., d k_b0 .., padding]:
+ * every row is written, the sum of the leaf's contributions in K17b's fixed tree without float
+ * atomics (the same inputs give the same bits on every call); rows of leaves no ray took and all
+ * padding columns are +0.  An entry of the walk stays 16 + 4 + 4 bytes (e_r, e_g, e_b, d sigma, the
+ * leaf, the ray): Y_b(u) is rebuilt from the ray's direction when the entries are summed.
+ *
+ * The read-back of the entry total, *entries and the workspace protocol are those of
+ * ffn_octree_render_volume_backward, with ffn_octree_grad_sh_workspace_bytes(n, num_leaves,
+ * max_entries, degree) bytes, which grow by less than 96 bytes per additional entry.  degree is 1 or
+ * 2; 3 (degree + 1)^2 + 1 <= row_stride <= 64, a multiple of 4; n * (3 * 2^(depth-1) + 1) < 2^31. */
+int64_t ffn_octree_grad_sh_workspace_bytes(int64_t n, int64_t num_leaves, int64_t max_entries,
+                                           int degree);
+
+int ffn_octree_render_volume_sh_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
+    int row_stride, void* stream);
+
+/* K19c.  The projection after an optimiser step, in place on leaf_rows (num_leaves, row_stride) f32
+ * in the device layout, 16-byte aligned: density = max(x, 0) (NaN and -0 become +0); a coefficient
+ * that is NaN becomes 0 and is otherwise untouched (it lives in logit space); padding untouched. */
+int ffn_octree_project_sh(float* leaf_rows, int64_t num_leaves, int row_stride, int degree,
+                          void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

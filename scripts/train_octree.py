@@ -1,8 +1,9 @@
 """Fits the leaf values of a baked octree (``scripts/bake_octree.py``, or a density tree of
 ``OcTree.build_from_model``) to the training images through the tree's own volume renderer
 (``fit_octree``: kernels K15, K6, K17a-c, K7), and writes the fitted tree in the reference's file
-format, ready for ``scripts/render_octree.py --mode volume``.  The structure of the tree does not
-change.  No counterpart in the reference.
+format, ready for ``scripts/render_octree.py --mode volume``.  A tree whose file carries an
+``sh_degree`` (``OcTree.bake_sh``) is fitted by ``fit_octree_sh`` (K18a, K6, K19a-c, K7) and keeps
+its degree.  The structure of the tree does not change.  No counterpart in the reference.
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.
@@ -51,9 +52,12 @@ def main():
     if train is None or val is None:
         return 1
     lr = octree_fit.LEARNING_RATE if args.lr is None else args.lr
-    fitted, log = ffn.fit_octree(tree, train, val, args.batch_size, lr, args.steps,
-                                 args.report_interval, center=args.center,
-                                 min_transmittance=args.min_transmittance, seed=args.seed)
+    fit = ffn.fit_octree
+    if tree.sh_degree is not None:
+        print("SH leaves of degree %d" % tree.sh_degree)
+        fit = ffn.fit_octree_sh
+    fitted, log = fit(tree, train, val, args.batch_size, lr, args.steps, args.report_interval,
+                      center=args.center, min_transmittance=args.min_transmittance, seed=args.seed)
     if log:
         print("loss first %.6g last %.6g over %d steps" % (log[0].loss, log[-1].loss, len(log)))
     fitted.save(args.output_path)
