@@ -47,6 +47,9 @@ SOURCES = {
     # sums of stored entries in a fixed order: plain adds.  K17b-5 turns a sum of -0 into +0 by
     # adding 0.0f, which -ffast-math or -fno-signed-zeros would fold away: never add those here
     "octree_grad.hip": ["-ffp-contract=off"],
+    # d = a - b, s = sqrt(fma(d, d, eps^2)), (s - eps) * scale, (d / s) * scale: only the written
+    # fma; tv_finish's + 0.0f is K17b-5's (no -ffast-math here either)
+    "octree_tv.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

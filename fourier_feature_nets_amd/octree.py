@@ -69,10 +69,16 @@ public signatures are the reference's, so files and calling code go both ways.  
   plus deterministic per-leaf sums; ``fit_octree`` optimises them against a dataset's images.  The
   structure of the tree is not changed.  No counterpart in the reference.
 
+* ``neighbors`` / ``total_variation`` (K20) have none either: the face adjacency of the sparse tree
+  (per leaf and direction the leaf of equal size or coarser on the other side; finer neighbours hold
+  the adjacency from their side) and the Charbonnier total-variation energy of ``leaf_data`` over
+  every pair of touching leaves, the prior that ``fit_octree`` / ``fit_octree_sh`` switch on with
+  ``tv_weight``.  Every face counts the same: no weight for its area or the centres' distance.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
-``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers`` and ``leaf_depths`` run on the
-GPU and raise without one.
+``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers``, ``leaf_depths``,
+``neighbors`` and ``total_variation`` run on the GPU and raise without one.
 """
 
 import os
@@ -321,6 +327,66 @@ class OcTree:
     def leaf_depths(self) -> np.ndarray:
         """The N depths for all leaves."""
         return self._geometry()[1]
+
+    def _neighbors_on_device(self) -> torch.Tensor:
+        dev = self._dev()
+        key = ("neighbors", str(dev))
+        if key not in self._cache:
+            self._cache[key] = ops.octree_neighbors(self._on_device("node_index"),
+                                                    self._on_device("leaf_index"))
+        return self._cache[key]
+
+    def neighbors(self) -> np.ndarray:
+        """(L,6) int64 (K20a): per leaf and direction ``-x, +x, -y, +y, -z, +z`` the number (its
+        position in the sorted leaf ids) of the leaf of equal size or coarser across that face; -1
+        at the cube's boundary, next to empty space, and where the other side is finer (the finer
+        leaves hold that adjacency from their side).  Computed once and cached like the geometry."""
+        if "neighbors_host" not in self._cache:
+            self._cache["neighbors_host"] = \
+                self._neighbors_on_device().cpu().numpy().astype(np.int64)
+        return self._cache["neighbors_host"]
+
+    def _tv_plan(self) -> "ops.OctreeTVPlan":
+        """The device plan of K20b / K20c (edges, incidences sorted by leaf), made once per tree."""
+        dev = self._dev()
+        key = ("tv_plan", str(dev))
+        if key not in self._cache:
+            self._cache[key] = ops.octree_tv_plan(self._neighbors_on_device(),
+                                                  self._on_device("leaf_index"))
+        return self._cache[key]
+
+    def _tv_rows(self) -> torch.Tensor:
+        """``leaf_data`` as the (L, stride) rows K20b reads: ``[r, g, b, sigma]`` of a plain tree,
+        the device layout of an SH tree."""
+        if self._leaf_data is None:
+            raise ValueError("OcTree.total_variation: the tree has no leaf_data (see OcTree.bake)")
+        if self._sh_degree is not None:
+            self._check_volume(0.0)
+            return self._sh_rows_on_device()
+        data = self._leaf_data
+        if np.ndim(data) != 2 or np.shape(data)[1] < 4:
+            raise ValueError("OcTree.total_variation: leaf_data must be (num_leaves, C >= 4) to "
+                             "hold a colour and a density, got %s" % (np.shape(data),))
+        rows = self._colors_on_device()
+        return rows if rows.shape[1] == 4 else rows[:, :4].contiguous()
+
+    def total_variation(self, weights=None, eps: float = 1e-2) -> float:
+        """The total-variation energy of the tree's own ``leaf_data`` (K20b): the mean over the pairs
+        of leaves that touch across a face (``neighbors``; every pair once) of ``sum_c w_c
+        (sqrt(d_c^2 + eps^2) - eps)``, ``d`` the difference of the two leaves' values -- Charbonnier,
+        smooth at 0 and linear for a jump.  Plain tree: ``weights = (rgb, sigma)``, default ``(1,
+        1)``; SH tree: ``weights = (band0, higher_bands, sigma)``, default ``(1, 1, 1)``.  0 for a
+        tree without touching leaves.  There is no geometric weight: a face counts the same whatever
+        its area or the distance of the two centres."""
+        eps = ops.octree_tv_check_eps(eps)
+        if self._leaf_data is None:
+            raise ValueError("OcTree.total_variation: the tree has no leaf_data (see OcTree.bake)")
+        stride = 4 if self._sh_degree is None else \
+            (ops.octree_sh_channels(self._sh_degree) + 3) // 4 * 4
+        lam = ops.octree_tv_weights(weights, stride, self._sh_degree)
+        rows = self._tv_rows()
+        value, _ = ops.octree_tv(rows, self._tv_plan(), lam, eps)
+        return float(value.item())
 
     def query(self, positions):
         """Index into the sorted leaf ids of the leaf containing each position, -1 outside the

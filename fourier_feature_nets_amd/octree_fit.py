@@ -13,6 +13,11 @@ the reference.
 (``OcTree.bake_sh``): the parameter is the ``(L, stride)`` buffer in the device layout K18a reads,
 the forward K18a, the backward K19a + K19b, the projection K19c (density ``>= 0``; the coefficients
 live in logit space and are not clamped).
+
+Both fields offer the total-variation prior of K20 (``csrc/octree_tv.hip``): ``total_variation`` is
+the Charbonnier energy between leaves that touch across a face, ``tv_backward`` its gradient,
+deterministic and without a host sync, and ``tv_weight`` on both fit loops adds it to the data
+term's gradient.  It is off by default, and off means not entered.
 """
 
 import time
@@ -66,7 +71,30 @@ def _refuse_sh(tree: OcTree, who: str):
                          "use OctreeSHField / fit_octree_sh" % (who, tree.sh_degree))
 
 
-class OctreeField(torch.nn.Module):
+class _TotalVariation:
+    """K20 for a field: the energy and its gradient on the field's own rows.  The field supplies
+    ``_tv_weights`` (its columns) and ``_tree``."""
+
+    def total_variation(self, weights=None, eps: float = 1e-2, data=None) -> torch.Tensor:
+        """K20b: the total-variation energy (``OcTree.total_variation``) of ``data`` (default: the
+        parameter) as a device scalar; no host sync."""
+        rows = self.data.detach() if data is None else data
+        value, _ = ops.octree_tv(rows, self._tree._tv_plan(), self._tv_weights(weights), eps)
+        return value
+
+    def tv_backward(self, weights=None, eps: float = 1e-2, data=None, out=None,
+                    accumulate: bool = False) -> torch.Tensor:
+        """K20b + K20c: the gradient of ``total_variation`` with respect to ``data``, in its shape;
+        with ``accumulate`` added to the content of ``out`` (one add per element).  ``weights``
+        scale the columns, so a caller's ``tv_weight`` is passed here as it is.  Deterministic, no
+        host sync."""
+        rows = self.data.detach() if data is None else data
+        _, grad = ops.octree_tv(rows, self._tree._tv_plan(), self._tv_weights(weights), eps, out,
+                                accumulate)
+        return grad
+
+
+class OctreeField(_TotalVariation, torch.nn.Module):
     """The leaf values of a baked tree as a parameter.  ``data`` (L,4) float32 ``[r, g, b, sigma]``
     on the device, initialised from ``tree.leaf_data()``."""
 
@@ -113,6 +141,9 @@ class OctreeField(torch.nn.Module):
             starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
             tree._on_device("leaf_index"), data, t_min, background, min_transmittance)
 
+    def _tv_weights(self, weights):
+        return ops.octree_tv_weights(weights, 4, None)
+
     def _project(self, data):
         return ops.octree_project(data)
 
@@ -126,7 +157,7 @@ class OctreeField(torch.nn.Module):
         return new
 
 
-class OctreeSHField(torch.nn.Module):
+class OctreeSHField(_TotalVariation, torch.nn.Module):
     """The leaf values of an SH tree (``OcTree.bake_sh``) as a parameter.  ``data`` (L, stride)
     float32 on the device in the layout K18a reads (``ops.octree_sh_device_layout``:
     ``[sigma, k_r.., k_g.., k_b.., 0 ..]``), so that a step never repacks and Adam runs on the flat
@@ -157,6 +188,9 @@ class OctreeSHField(torch.nn.Module):
             starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
             tree._on_device("leaf_index"), data, self.sh_degree, t_min, background,
             min_transmittance)
+
+    def _tv_weights(self, weights):
+        return ops.octree_tv_weights(weights, int(self.data.shape[1]), self.sh_degree)
 
     def _project(self, data):
         return ops.octree_project_sh(data, self.sh_degree)
@@ -223,7 +257,8 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
                report_interval: int = 500, center=None, t_min: float = 0.0,
                min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
                max_norm: float = MAX_NORM, seed: int = 20080524,
-               verbose: bool = True) -> Tuple[OcTree, List[FitLogEntry]]:
+               verbose: bool = True, tv_weight=None,
+               tv_eps: float = 1e-2) -> Tuple[OcTree, List[FitLogEntry]]:
     """Optimises the leaf values of a baked ``tree`` against the images of ``train_dataset`` (an
     ``ImageDataset``) through ``render_volume`` with a black background; -> (a new ``OcTree`` of the
     same structure, log).  One step: a batch of ray ids from a seeded shuffle of EVERY ray of every
@@ -233,10 +268,20 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
     log holds ``(step, loss, val_psnr)`` -- every step's training loss, ``val_psnr`` (over all rays
     of ``val_dataset``'s cameras) at steps below 10 and multiples of ``report_interval``, else NaN
     -- and report steps are printed as ``Raycaster.fit`` prints them.  The only host
-    synchronisation of a step is the read-back inside K17b; the losses are fetched at the end."""
+    synchronisation of a step is the read-back inside K17b; the losses are fetched at the end.
+
+    ``tv_weight = (rgb, sigma)`` switches the total-variation prior of ``OcTree.total_variation`` on
+    (K20): with a non-zero entry the step adds ``tv_weight * dR/d(data)`` (``tv_backward`` with
+    ``accumulate``, ``tv_eps`` the Charbonnier eps) to the gradient of the data term after K17b, then
+    K7 and K17c as before -- no further host sync.  The logged ``loss`` stays the data term; report
+    lines gain ``tv:``, the weighted energy.  With the default of all zeros the TV code is not
+    entered and the result is today's bit for bit (``None``, the default, is all zeros: the two fit
+    loops keep one signature).  ``tv_weight`` and ``tv_eps`` are checked like every other argument
+    before the first step, whether the prior is on or not: ``tv_eps <= 0`` raises with a zero
+    weight too."""
     return _fit("fit_octree", OctreeField, tree, train_dataset, val_dataset, batch_size,
                 learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
-                clip_value, max_norm, seed, verbose)
+                clip_value, max_norm, seed, verbose, tv_weight, tv_eps)
 
 
 def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 4096,
@@ -244,21 +289,24 @@ def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int
                   report_interval: int = 500, center=None, t_min: float = 0.0,
                   min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
                   max_norm: float = MAX_NORM, seed: int = 20080524,
-                  verbose: bool = True) -> Tuple[OcTree, List[FitLogEntry]]:
+                  verbose: bool = True, tv_weight=None,
+                  tv_eps: float = 1e-2) -> Tuple[OcTree, List[FitLogEntry]]:
     """``fit_octree`` for a tree with SH leaves (``OcTree.bake_sh``): the same arguments, defaults,
     seeded shuffle, log and report lines; -> (a new SH ``OcTree`` of the same structure and
     ``sh_degree``, log).  One step: K18a, K6, K19a + K19b, K7 on the flat ``(L stride,)`` buffer in
     the device layout, K19c (density ``>= 0``, NaN -> 0; the logit-space coefficients are not
-    clamped).  The default learning rate is ``fit_octree``'s."""
+    clamped).  The default learning rate is ``fit_octree``'s.  ``tv_weight = (band0, higher_bands,
+    sigma)`` and ``tv_eps`` as in ``fit_octree`` (K20), on the rows of the device layout."""
     return _fit("fit_octree_sh", OctreeSHField, tree, train_dataset, val_dataset, batch_size,
                 learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
-                clip_value, max_norm, seed, verbose)
+                clip_value, max_norm, seed, verbose, tv_weight, tv_eps)
 
 
 def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning_rate, num_steps,
-         report_interval, center, t_min, min_transmittance, clip_value, max_norm, seed, verbose):
-    """The loop of ``fit_octree`` / ``fit_octree_sh``; the field supplies the render, the backward
-    and the projection."""
+         report_interval, center, t_min, min_transmittance, clip_value, max_norm, seed, verbose,
+         tv_weight, tv_eps):
+    """The loop of ``fit_octree`` / ``fit_octree_sh``; the field supplies the render, the backward,
+    the TV gradient and the projection."""
     batch_size, num_steps = int(batch_size), int(num_steps)
     if batch_size < 1 or num_steps < 0 or int(report_interval) < 1:
         raise ValueError("%s: batch_size >= 1, num_steps >= 0, report_interval >= 1" % who)
@@ -278,6 +326,9 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
     sampler = train_dataset.sampler
     dev = sampler.starts.device
     field = field_type(tree, center, dev)
+    tv_eps = ops.octree_tv_check_eps(tv_eps)
+    # (refuses a tuple of the wrong shape; None is off, as the default of all zeros)
+    tv_on = tv_weight is not None and bool(field._tv_weights(tv_weight).any())
     data = field.data.detach()
     flat = data.view(-1)
     grads = torch.empty_like(data)
@@ -308,6 +359,8 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
             losses.append(ops.loss_value(sums, count, aw))
             field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
                            min_transmittance, data=data, out=grads)
+            if tv_on:
+                field.tv_backward(tv_weight, tv_eps, data=data, out=grads, accumulate=True)
             ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
                           clip_value=clip_value, max_norm=max_norm, scratch=scratch)
             field._project(data)
@@ -322,6 +375,9 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
                     print("{:07}".format(step), "{:2f} s/step".format(per_step),
                           "loss: {:2f}".format(float(losses[-1].item())),
                           "val_psnr: {:2f}".format(reports[step]),
+                          *(["tv: {:2f}".format(float(
+                              field.total_variation(tv_weight, tv_eps, data).item()))]
+                            if tv_on else []),
                           "lr: {:.2e}".format(learning_rate), "eta:", eta)
             step += 1
     values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)

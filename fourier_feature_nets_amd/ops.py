@@ -994,6 +994,194 @@ def octree_project_sh(leaf_rows: torch.Tensor, degree: int) -> torch.Tensor:
     return leaf_rows
 
 
+def octree_neighbors(node_index: torch.Tensor, leaf_index: torch.Tensor) -> torch.Tensor:
+    """K20a.  Sorted int64 id arrays -> (L,6) int32: per leaf and direction (-x, +x, -y, +y, -z, +z)
+    the number of the leaf of equal size or coarser across that face, -1 for the cube's boundary,
+    empty space or finer leaves (which hold the adjacency from their side)."""
+    leaves = leaf_index.numel()
+    out = torch.empty((leaves, 6), dtype=torch.int32, device=leaf_index.device)
+    if leaves > 0:
+        _call("ffn_octree_neighbors",
+              _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+              c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),
+              c_i64(leaves), _dev(out, torch.int32))
+    return out
+
+
+TV_CHUNK = 16
+
+
+class OctreeTVPlan:
+    """What K20b / K20c read of a tree's face adjacency, on the device (include/ffn_hip.h, K20):
+    ``edge_i`` / ``edge_j`` (E,), the 2 E incidences stably sorted by leaf (``inc_leaf``,
+    ``inc_code = 2 edge + [the leaf is the edge's j]``), every leaf's range ``seg_lo`` / ``seg_hi``
+    in that order, ``seg_base`` and ``longest``, the longest incidence list.  Made once per tree by
+    ``octree_tv_plan``; the workspace of the per-step kernels is kept here between calls."""
+
+    def __init__(self, num_leaves, edge_i, edge_j, inc_leaf, inc_code, seg_lo, seg_hi, seg_base,
+                 longest):
+        self.num_leaves, self.num_edges = int(num_leaves), int(edge_i.numel())
+        self.longest = int(longest)
+        self.edge_i, self.edge_j = edge_i, edge_j
+        self.inc_leaf, self.inc_code = inc_leaf, inc_code
+        self.seg_lo, self.seg_hi, self.seg_base = seg_lo, seg_hi, seg_base
+        self.device = seg_lo.device
+        self._workspace = {}
+
+    def workspace(self, stride: int) -> Optional[torch.Tensor]:
+        if self.num_edges == 0:
+            return None
+        if stride not in self._workspace:
+            need = octree_tv_workspace_bytes(self.num_leaves, self.num_edges, stride)
+            self._workspace[stride] = torch.empty(((need + 3) // 4,), dtype=torch.float32,
+                                                  device=self.device)
+        return self._workspace[stride]
+
+
+def octree_tv_plan(neighbors: torch.Tensor, leaf_index: torch.Tensor) -> OctreeTVPlan:
+    """The plan of K20b / K20c from the (L,6) table of ``octree_neighbors`` and the sorted leaf ids:
+    index plumbing on the device (``torch.nonzero``, one stable sort, two cumulative sums), once per
+    tree; it reads the edge count and the longest incidence list back.  ``(i, dir)`` is an edge when
+    ``j = neighbors[i, dir] >= 0`` and ``level(j) < level(i)`` or ``dir`` is a + direction; edges are
+    numbered in ``(i, dir)`` order.  More than ``6 L`` edges or ``2 E >= 2^31`` are refused."""
+    leaves = leaf_index.numel()
+    if neighbors.dim() != 2 or tuple(neighbors.shape) != (leaves, 6) or neighbors.dtype != torch.int32:
+        raise ValueError("octree tv_plan: neighbors must be (num_leaves, 6) int32, got %s %s for %d "
+                         "leaves" % (tuple(neighbors.shape), neighbors.dtype, leaves))
+    if leaves < 1:
+        raise ValueError("octree tv_plan: a tree needs at least one leaf")
+    dev = leaf_index.device
+    _, levels = octree_leaf_geometry(leaf_index, 1.0)
+    nb = neighbors.to(torch.int64)
+    other = levels[nb.clamp(min=0)]
+    plus = torch.tensor([False, True] * 3, device=dev)
+    mask = (nb >= 0) & ((other < levels[:, None]) | plus[None, :])
+    at = torch.nonzero(mask.reshape(-1)).reshape(-1)              # (i, dir) order
+    edge_i = (at // 6).to(torch.int32)
+    edge_j = nb.reshape(-1)[at].to(torch.int32)
+    edges = int(at.numel())
+    if edges > 6 * leaves or 2 * edges >= 2 ** 31:     # the incidence numbers 2 e + 1 are int32
+        raise ValueError("octree tv_plan: %d edges for %d leaves; E <= 6 L and 2 E < 2^31"
+                         % (edges, leaves))
+    code = torch.arange(2 * edges, dtype=torch.int32, device=dev)
+    leaf = torch.stack([edge_i, edge_j], 1).reshape(-1)
+    inc_leaf, order = torch.sort(leaf, stable=True)
+    inc_code = code[order]
+    counts = torch.bincount(inc_leaf.to(torch.int64), minlength=leaves)
+    seg_hi = torch.cumsum(counts, 0)
+    seg_lo = seg_hi - counts
+    before = torch.cumsum((counts > 0).to(torch.int64), 0) - (counts > 0).to(torch.int64)
+    seg_base = seg_lo // TV_CHUNK + before
+    longest = int(counts.max().item())
+    return OctreeTVPlan(leaves, edge_i.contiguous(), edge_j.contiguous(),
+                        inc_leaf.to(torch.int32).contiguous(), inc_code.contiguous(),
+                        seg_lo.to(torch.int32), seg_hi.to(torch.int32), seg_base.to(torch.int32),
+                        longest)
+
+
+def octree_tv_workspace_bytes(num_leaves: int, num_edges: int, stride: int) -> int:
+    """Bytes of workspace ``octree_tv`` needs."""
+    fn = _lib.load().ffn_octree_tv_workspace_bytes
+    fn.restype = ctypes.c_int64
+    size = fn(c_i64(num_leaves), c_i64(num_edges), c_i(stride))
+    if size < 0:
+        raise _lib.FfnError("ffn_octree_tv_workspace_bytes failed: %s"
+                            % _lib.load().ffn_last_error_string().decode())
+    return int(size)
+
+
+def octree_tv_weights(weights, stride: int, degree: Optional[int] = None) -> np.ndarray:
+    """The per-column weight vector of K20b, float32 (stride,), padding 0.  A plain tree (``degree``
+    None, stride 4, ``[r, g, b, sigma]``): ``weights = (rgb, sigma)``.  An SH tree in the device
+    layout ``[sigma, k_r.., k_g.., k_b.., 0 ..]``: ``weights = (band0, higher_bands, sigma)``.
+    ``None`` is all ones.  Needs no GPU."""
+    count = 2 if degree is None else 3
+    if weights is None:
+        weights = (1.0,) * count
+    try:
+        values = [float(w) for w in weights]
+    except TypeError:
+        raise ValueError("octree tv: weights must be %d numbers, got %r" % (count, weights))
+    if len(values) != count:
+        raise ValueError("octree tv: weights must be %d numbers (%s), got %r"
+                         % (count, "rgb, sigma" if degree is None else "band0, higher_bands, sigma",
+                            weights))
+    if not all(0.0 <= v < float("inf") for v in values):       # NaN fails too
+        raise ValueError("octree tv: weights must be finite and >= 0, got %r" % (weights,))
+    out = np.zeros((stride,), np.float32)
+    if degree is None:
+        if stride != 4:
+            raise ValueError("octree tv: a plain tree has rows of 4 floats, got stride %d" % stride)
+        out[:3], out[3] = values[0], values[1]
+        return out
+    channels = octree_sh_channels(degree)
+    bases = (channels - 1) // 3
+    if stride < channels or stride % 4 != 0:
+        raise ValueError("octree tv: stride must be a multiple of 4 and >= %d for degree %d, got %d"
+                         % (channels, degree, stride))
+    out[0] = values[2]
+    for c in range(3):
+        out[1 + c * bases] = values[0]
+        out[2 + c * bases:1 + (c + 1) * bases] = values[1]
+    return out
+
+
+def octree_tv_check_eps(eps) -> float:
+    """``eps`` as a float; ValueError unless it is a positive finite number.  Needs no GPU."""
+    eps = float(eps)
+    if not 0.0 < eps < float("inf"):                           # NaN fails too
+        raise ValueError("octree tv: eps must be positive and finite, got %r" % (eps,))
+    return eps
+
+
+def octree_tv(rows: torch.Tensor, plan: OctreeTVPlan, weights, eps: float,
+              d_rows: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """K20b + K20c.  rows (L, stride) float32, stride a multiple of 4; ``weights`` a (stride,) vector
+    of per-column weights (``octree_tv_weights``), finite and >= 0; -> (value, d_rows): the
+    Charbonnier energy ``(1/E) sum_e sum_c w_c (sqrt(d^2 + eps^2) - eps)`` over the plan's edges as a
+    device scalar, and its gradient (L, stride), every row written (``accumulate``: added to the
+    content of the ``d_rows`` passed in).  Deterministic, no float atomics, no host sync.  No
+    geometric weight: every face counts the same whatever its area or the distance of the
+    centres."""
+    if not isinstance(plan, OctreeTVPlan):
+        raise TypeError("octree tv: plan must be an OctreeTVPlan (ops.octree_tv_plan)")
+    eps = octree_tv_check_eps(eps)
+    if rows.dim() != 2 or rows.shape[1] % 4 != 0 or not 4 <= rows.shape[1] <= 64:
+        raise ValueError("octree tv: rows must be (num_leaves, stride) with stride a multiple of 4 "
+                         "in 4 .. 64, got %s" % (tuple(rows.shape),))
+    leaves, stride = rows.shape
+    if leaves != plan.num_leaves:
+        raise ValueError("octree tv: the plan is of a tree with %d leaves, rows has %d"
+                         % (plan.num_leaves, leaves))
+    lam = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if len(lam) != stride:
+        raise ValueError("octree tv: %d weights for rows of %d floats" % (len(lam), stride))
+    if not (np.isfinite(lam).all() and (lam >= 0).all()):
+        raise ValueError("octree tv: weights must be finite and >= 0, got %r" % (lam.tolist(),))
+    if rows.data_ptr() % 16 != 0:
+        raise ValueError("octree tv: rows must be 16-byte aligned")
+    if accumulate and d_rows is None:
+        raise ValueError("octree tv: accumulate needs the d_rows to add to")
+    if d_rows is None:
+        d_rows = torch.empty_like(rows)
+    if d_rows.shape != rows.shape:
+        raise ValueError("octree tv: d_rows must be %s, got %s" % (tuple(rows.shape),
+                                                                   tuple(d_rows.shape)))
+    if d_rows.data_ptr() % 16 != 0:
+        raise ValueError("octree tv: d_rows must be 16-byte aligned")
+    value = torch.empty((), dtype=torch.float32, device=rows.device)
+    workspace = plan.workspace(stride)
+    host = (ctypes.c_float * stride)(*[float(v) for v in lam])
+    _call("ffn_octree_tv", _dev(rows, name="rows"), c_i64(leaves), c_i(stride),
+          _dev(plan.edge_i, torch.int32), _dev(plan.edge_j, torch.int32), c_i64(plan.num_edges),
+          _dev(plan.inc_leaf, torch.int32), _dev(plan.inc_code, torch.int32),
+          _dev(plan.seg_lo, torch.int32), _dev(plan.seg_hi, torch.int32),
+          _dev(plan.seg_base, torch.int32), c_i64(plan.longest), host, c_f(eps), _dev(value),
+          _dev(d_rows, name="d_rows"), c_i(1 if accumulate else 0), _dev(workspace),
+          c_i64(0 if workspace is None else workspace.numel() * 4))
+    return value, d_rows
+
+
 def octree_bake(logits: torch.Tensor) -> torch.Tensor:
     """Raw model logits (L,4) [r, g, b, sigma] -> (L,4) float32 [sigmoid(r), sigmoid(g),
     sigmoid(b), softplus(sigma)], the activations of the compositing kernels bit for bit."""

@@ -1060,6 +1060,59 @@ int ffn_octree_render_volume_sh_backward(
 int ffn_octree_project_sh(float* leaf_rows, int64_t num_leaves, int row_stride, int degree,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K20  a total-variation prior between leaves that touch across a face (csrc/octree_tv.hip).  No
+ * counterpart in the reference.
+ *
+ * K20a.  neighbors (num_leaves, 6) int32, directions -x, +x, -y, +y, -z, +z.  A leaf's id gives its
+ * level d and its cell (ix, iy, iz) on the 2^d grid (child index 4 [x] + 2 [y] + [z], as K12).  One
+ * cell along the axis: outside [0, 2^d) the answer is -1; otherwise that cell's path is followed from
+ * the root (id = 8 id + 1 + child) with K12j's binary searches.  An id in leaf_index answers with its
+ * position in leaf_index (a leaf of equal size or coarser); an id in neither index is empty space,
+ * -1; an id that is still an interior node at level d means finer leaves on the other side, -1: they
+ * hold the adjacency from their side.  A root-only tree has no neighbours.  Integers only. */
+int ffn_octree_neighbors(const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index,
+                         int64_t num_leaves, int32_t* neighbors, void* stream);
+
+/* K20b + K20c.  The plan, made once per tree by the caller, all arrays int32 on the device:
+ * (i, dir) is an EDGE when j = neighbors[i][dir] >= 0 and (level(j) < level(i) or dir is a +
+ * direction): every touching pair once.  Edges are numbered in (i, dir) order: edge_i, edge_j
+ * (num_edges each).  Edge e has the incidences 2 e = (leaf edge_i[e], +) and 2 e + 1 = (leaf
+ * edge_j[e], -); inc_leaf / inc_code (2 num_edges each) hold the incidences' leaves and numbers
+ * stably sorted by leaf, seg_lo / seg_hi (num_leaves each) leaf l's range [lo, hi) in that order
+ * (hi == lo without an incidence), seg_base[l] = seg_lo[l] / 16 + (leaves with an incidence before
+ * l), longest = max (hi - lo).  num_edges <= 6 num_leaves, 2 num_edges < 2^31.
+ *
+ * rows (num_leaves, stride) f32, 16-byte aligned, stride a multiple of 4 in 4 .. 64: [r, g, b, sigma]
+ * or the device layout of K18a.  lambda: stride floats in HOST memory, finite and >= 0 (0 for
+ * padding columns).  eps > 0.  With d = rows[i][c] - rows[j][c] over the edges (i, j):
+ *   R          = (1 / E) sum_e sum_c lambda_c (sqrt(d^2 + eps^2) - eps)         (Charbonnier)
+ *   dR/drows[i][c] += (lambda_c / E) d / sqrt(d^2 + eps^2),   dR/drows[j][c] -= the same
+ * in f32, in this order: scale_c = lambda_c / (float)E on the host; d = a - b; s = sqrtf(fmaf(d, d,
+ * eps * eps)); the term (s - eps) * scale_c; the derivative (d / s) * scale_c.  No fused
+ * multiply-add but the one written; sqrt and division are IEEE.  There is no geometric weight for
+ * the face's area or the distance of the centres.
+ *
+ * *value (device) = R: a thread adds its four columns ((x + y) + z) + w, a workgroup of 256 (edge,
+ * quad) threads its terms in a fixed shuffle / LDS tree, one workgroup the partials in index order.
+ * d_rows (num_leaves, stride), 16-byte aligned, may be null (the energy alone): leaf l's row is the
+ * sum of its incidences' signed derivatives in the sorted order, in runs of 16 and runs of 16 partial
+ * sums (K17b's tree: no thread adds more than 16 terms), every row written, +0 for a leaf without
+ * an incidence and for a column of weight 0; with accumulate != 0, d_rows = d_rows + that sum, one
+ * add per element.  No float atomics and no read-back: the same inputs give the same bits.
+ * num_edges == 0: *value = 0, d_rows zero (untouched with accumulate).  The indices of a plan are
+ * held against num_leaves and num_edges where they are used: a plan of another tree gives wrong
+ * sums, not an access outside the buffers.  workspace: 16-byte aligned,
+ * ffn_octree_tv_workspace_bytes(num_leaves, num_edges, stride) bytes (-1: bad shape). */
+int64_t ffn_octree_tv_workspace_bytes(int64_t num_leaves, int64_t num_edges, int stride);
+
+int ffn_octree_tv(const float* rows, int64_t num_leaves, int stride, const int32_t* edge_i,
+                  const int32_t* edge_j, int64_t num_edges, const int32_t* inc_leaf,
+                  const int32_t* inc_code, const int32_t* seg_lo, const int32_t* seg_hi,
+                  const int32_t* seg_base, int64_t longest, const float* lambda, float eps,
+                  float* value, float* d_rows, int accumulate, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

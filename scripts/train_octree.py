@@ -3,7 +3,8 @@
 (``fit_octree``: kernels K15, K6, K17a-c, K7), and writes the fitted tree in the reference's file
 format, ready for ``scripts/render_octree.py --mode volume``.  A tree whose file carries an
 ``sh_degree`` (``OcTree.bake_sh``) is fitted by ``fit_octree_sh`` (K18a, K6, K19a-c, K7) and keeps
-its degree.  The structure of the tree does not change.  No counterpart in the reference.
+its degree.  ``--tv-weight`` / ``--tv-eps`` switch the total-variation prior between touching
+leaves on (K20).  The structure of the tree does not change.  No counterpart in the reference.
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.
@@ -31,6 +32,10 @@ TRAIN_OCTREE = [
                                  help="End a ray's walk once its transmittance is at or below this")),
     ("--report-interval", dict(type=int, default=500, help="Steps between validation reports")),
     ("--seed", dict(type=int, default=20080524, help="Seed of the ray shuffle")),
+    ("--tv-weight", dict(type=float, nargs="+", default=None, metavar="W",
+                         help="Weights of the total-variation prior (K20): RGB SIGMA for a plain "
+                              "tree, BAND0 HIGHER_BANDS SIGMA for an SH tree (default: off)")),
+    ("--tv-eps", dict(type=float, default=1e-2, help="The Charbonnier eps of the prior")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -56,8 +61,19 @@ def main():
     if tree.sh_degree is not None:
         print("SH leaves of degree %d" % tree.sh_degree)
         fit = ffn.fit_octree_sh
+    prior = {}
+    if args.tv_weight is not None:
+        want = 2 if tree.sh_degree is None else 3
+        if len(args.tv_weight) != want:
+            print("--tv-weight takes %d numbers for this tree (%s), got %d"
+                  % (want, "RGB SIGMA" if want == 2 else "BAND0 HIGHER_BANDS SIGMA",
+                     len(args.tv_weight)))
+            return 1
+        prior = dict(tv_weight=tuple(args.tv_weight), tv_eps=args.tv_eps)
+        print("total-variation prior:", " ".join("%g" % w for w in args.tv_weight), "eps %g" % args.tv_eps)
     fitted, log = fit(tree, train, val, args.batch_size, lr, args.steps, args.report_interval,
-                      center=args.center, min_transmittance=args.min_transmittance, seed=args.seed)
+                      center=args.center, min_transmittance=args.min_transmittance, seed=args.seed,
+                      **prior)
     if log:
         print("loss first %.6g last %.6g over %d steps" % (log[0].loss, log[-1].loss, len(log)))
     fitted.save(args.output_path)
