@@ -409,78 +409,56 @@ struct GradWorkspace {
     int32_t* ray_slots;     // n + 1
     float* ray_color;       // 3n
     float* ray_trans;       // n
-    int32_t* block_sums;    // of the longer of the two scans
-    float4* values;         // capacity, ray-major; then the odd reduce levels' target
-    float4* sums;           // capacity
+    int32_t* block_sums;    // of the longest of the scans
+    float4* values;         // capacity, ray-major; K17b: then the odd reduce levels' target
+    float4* sums;           // capacity (K17b only: K19b's partial sums are rows)
     int32_t* keys[2];       // capacity each
     int32_t* order[2];      // capacity each
     int32_t* table;         // 256 * tiles
     int32_t* seg_lo;        // num_leaves
     int32_t* seg_hi;        // num_leaves
-};
-
-static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
-
-static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, GradWorkspace* ws,
-                           char* base) {
-    const int64_t tiles = (capacity + kSortTile - 1) / kSortTile;
-    const int64_t longest = 256 * tiles > n ? 256 * tiles : n;
-    const int64_t blocks = (longest + kGradScanBlock - 1) / kGradScanBlock + 1;
-    const int64_t sizes[13] = {4 * (n + 1), 12 * n, 4 * n, 4 * blocks, 16 * capacity, 16 * capacity,
-                               4 * capacity, 4 * capacity, 4 * capacity, 4 * capacity,
-                               4 * 256 * tiles, 4 * num_leaves, 4 * num_leaves};
-    GradWorkspace scratch;
-    GradWorkspace* w = ws != nullptr ? ws : &scratch;
-    void** slots[13] = {(void**)&w->ray_slots, (void**)&w->ray_color, (void**)&w->ray_trans,
-                        (void**)&w->block_sums, (void**)&w->values, (void**)&w->sums,
-                        (void**)&w->keys[0], (void**)&w->keys[1], (void**)&w->order[0],
-                        (void**)&w->order[1], (void**)&w->table, (void**)&w->seg_lo,
-                        (void**)&w->seg_hi};
-    int64_t off = 0;
-    for (int r = 0; r < 13; ++r) {
-        *slots[r] = base != nullptr ? base + off : nullptr;
-        off += align256(sizes[r]);
-    }
-    return off;
-}
-
-struct GradSHWorkspace {
-    GradWorkspace k;        // K17b's (k.sums is not laid out: the partial sums are rows)
+    // K19b only
     int32_t* rays;          // capacity: the ray of every entry
     int32_t* before;        // num_leaves
     float4* rows[2];        // row_capacity rows of sh_width(degree) floats each
     int64_t row_capacity;
 };
 
-// E / 16 + min(E, L) rows hold every level's partial sums; the second term is taken at L so that the
-// size stays affine in max_entries
-static int64_t grad_sh_layout(int64_t n, int64_t num_leaves, int64_t capacity, int degree,
-                              GradSHWorkspace* ws, char* base) {
+static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
+// The buffers of K17b (degree 0) or K19b (degree 1, 2) behind one another from `base` (null: sizes
+// only) -> the bytes they take; a buffer the kind does not use stays null.  K19b: E / 16 + min(E, L)
+// rows hold every level's partial sums; the second term is taken at L so that the size stays affine
+// in max_entries.
+static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, int degree,
+                           GradWorkspace* ws, char* base) {
+    const bool sh = degree > 0;
     const int64_t tiles = (capacity + kSortTile - 1) / kSortTile;
     int64_t longest = 256 * tiles > n ? 256 * tiles : n;
-    if (num_leaves > longest) longest = num_leaves;
+    if (sh && num_leaves > longest) longest = num_leaves;     // the scan of `before`
     const int64_t blocks = (longest + kGradScanBlock - 1) / kGradScanBlock + 1;
-    const int64_t row_capacity = capacity / kGradChunk + num_leaves + 1;
-    const int64_t row_bytes = 4 * (int64_t)sh_width(degree);
-    const int64_t sizes[16] = {4 * (n + 1), 12 * n, 4 * n, 4 * blocks, 16 * capacity, 4 * capacity,
-                               4 * capacity, 4 * capacity, 4 * capacity, 4 * 256 * tiles,
-                               4 * num_leaves, 4 * num_leaves, 4 * capacity, 4 * num_leaves,
-                               row_bytes * row_capacity, row_bytes * row_capacity};
-    GradSHWorkspace scratch;
-    GradSHWorkspace* w = ws != nullptr ? ws : &scratch;
-    void** slots[16] = {(void**)&w->k.ray_slots, (void**)&w->k.ray_color, (void**)&w->k.ray_trans,
-                        (void**)&w->k.block_sums, (void**)&w->k.values, (void**)&w->k.keys[0],
-                        (void**)&w->k.keys[1], (void**)&w->k.order[0], (void**)&w->k.order[1],
-                        (void**)&w->k.table, (void**)&w->k.seg_lo, (void**)&w->k.seg_hi,
-                        (void**)&w->rays, (void**)&w->before, (void**)&w->rows[0],
-                        (void**)&w->rows[1]};
+    const int64_t row_capacity = sh ? capacity / kGradChunk + num_leaves + 1 : 0;
+    const int64_t rows_bytes = sh ? 4 * (int64_t)sh_width(degree) * row_capacity : 0;
+    GradWorkspace scratch;
+    GradWorkspace& w = ws != nullptr ? *ws : scratch;
+    w = GradWorkspace{};
+    w.row_capacity = row_capacity;
+    const struct { void** slot; int64_t bytes; bool used; } buffers[] = {
+        {(void**)&w.ray_slots, 4 * (n + 1), true},      {(void**)&w.ray_color, 12 * n, true},
+        {(void**)&w.ray_trans, 4 * n, true},            {(void**)&w.block_sums, 4 * blocks, true},
+        {(void**)&w.values, 16 * capacity, true},       {(void**)&w.sums, 16 * capacity, !sh},
+        {(void**)&w.keys[0], 4 * capacity, true},       {(void**)&w.keys[1], 4 * capacity, true},
+        {(void**)&w.order[0], 4 * capacity, true},      {(void**)&w.order[1], 4 * capacity, true},
+        {(void**)&w.table, 4 * 256 * tiles, true},      {(void**)&w.seg_lo, 4 * num_leaves, true},
+        {(void**)&w.seg_hi, 4 * num_leaves, true},      {(void**)&w.rays, 4 * capacity, sh},
+        {(void**)&w.before, 4 * num_leaves, sh},        {(void**)&w.rows[0], rows_bytes, sh},
+        {(void**)&w.rows[1], rows_bytes, sh}};
     int64_t off = 0;
-    for (int r = 0; r < 16; ++r) {
-        *slots[r] = base != nullptr ? base + off : nullptr;
-        off += align256(sizes[r]);
+    for (const auto& b : buffers) {
+        if (!b.used) continue;
+        if (base != nullptr) *b.slot = base + off;
+        off += align256(b.bytes);
     }
-    w->k.sums = nullptr;
-    w->row_capacity = row_capacity;
     return off;
 }
 
@@ -519,61 +497,49 @@ static inline bool grad_shape(int64_t n, int64_t num_leaves, int64_t max_entries
            max_entries >= 0 && max_entries <= kGradMaxEntries;
 }
 
-}  // namespace ffn
-
-using namespace ffn;
-
-extern "C" int64_t ffn_octree_grad_workspace_bytes(int64_t n, int64_t num_leaves,
-                                                   int64_t max_entries) {
+static int64_t grad_workspace_bytes(const char* who, int64_t n, int64_t num_leaves,
+                                    int64_t max_entries, int degree) {
     if (!grad_shape(n, num_leaves, max_entries)) {
-        fail_arg("ffn_octree_grad_workspace_bytes: shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, "
-                 "0 <= max_entries < 2^31)");
+        fail_who(who, "shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, 0 <= max_entries < 2^31)");
         return -1;
     }
-    return grad_layout(n, num_leaves, max_entries, nullptr, nullptr);
+    return grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr);
 }
 
-extern "C" int ffn_octree_render_volume_backward(
-    const float* starts, const float* directions, int64_t n, float scale, int depth,
-    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
-    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
-    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
-    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
-    void* stream) {
-    const char* who = "ffn_octree_render_volume_backward";
-    if (entries != nullptr) *entries = -1;
-    if (channels < 4) return fail_arg("ffn_octree_render_volume_backward: channels >= 4");
-    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_backward: t_min is NaN");
-    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
-        return fail_arg("ffn_octree_render_volume_backward: 0 <= min_transmittance < 1");
-    if (!leaf_data || !d_color || !d_alpha || !d_leaf_data || !workspace)
-        return fail_arg("ffn_octree_render_volume_backward: null argument");
-    if (int err = octree_check_walk_args(who, starts, directions, n, depth, node_index, num_nodes,
-                                         leaf_index, num_leaves))
-        return err;
-    if (channels == 4 && ((uintptr_t)leaf_data & 15) != 0)
-        return fail_arg("ffn_octree_render_volume_backward: leaf_data with 4 channels must be "
-                        "16-byte aligned");
-    if (((uintptr_t)d_leaf_data & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
-        return fail_arg("ffn_octree_render_volume_backward: d_leaf_data and workspace must be "
-                        "16-byte aligned");
+// what the front half of a backward leaves for its reduce: the e > 0 entries sorted by leaf
+struct GradEntries {
+    GradWorkspace ws;
+    int32_t e;
+    const int32_t* keys;
+    const int32_t* order;
+    unsigned over_entries;  // workgroups of 256 over the entries
+    int levels;             // of the reduce
+};
+
+// The front half of both backwards, for a walk whose arguments the entry point has checked: the
+// workspace laid out for grad.leaves.degree, the first walk (counts, C and T_{n+1} per ray), the
+// scan, the read-back of the total E (*entries, where the caller wants it) and its refusal, the
+// second walk (the entries), sort and bounds.  E == 0: every row of d_leaves (row_bytes each) is
+// zeroed here and got->e is 0: nothing is left to reduce.
+static int grad_entries(const char* who, GradWalk& grad, void* workspace, int64_t workspace_bytes,
+                        int64_t max_entries, void* d_leaves, int64_t row_bytes, int64_t* entries,
+                        GradEntries* got) {
+    const int64_t n = grad.walk.n, num_leaves = grad.walk.num_leaves;
+    const int degree = grad.leaves.degree;
+    const hipStream_t st = grad.walk.stream;
+    got->e = 0;
     // a ray crosses at most 3 * 2^(depth-1) + 1 regions: the entry offsets stay below 2^31
     if (!grad_shape(n, num_leaves, max_entries) ||
-        n * (3 * ((int64_t)1 << (depth - 1)) + 1) > kGradMaxEntries)
-        return fail_arg("ffn_octree_render_volume_backward: shape (n * (3 * 2^(depth-1) + 1) < 2^31: "
-                        "split the rays)");
-    if (workspace_bytes < grad_layout(n, num_leaves, max_entries, nullptr, nullptr))
-        return fail_arg("ffn_octree_render_volume_backward: workspace too small for max_entries");
-    hipStream_t st = (hipStream_t)stream;
-    GradWorkspace ws;
-    grad_layout(n, num_leaves, max_entries, &ws, (char*)workspace);
+        n * (3 * ((int64_t)1 << (grad.walk.depth - 1)) + 1) > kGradMaxEntries)
+        return fail_who(who, "shape (n * (3 * 2^(depth-1) + 1) < 2^31: split the rays)");
+    if (workspace_bytes < grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr))
+        return fail_who(who, "workspace too small for max_entries");
+    GradWorkspace& ws = got->ws;
+    grad_layout(n, num_leaves, max_entries, degree, &ws, (char*)workspace);
+    grad.ray_slots = ws.ray_slots; grad.ray_color = ws.ray_color; grad.ray_trans = ws.ray_trans;
+    grad.entry_values = ws.values; grad.entry_leaves = ws.keys[0]; grad.entry_rays = ws.rays;
 
-    // K17a, first walk: counts, C and T_{n+1} per ray
-    if (int err = octree_grad_walk(who, starts, directions, n, scale, depth, node_index, num_nodes,
-                                   leaf_index, num_leaves, t_min, leaf_data, channels, bg_r, bg_g,
-                                   bg_b, min_transmittance, d_color, d_alpha, ws.ray_slots,
-                                   ws.ray_color, ws.ray_trans, ws.values, ws.keys[0], 0, st))
-        return err;
+    if (int err = octree_grad_walk(who, grad, 0)) return err;
     exclusive_scan(ws.ray_slots, n, ws.block_sums, ws.ray_slots + n, st);
     int32_t total = 0;
     hipError_t copied = hipMemcpyAsync(&total, ws.ray_slots + n, 4, hipMemcpyDeviceToHost, st);
@@ -589,36 +555,66 @@ extern "C" int ffn_octree_render_volume_backward(
                  who, (long long)total, (long long)max_entries);
         return fail_arg(text);
     }
-    const int32_t e = total;
-    if (e == 0) {
-        (void)hipMemsetAsync(d_leaf_data, 0, 16 * num_leaves, st);
+    if (total == 0) {
+        (void)hipMemsetAsync(d_leaves, 0, row_bytes * num_leaves, st);
         return check_launch(who);
     }
-    // K17a, second walk: the entries
-    if (int err = octree_grad_walk(who, starts, directions, n, scale, depth, node_index, num_nodes,
-                                   leaf_index, num_leaves, t_min, leaf_data, channels, bg_r, bg_g,
-                                   bg_b, min_transmittance, d_color, d_alpha, ws.ray_slots,
-                                   ws.ray_color, ws.ray_trans, ws.values, ws.keys[0], 1, st))
-        return err;
-
-    const int32_t* keys = nullptr;
-    const int32_t* order = nullptr;
-    sort_and_bounds(ws, e, num_leaves, st, &keys, &order);
-    const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
+    if (int err = octree_grad_walk(who, grad, 1)) return err;
+    got->e = total;
+    sort_and_bounds(ws, got->e, num_leaves, st, &got->keys, &got->order);
+    got->over_entries = (unsigned)(((int64_t)got->e + 255) / 256);
     // a ray takes a leaf once: no list is longer than min(n, e)
-    const int64_t longest = n < e ? n : e;
-    int levels = 1;
-    for (int64_t reach = kGradChunk; reach < longest; reach *= kGradChunk) ++levels;
+    const int64_t longest = n < got->e ? n : got->e;
+    got->levels = 1;
+    for (int64_t reach = kGradChunk; reach < longest; reach *= kGradChunk) ++got->levels;
+    return 0;
+}
+
+}  // namespace ffn
+
+using namespace ffn;
+
+extern "C" int64_t ffn_octree_grad_workspace_bytes(int64_t n, int64_t num_leaves,
+                                                   int64_t max_entries) {
+    return grad_workspace_bytes("ffn_octree_grad_workspace_bytes", n, num_leaves, max_entries, 0);
+}
+
+extern "C" int ffn_octree_render_volume_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    void* stream) {
+    const char* who = "ffn_octree_render_volume_backward";
+    GradWalk grad{{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                   num_leaves, t_min, (hipStream_t)stream},
+                  {leaf_data, channels, 0, bg_r, bg_g, bg_b, min_transmittance}, d_color, d_alpha};
+    if (entries != nullptr) *entries = -1;
+    if (channels < 4) return fail_who(who, "channels >= 4");
+    if (int err = check_volume_args(who, grad.walk, grad.leaves,
+                                    !d_color || !d_alpha || !d_leaf_data || !workspace))
+        return err;
+    if (channels == 4 && misaligned16(leaf_data))
+        return fail_who(who, "leaf_data with 4 channels must be 16-byte aligned");
+    if (misaligned16(d_leaf_data) || misaligned16(workspace))
+        return fail_who(who, "d_leaf_data and workspace must be 16-byte aligned");
+    GradEntries got;
+    const int err = grad_entries(who, grad, workspace, workspace_bytes, max_entries, d_leaf_data, 16,
+                                 entries, &got);
+    if (err != 0 || got.e == 0) return err;
+    const GradWorkspace& ws = got.ws;
     const float4* src = ws.values;
-    for (int level = 0; level < levels; ++level) {
+    for (int level = 0; level < got.levels; ++level) {
         float4* dst = (level & 1) ? ws.values : ws.sums;
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3(over_entries), dim3(256), 0, st, keys,
-                           level == 0 ? order : (const int32_t*)nullptr, src, dst, e,
-                           (int32_t)num_leaves, ws.seg_lo, ws.seg_hi, level);
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3(got.over_entries), dim3(256), 0, grad.walk.stream,
+                           got.keys, level == 0 ? got.order : (const int32_t*)nullptr, src, dst,
+                           got.e, (int32_t)num_leaves, ws.seg_lo, ws.seg_hi, level);
         src = dst;
     }
     hipLaunchKernelGGL(grad_finish_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0,
-                       st, src, ws.seg_lo, ws.seg_hi, num_leaves, (float4*)d_leaf_data);
+                       grad.walk.stream, src, ws.seg_lo, ws.seg_hi, num_leaves,
+                       (float4*)d_leaf_data);
     return check_launch(who);
 }
 
@@ -638,12 +634,8 @@ extern "C" int64_t ffn_octree_grad_sh_workspace_bytes(int64_t n, int64_t num_lea
         fail_arg("ffn_octree_grad_sh_workspace_bytes: degree is 1 or 2");
         return -1;
     }
-    if (!grad_shape(n, num_leaves, max_entries)) {
-        fail_arg("ffn_octree_grad_sh_workspace_bytes: shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, "
-                 "0 <= max_entries < 2^31)");
-        return -1;
-    }
-    return grad_sh_layout(n, num_leaves, max_entries, degree, nullptr, nullptr);
+    return grad_workspace_bytes("ffn_octree_grad_sh_workspace_bytes", n, num_leaves, max_entries,
+                                degree);
 }
 
 extern "C" int ffn_octree_render_volume_sh_backward(
@@ -654,102 +646,53 @@ extern "C" int ffn_octree_render_volume_sh_backward(
     int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
     int row_stride, void* stream) {
     const char* who = "ffn_octree_render_volume_sh_backward";
+    GradWalk grad{{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                   num_leaves, t_min, (hipStream_t)stream},
+                  {leaf_rows, row_stride, degree, bg_r, bg_g, bg_b, min_transmittance}, d_color,
+                  d_alpha};
     if (entries != nullptr) *entries = -1;
-    if (degree != 1 && degree != 2)
-        return fail_arg("ffn_octree_render_volume_sh_backward: degree is 1 or 2");
+    if (degree != 1 && degree != 2) return fail_who(who, "degree is 1 or 2");
     if (row_stride < 3 * sh_bases(degree) + 1 || row_stride % 4 != 0 || row_stride > 64)
-        return fail_arg("ffn_octree_render_volume_sh_backward: row_stride is a multiple of 4, "
-                        "3 * (degree + 1)^2 + 1 <= row_stride <= 64");
-    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_sh_backward: t_min is NaN");
-    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
-        return fail_arg("ffn_octree_render_volume_sh_backward: 0 <= min_transmittance < 1");
-    if (!leaf_rows || !d_color || !d_alpha || !d_leaf_rows || !workspace)
-        return fail_arg("ffn_octree_render_volume_sh_backward: null argument");
-    if (int err = octree_check_walk_args(who, starts, directions, n, depth, node_index, num_nodes,
-                                         leaf_index, num_leaves))
+        return fail_who(who, "row_stride is a multiple of 4, 3 * (degree + 1)^2 + 1 <= row_stride "
+                             "<= 64");
+    if (int err = check_volume_args(who, grad.walk, grad.leaves,
+                                    !d_color || !d_alpha || !d_leaf_rows || !workspace))
         return err;
-    if (((uintptr_t)leaf_rows & 15) != 0 || ((uintptr_t)d_leaf_rows & 15) != 0 ||
-        ((uintptr_t)workspace & 15) != 0)
-        return fail_arg("ffn_octree_render_volume_sh_backward: leaf_rows, d_leaf_rows and workspace "
-                        "must be 16-byte aligned");
-    // a ray crosses at most 3 * 2^(depth-1) + 1 regions: the entry offsets stay below 2^31
-    if (!grad_shape(n, num_leaves, max_entries) ||
-        n * (3 * ((int64_t)1 << (depth - 1)) + 1) > kGradMaxEntries)
-        return fail_arg("ffn_octree_render_volume_sh_backward: shape (n * (3 * 2^(depth-1) + 1) < "
-                        "2^31: split the rays)");
-    if (workspace_bytes < grad_sh_layout(n, num_leaves, max_entries, degree, nullptr, nullptr))
-        return fail_arg("ffn_octree_render_volume_sh_backward: workspace too small for max_entries");
-    hipStream_t st = (hipStream_t)stream;
-    GradSHWorkspace ws;
-    grad_sh_layout(n, num_leaves, max_entries, degree, &ws, (char*)workspace);
-
-    // K19a, first walk: counts, C and T_{n+1} per ray
-    if (int err = octree_grad_sh_walk(who, starts, directions, n, scale, depth, node_index,
-                                      num_nodes, leaf_index, num_leaves, t_min, leaf_rows,
-                                      row_stride, degree, bg_r, bg_g, bg_b, min_transmittance,
-                                      d_color, d_alpha, ws.k.ray_slots, ws.k.ray_color,
-                                      ws.k.ray_trans, ws.k.values, ws.k.keys[0], ws.rays, 0, st))
-        return err;
-    exclusive_scan(ws.k.ray_slots, n, ws.k.block_sums, ws.k.ray_slots + n, st);
-    int32_t total = 0;
-    hipError_t copied = hipMemcpyAsync(&total, ws.k.ray_slots + n, 4, hipMemcpyDeviceToHost, st);
-    if (copied == hipSuccess) copied = hipStreamSynchronize(st);
-    if (copied != hipSuccess) {
-        set_error(who, copied);
-        return (int)copied;
-    }
-    if (entries != nullptr) *entries = total;
-    if (total < 0 || total > max_entries) {
-        char text[160];
-        snprintf(text, sizeof text, "%s: the rays take %lld leaves, the workspace holds %lld entries",
-                 who, (long long)total, (long long)max_entries);
-        return fail_arg(text);
-    }
-    const int32_t e = total;
-    if (e == 0) {
-        (void)hipMemsetAsync(d_leaf_rows, 0, 4 * (int64_t)row_stride * num_leaves, st);
-        return check_launch(who);
-    }
-    // K19a, second walk: the entries
-    if (int err = octree_grad_sh_walk(who, starts, directions, n, scale, depth, node_index,
-                                      num_nodes, leaf_index, num_leaves, t_min, leaf_rows,
-                                      row_stride, degree, bg_r, bg_g, bg_b, min_transmittance,
-                                      d_color, d_alpha, ws.k.ray_slots, ws.k.ray_color,
-                                      ws.k.ray_trans, ws.k.values, ws.k.keys[0], ws.rays, 1, st))
-        return err;
-    const int32_t* keys = nullptr;
-    const int32_t* order = nullptr;
-    sort_and_bounds(ws.k, e, num_leaves, st, &keys, &order);
-    const unsigned over_entries = (unsigned)(((int64_t)e + 255) / 256);
+    if (misaligned16(leaf_rows) || misaligned16(d_leaf_rows) || misaligned16(workspace))
+        return fail_who(who, "leaf_rows, d_leaf_rows and workspace must be 16-byte aligned");
+    GradEntries got;
+    const int err = grad_entries(who, grad, workspace, workspace_bytes, max_entries, d_leaf_rows,
+                                 4 * (int64_t)row_stride, entries, &got);
+    if (err != 0 || got.e == 0) return err;
+    const GradWorkspace& ws = got.ws;
+    const hipStream_t st = grad.walk.stream;
     const unsigned over_leaves = (unsigned)((num_leaves + 255) / 256);
-    hipLaunchKernelGGL(grad_sh_nonempty_kernel, dim3(over_leaves), dim3(256), 0, st, ws.k.seg_lo,
-                       ws.k.seg_hi, num_leaves, ws.before);
-    exclusive_scan(ws.before, num_leaves, ws.k.block_sums, nullptr, st);
+    hipLaunchKernelGGL(grad_sh_nonempty_kernel, dim3(over_leaves), dim3(256), 0, st, ws.seg_lo,
+                       ws.seg_hi, num_leaves, ws.before);
+    exclusive_scan(ws.before, num_leaves, ws.block_sums, nullptr, st);
     const int quads = sh_width(degree) / 4;
     if (degree == 1)
-        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<1>, dim3(over_entries), dim3(256), 0, st, keys,
-                           order, ws.k.values, ws.rays, directions, n, ws.rows[0], ws.row_capacity,
-                           e, (int32_t)num_leaves, ws.k.seg_lo, ws.k.seg_hi, ws.before);
+        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<1>, dim3(got.over_entries), dim3(256), 0, st,
+                           got.keys, got.order, ws.values, ws.rays, directions, n, ws.rows[0],
+                           ws.row_capacity, got.e, (int32_t)num_leaves, ws.seg_lo, ws.seg_hi,
+                           ws.before);
     else
-        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<2>, dim3(over_entries), dim3(256), 0, st, keys,
-                           order, ws.k.values, ws.rays, directions, n, ws.rows[0], ws.row_capacity,
-                           e, (int32_t)num_leaves, ws.k.seg_lo, ws.k.seg_hi, ws.before);
-    // a ray takes a leaf once: no list is longer than min(n, e)
-    const int64_t longest = n < e ? n : e;
-    int levels = 1;
-    for (int64_t reach = kGradChunk; reach < longest; reach *= kGradChunk) ++levels;
+        hipLaunchKernelGGL(grad_sh_reduce_first_kernel<2>, dim3(got.over_entries), dim3(256), 0, st,
+                           got.keys, got.order, ws.values, ws.rays, directions, n, ws.rows[0],
+                           ws.row_capacity, got.e, (int32_t)num_leaves, ws.seg_lo, ws.seg_hi,
+                           ws.before);
     const float4* src = ws.rows[0];
-    for (int level = 1; level < levels; ++level) {
+    for (int level = 1; level < got.levels; ++level) {
         float4* dst = ws.rows[level & 1];
-        hipLaunchKernelGGL(grad_sh_reduce_kernel, dim3(over_entries), dim3(256), 0, st, keys, src,
-                           dst, ws.row_capacity, quads, e, (int32_t)num_leaves, ws.k.seg_lo,
-                           ws.k.seg_hi, ws.before, level);
+        hipLaunchKernelGGL(grad_sh_reduce_kernel, dim3(got.over_entries), dim3(256), 0, st, got.keys,
+                           src, dst, ws.row_capacity, quads, got.e, (int32_t)num_leaves, ws.seg_lo,
+                           ws.seg_hi, ws.before, level);
         src = dst;
     }
     const int stride_quads = row_stride / 4;
     hipLaunchKernelGGL(grad_sh_finish_kernel,
                        dim3((unsigned)((num_leaves * stride_quads + 255) / 256)), dim3(256), 0, st,
-                       src, quads, ws.k.seg_lo, ws.k.seg_hi, ws.before, num_leaves, stride_quads,
+                       src, quads, ws.seg_lo, ws.seg_hi, ws.before, num_leaves, stride_quads,
                        (float4*)d_leaf_rows);
     return check_launch(who);
 }

@@ -523,79 +523,72 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     }
 }
 
-static int check_walk_args(const char* who, const float* starts, const float* directions,
-                           int64_t n, int depth, const int64_t* node_index, int64_t num_nodes,
-                           const int64_t* leaf_index, int64_t num_leaves) {
-    char text[160];
-    if (n < 1 || n >= kWalkMaxRays || depth < 1 || depth > kWalkMaxDepth || num_leaves < 1 ||
-        num_nodes < 0) {
-        snprintf(text, sizeof text, "%s: shape (1 <= n < 2^31, 1 <= depth <= 11, num_leaves >= 1)", who);
-        return fail_arg(text);
-    }
-    if (!starts || !directions || !leaf_index || (num_nodes > 0 && !node_index)) {
-        snprintf(text, sizeof text, "%s: null argument", who);
-        return fail_arg(text);
-    }
+int check_walk_args(const char* who, const Walk& walk) {
+    if (walk.n < 1 || walk.n >= kWalkMaxRays || walk.depth < 1 || walk.depth > kWalkMaxDepth ||
+        walk.num_leaves < 1 || walk.num_nodes < 0)
+        return fail_who(who, "shape (1 <= n < 2^31, 1 <= depth <= 11, num_leaves >= 1)");
+    if (!walk.starts || !walk.directions || !walk.leaf_index ||
+        (walk.num_nodes > 0 && !walk.node_index))
+        return fail_who(who, "null argument");
     return 0;
 }
 
-// K17a, launched by ffn_octree_render_volume_backward (csrc/octree_grad.hip), which has checked
-// the arguments
-int octree_grad_walk(const char* who, const float* starts, const float* directions, int64_t n,
-                     float scale, int depth, const int64_t* node_index, int64_t num_nodes,
-                     const int64_t* leaf_index, int64_t num_leaves, float t_min,
-                     const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
-                     float min_transmittance, const float* d_color, const float* d_alpha,
-                     int32_t* ray_slots, float* ray_color, float* ray_trans, float4* entry_values,
-                     int32_t* entry_leaves, int phase, hipStream_t stream) {
-    FirstHit first{};
-    first.leaf_data = leaf_data; first.channels = channels;
-    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
-    first.min_transmittance = min_transmittance;
-    first.color = ray_color; first.alpha = ray_trans;
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<kGrad>, dim3(blocks), dim3(kWalkThreads), 0, stream,
-                       starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
-                       num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min, 0.0f,
-                       (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
+int check_volume_args(const char* who, const Walk& walk, const VolumeLeaves& leaves,
+                      bool any_null) {
+    if (walk.t_min != walk.t_min) return fail_who(who, "t_min is NaN");
+    if (!(leaves.min_transmittance >= 0.0f && leaves.min_transmittance < 1.0f))
+        return fail_who(who, "0 <= min_transmittance < 1");
+    if (!leaves.data || any_null) return fail_who(who, "null argument");
+    return check_walk_args(who, walk);
+}
+
+// one launch of mode kMode; what the mode leaves idle stays at its default
+template <int kMode>
+static int launch_walk(const char* who, const Walk& walk, const FirstHit& first = FirstHit{},
+                       int max_length = 0, float* t_stops = nullptr, int64_t* leaves = nullptr,
+                       float pad = 0.0f, float* span_in = nullptr, float* span_out = nullptr,
+                       uint8_t* span_hit = nullptr) {
+    const unsigned blocks = (unsigned)((walk.n + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_walk_kernel<kMode>, dim3(blocks), dim3(kWalkThreads), 0, walk.stream,
+                       walk.starts, walk.directions, walk.n, walk.scale, walk.depth,
+                       walk.node_index, walk.num_nodes, walk.leaf_index, walk.num_leaves,
+                       max_length, t_stops, leaves, walk.t_min, pad, span_in, span_out, span_hit,
+                       first);
     return check_launch(who);
 }
 
-// K19a, launched by ffn_octree_render_volume_sh_backward (csrc/octree_grad.hip), which has checked
-// the arguments
-int octree_grad_sh_walk(const char* who, const float* starts, const float* directions, int64_t n,
-                        float scale, int depth, const int64_t* node_index, int64_t num_nodes,
-                        const int64_t* leaf_index, int64_t num_leaves, float t_min,
-                        const float* leaf_rows, int row_stride, int degree, float bg_r, float bg_g,
-                        float bg_b, float min_transmittance, const float* d_color,
-                        const float* d_alpha, int32_t* ray_slots, float* ray_color,
-                        float* ray_trans, float4* entry_values, int32_t* entry_leaves,
-                        int32_t* entry_rays, int phase, hipStream_t stream) {
-    FirstHit first{};
-    first.leaf = (int64_t*)entry_rays;
-    first.leaf_data = leaf_rows; first.channels = row_stride;
-    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
-    first.min_transmittance = min_transmittance;
-    first.color = ray_color; first.alpha = ray_trans;
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    if (degree == 1)
-        hipLaunchKernelGGL(octree_walk_kernel<kGradSH1>, dim3(blocks), dim3(kWalkThreads), 0, stream,
-                           starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
-                           num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min,
-                           0.0f, (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
-    else
-        hipLaunchKernelGGL(octree_walk_kernel<kGradSH2>, dim3(blocks), dim3(kWalkThreads), 0, stream,
-                           starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
-                           num_leaves, phase, (float*)entry_values, (int64_t*)entry_leaves, t_min,
-                           0.0f, (float*)d_color, (float*)d_alpha, (uint8_t*)ray_slots, first);
-    return check_launch(who);
+// the SH modes come in pairs: kDegree1 is degree 1's, kDegree1 + 1 degree 2's
+template <int kDegree1, typename... Args>
+static int launch_walk_sh(int degree, const Args&... args) {
+    return degree == 1 ? launch_walk<kDegree1>(args...) : launch_walk<kDegree1 + 1>(args...);
 }
 
-int octree_check_walk_args(const char* who, const float* starts, const float* directions,
-                           int64_t n, int depth, const int64_t* node_index, int64_t num_nodes,
-                           const int64_t* leaf_index, int64_t num_leaves) {
-    return check_walk_args(who, starts, directions, n, depth, node_index, num_nodes, leaf_index,
-                           num_leaves);
+// what the volume modes read of `first`: the leaves, the background and the three per-ray outputs
+static FirstHit volume_first_hit(const VolumeLeaves& leaves, float* color, float* alpha,
+                                 float* depth) {
+    FirstHit first{};
+    first.leaf_data = leaves.data; first.channels = leaves.stride;
+    first.bg_r = leaves.bg_r; first.bg_g = leaves.bg_g; first.bg_b = leaves.bg_b;
+    first.min_transmittance = leaves.min_transmittance;
+    first.color = color; first.alpha = alpha; first.depth = depth;
+    return first;
+}
+
+// K17a / K19a: the typed buffers of the gradient walk onto the idle parameters, as the comment above
+// the kernel lays them out
+int octree_grad_walk(const char* who, const GradWalk& grad, int phase) {
+    FirstHit first = volume_first_hit(grad.leaves, grad.ray_color, grad.ray_trans, nullptr);
+    first.leaf = (int64_t*)grad.entry_rays;
+    float* values = (float*)grad.entry_values;                  // t_stops
+    int64_t* entry_leaves = (int64_t*)grad.entry_leaves;        // leaves
+    float* d_color = const_cast<float*>(grad.d_color);          // span_in
+    float* d_alpha = const_cast<float*>(grad.d_alpha);          // span_out
+    uint8_t* slots = (uint8_t*)grad.ray_slots;                  // span_hit; max_length: the phase
+    if (grad.leaves.degree == 0)
+        return launch_walk<kGrad>(who, grad.walk, first, phase, values, entry_leaves, 0.0f, d_color,
+                                  d_alpha, slots);
+    return launch_walk_sh<kGradSH1>(grad.leaves.degree, who, grad.walk, first, phase, values,
+                                    entry_leaves, 0.0f, d_color, d_alpha, slots);
 }
 
 }  // namespace ffn
@@ -606,47 +599,27 @@ extern "C" int ffn_octree_walk(const float* starts, const float* directions, int
                                int depth, const int64_t* node_index, int64_t num_nodes,
                                const int64_t* leaf_index, int64_t num_leaves, int max_length,
                                float* t_stops, int64_t* leaves, void* stream) {
-    if (int err = check_walk_args("ffn_octree_walk", starts, directions, n, depth, node_index,
-                                  num_nodes, leaf_index, num_leaves))
-        return err;
+    const char* who = "ffn_octree_walk";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, 0.0f, (hipStream_t)stream};
+    if (int err = check_walk_args(who, walk)) return err;
     if (max_length < 2 || max_length > (1 << 16))
         return fail_arg("ffn_octree_walk: 2 <= max_length <= 65536");
     if (!t_stops || !leaves) return fail_arg("ffn_octree_walk: null argument");
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<kPath>, dim3(blocks), dim3(kWalkThreads), 0,
-                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                       num_nodes, leaf_index, num_leaves, max_length, t_stops, leaves, 0.0f, 0.0f,
-                       (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, FirstHit{});
-    return check_launch("ffn_octree_walk");
+    return launch_walk<kPath>(who, walk, FirstHit{}, max_length, t_stops, leaves);
 }
 
 extern "C" int ffn_octree_spans(const float* starts, const float* directions, int64_t n, float scale,
                                 int depth, const int64_t* node_index, int64_t num_nodes,
                                 const int64_t* leaf_index, int64_t num_leaves, float t_min,
                                 float pad, float* t_in, float* t_out, uint8_t* hit, void* stream) {
-    if (int err = check_walk_args("ffn_octree_spans", starts, directions, n, depth, node_index,
-                                  num_nodes, leaf_index, num_leaves))
-        return err;
+    const char* who = "ffn_octree_spans";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
+    if (int err = check_walk_args(who, walk)) return err;
     if (!t_in || !t_out || !hit) return fail_arg("ffn_octree_spans: null argument");
     if (!(pad >= 0.0f)) return fail_arg("ffn_octree_spans: pad >= 0");
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<kSpan>, dim3(blocks), dim3(kWalkThreads), 0,
-                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
-                       t_min, pad, t_in, t_out, hit, FirstHit{});
-    return check_launch("ffn_octree_spans");
-}
-
-static int launch_first_hit(const char* who, const float* starts, const float* directions,
-                            int64_t n, float scale, int depth, const int64_t* node_index,
-                            int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
-                            float t_min, const FirstHit& first, void* stream) {
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<kFirstHit>, dim3(blocks), dim3(kWalkThreads), 0,
-                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
-                       t_min, 0.0f, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
-    return check_launch(who);
+    return launch_walk<kSpan>(who, walk, FirstHit{}, 0, nullptr, nullptr, pad, t_in, t_out, hit);
 }
 
 extern "C" int ffn_octree_first_hit(const float* starts, const float* directions, int64_t n,
@@ -654,16 +627,16 @@ extern "C" int ffn_octree_first_hit(const float* starts, const float* directions
                                     int64_t num_nodes, const int64_t* leaf_index,
                                     int64_t num_leaves, float t_min, int64_t* leaf, float* t_hit,
                                     int8_t* face, void* stream) {
+    const char* who = "ffn_octree_first_hit";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
     // scalars first: which check refuses does not depend on the pointers
     if (t_min != t_min) return fail_arg("ffn_octree_first_hit: t_min is NaN");
-    if (int err = check_walk_args("ffn_octree_first_hit", starts, directions, n, depth, node_index,
-                                  num_nodes, leaf_index, num_leaves))
-        return err;
+    if (int err = check_walk_args(who, walk)) return err;
     if (!leaf || !t_hit || !face) return fail_arg("ffn_octree_first_hit: null argument");
     FirstHit first{};
     first.leaf = leaf; first.t_hit = t_hit; first.face = face;
-    return launch_first_hit("ffn_octree_first_hit", starts, directions, n, scale, depth,
-                            node_index, num_nodes, leaf_index, num_leaves, t_min, first, stream);
+    return launch_walk<kFirstHit>(who, walk, first);
 }
 
 extern "C" int ffn_octree_render(const float* starts, const float* directions, int64_t n,
@@ -673,13 +646,14 @@ extern "C" int ffn_octree_render(const float* starts, const float* directions, i
                                  float bg_g, float bg_b, int shading, float* color, float* alpha,
                                  float* depth_out, int64_t* leaf, float* t_hit, int8_t* face,
                                  void* stream) {
+    const char* who = "ffn_octree_render";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
     if (channels < 3) return fail_arg("ffn_octree_render: channels >= 3");
     if (shading != FFN_OCTREE_SHADING_FLAT && shading != FFN_OCTREE_SHADING_FACES)
         return fail_arg("ffn_octree_render: unknown shading mode");
     if (t_min != t_min) return fail_arg("ffn_octree_render: t_min is NaN");
-    if (int err = check_walk_args("ffn_octree_render", starts, directions, n, depth, node_index,
-                                  num_nodes, leaf_index, num_leaves))
-        return err;
+    if (int err = check_walk_args(who, walk)) return err;
     if (!leaf_data || !color || !alpha || !depth_out)
         return fail_arg("ffn_octree_render: null argument");
     FirstHit first{};
@@ -687,8 +661,7 @@ extern "C" int ffn_octree_render(const float* starts, const float* directions, i
     first.leaf_data = leaf_data; first.channels = channels; first.shading = shading;
     first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
     first.color = color; first.alpha = alpha; first.depth = depth_out;
-    return launch_first_hit("ffn_octree_render", starts, directions, n, scale, depth, node_index,
-                            num_nodes, leaf_index, num_leaves, t_min, first, stream);
+    return launch_walk<kFirstHit>(who, walk, first);
 }
 
 extern "C" int ffn_octree_render_volume(const float* starts, const float* directions, int64_t n,
@@ -698,29 +671,16 @@ extern "C" int ffn_octree_render_volume(const float* starts, const float* direct
                                         int channels, float bg_r, float bg_g, float bg_b,
                                         float min_transmittance, float* color, float* alpha,
                                         float* depth_out, void* stream) {
+    const char* who = "ffn_octree_render_volume";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
+    const VolumeLeaves rows{leaf_data, channels, 0, bg_r, bg_g, bg_b, min_transmittance};
     if (channels < 4) return fail_arg("ffn_octree_render_volume: channels >= 4");
-    if (t_min != t_min) return fail_arg("ffn_octree_render_volume: t_min is NaN");
-    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
-        return fail_arg("ffn_octree_render_volume: 0 <= min_transmittance < 1");
-    if (!leaf_data || !color || !alpha || !depth_out)
-        return fail_arg("ffn_octree_render_volume: null argument");
-    if (int err = check_walk_args("ffn_octree_render_volume", starts, directions, n, depth,
-                                  node_index, num_nodes, leaf_index, num_leaves))
-        return err;
+    if (int err = check_volume_args(who, walk, rows, !color || !alpha || !depth_out)) return err;
     // four channels are read as one 16-byte load per leaf
-    if (channels == 4 && ((uintptr_t)leaf_data & 15) != 0)
+    if (channels == 4 && misaligned16(leaf_data))
         return fail_arg("ffn_octree_render_volume: leaf_data with 4 channels must be 16-byte aligned");
-    FirstHit first{};
-    first.leaf_data = leaf_data; first.channels = channels;
-    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
-    first.min_transmittance = min_transmittance;
-    first.color = color; first.alpha = alpha; first.depth = depth_out;
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    hipLaunchKernelGGL(octree_walk_kernel<kVolume>, dim3(blocks), dim3(kWalkThreads), 0,
-                       (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                       num_nodes, leaf_index, num_leaves, 0, (float*)nullptr, (int64_t*)nullptr,
-                       t_min, 0.0f, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
-    return check_launch("ffn_octree_render_volume");
+    return launch_walk<kVolume>(who, walk, volume_first_hit(rows, color, alpha, depth_out));
 }
 
 extern "C" int ffn_octree_render_volume_sh(const float* starts, const float* directions, int64_t n,
@@ -731,42 +691,22 @@ extern "C" int ffn_octree_render_volume_sh(const float* starts, const float* dir
                                            float min_transmittance, float* color, float* alpha,
                                            float* depth_out, int degree, int row_stride,
                                            void* stream) {
+    const char* who = "ffn_octree_render_volume_sh";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
+    const VolumeLeaves rows{leaf_data, row_stride, degree, bg_r, bg_g, bg_b, min_transmittance};
     if (degree != 1 && degree != 2) return fail_arg("ffn_octree_render_volume_sh: degree is 1 or 2");
     if (channels != 3 * (degree + 1) * (degree + 1) + 1)
         return fail_arg("ffn_octree_render_volume_sh: channels == 3 * (degree + 1)^2 + 1");
     if (row_stride < channels || row_stride % 4 != 0 || row_stride > 64)
         return fail_arg("ffn_octree_render_volume_sh: row_stride is a multiple of 4, channels <= "
                         "row_stride <= 64");
-    if (t_min != t_min) return fail_arg("ffn_octree_render_volume_sh: t_min is NaN");
-    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))
-        return fail_arg("ffn_octree_render_volume_sh: 0 <= min_transmittance < 1");
-    if (!leaf_data || !color || !alpha || !depth_out)
-        return fail_arg("ffn_octree_render_volume_sh: null argument");
-    if (int err = check_walk_args("ffn_octree_render_volume_sh", starts, directions, n, depth,
-                                  node_index, num_nodes, leaf_index, num_leaves))
-        return err;
+    if (int err = check_volume_args(who, walk, rows, !color || !alpha || !depth_out)) return err;
     // a row is read as 16-byte loads
-    if (((uintptr_t)leaf_data & 15) != 0)
+    if (misaligned16(leaf_data))
         return fail_arg("ffn_octree_render_volume_sh: leaf_data must be 16-byte aligned");
-    FirstHit first{};
-    first.leaf_data = leaf_data; first.channels = row_stride;
-    first.bg_r = bg_r; first.bg_g = bg_g; first.bg_b = bg_b;
-    first.min_transmittance = min_transmittance;
-    first.color = color; first.alpha = alpha; first.depth = depth_out;
-    const unsigned blocks = (unsigned)((n + kWalkThreads - 1) / kWalkThreads);
-    if (degree == 1)
-        hipLaunchKernelGGL(octree_walk_kernel<kVolumeSH1>, dim3(blocks), dim3(kWalkThreads), 0,
-                           (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                           num_nodes, leaf_index, num_leaves, 0, (float*)nullptr,
-                           (int64_t*)nullptr, t_min, 0.0f, (float*)nullptr, (float*)nullptr,
-                           (uint8_t*)nullptr, first);
-    else
-        hipLaunchKernelGGL(octree_walk_kernel<kVolumeSH2>, dim3(blocks), dim3(kWalkThreads), 0,
-                           (hipStream_t)stream, starts, directions, n, scale, depth, node_index,
-                           num_nodes, leaf_index, num_leaves, 0, (float*)nullptr,
-                           (int64_t*)nullptr, t_min, 0.0f, (float*)nullptr, (float*)nullptr,
-                           (uint8_t*)nullptr, first);
-    return check_launch("ffn_octree_render_volume_sh");
+    return launch_walk_sh<kVolumeSH1>(degree, who, walk,
+                                      volume_first_hit(rows, color, alpha, depth_out));
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

@@ -94,26 +94,26 @@ class _TotalVariation:
         return grad
 
 
-class OctreeField(_TotalVariation, torch.nn.Module):
-    """The leaf values of a baked tree as a parameter.  ``data`` (L,4) float32 ``[r, g, b, sigma]``
-    on the device, initialised from ``tree.leaf_data()``."""
+class _LeafField(_TotalVariation, torch.nn.Module):
+    """What ``OctreeField`` and ``OctreeSHField`` share: the tree, its centre and device, the
+    parameter ``data``, the differentiable ``forward`` and ``tree()``.  The subclass supplies the
+    rows of ``data``, ``sh_degree`` (None: plain leaves), the workspace, ``_render``, ``backward``,
+    ``_tv_weights``, ``_project`` and ``_file_layout``."""
 
-    def __init__(self, tree: OcTree, center=None, device=None):
+    def __init__(self, tree: OcTree, rows, sh_degree, center, device, workspace):
         super().__init__()
-        _refuse_sh(tree, "OctreeField")
-        tree._check_volume(0.0)
-        values = np.asarray(tree.leaf_data())[:, :4]      # further channels are never rendered
+        self.sh_degree = sh_degree
         if center is None:
             center = tree.center
         self.center = None if center is None else tuple(float(c) for c in center)
         if self.center is not None and len(self.center) != 3:
-            raise ValueError("OctreeField: center has three components")
+            raise ValueError("%s: center has three components" % type(self).__name__)
         if device is not None:
             tree._device = torch.device(device)
         self._tree = tree
         self.data = torch.nn.Parameter(torch.from_numpy(
-            np.ascontiguousarray(values, dtype=np.float32)).to(tree._dev()))
-        self.workspace = ops.OctreeGradWorkspace()
+            np.ascontiguousarray(rows, dtype=np.float32)).to(tree._dev()))
+        self.workspace = workspace
 
     def forward(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
                 min_transmittance: float = 0.0) -> RenderResult:
@@ -126,20 +126,43 @@ class OctreeField(_TotalVariation, torch.nn.Module):
         return RenderResult(*_RenderVolume.apply(self.data, self, starts, directions, float(t_min),
                                                  background, float(min_transmittance)))
 
+    def _geometry(self):
+        tree = self._tree
+        return (tree._scale, tree.depth, tree._on_device("node_index"),
+                tree._on_device("leaf_index"))
+
+    def tree(self) -> OcTree:
+        """A new ``OcTree`` (file layout) with the same ``sh_degree``, structure and centre and the
+        current data."""
+        old = self._tree
+        new = OcTree(old._scale, old._node_index, old._leaf_index,
+                     self._file_layout(self.data.detach().cpu().numpy()), self.sh_degree)
+        new._device = old._device
+        new._center = self.center
+        return new
+
+
+class OctreeField(_LeafField):
+    """The leaf values of a baked tree as a parameter.  ``data`` (L,4) float32 ``[r, g, b, sigma]``
+    on the device, initialised from ``tree.leaf_data()``."""
+
+    def __init__(self, tree: OcTree, center=None, device=None):
+        _refuse_sh(tree, "OctreeField")
+        tree._check_volume(0.0)
+        values = np.asarray(tree.leaf_data())[:, :4]      # further channels are never rendered
+        super().__init__(tree, values, None, center, device, ops.OctreeGradWorkspace())
+
     def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
                  min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
         """K17a + K17b: d(data) (L,4) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
-        tree = self._tree
         return ops.octree_render_volume_backward(
-            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
-            tree._on_device("leaf_index"), self.data.detach() if data is None else data, d_color,
-            d_alpha, float(t_min), background, float(min_transmittance), self.workspace, out)
+            starts, directions, *self._geometry(), self.data.detach() if data is None else data,
+            d_color, d_alpha, float(t_min), background, float(min_transmittance), self.workspace,
+            out)
 
     def _render(self, data, starts, directions, t_min, background, min_transmittance):
-        tree = self._tree
-        return ops.octree_render_volume(
-            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
-            tree._on_device("leaf_index"), data, t_min, background, min_transmittance)
+        return ops.octree_render_volume(starts, directions, *self._geometry(), data, t_min,
+                                        background, min_transmittance)
 
     def _tv_weights(self, weights):
         return ops.octree_tv_weights(weights, 4, None)
@@ -147,47 +170,36 @@ class OctreeField(_TotalVariation, torch.nn.Module):
     def _project(self, data):
         return ops.octree_project(data)
 
-    def tree(self) -> OcTree:
-        """A new ``OcTree`` with the same structure and centre and the current data."""
-        old = self._tree
-        new = OcTree(old._scale, old._node_index, old._leaf_index,
-                     self.data.detach().cpu().numpy().copy())
-        new._device = old._device
-        new._center = self.center
-        return new
+    def _file_layout(self, rows):
+        return rows.copy()
 
 
-class OctreeSHField(_TotalVariation, torch.nn.Module):
+class OctreeSHField(_LeafField):
     """The leaf values of an SH tree (``OcTree.bake_sh``) as a parameter.  ``data`` (L, stride)
     float32 on the device in the layout K18a reads (``ops.octree_sh_device_layout``:
     ``[sigma, k_r.., k_g.., k_b.., 0 ..]``), so that a step never repacks and Adam runs on the flat
     buffer; the padding has a zero gradient and stays zero."""
 
     def __init__(self, tree: OcTree, center=None, device=None):
-        super().__init__()
         if not isinstance(tree, OcTree) or tree.sh_degree is None:
             raise ValueError("OctreeSHField: the tree has no SH leaves (sh_degree is None); a plain "
                              "baked tree is fitted by OctreeField / fit_octree")
         tree._check_volume(0.0)
-        self.sh_degree = int(tree.sh_degree)
-        rows = ops.octree_sh_device_layout(np.asarray(tree.leaf_data()), self.sh_degree)
-        if center is None:
-            center = tree.center
-        self.center = None if center is None else tuple(float(c) for c in center)
-        if self.center is not None and len(self.center) != 3:
-            raise ValueError("OctreeSHField: center has three components")
-        if device is not None:
-            tree._device = torch.device(device)
-        self._tree = tree
-        self.data = torch.nn.Parameter(torch.from_numpy(rows).to(tree._dev()))
-        self.workspace = ops.OctreeGradSHWorkspace(self.sh_degree)
+        degree = int(tree.sh_degree)
+        rows = ops.octree_sh_device_layout(np.asarray(tree.leaf_data()), degree)
+        super().__init__(tree, rows, degree, center, device, ops.OctreeGradSHWorkspace(degree))
+
+    def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
+                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
+        """K19a + K19b: d(data) (L, stride) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
+        return ops.octree_render_volume_sh_backward(
+            starts, directions, *self._geometry(), self.data.detach() if data is None else data,
+            self.sh_degree, d_color, d_alpha, float(t_min), background, float(min_transmittance),
+            self.workspace, out)
 
     def _render(self, data, starts, directions, t_min, background, min_transmittance):
-        tree = self._tree
-        return ops.octree_render_volume_sh(
-            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
-            tree._on_device("leaf_index"), data, self.sh_degree, t_min, background,
-            min_transmittance)
+        return ops.octree_render_volume_sh(starts, directions, *self._geometry(), data,
+                                           self.sh_degree, t_min, background, min_transmittance)
 
     def _tv_weights(self, weights):
         return ops.octree_tv_weights(weights, int(self.data.shape[1]), self.sh_degree)
@@ -195,37 +207,8 @@ class OctreeSHField(_TotalVariation, torch.nn.Module):
     def _project(self, data):
         return ops.octree_project_sh(data, self.sh_degree)
 
-    def forward(self, starts, directions, t_min: float = 0.0, background=(0, 0, 0),
-                min_transmittance: float = 0.0) -> RenderResult:
-        """``tree.render_volume`` of the current data, bit for bit, as device tensors;
-        differentiable with respect to ``data`` (colour and alpha; depth has no gradient)."""
-        self._tree._check_volume(min_transmittance)
-        starts, directions, _ = self._tree._rays(starts, directions)
-        background = tuple(float(v) for v in background)
-        return RenderResult(*_RenderVolume.apply(self.data, self, starts, directions,
-                                                   float(t_min), background,
-                                                   float(min_transmittance)))
-
-    def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
-                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
-        """K19a + K19b: d(data) (L, stride) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
-        tree = self._tree
-        return ops.octree_render_volume_sh_backward(
-            starts, directions, tree._scale, tree.depth, tree._on_device("node_index"),
-            tree._on_device("leaf_index"), self.data.detach() if data is None else data,
-            self.sh_degree, d_color, d_alpha, float(t_min), background, float(min_transmittance),
-            self.workspace, out)
-
-    def tree(self) -> OcTree:
-        """A new SH ``OcTree`` (file layout) with the same ``sh_degree``, structure and centre and
-        the current data."""
-        old = self._tree
-        new = OcTree(old._scale, old._node_index, old._leaf_index,
-                     ops.octree_sh_file_layout(self.data.detach().cpu().numpy(), self.sh_degree),
-                     self.sh_degree)
-        new._device = old._device
-        new._center = self.center
-        return new
+    def _file_layout(self, rows):
+        return ops.octree_sh_file_layout(rows, self.sh_degree)
 
 
 def _validation_psnr(field, dataset, t_min, min_transmittance) -> float:

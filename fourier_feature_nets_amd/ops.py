@@ -679,6 +679,33 @@ def octree_render(starts: torch.Tensor, directions: torch.Tensor, scale: float, 
     return color, alpha, depth_out
 
 
+def _check_leaf_data(who, leaf_data, leaf_index):
+    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
+        raise ValueError("%s: leaf_data must be (num_leaves, C >= 4), got %s for %d leaves"
+                         % (who, tuple(leaf_data.shape), leaf_index.numel()))
+
+
+def _check_min_transmittance(who, min_transmittance):
+    if not 0.0 <= min_transmittance < 1.0:
+        raise ValueError("%s: min_transmittance must lie in [0, 1), got %r"
+                         % (who, min_transmittance,))
+
+
+def _render_volume(name, walk, t_min, leaf_block, background, min_transmittance, tail=()):
+    """A volume render through entry point ``name`` -> color (N,3), alpha (N), depth (N).
+    ``walk``: the arguments of ``_walk_args``; ``leaf_block()``: the leaf arguments after
+    ``t_min``; ``tail``: those after the outputs."""
+    n, dev = walk[0].shape[0], walk[0].device
+    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n > 0:
+        r, g, b = [float(v) for v in background]
+        _call(name, *_walk_args(*walk), c_f(t_min), *leaf_block(), c_f(r), c_f(g), c_f(b),
+              c_f(min_transmittance), _dev(color), _dev(alpha), _dev(depth_out), *tail)
+    return color, alpha, depth_out
+
+
 def octree_render_volume(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
                          node_index: torch.Tensor, leaf_index: torch.Tensor,
                          leaf_data: torch.Tensor, t_min: float = 0.0,
@@ -687,24 +714,12 @@ def octree_render_volume(starts: torch.Tensor, directions: torch.Tensor, scale: 
     them -> color (N,3), alpha (N), depth (N), composited front to back over the leaves every ray
     crosses after ``t_min``; the walk of a ray ends once its transmittance is at or below
     ``min_transmittance``."""
-    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
-        raise ValueError("octree render_volume: leaf_data must be (num_leaves, C >= 4), got %s "
-                         "for %d leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
-    if not 0.0 <= min_transmittance < 1.0:
-        raise ValueError("octree render_volume: min_transmittance must lie in [0, 1), got %r"
-                         % (min_transmittance,))
-    n = starts.shape[0]
-    dev = starts.device
-    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
-    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
-    if n > 0:
-        r, g, b = [float(v) for v in background]
-        _call("ffn_octree_render_volume", *_walk_args(starts, directions, scale, depth,
-                                                      node_index, leaf_index),
-              c_f(t_min), _dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1]), c_f(r),
-              c_f(g), c_f(b), c_f(min_transmittance), _dev(color), _dev(alpha), _dev(depth_out))
-    return color, alpha, depth_out
+    _check_leaf_data("octree render_volume", leaf_data, leaf_index)
+    _check_min_transmittance("octree render_volume", min_transmittance)
+    return _render_volume("ffn_octree_render_volume",
+                          (starts, directions, scale, depth, node_index, leaf_index), t_min,
+                          lambda: (_dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1])),
+                          background, min_transmittance)
 
 
 def octree_sh_channels(degree: int) -> int:
@@ -728,6 +743,17 @@ def octree_sh_device_layout(leaf_data: np.ndarray, degree: int) -> np.ndarray:
     return rows
 
 
+def _check_leaf_rows(who, leaf_rows, leaf_index, degree) -> int:
+    """SH rows in the device layout, one per leaf -> the channels of ``degree``."""
+    channels = octree_sh_channels(degree)
+    if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
+            or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
+        raise ValueError("%s: leaf_rows must be (num_leaves, stride) with stride a multiple of 4 "
+                         "and >= %d, got %s for %d leaves"
+                         % (who, channels, tuple(leaf_rows.shape), leaf_index.numel()))
+    return channels
+
+
 def octree_render_volume_sh(starts: torch.Tensor, directions: torch.Tensor, scale: float,
                             depth: int, node_index: torch.Tensor, leaf_index: torch.Tensor,
                             leaf_rows: torch.Tensor, degree: int, t_min: float = 0.0,
@@ -735,28 +761,12 @@ def octree_render_volume_sh(starts: torch.Tensor, directions: torch.Tensor, scal
     """K18a.  ``octree_render_volume`` with a view-dependent leaf colour: leaf_rows (L, stride)
     float32 in the device layout of ``octree_sh_device_layout`` -> color (N,3), alpha (N),
     depth (N)."""
-    channels = octree_sh_channels(degree)
-    if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
-            or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
-        raise ValueError("octree render_volume_sh: leaf_rows must be (num_leaves, stride) with "
-                         "stride a multiple of 4 and >= %d, got %s for %d leaves"
-                         % (channels, tuple(leaf_rows.shape), leaf_index.numel()))
-    if not 0.0 <= min_transmittance < 1.0:
-        raise ValueError("octree render_volume_sh: min_transmittance must lie in [0, 1), got %r"
-                         % (min_transmittance,))
-    n = starts.shape[0]
-    dev = starts.device
-    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
-    depth_out = torch.empty((n,), dtype=torch.float32, device=dev)
-    if n > 0:
-        r, g, b = [float(v) for v in background]
-        _call("ffn_octree_render_volume_sh", *_walk_args(starts, directions, scale, depth,
-                                                         node_index, leaf_index),
-              c_f(t_min), _dev(leaf_rows, name="leaf_rows"), c_i(channels), c_f(r), c_f(g),
-              c_f(b), c_f(min_transmittance), _dev(color), _dev(alpha), _dev(depth_out),
-              c_i(degree), c_i(leaf_rows.shape[1]))
-    return color, alpha, depth_out
+    channels = _check_leaf_rows("octree render_volume_sh", leaf_rows, leaf_index, degree)
+    _check_min_transmittance("octree render_volume_sh", min_transmittance)
+    return _render_volume("ffn_octree_render_volume_sh",
+                          (starts, directions, scale, depth, node_index, leaf_index), t_min,
+                          lambda: (_dev(leaf_rows, name="leaf_rows"), c_i(channels)), background,
+                          min_transmittance, (c_i(degree), c_i(leaf_rows.shape[1])))
 
 
 def octree_sh_accumulate(logits: torch.Tensor, leaf_data: torch.Tensor, weights, inv_views: float,
@@ -783,16 +793,20 @@ def octree_sh_accumulate(logits: torch.Tensor, leaf_data: torch.Tensor, weights,
     return leaf_data
 
 
+def _grad_workspace_bytes(name, *args):
+    fn = getattr(_lib.load(), name)
+    fn.restype = ctypes.c_int64
+    size = fn(*args)
+    if size < 0:
+        raise _lib.FfnError("%s failed: %s" % (name, _lib.load().ffn_last_error_string().decode()))
+    return int(size)
+
+
 def octree_grad_workspace_bytes(n: int, num_leaves: int, max_entries: int) -> int:
     """Bytes of workspace ``octree_render_volume_backward`` needs for ``n`` rays, ``num_leaves``
     leaves and up to ``max_entries`` (ray, taken leaf) pairs."""
-    fn = _lib.load().ffn_octree_grad_workspace_bytes
-    fn.restype = ctypes.c_int64
-    size = fn(c_i64(n), c_i64(num_leaves), c_i64(max_entries))
-    if size < 0:
-        raise _lib.FfnError("ffn_octree_grad_workspace_bytes failed: %s"
-                            % _lib.load().ffn_last_error_string().decode())
-    return int(size)
+    return _grad_workspace_bytes("ffn_octree_grad_workspace_bytes", c_i64(n), c_i64(num_leaves),
+                                 c_i64(max_entries))
 
 
 class OctreeGradWorkspace:
@@ -825,6 +839,47 @@ class OctreeGradWorkspace:
         self.shape = (n, num_leaves)
 
 
+def _render_volume_backward(name, walk, t_min, leaf_block, background, min_transmittance, grads,
+                            workspace, out, width, degree=None, tail=()):
+    """The backward of a volume render through entry point ``name``: the output (num_leaves,
+    ``width``), the call on ``workspace`` and, when the rays take more leaves than it holds, its
+    growth and ONE repeat.  ``walk``: the arguments of ``_walk_args``; ``leaf_block()``: the leaf
+    arguments after ``t_min``; ``tail``: those after ``entries``; ``degree``: of SH rows."""
+    who = "octree " + name[len("ffn_octree_"):]
+    starts, leaf_index = walk[0], walk[5]
+    d_color, d_alpha = grads
+    n, leaves = starts.shape[0], leaf_index.numel()
+    if d_color.shape != (n, 3) or d_alpha.shape != (n,):
+        raise ValueError("%s: d_color must be (N,3) and d_alpha (N,)" % who)
+    dev = starts.device
+    if out is None:
+        out = torch.empty((leaves, width), dtype=torch.float32, device=dev)
+    if out.shape != (leaves, width):
+        raise ValueError("%s: %s must be (num_leaves, %d)"
+                         % (who, "d_leaf_data" if degree is None else "d_leaf_rows", width))
+    if n == 0:
+        return out.zero_()
+    if degree is not None and getattr(workspace, "degree", None) != degree:
+        raise ValueError("%s: the workspace is not one of degree %d" % (who, degree))
+    r, g, b = [float(v) for v in background]
+    entries = c_i64(-1)
+    workspace.fit(n, leaves, dev)
+    for attempt in range(2):
+        try:
+            _call(name, *_walk_args(*walk), c_f(t_min), *leaf_block(), c_f(r), c_f(g), c_f(b),
+                  c_f(min_transmittance), _dev(d_color, name="d_color"),
+                  _dev(d_alpha, name="d_alpha"), _dev(workspace.buffer),
+                  c_i64(workspace.buffer.numel() * 4), c_i64(workspace.max_entries), _dev(out),
+                  ctypes.byref(entries), *tail)
+            break
+        except _lib.FfnError:
+            if attempt == 1 or entries.value <= workspace.max_entries:
+                raise
+            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
+    workspace.entries = int(entries.value)
+    return out
+
+
 def octree_render_volume_backward(starts: torch.Tensor, directions: torch.Tensor, scale: float,
                                   depth: int, node_index: torch.Tensor, leaf_index: torch.Tensor,
                                   leaf_data: torch.Tensor, d_color: torch.Tensor,
@@ -836,43 +891,16 @@ def octree_render_volume_backward(starts: torch.Tensor, directions: torch.Tensor
     d_leaf_data (L,4) float32 [d r, d g, d b, d sigma], every row written, deterministic (no float
     atomics).  One read-back (the number of (ray, taken leaf) pairs) per call; when the workspace
     turns out too small for them it is grown and the call repeated."""
-    if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
-        raise ValueError("octree render_volume_backward: leaf_data must be (num_leaves, C >= 4), "
-                         "got %s for %d leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
-    if not 0.0 <= min_transmittance < 1.0:
-        raise ValueError("octree render_volume_backward: min_transmittance must lie in [0, 1), "
-                         "got %r" % (min_transmittance,))
-    n, leaves = starts.shape[0], leaf_index.numel()
-    if d_color.shape != (n, 3) or d_alpha.shape != (n,):
-        raise ValueError("octree render_volume_backward: d_color must be (N,3) and d_alpha (N,)")
-    dev = starts.device
-    if d_leaf_data is None:
-        d_leaf_data = torch.empty((leaves, 4), dtype=torch.float32, device=dev)
-    if d_leaf_data.shape != (leaves, 4):
-        raise ValueError("octree render_volume_backward: d_leaf_data must be (num_leaves, 4)")
-    if n == 0:
-        return d_leaf_data.zero_()
+    who = "octree render_volume_backward"
+    _check_leaf_data(who, leaf_data, leaf_index)
+    _check_min_transmittance(who, min_transmittance)
     if workspace is None:
         workspace = OctreeGradWorkspace()
-    r, g, b = [float(v) for v in background]
-    entries = c_i64(-1)
-    workspace.fit(n, leaves, dev)
-    for attempt in range(2):
-        try:
-            _call("ffn_octree_render_volume_backward",
-                  *_walk_args(starts, directions, scale, depth, node_index, leaf_index),
-                  c_f(t_min), _dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1]), c_f(r),
-                  c_f(g), c_f(b), c_f(min_transmittance), _dev(d_color, name="d_color"),
-                  _dev(d_alpha, name="d_alpha"), _dev(workspace.buffer),
-                  c_i64(workspace.buffer.numel() * 4), c_i64(workspace.max_entries),
-                  _dev(d_leaf_data), ctypes.byref(entries))
-            break
-        except _lib.FfnError:
-            if attempt == 1 or entries.value <= workspace.max_entries:
-                raise
-            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
-    workspace.entries = int(entries.value)
-    return d_leaf_data
+    return _render_volume_backward(
+        "ffn_octree_render_volume_backward",
+        (starts, directions, scale, depth, node_index, leaf_index), t_min,
+        lambda: (_dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1])), background,
+        min_transmittance, (d_color, d_alpha), workspace, d_leaf_data, 4)
 
 
 def octree_project(leaf_data: torch.Tensor) -> torch.Tensor:
@@ -902,13 +930,8 @@ def octree_sh_file_layout(leaf_rows: np.ndarray, degree: int) -> np.ndarray:
 def octree_grad_sh_workspace_bytes(n: int, num_leaves: int, max_entries: int, degree: int) -> int:
     """Bytes of workspace ``octree_render_volume_sh_backward`` needs for ``n`` rays, ``num_leaves``
     leaves and up to ``max_entries`` (ray, taken leaf) pairs at ``degree``."""
-    fn = _lib.load().ffn_octree_grad_sh_workspace_bytes
-    fn.restype = ctypes.c_int64
-    size = fn(c_i64(n), c_i64(num_leaves), c_i64(max_entries), c_i(degree))
-    if size < 0:
-        raise _lib.FfnError("ffn_octree_grad_sh_workspace_bytes failed: %s"
-                            % _lib.load().ffn_last_error_string().decode())
-    return int(size)
+    return _grad_workspace_bytes("ffn_octree_grad_sh_workspace_bytes", c_i64(n), c_i64(num_leaves),
+                                 c_i64(max_entries), c_i(degree))
 
 
 class OctreeGradSHWorkspace(OctreeGradWorkspace):
@@ -935,50 +958,17 @@ def octree_render_volume_sh_backward(starts: torch.Tensor, directions: torch.Ten
     d_leaf_rows (L, stride) float32 in the device layout of ``leaf_rows`` [d sigma, d k_r..,
     d k_g.., d k_b.., 0 ..], every row written, deterministic (no float atomics).  The read-back and
     the grow-and-repeat of the workspace are those of ``octree_render_volume_backward``."""
-    channels = octree_sh_channels(degree)
-    if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
-            or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
-        raise ValueError("octree render_volume_sh_backward: leaf_rows must be (num_leaves, stride) "
-                         "with stride a multiple of 4 and >= %d, got %s for %d leaves"
-                         % (channels, tuple(leaf_rows.shape), leaf_index.numel()))
-    if not 0.0 <= min_transmittance < 1.0:
-        raise ValueError("octree render_volume_sh_backward: min_transmittance must lie in [0, 1), "
-                         "got %r" % (min_transmittance,))
-    n, leaves, stride = starts.shape[0], leaf_index.numel(), leaf_rows.shape[1]
-    if d_color.shape != (n, 3) or d_alpha.shape != (n,):
-        raise ValueError("octree render_volume_sh_backward: d_color must be (N,3) and d_alpha (N,)")
-    dev = starts.device
-    if d_leaf_rows is None:
-        d_leaf_rows = torch.empty((leaves, stride), dtype=torch.float32, device=dev)
-    if d_leaf_rows.shape != (leaves, stride):
-        raise ValueError("octree render_volume_sh_backward: d_leaf_rows must be (num_leaves, %d)"
-                         % stride)
-    if n == 0:
-        return d_leaf_rows.zero_()
+    who = "octree render_volume_sh_backward"
+    _check_leaf_rows(who, leaf_rows, leaf_index, degree)
+    _check_min_transmittance(who, min_transmittance)
     if workspace is None:
         workspace = OctreeGradSHWorkspace(degree)
-    if getattr(workspace, "degree", None) != degree:
-        raise ValueError("octree render_volume_sh_backward: the workspace is not one of degree %d"
-                         % degree)
-    r, g, b = [float(v) for v in background]
-    entries = c_i64(-1)
-    workspace.fit(n, leaves, dev)
-    for attempt in range(2):
-        try:
-            _call("ffn_octree_render_volume_sh_backward",
-                  *_walk_args(starts, directions, scale, depth, node_index, leaf_index),
-                  c_f(t_min), _dev(leaf_rows, name="leaf_rows"), c_f(r), c_f(g), c_f(b),
-                  c_f(min_transmittance), _dev(d_color, name="d_color"),
-                  _dev(d_alpha, name="d_alpha"), _dev(workspace.buffer),
-                  c_i64(workspace.buffer.numel() * 4), c_i64(workspace.max_entries),
-                  _dev(d_leaf_rows), ctypes.byref(entries), c_i(degree), c_i(stride))
-            break
-        except _lib.FfnError:
-            if attempt == 1 or entries.value <= workspace.max_entries:
-                raise
-            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
-    workspace.entries = int(entries.value)
-    return d_leaf_rows
+    return _render_volume_backward(
+        "ffn_octree_render_volume_sh_backward",
+        (starts, directions, scale, depth, node_index, leaf_index), t_min,
+        lambda: (_dev(leaf_rows, name="leaf_rows"),), background, min_transmittance,
+        (d_color, d_alpha), workspace, d_leaf_rows, leaf_rows.shape[1], degree,
+        (c_i(degree), c_i(leaf_rows.shape[1])))
 
 
 def octree_project_sh(leaf_rows: torch.Tensor, degree: int) -> torch.Tensor:

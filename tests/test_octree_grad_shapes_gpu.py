@@ -271,3 +271,26 @@ def test_exact_workspace_and_refusal():
                   _lib.c_i64(ws.max_entries), ops._dev(out), ctypes.byref(told))
     assert told.value == entries
     assert (out.cpu().numpy() == 7.0).all()                   # nothing was written
+
+
+# (n, num_leaves, max_entries) -> bytes for plain leaves, SH degree 1, SH degree 2: what the library
+# returned before the two layout tables became one.  Host arithmetic only; a change of any buffer's
+# size, presence or alignment shows here without a fault.
+WORKSPACE_BYTES = {
+    (1, 1, 0): (1536, 2304, 2304),
+    (64, 8, 1024): (52480, 50176, 56832),
+    (1000, 64, 2000): (119808, 120832, 139264),
+    (4096, 100000, 1 << 17): (7305216, 19981568, 30368000),
+    (4097, 100001, (1 << 17) + 1): (7308288, 19984640, 30371072),
+}
+
+
+@pytest.mark.parametrize("shape", sorted(WORKSPACE_BYTES))
+@pytest.mark.parametrize("degree", [0, 1, 2])
+def test_workspace_bytes_are_the_recorded_ones(shape, degree):
+    from fourier_feature_nets_amd import ops
+    if degree == 0:
+        got = ops.octree_grad_workspace_bytes(*shape)
+    else:
+        got = ops.octree_grad_sh_workspace_bytes(*shape, degree)
+    assert got == WORKSPACE_BYTES[shape][degree]
