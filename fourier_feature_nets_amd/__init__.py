@@ -10,8 +10,9 @@ from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
-from .octree import OcTree
-from .octree_fit import FitLogEntry, OctreeField, OctreeSHField, fit_octree, fit_octree_sh
+from .octree import OcTree, refine_actions
+from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, fit_octree,
+                         fit_octree_adaptive, fit_octree_sh, leaf_weights_over)
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
@@ -39,6 +40,7 @@ __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RegressionEngine",
+           "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
-           "exponential_lr_decay", "fit_octree", "fit_octree_sh", "linspace", "load_model", "orbit"]
+           "exponential_lr_decay", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
+           "linspace", "load_model", "orbit", "refine_actions"]

@@ -495,6 +495,57 @@ merge_scatter_kernel(const uint8_t* __restrict__ flags, const int* __restrict__ 
     data_out[o] = head ? sibling_mean(data + i) : data[i];
 }
 
+// ------------------------------------------------------------------------------- K21b
+// A fitted tree rebuilt from one decision per leaf: 0 drop, 1 keep, 2 split into its eight children,
+// which take the leaf's row.  No reference counterpart (its prune merges the deepest level only).
+//
+// Leaves come in path-code order, and that order survives: a leaf replaced in place by its children in
+// child order 4 bx + 2 by + bz stays sorted.  Leaf i owns the eight SLOTS 8 i .. 8 i + 7; a keep sets
+// the flag of slot 8 i, a split all eight, so the K12b/c flag scan over the 8 L slots gives every
+// output leaf its place and *total the new leaf count, without an atomic and without a search for the
+// source leaf of an output leaf.  An action above 2 sets no flag here; the caller refuses it.
+__global__ void __launch_bounds__(kOctThreads)
+refine_flags_kernel(const uint8_t* __restrict__ action, int64_t slots, uint8_t* __restrict__ flags) {
+    const int64_t t = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (t >= slots) return;
+    const uint8_t a = action[t >> 3];
+    flags[t] = a == 2 || (a == 1 && (t & 7) == 0);
+}
+
+// one thread per (slot, chunk of four row values); a set slot is an output leaf.  Chunk 0 also writes
+// the leaf's id and where it came from.  The row is moved as integers, bit for bit: 16 bytes at a time
+// when kVector (channels a multiple of 4, both arrays 16-byte aligned), word by word otherwise (the
+// file-layout SH rows have 13 and 28 channels, and a sliced array need not be aligned).
+template <bool kVector>
+__global__ void __launch_bounds__(kOctThreads)
+refine_scatter_kernel(const uint8_t* __restrict__ action, const uint8_t* __restrict__ flags,
+                      const int* __restrict__ offsets, const int64_t* __restrict__ leaf_ids,
+                      const uint32_t* __restrict__ rows, int64_t slots, int channels, int chunks,
+                      int64_t out_leaves, int64_t* __restrict__ ids_out,
+                      uint32_t* __restrict__ rows_out, int32_t* __restrict__ parent) {
+    const int64_t t = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
+    if (t >= slots * chunks) return;
+    const int64_t slot = t / chunks;
+    const int chunk = (int)(t - slot * chunks);
+    if (!flags[slot]) return;
+    const int64_t o = offsets[slot];
+    if (o >= out_leaves) return;   // the caller sized the outputs by the scan's total: never taken
+    const int64_t leaf = slot >> 3;
+    if (chunk == 0) {
+        const int64_t id = leaf_ids[leaf];
+        ids_out[o] = action[leaf] == 2 ? 8 * id + 1 + (slot & 7) : id;
+        parent[o] = (int32_t)leaf;
+    }
+    if (kVector) {
+        // chunk < channels / 4 here (chunks == channels / 4 >= 1)
+        reinterpret_cast<uint4*>(rows_out)[o * chunks + chunk] =
+            reinterpret_cast<const uint4*>(rows)[leaf * chunks + chunk];
+    } else {
+        const int end = min(4 * chunk + 4, channels);
+        for (int c = 4 * chunk; c < end; ++c) rows_out[o * channels + c] = rows[leaf * channels + c];
+    }
+}
+
 // composite.hip: activations and sigma * side > tau of one chunk
 void launch_octree_density_flags(const float* logits, int64_t count, float tau, float side,
                                  float* activated, uint8_t* flags, hipStream_t stream);
@@ -508,6 +559,8 @@ static const int64_t kOctMaxPoints = ((int64_t)1 << 31) - kScanTile;
 extern "C" int64_t ffn_octree_scan_tiles(int64_t n) { return n < 0 ? -1 : scan_tiles(n); }
 
 extern "C" int ffn_octree_max_depth(void) { return kOctMaxDepth; }
+
+extern "C" int64_t ffn_octree_max_points(void) { return kOctMaxPoints; }
 
 extern "C" int ffn_octree_surface_points(const float* alpha, const float* depth, const float* starts,
                                          const float* directions, const float* color, int64_t n,
@@ -690,4 +743,47 @@ extern "C" int ffn_octree_merge_level(const int* codes, const int* levels, const
     hipLaunchKernelGGL(merge_scatter_kernel, grid, block, 0, s, flags, offsets, merge, codes, levels,
                        (const float4*)data, n, codes_out, levels_out, (float4*)data_out);
     return check_launch("ffn_octree_merge_level");
+}
+
+extern "C" int ffn_octree_refine_count(const uint8_t* action, int64_t num_leaves, uint8_t* flags,
+                                       int* offsets, int* tile_sums, int* total, void* stream) {
+    if (num_leaves < 1 || num_leaves > kOctMaxPoints / 8)
+        return fail_arg("ffn_octree_refine_count: shape (1 <= num_leaves, 8 num_leaves < 2^31)");
+    if (!action || !flags || !offsets || !tile_sums || !total)
+        return fail_arg("ffn_octree_refine_count: null argument");
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t slots = 8 * num_leaves;
+    hipLaunchKernelGGL(refine_flags_kernel, dim3(oct_blocks(slots)), dim3(kOctThreads), 0, s, action,
+                       slots, flags);
+    return scan_flags(flags, slots, tile_sums, offsets, total, s);
+}
+
+extern "C" int ffn_octree_refine_scatter(const uint8_t* action, const uint8_t* flags,
+                                         const int* offsets, const int64_t* leaf_ids,
+                                         const float* rows, int64_t num_leaves, int channels,
+                                         int64_t out_leaves, int64_t* ids_out, float* rows_out,
+                                         int32_t* parent, void* stream) {
+    if (num_leaves < 1 || num_leaves > kOctMaxPoints / 8 || channels < 0 || channels > 1024 ||
+        out_leaves < 1 || out_leaves > 8 * num_leaves)
+        return fail_arg("ffn_octree_refine_scatter: shape (1 <= num_leaves, 8 num_leaves < 2^31, "
+                        "0 <= channels <= 1024, 1 <= out_leaves <= 8 num_leaves)");
+    if (!action || !flags || !offsets || !leaf_ids || !ids_out || !parent ||
+        (channels > 0 && (!rows || !rows_out)))
+        return fail_arg("ffn_octree_refine_scatter: null argument");
+    const bool vector = channels > 0 && channels % 4 == 0 && !misaligned16(rows, rows_out);
+    const int chunks = channels == 0 ? 1 : (channels + 3) / 4;
+    const int64_t slots = 8 * num_leaves;
+    const int64_t blocks = (slots * chunks + kOctThreads - 1) / kOctThreads;
+    if (blocks >= ((int64_t)1 << 31) / kOctThreads * 2)      // blocks * threads < 2^32
+        return fail_arg("ffn_octree_refine_scatter: 8 num_leaves * ceil(channels / 4) < 2^32");
+    const hipStream_t s = (hipStream_t)stream;
+    if (vector)
+        hipLaunchKernelGGL(refine_scatter_kernel<true>, dim3((unsigned)blocks), dim3(kOctThreads), 0,
+                           s, action, flags, offsets, leaf_ids, (const uint32_t*)rows, slots,
+                           channels, chunks, out_leaves, ids_out, (uint32_t*)rows_out, parent);
+    else
+        hipLaunchKernelGGL(refine_scatter_kernel<false>, dim3((unsigned)blocks), dim3(kOctThreads),
+                           0, s, action, flags, offsets, leaf_ids, (const uint32_t*)rows, slots,
+                           channels, chunks, out_leaves, ids_out, (uint32_t*)rows_out, parent);
+    return check_launch("ffn_octree_refine_scatter");
 }

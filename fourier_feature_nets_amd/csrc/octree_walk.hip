@@ -96,6 +96,26 @@
 // 0 bytes of LDS, occupancy 7 / 5 waves per SIMD (kGradSH1 is held to 7 by its 102 SGPRs; the whole row is held as in K18a: 7 16-byte loads at
 // degree 2; it did not need to be consumed channel by channel).  The seven older instantiations
 // compile to the instructions they had before (38 / 40 / 50 / 53 / 61 / 56 / 72 VGPRs).
+//
+// K21a  Per-leaf maximum weight: a tenth mode (kLeafWeight).  K15's walk without its colours and without
+// any per-ray output: the taken-leaf rule, t0, the chord, sigma = max(density, 0), a, w = T a, T and the
+// early end are K15's operations in K15's order, so w has the bits K15 composites with.  The density is
+// read alone, at first.shading floats into a row of first.channels floats (3 of 4 on plain rows, 0 of
+// 16 / 28 on the SH device layout): one mode serves plain and SH trees.  Per taken leaf with w > 0 the
+// walk raises weights[leaf] to w.  weights holds f32 bit patterns as uint32: for w >= 0 the pattern is
+// monotone in w, so the maximum is an INTEGER atomicMax -- exact, and independent of the order of the
+// rays and of how they are split over calls (no float atomic, the same bits every call).  The atomic
+// returns nothing to the lane and sits off the dependent chain of the binary searches.  Contention: the
+// lanes of a wave are neighbouring rays and often sit in the same leaf, and a leaf in front of the
+// camera is hit by thousands of rays; same-address atomics are serialised in L2.  A plain load comes
+// first and the atomic is skipped when the stored value is already >= w: after the first few rays a
+// hot leaf costs a cached load.  The load may be stale (a value only grows), which can only send an
+// atomic that changes nothing: the result does not depend on the shortcut.
+// The idle parameters carry its buffers, as for kGrad: span_hit the uint32 weights, first.shading the
+// density's offset in a row.
+// Resource report, kLeafWeight: 39 VGPRs, 80 SGPRs, 0 bytes of scratch, 0 spills,
+// 0 bytes of LDS, occupancy 8 waves per SIMD; the nine older instantiations compile to the
+// instructions they had before (38 / 40 / 50 / 53 / 61 / 56 / 72 / 64 / 82 VGPRs).
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
@@ -191,7 +211,7 @@ struct FirstHit {
 };
 
 enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
-                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8 };
+                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
@@ -206,6 +226,9 @@ enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVo
 //            float4 values and leaves their int32 leaf numbers.
 // kGradSH1 / kGradSH2: K19a, kGrad with the leaf colour of K18a.  As kGrad, and first.leaf carries
 //            the entries' int32 ray numbers; first.leaf_data / first.channels as kVolumeSH*.
+// kLeafWeight: K21a.  span_hit the (num_leaves) uint32 weights (f32 bit patterns, raised, never
+//            lowered), first.leaf_data / first.channels rows and their stride, first.shading the
+//            density's offset in a row.  Nothing is written per ray.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -258,7 +281,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad
+    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad || kMode == kLeafWeight
                            ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
@@ -267,6 +290,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     float4* entry_values = reinterpret_cast<float4*>(t_stops);
     int32_t* entry_leaves = reinterpret_cast<int32_t*>(leaves);
     int32_t* entry_rays = reinterpret_cast<int32_t*>(first.leaf);        // K19a
+    unsigned* leaf_weights = reinterpret_cast<unsigned*>(span_hit);      // K21a
     int taken = 0, base = 0, mine = 0;
     float c_r = 0.0f, c_g = 0.0f, c_b = 0.0f, t_end = 0.0f, g_r = 0.0f, g_g = 0.0f, g_b = 0.0f,
           g_a = 0.0f;
@@ -445,6 +469,21 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 ++taken;
                 if (trans <= first.min_transmittance) break;
             }
+        } else if (kMode == kLeafWeight) {
+            if (leaf >= 0 && t_exit > t_min) {
+                const float ls = first.leaf_data[leaf * first.channels + first.shading];
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                if (w > 0.0f) {                                // a NaN w fails too
+                    const unsigned bits = __float_as_uint(w);
+                    if (leaf_weights[leaf] < bits) atomicMax(leaf_weights + leaf, bits);
+                }
+                trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
         } else if (kSpans) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (!any_leaf) first_in = t > t_min ? t : t_min;
@@ -506,6 +545,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
             first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
             first.alpha[r] = trans;
         }
+    } else if (kMode == kLeafWeight) {
+        // nothing per ray
     } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
         const float side = 2.0f * scale / (float)cells;
@@ -707,6 +748,25 @@ extern "C" int ffn_octree_render_volume_sh(const float* starts, const float* dir
         return fail_arg("ffn_octree_render_volume_sh: leaf_data must be 16-byte aligned");
     return launch_walk_sh<kVolumeSH1>(degree, who, walk,
                                       volume_first_hit(rows, color, alpha, depth_out));
+}
+
+extern "C" int ffn_octree_leaf_weights(const float* starts, const float* directions, int64_t n,
+                                       float scale, int depth, const int64_t* node_index,
+                                       int64_t num_nodes, const int64_t* leaf_index,
+                                       int64_t num_leaves, float t_min, const float* leaf_data,
+                                       int stride, int sigma_offset, float min_transmittance,
+                                       uint32_t* weights, void* stream) {
+    const char* who = "ffn_octree_leaf_weights";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
+    const VolumeLeaves rows{leaf_data, stride, 0, 0.0f, 0.0f, 0.0f, min_transmittance};
+    if (stride < 1 || sigma_offset < 0 || sigma_offset >= stride)
+        return fail_arg("ffn_octree_leaf_weights: stride >= 1, 0 <= sigma_offset < stride");
+    if (int err = check_volume_args(who, walk, rows, !weights)) return err;
+    FirstHit first = volume_first_hit(rows, nullptr, nullptr, nullptr);
+    first.shading = sigma_offset;
+    return launch_walk<kLeafWeight>(who, walk, first, 0, nullptr, nullptr, 0.0f, nullptr, nullptr,
+                                    (uint8_t*)weights);
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

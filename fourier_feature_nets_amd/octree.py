@@ -66,8 +66,19 @@ public signatures are the reference's, so files and calling code go both ways.  
 
 * fitting lives in ``octree_fit.py`` (K17): ``OctreeField`` makes the leaf values of a baked tree a
   parameter whose forward is ``render_volume`` bit for bit and whose backward is the gradient walk
-  plus deterministic per-leaf sums; ``fit_octree`` optimises them against a dataset's images.  The
-  structure of the tree is not changed.  No counterpart in the reference.
+  plus deterministic per-leaf sums; ``fit_octree`` optimises them against a dataset's images.  A
+  fit keeps the structure of the tree; ``leaf_weights`` / ``refine`` (K21) change it between fits.
+  No counterpart in the reference.
+
+* ``leaf_weights`` / ``refine`` / ``refine_actions`` (K21) have none either (the reference's ``prune``,
+  kept as it is, merges the deepest level into its parents).  ``leaf_weights`` measures per leaf the
+  largest compositing weight ``w = T a`` any ray of a set gives it, on ``render_volume``'s own walk
+  (an integer maximum over f32 bit patterns: the same bits for the same rays in any order, in one
+  call or many).  ``refine`` rebuilds the tree from one decision per leaf -- drop, keep, split into
+  eight children that inherit the leaf's row bit for bit -- and says where every new leaf came
+  from; ``refine_actions`` is the threshold policy between the two.  Splitting changes no render
+  beyond rounding: ``exp(-s L1) exp(-s L2) = exp(-s (L1 + L2))``.  ``octree_fit.fit_octree_adaptive``
+  alternates fitting and refining.
 
 * ``neighbors`` / ``total_variation`` (K20) have none either: the face adjacency of the sparse tree
   (per leaf and direction the leaf of equal size or coarser on the other side; finer neighbours hold
@@ -78,7 +89,8 @@ public signatures are the reference's, so files and calling code go both ways.  
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
 ``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers``, ``leaf_depths``,
-``neighbors`` and ``total_variation`` run on the GPU and raise without one.
+``neighbors``, ``total_variation``, ``leaf_weights`` and ``refine`` run on the GPU and raise without
+one; ``refine_actions`` is numpy.
 """
 
 import os
@@ -150,6 +162,38 @@ def sh_basis(directions, degree: int) -> np.ndarray:
         out[:, 7] = -SH_Y2[0] * x * z
         out[:, 8] = SH_Y2[2] * (x * x - y * y)
     return out
+
+
+def refine_actions(weights, depths, prune_below: float = 1e-2, split_above=1e-1,
+                   max_depth: Optional[int] = None) -> np.ndarray:
+    """The threshold policy of K21, pure numpy: per leaf 0 (drop) where ``weight < prune_below``,
+    2 (split) where ``weight >= split_above`` and ``depth < max_depth - 1``, 1 (keep) otherwise ->
+    (L,) uint8 for ``OcTree.refine``.  ``weights`` (L,) from ``OcTree.leaf_weights``, ``depths`` (L,)
+    from ``leaf_depths()`` (the root has depth 0).  ``max_depth`` is the depth the refined tree may
+    reach, at most and by default ``ops.octree_max_depth()``: a leaf at level ``max_depth - 1`` is
+    kept, not split.  ``split_above=None`` never splits; ``prune_below > split_above`` raises (a leaf
+    could be asked to go and to split).  A NaN weight is kept.  The defaults 1e-2 / 1e-1 are
+    starting values and UNTUNED."""
+    weights = np.asarray(weights, dtype=np.float64).reshape(-1)
+    depths = np.asarray(depths).reshape(-1)
+    if weights.shape != depths.shape:
+        raise ValueError("refine_actions: weights %s and depths %s must have one entry per leaf"
+                         % (weights.shape, depths.shape))
+    prune_below = float(prune_below)
+    limit = ops.octree_max_depth()       # a host function of the library: no GPU needed
+    max_depth = limit if max_depth is None else int(max_depth)
+    if max_depth < 1 or max_depth > limit:
+        raise ValueError("refine_actions: max_depth %d is outside what the path codes hold "
+                         "(1 .. %d)" % (max_depth, limit))
+    if prune_below != prune_below or (split_above is not None and not
+                                      prune_below <= float(split_above)):       # NaN fails too
+        raise ValueError("refine_actions: prune_below %r must not exceed split_above %r"
+                         % (prune_below, split_above))
+    action = np.full(weights.shape, ops.OCTREE_KEEP, np.uint8)
+    if split_above is not None:
+        action[(weights >= float(split_above)) & (depths < max_depth - 1)] = ops.OCTREE_SPLIT
+    action[weights < prune_below] = ops.OCTREE_DROP
+    return action
 
 
 Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
@@ -490,24 +534,21 @@ class OcTree:
             raise ValueError("OcTree.render: leaf_data must be (num_leaves, C >= 3) to hold a "
                              "colour, got %s" % (np.shape(data),))
 
-    def _check_volume(self, min_transmittance):
+    def _check_volume(self, min_transmittance, who="OcTree.render_volume"):
         data = self._leaf_data
         if data is None:
-            raise ValueError("OcTree.render_volume: the tree has no leaf_data to composite "
-                             "(see OcTree.bake)")
+            raise ValueError("%s: the tree has no leaf_data to composite (see OcTree.bake)" % who)
         if np.ndim(data) != 2 or np.shape(data)[1] < 4:
-            raise ValueError("OcTree.render_volume: leaf_data must be (num_leaves, C >= 4) to "
-                             "hold a colour and a density, got %s (see OcTree.bake)"
-                             % (np.shape(data),))
+            raise ValueError("%s: leaf_data must be (num_leaves, C >= 4) to hold a colour and a "
+                             "density, got %s (see OcTree.bake)" % (who, np.shape(data),))
         if not 0.0 <= float(min_transmittance) < 1.0:        # NaN fails too
-            raise ValueError("OcTree.render_volume: min_transmittance must lie in [0, 1), got %r"
-                             % (min_transmittance,))
+            raise ValueError("%s: min_transmittance must lie in [0, 1), got %r"
+                             % (who, min_transmittance,))
         if self._sh_degree is not None:
             channels = 3 * _sh_bases(self._sh_degree) + 1
             if np.shape(data)[1] != channels:
-                raise ValueError("OcTree.render_volume: sh_degree %d needs leaf_data of shape "
-                                 "(num_leaves, %d), got %s" % (self._sh_degree, channels,
-                                                               np.shape(data)))
+                raise ValueError("%s: sh_degree %d needs leaf_data of shape (num_leaves, %d), got "
+                                 "%s" % (who, self._sh_degree, channels, np.shape(data)))
 
     def _sh_rows_on_device(self) -> torch.Tensor:
         """The SH ``leaf_data`` in the layout K18a reads (``ops.octree_sh_device_layout``: density
@@ -578,6 +619,79 @@ class OcTree:
             self._on_device("leaf_index"), self._colors_on_device(), float(t_min), background,
             float(min_transmittance)))
         return out.numpy() if as_numpy else out
+
+    def leaf_weights(self, starts, directions, t_min: float = 0.0, min_transmittance: float = 0.0,
+                     out=None):
+        """Per leaf the largest compositing weight ``w = T * a`` that any of the rays gives it
+        (K21a), on the walk and with the operations of ``render_volume``: 0 for a leaf no ray takes,
+        that lies behind the ``min_transmittance`` cut of every ray, or whose density is 0, negative
+        or NaN.  Works on plain and SH trees alike (the weight does not depend on colour).  Inputs as
+        for ``render_volume``; -> (L,) float32, numpy for numpy rays.  With ``out`` (a (L,) float32
+        device tensor, as a call with device rays returns) the maxima fold into it: the same rays
+        give the same bits in any order, in one call or many."""
+        self._check_volume(min_transmittance, "OcTree.leaf_weights")   # before any device is needed
+        starts, directions, as_numpy = self._rays(starts, directions)
+        if self._sh_degree is not None:
+            rows, offset = self._sh_rows_on_device(), 0
+        else:
+            rows, offset = self._colors_on_device(), 3
+        weights = ops.octree_leaf_weights(
+            starts, directions, self._scale, self.depth, self._on_device("node_index"),
+            self._on_device("leaf_index"), rows, int(rows.shape[1]), offset, float(t_min),
+            float(min_transmittance), out)
+        return weights.cpu().numpy() if as_numpy else weights
+
+    def refine(self, action) -> Tuple["OcTree", np.ndarray]:
+        """A NEW tree from one decision per leaf (K21b): ``action`` (L,) with 0 drop, 1 keep, 2 split
+        into the eight children, which inherit the leaf's ``leaf_data`` row bit for bit (see
+        ``refine_actions``).  -> ``(tree, parent)``; ``parent`` (L',) int64 numpy is the number of
+        the leaf of THIS tree that a new leaf is or came from.  ``leaf_data`` (or its absence),
+        ``sh_degree``, ``scale``, the centre and the device carry over; caches start empty.  All ones
+        gives this tree's ``node_index``, ``leaf_index`` and ``leaf_data`` again.  Interior nodes
+        whose leaves are all dropped go with them.  Raises ``ValueError`` when no leaf would be
+        left, when a leaf at level ``ops.octree_max_depth() - 1`` is to split (the ray walk holds
+        11 levels), for an action of the wrong length or with a value above 2, and when the new
+        leaf count could reach 2^31.  This tree is not modified."""
+        action = np.asarray(action)
+        if action.dtype.kind not in "iub":
+            raise ValueError("OcTree.refine: action holds the integers 0, 1, 2, got dtype %s"
+                             % action.dtype)
+        ops.octree_refine_check_action(action, self.num_leaves)
+        if len(action) and (int(action.max()) > ops.OCTREE_SPLIT or int(action.min()) < 0):
+            raise ValueError("OcTree.refine: an action is 0 (drop), 1 (keep) or 2 (split), got "
+                             "values in [%d, %d]" % (int(action.min()), int(action.max())))
+        if not (action != ops.OCTREE_DROP).any():
+            raise ValueError("OcTree.refine: the action leaves no leaf; a tree needs at least one")
+        split = action == ops.OCTREE_SPLIT
+        if split.any():
+            deepest = int(_id_depths(self._leaf_index[split]).max())
+            limit = ops.octree_max_depth()
+            if deepest >= limit - 1:
+                raise ValueError("OcTree.refine: a leaf at level %d cannot split: the tree would be "
+                                 "deeper than the ray walk's limit of %d levels "
+                                 "(octree_max_depth())" % (deepest, limit))
+        dev = self._dev()
+        rows = None
+        data = self._leaf_data
+        if data is not None:
+            data = np.ascontiguousarray(data)
+            # (K21b moves float32 rows; anything else, a float64 file of the reference say, is
+            # gathered on the host by ``parent`` below)
+            if data.dtype == np.float32 and data.ndim == 2 and len(data) == self.num_leaves:
+                rows = torch.from_numpy(data).to(dev)
+        leaf_ids, node_ids, rows, parent = ops.octree_refine(
+            self._on_device("leaf_index"), rows,
+            torch.from_numpy(np.ascontiguousarray(action, dtype=np.uint8)).to(dev), self.depth)
+        parent = parent.cpu().numpy().astype(np.int64)
+        if rows is not None:
+            data = rows.cpu().numpy()
+        elif data is not None:
+            data = data[parent]
+        tree = OcTree(self._scale, node_ids.cpu().numpy(), leaf_ids.cpu().numpy(), data,
+                      self._sh_degree)
+        tree._device = self._device
+        tree._center = self._center
+        return tree, parent
 
     def bake(self, model, center=None, view=(0, 0, 1), batch_size: int = 1 << 20) -> "OcTree":
         """A NEW tree of the same structure and centre whose ``leaf_data`` (L,4) float32 holds the

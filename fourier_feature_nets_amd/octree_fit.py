@@ -6,8 +6,8 @@ leaf.  ``OctreeField`` makes the leaf values a parameter: its forward is ``OcTre
 (``csrc/octree_walk.hip``, ``csrc/octree_grad.hip``), deterministic and without float atomics.
 ``fit_octree`` is the training loop on the kernels of the NeRF path: K6 (loss and its gradient),
 K17a + K17b, K7 (clip and Adam) on the flat ``(4 L,)`` buffer, K17c (projection onto
-``0 <= rgb <= 1``, ``sigma >= 0``).  The structure of the tree does not change.  No counterpart in
-the reference.
+``0 <= rgb <= 1``, ``sigma >= 0``).  A fit does not change the structure of the tree.  No counterpart
+in the reference.
 
 ``OctreeSHField`` and ``fit_octree_sh`` (K19) are the same for a tree with spherical-harmonic leaves
 (``OcTree.bake_sh``): the parameter is the ``(L, stride)`` buffer in the device layout K18a reads,
@@ -18,6 +18,10 @@ Both fields offer the total-variation prior of K20 (``csrc/octree_tv.hip``): ``t
 the Charbonnier energy between leaves that touch across a face, ``tv_backward`` its gradient,
 deterministic and without a host sync, and ``tv_weight`` on both fit loops adds it to the data
 term's gradient.  It is off by default, and off means not entered.
+
+``leaf_weights_over`` and ``fit_octree_adaptive`` (K21) change the structure between fits: the first
+folds ``OcTree.leaf_weights`` (K21a) over every ray of a dataset, the second alternates a fit with
+measure -> ``refine_actions`` -> ``OcTree.refine`` (K21b).  With ``rounds=0`` it is the plain fit.
 """
 
 import time
@@ -27,10 +31,19 @@ import numpy as np
 import torch
 
 from . import ops
-from .octree import OcTree
+from .octree import OcTree, refine_actions
 from .utils import RenderResult
 
 FitLogEntry = NamedTuple("FitLogEntry", [("step", int), ("loss", float), ("val_psnr", float)])
+# one round of fit_octree_adaptive: leaves_before = dropped + split + kept, leaves_after = kept +
+# 8 split; weight_quantiles the (min, 25 %, 50 %, 75 %, max) of the measured per-leaf weights
+RefineReport = NamedTuple("RefineReport", [("round", int), ("leaves_before", int), ("dropped", int),
+                                           ("split", int), ("leaves_after", int),
+                                           ("depth_before", int), ("depth_after", int),
+                                           ("weight_quantiles", Tuple[float, ...])])
+# starting values, untuned (see refine_actions)
+PRUNE_BELOW = 1e-2
+SPLIT_ABOVE = 1e-1
 
 # Raycaster.fit's clipping (ops.clip_adam's defaults)
 CLIP_VALUE = 0.1
@@ -367,3 +380,103 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
     log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
            for k in range(len(values))]
     return field.tree(), log
+
+
+def leaf_weights_over(tree: OcTree, dataset, center=None, t_min: float = 0.0,
+                      min_transmittance: float = 0.0) -> np.ndarray:
+    """``OcTree.leaf_weights`` (K21a) folded over every ray of every camera of ``dataset`` (an
+    ``ImageDataset``), camera by camera into one buffer -> (L,) float32 numpy.  The rays are those of
+    the validation PSNR of the fits: ``sampler.starts - center`` and ``sampler.directions``, the
+    sampler's validity mask not applied.  ``center`` defaults to ``tree.center``, which a loaded
+    tree does not have."""
+    tree._check_volume(min_transmittance, "leaf_weights_over")
+    if center is None:
+        center = tree.center
+    if center is None:
+        raise ValueError("leaf_weights_over: a loaded tree does not know the centre of its root "
+                         "cube (the file has no place for it); pass center=")
+    center = tuple(float(c) for c in center)
+    if len(center) != 3:
+        raise ValueError("leaf_weights_over: center has three components")
+    sampler = dataset.sampler
+    per = sampler.rays_per_camera
+    if sampler.num_cameras < 1 or per < 1:
+        raise ValueError("leaf_weights_over: the dataset has no rays (%d cameras of %d rays)"
+                         % (sampler.num_cameras, per))
+    shift = torch.tensor(center, dtype=torch.float32, device=sampler.starts.device)
+    out = None
+    for camera in range(sampler.num_cameras):
+        rays = slice(camera * per, (camera + 1) * per)
+        out = tree.leaf_weights(sampler.starts[rays] - shift, sampler.directions[rays], t_min,
+                                min_transmittance, out)
+    return out.cpu().numpy()
+
+
+def fit_octree_adaptive(tree: OcTree, train_dataset, val_dataset=None, rounds: int = 1,
+                        prune_below: float = PRUNE_BELOW, split_above=SPLIT_ABOVE,
+                        max_depth=None, **fit_kwargs):
+    """Fits a tree and refines its structure in turns (K21); -> ``(tree, logs, reports)``.
+
+    The fit is ``fit_octree`` or, for a tree with ``sh_degree``, ``fit_octree_sh``, called with
+    ``fit_kwargs`` as they are (``num_steps`` is the length of EVERY fit).  A round is: fit,
+    ``leaf_weights_over`` the training rays (with the fit's ``center``, ``t_min`` and
+    ``min_transmittance``), ``refine_actions(weights, leaf_depths, prune_below, split_above,
+    max_depth)``, ``OcTree.refine``; a last fit closes, so ``rounds`` rounds are ``rounds + 1``
+    fits.  Every fit starts its Adam moments and its step count at zero and its seeded shuffle
+    anew: the optimiser's state belongs to the leaves of one structure and is not carried across a
+    refine.  ``prune_below`` / ``split_above`` default to 1e-2 / 1e-1, starting values that are
+    UNTUNED; ``max_depth`` as in ``refine_actions``.
+
+    ``logs`` is the list of the fits' logs in order, ``reports`` one ``RefineReport`` per round.
+    ``rounds=0`` is one call of the plain fit: its tree and its log unchanged (``logs`` IS that log,
+    not a list around it) and no reports.  A round whose action would leave no leaf raises, as
+    ``refine`` does."""
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError("fit_octree_adaptive: rounds >= 0, got %d" % rounds)
+    if not isinstance(tree, OcTree):
+        raise ValueError("fit_octree_adaptive: tree is an OcTree")
+    fit = fit_octree if tree.sh_degree is None else fit_octree_sh
+    if rounds == 0:
+        tree, log = fit(tree, train_dataset, val_dataset, **fit_kwargs)
+        return tree, log, []
+    refine_actions(np.zeros(0), np.zeros(0, np.int32), prune_below, split_above, max_depth)
+    center = fit_kwargs.get("center")
+    center = tree.center if center is None else center
+    verbose = fit_kwargs.get("verbose", True)
+    logs, reports = [], []
+    for number in range(rounds):
+        tree, log = fit(tree, train_dataset, val_dataset, **fit_kwargs)
+        logs.append(log)
+        weights = leaf_weights_over(tree, train_dataset, center, fit_kwargs.get("t_min", 0.0),
+                                    fit_kwargs.get("min_transmittance", 0.0))
+        report, tree = refine_once(tree, weights, number, prune_below, split_above, max_depth)
+        reports.append(report)
+        if verbose:
+            print(format_refine_report(report))
+    tree, log = fit(tree, train_dataset, val_dataset, **fit_kwargs)
+    logs.append(log)
+    return tree, logs, reports
+
+
+def refine_once(tree, weights, number, prune_below, split_above, max_depth):
+    """One ``refine_actions`` + ``OcTree.refine`` on measured ``weights`` (``leaf_weights_over``) ->
+    ``(RefineReport, the new tree)``; ``number`` is the report's round.  What a round of
+    ``fit_octree_adaptive`` does between two fits, and all of scripts/refine_octree.py."""
+    action = refine_actions(weights, tree.leaf_depths(), prune_below, split_above, max_depth)
+    new, _ = tree.refine(action)
+    quantiles = tuple(float(q) for q in np.quantile(weights.astype(np.float64),
+                                                    [0.0, 0.25, 0.5, 0.75, 1.0]))
+    report = RefineReport(number, tree.num_leaves, int((action == ops.OCTREE_DROP).sum()),
+                          int((action == ops.OCTREE_SPLIT).sum()), new.num_leaves, tree.depth,
+                          new.depth, quantiles)
+    return report, new
+
+
+def format_refine_report(report: RefineReport) -> str:
+    """One line for a ``RefineReport``, as ``fit_octree_adaptive`` and scripts/refine_octree.py print it."""
+    return ("refine {}: leaves {} -> {} (dropped {}, split {}), depth {} -> {}, weight quantiles "
+            "min/25/50/75/max {}".format(report.round, report.leaves_before, report.leaves_after,
+                                         report.dropped, report.split, report.depth_before,
+                                         report.depth_after,
+                                         " ".join("%.3g" % q for q in report.weight_quantiles)))

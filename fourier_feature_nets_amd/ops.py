@@ -1240,3 +1240,129 @@ def octree_merge_level(codes: torch.Tensor, levels: torch.Tensor, data: torch.Te
           _dev(total, torch.int32))
     k = int(total.item())
     return codes_out[:k].clone(), levels_out[:k].clone(), data_out[:k].clone()
+
+
+# --------------------------------------------------------------------------------- K21
+def octree_leaf_weights(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                        node_index: torch.Tensor, leaf_index: torch.Tensor, rows: torch.Tensor,
+                        stride: int, sigma_offset: int, t_min: float = 0.0,
+                        min_transmittance: float = 0.0,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K21a.  Per leaf the largest compositing weight ``w = T * a`` that any of the rays gives it on
+    the walk of ``octree_render_volume`` -> (L,) float32.  ``rows`` (L, stride) float32 of which only
+    the density ``rows[:, sigma_offset]`` is read: stride 4 and offset 3 for ``[r, g, b, sigma]``,
+    the stride of ``octree_sh_device_layout`` and offset 0 for SH rows.  With ``out`` (L,) float32
+    given the maxima fold into it (and it is returned): cameras or chunks of rays, in any order,
+    give the bits of one call over all of them.  ``out`` holds weights, that is values >= 0."""
+    stride, sigma_offset = int(stride), int(sigma_offset)
+    if (rows.dim() != 2 or rows.shape[0] != leaf_index.numel() or rows.shape[1] != stride
+            or stride < 1 or not 0 <= sigma_offset < stride):
+        raise ValueError("octree leaf_weights: rows must be (num_leaves, stride) with 0 <= "
+                         "sigma_offset < stride, got %s for %d leaves, stride %d, sigma_offset %d"
+                         % (tuple(rows.shape), leaf_index.numel(), stride, sigma_offset))
+    _check_min_transmittance("octree leaf_weights", min_transmittance)
+    if out is None:
+        out = torch.zeros((leaf_index.numel(),), dtype=torch.float32, device=starts.device)
+    elif out.shape != (leaf_index.numel(),):
+        raise ValueError("octree leaf_weights: out must be (num_leaves,) = (%d,), got %s"
+                         % (leaf_index.numel(), tuple(out.shape)))
+    if starts.shape[0] > 0:
+        _call("ffn_octree_leaf_weights", *_walk_args(starts, directions, scale, depth, node_index,
+                                                     leaf_index),
+              c_f(t_min), _dev(rows, name="rows"), c_i(stride), c_i(sigma_offset),
+              c_f(min_transmittance), _dev(out, name="out"))
+    return out
+
+
+OCTREE_DROP, OCTREE_KEEP, OCTREE_SPLIT = 0, 1, 2
+
+
+def octree_max_points() -> int:
+    """The most elements one K12 flag scan holds (a host function of the library: no GPU needed)."""
+    fn = _lib.load().ffn_octree_max_points
+    fn.restype = ctypes.c_int64
+    return int(fn())
+
+
+def octree_refine_check_action(action, num_leaves: int) -> None:
+    """The refusals of ``octree_refine`` that need no device: ``action`` (numpy or tensor) is
+    one-dimensional, of the tree's leaf count, and 8 of its slots per leaf fit one scan."""
+    if action.ndim != 1 or action.shape[0] != num_leaves:
+        raise ValueError("octree refine: action must be (num_leaves,) = (%d,), got %s"
+                         % (num_leaves, tuple(action.shape)))
+    if 8 * num_leaves > octree_max_points():
+        raise ValueError("octree refine: %d leaves could become %d, a new leaf count at or over "
+                         "the limit of 2^31" % (num_leaves, 8 * num_leaves))
+
+
+def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: torch.Tensor,
+                  depth: int):
+    """K21b.  ``leaf_ids`` (L,) int64 sorted (a tree's ``leaf_index``), ``rows`` (L,C) float32 or
+    None, ``action`` (L,) uint8: 0 drop, 1 keep, 2 split into the eight children, which inherit the
+    row bit for bit.  ``depth`` is the tree's (1 + its deepest level); a leaf id deeper than that is
+    refused.  -> ``(leaf_ids, node_ids, rows, parent)`` of the new tree, sorted by id; ``parent``
+    (L',) int64 is the number of the old leaf a new one came from.  Raises ``ValueError`` for an
+    action of the wrong length or with a value above 2, when no leaf is left, when a split leaf sits
+    at level ``octree_max_depth() - 1`` (the tree would pass the ray walk's depth limit of 11) and
+    when the new leaf count could reach 2^31.  Reads one small block of counts back; the sort to code
+    order and back to id order, the interior nodes (K12h) and the permutations are plumbing."""
+    num = leaf_ids.shape[0]
+    dev = leaf_ids.device
+    depth = int(depth)
+    limit = octree_max_depth()
+    if num < 1 or depth < 1 or depth > limit:
+        raise ValueError("octree refine: at least one leaf and 1 <= depth <= %d, got %d leaves, "
+                         "depth %d" % (limit, num, depth))
+    octree_refine_check_action(action, num)
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != num):
+        raise ValueError("octree refine: rows must be (num_leaves, C) = (%d, C), got %s"
+                         % (num, tuple(rows.shape)))
+    channels = 0 if rows is None else int(rows.shape[1])
+    # (code, level) from the ids: integer plumbing, as in build_from_model
+    first_id = torch.tensor([(8 ** k - 1) // 7 for k in range(limit + 1)], dtype=torch.int64,
+                            device=dev)
+    levels = torch.searchsorted(first_id, leaf_ids, right=True) - 1
+    codes = (leaf_ids - first_id[levels]) << (3 * (limit - 1 - levels).clamp(min=0))
+    codes, order = torch.sort(codes)                   # id order -> code order
+    ids_c = leaf_ids[order].contiguous()
+    action_c = action[order].contiguous()
+    rows_c = None if rows is None or channels == 0 else rows[order].contiguous()
+    flags, offsets, tiles = _scan_scratch(8 * num, dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    # the scan runs before the action's values and the levels are judged, so that the new count and
+    # what the refusals need come back in ONE read-back; a value above 2 sets no flag in the kernel
+    _call("ffn_octree_refine_count", _dev(action_c, torch.uint8, "action"), c_i64(num),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
+          _dev(total, torch.int32))
+    split = action == OCTREE_SPLIT
+    stats = torch.stack([total.to(torch.int64), action.max().to(torch.int64), levels.max(),
+                         torch.where(split, levels, -1).max(),
+                         torch.where(action == OCTREE_DROP, -1, levels).max()]).cpu().tolist()
+    count, top_action, top_level, top_split, top_kept = [int(v) for v in stats]
+    if top_action > OCTREE_SPLIT:
+        raise ValueError("octree refine: an action is 0 (drop), 1 (keep) or 2 (split), got %d"
+                         % top_action)
+    if top_level > depth - 1:
+        raise ValueError("octree refine: a leaf at level %d in a tree of depth %d"
+                         % (top_level, depth))
+    if top_split >= limit - 1:
+        raise ValueError("octree refine: a leaf at level %d cannot split: the tree would be deeper "
+                         "than the ray walk's limit of %d (octree_max_depth())"
+                         % (top_split, limit))
+    if count < 1:
+        raise ValueError("octree refine: the action leaves no leaf; a tree needs at least one")
+    new_ids = torch.empty((count,), dtype=torch.int64, device=dev)
+    parent = torch.empty((count,), dtype=torch.int32, device=dev)
+    new_rows = None if rows is None else torch.empty((count, channels), dtype=torch.float32,
+                                                     device=dev)
+    _call("ffn_octree_refine_scatter", _dev(action_c, torch.uint8, "action"),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(ids_c, torch.int64, "leaf_ids"),
+          _dev(rows_c, name="rows"), c_i64(num), c_i(channels), c_i64(count),
+          _dev(new_ids, torch.int64), _dev(new_rows if channels else None), _dev(parent, torch.int32))
+    new_depth = max(top_kept, top_split + 1) + 1
+    node_ids = octree_interior_nodes(new_ids, new_depth)      # wants code order
+    new_ids, back = torch.sort(new_ids)                       # code order -> id order
+    parent = order[parent.to(torch.int64)[back]]
+    if new_rows is not None:
+        new_rows = new_rows[back].contiguous()
+    return new_ids, torch.sort(node_ids)[0], new_rows, parent

@@ -1113,6 +1113,54 @@ int ffn_octree_tv(const float* rows, int64_t num_leaves, int stride, const int32
                   float* value, float* d_rows, int accumulate, void* workspace,
                   int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K21  refining a fitted tree: which leaves the rays see, and a rebuild from a decision per leaf.
+ * No counterpart in the reference (its prune merges the deepest level into its parents).
+ *
+ * K21a (csrc/octree_walk.hip, a tenth mode of the K13 kernel).  Arguments up to num_leaves and t_min
+ * as for ffn_octree_render_volume.  leaf_data (num_leaves, stride) f32 rows of which only the density
+ * leaf_data[leaf, sigma_offset] is read: stride 4 and offset 3 for [r, g, b, sigma], stride 16 / 28
+ * and offset 0 for the device layout of K18a; stride >= 1, 0 <= sigma_offset < stride, no alignment
+ * asked.  Per ray, K15's operations in K15's order on the same taken leaves (t_exit > t_min):
+ *     t0 = max(t, t_min);  L = (t_exit - t0) * norm;  sigma = fmaxf(density, 0);
+ *     a = 1 - expf(-(sigma * L));  w = T * a;  T = T * (1 - a);  ends when T <= min_transmittance
+ * so w has the bits ffn_octree_render_volume composites with.  For every taken leaf with w > 0:
+ *     weights[leaf] = max(weights[leaf], bits of w)
+ * weights (num_leaves) uint32 holds f32 bit patterns, monotone for w >= 0, so the maximum is an
+ * integer atomic maximum: exact, and the same bits for the same rays in any order, in one call or
+ * split over many.  The caller zeroes weights (all bits 0 = +0.0f) or lets calls fold into it;
+ * nothing is written per ray, and a leaf no ray takes with w > 0 keeps what it held.  A negative
+ * or NaN density weighs 0; a ray that misses the cube, or that K13 cannot follow, touches nothing.
+ * t_min must not be NaN; 0 <= min_transmittance < 1.  The trip bound of K13 holds. */
+int ffn_octree_leaf_weights(const float* starts, const float* directions, int64_t n, float scale,
+                            int depth, const int64_t* node_index, int64_t num_nodes,
+                            const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                            const float* leaf_data, int stride, int sigma_offset,
+                            float min_transmittance, uint32_t* weights, void* stream);
+
+/* K21b (csrc/octree.hip), in two calls around one read-back of the new leaf count.
+ * action (num_leaves) uint8 per leaf IN PATH-CODE ORDER: 0 drop, 1 keep, 2 split into the eight
+ * children, child order 4 bx + 2 by + bz (the order stays code order).  Leaf i owns the slots
+ * 8 i .. 8 i + 7: a keep flags slot 8 i, a split all eight, any other value none.
+ * ffn_octree_refine_count: flags / offsets (8 num_leaves each) and tile_sums
+ * (ffn_octree_scan_tiles(8 num_leaves)) as for ffn_octree_surface_points; *total (device) = the new
+ * leaf count.  8 num_leaves < 2^31, which holds the new count below 2^31 too.
+ * ffn_octree_refine_scatter: with the flags and offsets of the first call and out_leaves = *total,
+ * output leaf o of slot 8 i + k gets ids_out[o] = leaf_ids[i] (keep) or 8 leaf_ids[i] + 1 + k
+ * (split), parent[o] = i, and rows_out[o] = rows[i] bit for bit (rows (num_leaves, channels),
+ * channels >= 0, null when 0; moved 16 bytes at a time when channels is a multiple of 4 and both
+ * arrays are 16-byte aligned, word by word otherwise).  Nothing beyond out_leaves entries is
+ * written.  No atomics.  Whether a split leaf is too deep for K13 is the caller's check. */
+int64_t ffn_octree_max_points(void);   /* the most elements one K12 flag scan holds: 2^31 - 2048 */
+
+int ffn_octree_refine_count(const uint8_t* action, int64_t num_leaves, uint8_t* flags, int* offsets,
+                            int* tile_sums, int* total, void* stream);
+
+int ffn_octree_refine_scatter(const uint8_t* action, const uint8_t* flags, const int* offsets,
+                              const int64_t* leaf_ids, const float* rows, int64_t num_leaves,
+                              int channels, int64_t out_leaves, int64_t* ids_out, float* rows_out,
+                              int32_t* parent, void* stream);
+
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 

@@ -4,7 +4,10 @@
 format, ready for ``scripts/render_octree.py --mode volume``.  A tree whose file carries an
 ``sh_degree`` (``OcTree.bake_sh``) is fitted by ``fit_octree_sh`` (K18a, K6, K19a-c, K7) and keeps
 its degree.  ``--tv-weight`` / ``--tv-eps`` switch the total-variation prior between touching
-leaves on (K20).  The structure of the tree does not change.  No counterpart in the reference.
+leaves on (K20).  By default the structure of the tree does not change; ``--refine-rounds N`` makes
+it ``fit_octree_adaptive`` (K21): N times fit, measure the per-leaf weights over the training rays,
+drop the leaves below ``--prune-below`` and split those at or above ``--split-above``, then a last
+fit; ``--steps`` is the length of every fit.  No counterpart in the reference.
 
 The octree file has no place for the root cube's centre; ``voxelize_model.py`` prints it in the
 form ``--center`` takes.
@@ -36,6 +39,17 @@ TRAIN_OCTREE = [
                          help="Weights of the total-variation prior (K20): RGB SIGMA for a plain "
                               "tree, BAND0 HIGHER_BANDS SIGMA for an SH tree (default: off)")),
     ("--tv-eps", dict(type=float, default=1e-2, help="The Charbonnier eps of the prior")),
+    ("--refine-rounds", dict(type=int, default=0,
+                             help="Rounds of fit -> measure -> prune / split before the last fit "
+                                  "(K21; 0: the plain fit)")),
+    ("--prune-below", dict(type=float, default=None,
+                           help="Drop leaves whose largest ray weight is below this "
+                                "(default: fit_octree_adaptive's, untuned)")),
+    ("--split-above", dict(type=float, default=None,
+                           help="Split leaves whose largest ray weight is at least this "
+                                "(default: fit_octree_adaptive's, untuned)")),
+    ("--max-depth", dict(type=int, default=None,
+                         help="Deepest tree a split may make (default: the ray walk's limit)")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -71,9 +85,21 @@ def main():
             return 1
         prior = dict(tv_weight=tuple(args.tv_weight), tv_eps=args.tv_eps)
         print("total-variation prior:", " ".join("%g" % w for w in args.tv_weight), "eps %g" % args.tv_eps)
-    fitted, log = fit(tree, train, val, args.batch_size, lr, args.steps, args.report_interval,
-                      center=args.center, min_transmittance=args.min_transmittance, seed=args.seed,
-                      **prior)
+    if args.refine_rounds > 0:
+        policy = dict(max_depth=args.max_depth)
+        if args.prune_below is not None:
+            policy["prune_below"] = args.prune_below
+        if args.split_above is not None:
+            policy["split_above"] = args.split_above
+        fitted, logs, _ = ffn.fit_octree_adaptive(
+            tree, train, val, args.refine_rounds, batch_size=args.batch_size, learning_rate=lr,
+            num_steps=args.steps, report_interval=args.report_interval, center=args.center,
+            min_transmittance=args.min_transmittance, seed=args.seed, **policy, **prior)
+        log = [entry for part in logs for entry in part]
+    else:
+        fitted, log = fit(tree, train, val, args.batch_size, lr, args.steps, args.report_interval,
+                          center=args.center, min_transmittance=args.min_transmittance,
+                          seed=args.seed, **prior)
     if log:
         print("loss first %.6g last %.6g over %d steps" % (log[0].loss, log[-1].loss, len(log)))
     fitted.save(args.output_path)
