@@ -16,6 +16,7 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
+from .mesh import load_obj, normalize_points, procedural_torus, sample_mesh, triangle_counts
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -43,4 +44,5 @@ __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
-           "linspace", "load_model", "orbit", "refine_actions"]
+           "linspace", "load_model", "load_obj", "normalize_points", "orbit", "procedural_torus",
+           "refine_actions", "sample_mesh", "triangle_counts"]

@@ -50,6 +50,8 @@ SOURCES = {
     # d = a - b, s = sqrt(fma(d, d, eps^2)), (s - eps) * scale, (d / s) * scale: only the written
     # fma; tv_finish's + 0.0f is K17b-5's (no -ffast-math here either)
     "octree_tv.hip": ["-ffp-contract=off"],
+    # numpy rounds every product and sum of the barycentric and bilinear interpolation separately
+    "mesh.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

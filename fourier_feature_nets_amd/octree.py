@@ -86,6 +86,15 @@ public signatures are the reference's, so files and calling code go both ways.  
   every pair of touching leaves, the prior that ``fit_octree`` / ``fit_octree_sh`` switch on with
   ``tv_weight``.  Every face counts the same: no weight for its area or the centres' distance.
 
+* ``build_from_triangles`` (K22) is the reference's ``build_from_mesh`` from the point where the
+  file has been read: it takes the arrays of a textured mesh, draws the surface samples on the GPU
+  (``csrc/mesh.hip``: the reference's Basu-Owen points, barycentric interpolation and bilinear
+  texture lookup, operation by operation) and hands the cloud to ``build_from_samples`` without
+  a visit to the host.  The per-triangle counts come from a seeded multinomial (``mesh.py``), so
+  a seed names a tree; the reference draws them unseeded.  ``build_from_mesh(path)`` itself stays
+  a stub (trimesh is not a dependency); ``mesh.load_obj`` reads an OBJ and
+  ``scripts/mesh_to_octree.py`` is the path-taking entry.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
 ``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers``, ``leaf_depths``,
@@ -867,6 +876,41 @@ class OcTree:
                         up_dir=(0, 1, 0)) -> "OcTree":
         raise NotImplementedError("OcTree.build_from_mesh needs trimesh and is not part of the "
                                   "HIP path; sample the mesh and call build_from_samples")
+
+    @staticmethod
+    def build_from_triangles(vertices, triangles, uvs, texture, voxel_depth: int,
+                             min_leaf_size: int, up_dir=(0, 1, 0), seed: int = 0) -> "OcTree":
+        """Builds a colour OcTree from a textured triangle mesh: the reference's
+        ``build_from_mesh`` (octree.py:807-853) from the point where trimesh has read the file.
+
+        vertices (V,3), triangles (F,3) integers, uvs (V,2), texture (H,W,C) uint8 with C >= 3 and
+        row 0 at the top of the image (``mesh.load_obj`` and ``mesh.procedural_torus`` return
+        exactly these).  The vertices are normalised (``mesh.normalize_points`` with ``up_dir``),
+        ``8^(voxel_depth - 2) * min_leaf_size`` surface samples are spread over the triangles by
+        area (``mesh.triangle_counts`` with ``seed``; the reference draws them unseeded) and drawn
+        by K22 with the texture flipped vertically, so that ``v = 0`` is the bottom row of the
+        image; ``build_from_samples`` takes the cloud as it lies on the GPU."""
+        from . import mesh
+        voxel_depth, min_leaf_size = int(voxel_depth), int(min_leaf_size)
+        limit = ops.octree_max_depth()
+        if voxel_depth < 2 or voxel_depth > limit or min_leaf_size < 1:
+            raise ValueError("OcTree.build_from_triangles: 2 <= voxel_depth <= %d and "
+                             "min_leaf_size >= 1, got %d and %d"
+                             % (limit, voxel_depth, min_leaf_size))
+        texture = texture.cpu().numpy() if torch.is_tensor(texture) else np.asarray(texture)
+        if texture.ndim != 3:
+            raise ValueError("OcTree.build_from_triangles: texture must be (H,W,C), got %s"
+                             % (texture.shape,))
+        num_points = (8 ** (voxel_depth - 2)) * min_leaf_size
+        if num_points > ops.octree_max_points():
+            raise ValueError("OcTree.build_from_triangles: 8^(voxel_depth - 2) * min_leaf_size = "
+                             "%d samples; at most %d are supported"
+                             % (num_points, ops.octree_max_points()))
+        points = mesh.normalize_points(vertices, up_dir)
+        counts = mesh.triangle_counts(points, triangles, num_points, seed)
+        positions, colors = mesh.sample_mesh(points, triangles, uvs,
+                                             np.ascontiguousarray(texture[::-1]), counts)
+        return OcTree.build_from_samples(positions, voxel_depth, min_leaf_size, colors)
 
     @staticmethod
     def build_from_model(model, depth: int, center=(0, 0, 0), scale: float = 1.0,

@@ -1366,3 +1366,86 @@ def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: 
     if new_rows is not None:
         new_rows = new_rows[back].contiguous()
     return new_ids, torch.sort(node_ids)[0], new_rows, parent
+
+
+# --------------------------------------------------------------------------------- K22
+MESH_MAX_PER_TRIANGLE = 1 << 24     # the reference's f32 van der Corput digits hold below this
+MESH_MAX_TEXTURE_SIDE = 1 << 24     # a row or column index is exact in f32
+
+
+def mesh_sample_check(vertices, triangles, uvs, offsets, texture) -> int:
+    """The refusals of ``mesh_sample``, none of which needs a device: shapes, dtypes, vertex ids,
+    finite UVs, the prefix sum and its limits.  Tensors on any device (the small ones are read
+    back).  -> N, the number of samples.  Raises ``ValueError`` naming the argument."""
+    def want(name, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise ValueError("mesh_sample: %s must be a %s tensor, got %s"
+                             % (name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise ValueError("mesh_sample: %s must be (%s), got %s"
+                             % (name, ", ".join("*" if w is None else str(w) for w in shape),
+                                tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("mesh_sample: %s must be contiguous" % name)
+
+    want("vertices", vertices, torch.float32, (None, 3))
+    num_vertices = vertices.shape[0]
+    want("triangles", triangles, torch.int32, (None, 3))
+    num_triangles = triangles.shape[0]
+    want("uvs", uvs, torch.float32, (num_vertices, 2))
+    want("offsets", offsets, torch.int32, (num_triangles + 1,))
+    want("texture", texture, torch.uint8, (None, None, None))
+    if num_vertices < 1 or num_vertices > (2 ** 31 - 1) // 3:
+        raise ValueError("mesh_sample: vertices holds %d vertices; 1 .. (2^31 - 1) / 3 are "
+                         "supported" % num_vertices)
+    if num_triangles < 1 or num_triangles > (2 ** 31 - 1) // 3:
+        raise ValueError("mesh_sample: triangles holds %d triangles; 1 .. (2^31 - 1) / 3 are "
+                         "supported" % num_triangles)
+    height, width, channels = texture.shape
+    if (channels < 3 or not 1 <= height <= MESH_MAX_TEXTURE_SIDE
+            or not 1 <= width <= MESH_MAX_TEXTURE_SIDE or height * width * channels >= 2 ** 31):
+        raise ValueError("mesh_sample: texture must be (H, W, C) with C >= 3, 1 <= H, W <= 2^24 "
+                         "and fewer than 2^31 bytes, got %s" % (tuple(texture.shape),))
+    low, high = [int(v) for v in torch.stack([triangles.min(), triangles.max()]).cpu()]
+    if low < 0 or high >= num_vertices:
+        raise ValueError("mesh_sample: triangles indexes vertices %d .. %d, outside 0 .. %d"
+                         % (low, high, num_vertices - 1))
+    if not bool(torch.isfinite(uvs).all()):
+        raise ValueError("mesh_sample: uvs holds a NaN or an infinity")
+    steps = offsets.cpu().numpy().astype(np.int64)
+    counts = np.diff(steps)
+    if steps[0] != 0 or (counts < 0).any():
+        raise ValueError("mesh_sample: offsets must start at 0 and never decrease (the exclusive "
+                         "prefix sum of the per-triangle counts)")
+    if counts.max() >= MESH_MAX_PER_TRIANGLE:
+        raise ValueError("mesh_sample: offsets gives one triangle %d samples; fewer than 2^24 per "
+                         "triangle are supported" % counts.max())
+    total = int(steps[-1])
+    if total < 1 or total > octree_max_points():
+        raise ValueError("mesh_sample: offsets ends at N = %d samples; 1 .. %d are supported"
+                         % (total, octree_max_points()))
+    return total
+
+
+def mesh_sample(vertices: torch.Tensor, triangles: torch.Tensor, uvs: torch.Tensor,
+                offsets: torch.Tensor, texture: torch.Tensor, want_uvs: bool = False):
+    """K22.  Surface samples of a textured mesh.  vertices (V,3) f32 (already normalised), triangles
+    (F,3) int32, uvs (V,2) f32, offsets (F+1,) int32 (the exclusive prefix sum of the per-triangle
+    sample counts, ``offsets[F] = N``), texture (H,W,C) uint8 with C >= 3 and the row index growing
+    with ``v`` -> positions (N,3), colors (N,3) float32 [, sample_uvs (N,2)].  Sample ``k`` of a
+    triangle is the Basu-Owen point ``k + 1``; the same inputs give the same bits.  Bad input is a
+    ``ValueError`` (``mesh_sample_check``: the ids, the UVs and the offsets are read back once)."""
+    n = mesh_sample_check(vertices, triangles, uvs, offsets, texture)
+    dev = vertices.device
+    positions = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    sample_uvs = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_uvs else None
+    height, width, channels = texture.shape
+    _call("ffn_mesh_sample", _dev(vertices, name="vertices"), c_i64(vertices.shape[0]),
+          _dev(triangles, torch.int32, "triangles"), c_i64(triangles.shape[0]),
+          _dev(uvs, name="uvs"), _dev(offsets, torch.int32, "offsets"), c_i64(n),
+          _dev(texture, torch.uint8, "texture"), c_i(height), c_i(width), c_i(channels),
+          _dev(positions), _dev(colors), _dev(sample_uvs))
+    if want_uvs:
+        return positions, colors, sample_uvs
+    return positions, colors

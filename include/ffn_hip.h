@@ -1164,6 +1164,35 @@ int ffn_octree_refine_scatter(const uint8_t* action, const uint8_t* flags, const
 /* FFN_OCTREE_FACE_SHADE as the kernel was compiled with it, into table[7] (host memory). */
 void ffn_octree_face_shade(float* table);
 
+/* K22 (csrc/mesh.hip): surface samples of a textured triangle mesh, one thread per sample.  Replaces
+ * the reference's host-side sampler, octree.py:42-136 (_sample_regular_barys,
+ * _barycentric_interpolation, _sample_barycentric_point_cloud after the counts are drawn) and
+ * utils.py:197-241 (interpolate_bilinear) with the / 255 of octree.py:849.
+ * vertices (num_vertices,3) f32, triangles (num_triangles,3) i32, uvs (num_vertices,2) f32, offsets
+ * (num_triangles + 1) i32: the exclusive prefix sum of the per-triangle sample counts, offsets[0] = 0
+ * and offsets[num_triangles] = n.  texture (height, width, channels) u8, channels >= 3, row index
+ * growing with v.  positions (n,3), colors (n,3) f32; sample_uvs (n,2) f32 or null (not written).
+ * Sample s, every operation one rounded f32 operation in this order (no fma):
+ *     f: offsets[f] <= s < offsets[f + 1] (triangles of count 0 are skipped);  number = s - offsets[f] + 1
+ *     A = (1,0), B = (0,1), C = (0,0);  for i = 0 .. 15, d = (number >> 2 i) & 3:
+ *         d = 0: (A,B,C) = ((B+C)/2, (A+C)/2, (A+B)/2)      d = 1: (A, (A+B)/2, (A+C)/2)
+ *         d = 2: ((B+A)/2, B, (B+C)/2)                      d = 3: ((C+A)/2, (C+B)/2, C)
+ *     p = ((A + B) + C) / 3 (IEEE division);  (b0, b1, b2) = (p.x, p.y, 1 - (p.x + p.y))
+ *     value = (x0 b0 + x1 b1) + x2 b2 per component of the triangle's three positions and UVs
+ *     col = u width, row = v height;  j0 = floor(col), i0 = floor(row);  dj = col - j0, di = row - i0;
+ *     j0, i0, j0 + 1, i0 + 1 clamped to the image after that;  per channel 0 .. 2
+ *     (((1-di)(1-dj) t00 + (1-di) dj t01) + di (1-dj) t10) + di dj t11, then / 255 (IEEE division)
+ * The rounds are exact (multiples of 2^-16); d is the reference's digit while number < 2^24, which
+ * the caller checks, as it checks the vertex ids (0 <= id < num_vertices: the kernel clamps an id,
+ * so a bad one reads a wrong vertex, not foreign memory), the offsets and finite UVs.  A texel index
+ * is clamped in f32, so any u, v (NaN and infinities included) reads inside the texture.
+ * n <= ffn_octree_max_points(); height, width <= 2^24; height * width * channels < 2^31.  No
+ * atomics, no LDS, no dependence on the launch shape: the same inputs give the same bits. */
+int ffn_mesh_sample(const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                    int64_t num_triangles, const float* uvs, const int32_t* offsets, int64_t n,
+                    const uint8_t* texture, int height, int width, int channels, float* positions,
+                    float* colors, float* sample_uvs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
