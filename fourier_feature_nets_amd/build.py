@@ -52,6 +52,8 @@ SOURCES = {
     "octree_tv.hip": ["-ffp-contract=off"],
     # numpy rounds every product and sum of the barycentric and bilinear interpolation separately
     "mesh.hip": ["-ffp-contract=off"],
+    # the projection x = ((P00 px + P01 py) + P02 pz) + P03 rounds every product and sum separately
+    "carve.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -82,6 +82,21 @@ class CameraInfo(NamedTuple("CameraInfo", [("name", str), ("resolution", Resolut
         return Ray(starts.cpu().numpy(), dirs.cpu().numpy())
 
 
+def projection_matrices(cameras: List[CameraInfo]) -> np.ndarray:
+    """World -> homogeneous pixel, one 3x4 matrix per camera -> (C,3,4) float32:
+    ``P = ([[K,0],[0,1]] @ inv(E))[:3]``, the product ``CameraInfo.project`` forms, computed in
+    float64 and rounded once.  ``P @ [x, y, z, 1]`` is ``(u w, v w, w)`` with ``w > 0`` in front of
+    the camera; pixel ``(u, v)`` is the ray through those coordinates (``CameraInfo.raycast``).
+    What K23 (``ops.octree_carve_select``) takes as ``proj``."""
+    out = np.empty((len(cameras), 3, 4), np.float32)
+    for index, camera in enumerate(cameras):
+        proj = np.eye(4, dtype=np.float64)
+        proj[:3, :3] = np.asarray(camera.intrinsics, np.float64)
+        proj = proj @ np.linalg.inv(np.asarray(camera.extrinsics, np.float64))
+        out[index] = proj[:3]
+    return out
+
+
 def _axis_angle(axis: np.ndarray, angle: float) -> np.ndarray:
     """4x4 rotation about a unit axis (Rodrigues)."""
     axis = np.asarray(axis, np.float64)

@@ -29,6 +29,7 @@
 //   K12j query               containment, descent, binary search in the sorted id arrays
 //   K12k leaf_geometry       centre and depth of a leaf from its id alone
 #include "common.h"
+#include "octree_cells.h"
 
 namespace ffn {
 
@@ -395,7 +396,8 @@ leaf_geometry_kernel(const int64_t* __restrict__ leaf_index, int64_t num_leaves,
 //
 //   K16a cell_centers     code -> centre of the finest cell, the chain of K12k plus the cube centre
 //   K16b density_scatter  stable compaction of the cells octree_density_flags_kernel
-//                         (composite.hip, where the activations live) has flagged
+//                         (composite.hip, where the activations live) has flagged; K23
+//                         (carve.hip) flags its cells itself and shares this tail
 //   K16c merge_*          one bottom-up coarsening pass over the code-sorted leaf list
 __global__ void __launch_bounds__(kOctThreads)
 cell_centers_kernel(int64_t first_code, int64_t count, float ox, float oy, float oz, float scale,
@@ -403,18 +405,11 @@ cell_centers_kernel(int64_t first_code, int64_t count, float ox, float oy, float
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * kOctThreads + threadIdx.x;
     if (i >= count) return;
-    const int64_t code = first_code + i;
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
-    for (int level = 1; level < depth; ++level) {
-        const int child = (int)((code >> (3 * (depth - 1 - level))) & 7);
-        half *= 0.5f;
-        cx = (child & 4) ? cx + half : cx - half;
-        cy = (child & 2) ? cy + half : cy - half;
-        cz = (child & 1) ? cz + half : cz - half;
-    }
-    out[i * 3 + 0] = cx + ox;
-    out[i * 3 + 1] = cy + oy;
-    out[i * 3 + 2] = cz + oz;
+    float x, y, z;
+    oct_cell_center(first_code + i, ox, oy, oz, scale, depth, &x, &y, &z);
+    out[i * 3 + 0] = x;
+    out[i * 3 + 1] = y;
+    out[i * 3 + 2] = z;
 }
 
 __global__ void __launch_bounds__(kOctThreads)
@@ -549,6 +544,17 @@ refine_scatter_kernel(const uint8_t* __restrict__ action, const uint8_t* __restr
 // composite.hip: activations and sigma * side > tau of one chunk
 void launch_octree_density_flags(const float* logits, int64_t count, float tau, float side,
                                  float* activated, uint8_t* flags, hipStream_t stream);
+
+// the select tail of K16b and K23 (octree_cells.h)
+int octree_select_flagged(const uint8_t* flags, const float* rows, int64_t first_code,
+                          int64_t count, int* offsets, int* tile_sums, int* codes_out,
+                          float* data_out, int* total, hipStream_t stream) {
+    if (int err = scan_flags(flags, count, tile_sums, offsets, total, stream)) return err;
+    hipLaunchKernelGGL(density_scatter_kernel, dim3(oct_blocks(count)), dim3(kOctThreads), 0,
+                       stream, flags, offsets, (const float4*)rows, first_code, count, codes_out,
+                       (float4*)data_out);
+    return 0;
+}
 
 }  // namespace ffn
 
@@ -711,10 +717,9 @@ extern "C" int ffn_octree_density_select(const float* logits, int64_t first_code
                         "16-byte aligned");
     const hipStream_t s = (hipStream_t)stream;
     launch_octree_density_flags(logits, count, tau, side, activated, flags, s);
-    if (int err = scan_flags(flags, count, tile_sums, offsets, total, s)) return err;
-    hipLaunchKernelGGL(density_scatter_kernel, dim3(oct_blocks(count)), dim3(kOctThreads), 0, s,
-                       flags, offsets, (const float4*)activated, first_code, count, codes_out,
-                       (float4*)data_out);
+    if (int err = octree_select_flagged(flags, activated, first_code, count, offsets, tile_sums,
+                                        codes_out, data_out, total, s))
+        return err;
     return check_launch("ffn_octree_density_select");
 }
 

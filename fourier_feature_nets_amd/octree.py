@@ -95,11 +95,25 @@ public signatures are the reference's, so files and calling code go both ways.  
   a stub (trimesh is not a dependency); ``mesh.load_obj`` reads an OBJ and
   ``scripts/mesh_to_octree.py`` is the path-taking entry.
 
+* ``build_from_silhouettes`` (K23, ``csrc/carve.hip``) has none either: nothing in the reference
+  gets a tree from a dataset alone.  It is the grid loop of ``build_from_model`` with the model
+  replaced by a projection: the centre of every finest cell goes into every camera
+  (``cameras.projection_matrices``), a cell that lands on the background of a silhouette is carved
+  away, and a survivor starts with the mean colour of the pixels it lands on and one density for
+  all, so that ``images -> carve -> fit_octree[_adaptive] -> render_octree`` has no MLP in it.
+  A point sample per cell, not a conservative test; the colour ignores occlusion; the hull of few
+  views is fatter than the object.  Measured on one MI355X with the torus dataset of
+  ``scripts/make_mesh_npz.py`` and all 120 cameras (profiles/r21_octree_carve_microbench.json),
+  depth 8 / 10: 346 484 / 22 177 601 leaves, the build 7.4 / 525 ms wall, K23 with its scan and
+  scatter 0.35 / 14.9 ms on the device; carved from 116 cameras at depth 8 and fitted for 300
+  steps, 4 held-out cameras go from 24.4 to 27.3 dB (the mesh's own depth-8 tree: 28.0 dB).
+  Kernel times under rocprofv3 are unmeasured.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
-``bake``, ``bake_sh``, ``build_from_model``, ``render_volume``, ``leaf_centers``, ``leaf_depths``,
-``neighbors``, ``total_variation``, ``leaf_weights`` and ``refine`` run on the GPU and raise without
-one; ``refine_actions`` is numpy.
+``bake``, ``bake_sh``, ``build_from_model``, ``build_from_silhouettes``, ``render_volume``,
+``leaf_centers``, ``leaf_depths``, ``neighbors``, ``total_variation``, ``leaf_weights`` and ``refine``
+run on the GPU and raise without one; ``refine_actions`` is numpy.
 """
 
 import os
@@ -937,35 +951,17 @@ class OcTree:
 
         One sample per finest cell: structure thinner than a cell can be missed, and a leaf holds
         one colour (see ``bake``)."""
-        depth = int(depth)
-        limit = ops.octree_max_depth()
-        if depth < 1 or depth > limit:
-            raise ValueError("OcTree.build_from_model: depth %d is outside what the path codes "
-                             "hold (1 .. %d)" % (depth, limit))
+        depth, center, scale, batch_size, tolerances = OcTree._grid_arguments(
+            "OcTree.build_from_model", "center and view have three components",
+            depth, center, scale, batch_size, merge_tolerance)
         alpha_threshold = float(alpha_threshold)
         if not 0.0 <= alpha_threshold < 1.0:        # NaN fails too
             raise ValueError("OcTree.build_from_model: alpha_threshold must lie in [0, 1), got %r"
                              % (alpha_threshold,))
-        center = tuple(float(np.float32(c)) for c in center)
         view = tuple(float(v) for v in view)
-        batch_size = int(batch_size)
-        if len(center) != 3 or len(view) != 3 or batch_size < 1:
+        if len(view) != 3:
             raise ValueError("OcTree.build_from_model: center and view have three components and "
                              "batch_size is >= 1")
-        scale = float(np.float32(scale))
-        if not 0.0 < scale < float("inf"):
-            raise ValueError("OcTree.build_from_model: scale must be positive and finite, got %r"
-                             % (scale,))
-        tolerances = None
-        if merge_tolerance is not None:
-            pair = np.atleast_1d(np.asarray(merge_tolerance, dtype=np.float64)).reshape(-1)
-            if len(pair) == 1:
-                pair = np.repeat(pair, 2)
-            if len(pair) != 2 or not (pair >= 0).all():        # NaN fails too
-                raise ValueError("OcTree.build_from_model: merge_tolerance is None, one float "
-                                 ">= 0 or a pair (rgb_tol, sigma_tol) of them, got %r"
-                                 % (merge_tolerance,))
-            tolerances = (float(pair[0]), float(pair[1]))
         tau = float(np.float32(-np.log1p(-np.float64(alpha_threshold))))
         side = float(np.float32(2.0 * scale) / np.float32(2.0 ** (depth - 1)))
 
@@ -996,7 +992,41 @@ class OcTree:
         if not kept_codes:
             raise ValueError("OcTree.build_from_model: no leaf (no cell of depth %d with "
                              "sigma * side > %g)" % (depth, tau))
-        codes, data = torch.cat(kept_codes), torch.cat(kept_data)
+        return OcTree._from_cells(torch.cat(kept_codes), torch.cat(kept_data), depth, scale,
+                                  center, tolerances, device)
+
+    @staticmethod
+    def _grid_arguments(who, three, depth, center, scale, batch_size, merge_tolerance):
+        """What the dense-grid builders check alike -> depth, center and scale as f32 values,
+        batch_size, and merge_tolerance as ``None`` or ``(rgb_tol, sigma_tol)``."""
+        depth = int(depth)
+        limit = ops.octree_max_depth()
+        if depth < 1 or depth > limit:
+            raise ValueError("%s: depth %d is outside what the path codes hold (1 .. %d)"
+                             % (who, depth, limit))
+        center = tuple(float(np.float32(c)) for c in center)
+        batch_size = int(batch_size)
+        if len(center) != 3 or batch_size < 1:
+            raise ValueError("%s: %s and batch_size is >= 1" % (who, three))
+        scale = float(np.float32(scale))
+        if not 0.0 < scale < float("inf"):
+            raise ValueError("%s: scale must be positive and finite, got %r" % (who, scale))
+        tolerances = None
+        if merge_tolerance is not None:
+            pair = np.atleast_1d(np.asarray(merge_tolerance, dtype=np.float64)).reshape(-1)
+            if len(pair) == 1:
+                pair = np.repeat(pair, 2)
+            if len(pair) != 2 or not (pair >= 0).all():        # NaN fails too
+                raise ValueError("%s: merge_tolerance is None, one float >= 0 or a pair "
+                                 "(rgb_tol, sigma_tol) of them, got %r" % (who, merge_tolerance))
+            tolerances = (float(pair[0]), float(pair[1]))
+        return depth, center, scale, batch_size, tolerances
+
+    @staticmethod
+    def _from_cells(codes, data, depth, scale, center, tolerances, device) -> "OcTree":
+        """The tail of the dense-grid builders: the kept finest cells in code order (codes (K)
+        int32, data (K,4) float32 on the device) -> the optional merge passes, the ids, the
+        interior nodes and the tree in id order."""
         levels = torch.full_like(codes, depth - 1)
         if tolerances is not None:
             for level in range(depth - 1, 0, -1):
@@ -1014,6 +1044,89 @@ class OcTree:
         tree._device = device
         tree._center = center
         return tree
+
+    @staticmethod
+    def build_from_silhouettes(dataset, depth: int, center=(0, 0, 0), scale: float = 1.0,
+                               alpha_threshold: float = 0.5, dilate: int = 1, max_misses: int = 0,
+                               min_views: int = 2, cell_opacity: float = 0.5,
+                               merge_tolerance=None, batch_size: int = 1 << 20) -> "OcTree":
+        """Carves a tree out of the root cube from the images' silhouettes alone (K23; no
+        counterpart in the reference): a starting point for ``fit_octree`` that needs neither a
+        trained model nor the mesh.
+
+        ``dataset`` gives ``images`` ((C,H,W,4) uint8 RGBA, colour space RGB) and ``cameras``.  The
+        root cube is ``center +- scale`` and the grid that of ``build_from_model``: every cell of
+        level ``depth - 1`` is looked at once, ``batch_size`` consecutive path codes at a time.  A
+        pixel is foreground where its alpha is ``>= alpha_u8 = ceil(alpha_threshold * 255)``
+        (clamped to 1 .. 255); that mask is grown by ``dilate`` pixels (a square maximum filter,
+        once, before the kernel).  A cell's centre is projected into every camera to its nearest
+        pixel; the cell survives iff at most ``max_misses`` of the cameras that see it see it on the
+        background of the grown mask, and at least ``min_views`` cameras see it at all.  Its row is
+        ``[r, g, b, sigma0]``: the mean of the pixels it projects to whose own alpha is
+        ``>= alpha_u8`` (grey 0.5 if none), and ``sigma0 = -log1p(-cell_opacity) / side``, so that
+        one cell side starts at opacity ``cell_opacity`` (0 <= cell_opacity < 1).
+        ``merge_tolerance`` as for ``build_from_model``.
+
+        The limits: one sample per cell, at its centre, so structure thinner than a cell or than
+        a pixel's footprint can be carved away (``dilate`` and ``max_misses`` are the slack).  The
+        colour ignores occlusion: cameras on the far side of the object vote into the mean.  The
+        hull of few views is fatter than the object, and concavities that no silhouette shows
+        stay filled.  The defaults ``cell_opacity``, ``dilate`` and ``min_views`` are untuned
+        starting values."""
+        who = "OcTree.build_from_silhouettes"
+        depth, center, scale, batch_size, tolerances = OcTree._grid_arguments(
+            who, "center has three components", depth, center, scale, batch_size,
+            merge_tolerance)
+        alpha_threshold, cell_opacity = float(alpha_threshold), float(cell_opacity)
+        if not 0.0 <= alpha_threshold <= 1.0:        # NaN fails too
+            raise ValueError("%s: alpha_threshold must lie in [0, 1], got %r"
+                             % (who, alpha_threshold))
+        if not 0.0 <= cell_opacity < 1.0:
+            raise ValueError("%s: cell_opacity must lie in [0, 1), got %r" % (who, cell_opacity))
+        dilate, max_misses, min_views = int(dilate), int(max_misses), int(min_views)
+        if dilate < 0 or max_misses < 0 or min_views < 0:
+            raise ValueError("%s: dilate, max_misses and min_views must be >= 0, got %d, %d and %d"
+                             % (who, dilate, max_misses, min_views))
+        images = np.asarray(dataset.images)
+        if images.ndim != 4 or images.shape[-1] != 4 or images.dtype != np.uint8:
+            raise ValueError("%s: dataset.images must be (C,H,W,4) uint8 with an alpha channel, "
+                             "got %s %s" % (who, images.dtype, images.shape))
+        if getattr(dataset, "color_space", "RGB") != "RGB":
+            raise ValueError("%s: dataset.color_space must be RGB, got %r"
+                             % (who, dataset.color_space))
+        cameras = list(dataset.cameras)
+        if len(cameras) != len(images) or not cameras:
+            raise ValueError("%s: dataset has %d cameras for %d images"
+                             % (who, len(cameras), len(images)))
+        from .cameras import projection_matrices
+        alpha_u8 = min(max(int(np.ceil(alpha_threshold * 255)), 1), 255)
+        side = float(np.float32(2.0 * scale) / np.float32(2.0 ** (depth - 1)))
+        sigma0 = float(np.float32(-np.log1p(-np.float64(cell_opacity)) / np.float64(side)))
+
+        sampler = getattr(dataset, "sampler", None)
+        device = torch.device(getattr(sampler, "device", None) or "cuda")
+        images_u8 = torch.from_numpy(np.ascontiguousarray(images)).to(device)
+        proj = torch.from_numpy(projection_matrices(cameras)).to(device)
+        mask = (images_u8[..., 3] >= alpha_u8).to(torch.float32)
+        if dilate > 0:      # maxima of 0 / 1: exact
+            mask = torch.nn.functional.max_pool2d(mask[:, None], 2 * dilate + 1, stride=1,
+                                                  padding=dilate)[:, 0]
+        mask_u8 = mask.to(torch.uint8).contiguous()
+        cells = 8 ** (depth - 1)
+        kept_codes, kept_data = [], []
+        for first in range(0, cells, batch_size):
+            count = min(batch_size, cells - first)
+            codes, data = ops.octree_carve_select(images_u8, mask_u8, proj, first, count, center,
+                                                  scale, depth, alpha_u8, max_misses, min_views,
+                                                  sigma0)
+            if codes.shape[0] > 0:
+                kept_codes.append(codes)
+                kept_data.append(data)
+        if not kept_codes:
+            raise ValueError("%s: no leaf (every cell of depth %d is carved away or seen by fewer "
+                             "than %d cameras)" % (who, depth, min_views))
+        return OcTree._from_cells(torch.cat(kept_codes), torch.cat(kept_data), depth, scale,
+                                  center, tolerances, device)
 
     @staticmethod
     def build_from_samples(positions, depth: int, min_leaf_size: int, data=None) -> "OcTree":

@@ -1449,3 +1449,96 @@ def mesh_sample(vertices: torch.Tensor, triangles: torch.Tensor, uvs: torch.Tens
     if want_uvs:
         return positions, colors, sample_uvs
     return positions, colors
+
+
+# --------------------------------------------------------------------------------- K23
+def octree_carve_max_cameras() -> int:
+    """The most cameras K23 takes: ``255 * C`` must be exact in f32 (``C <= 2^24 / 255``)."""
+    fn = _lib.load().ffn_octree_carve_max_cameras
+    fn.restype = ctypes.c_int
+    return int(fn())
+
+
+def octree_carve_check(images_u8, mask_u8, proj, first_code, count, depth, alpha_u8, max_misses,
+                       min_views):
+    """The refusals of ``octree_carve_select``, none of which needs a device: shapes, dtypes,
+    contiguity, 4 channels, ``C >= 1`` and its limit, a finite ``proj`` (read back once), a chunk
+    that lies in the grid and fits the scan, and the ranges of the scalars.  Tensors on any device.
+    -> (C, H, W).  Raises ``ValueError`` naming the argument."""
+    def want(name, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise ValueError("octree_carve_select: %s must be a %s tensor, got %s"
+                             % (name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise ValueError("octree_carve_select: %s must be (%s), got %s"
+                             % (name, ", ".join("*" if w is None else str(w) for w in shape),
+                                tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("octree_carve_select: %s must be contiguous" % name)
+
+    want("images_u8", images_u8, torch.uint8, (None, None, None, 4))
+    cameras, height, width = images_u8.shape[:3]
+    want("mask_u8", mask_u8, torch.uint8, (cameras, height, width))
+    want("proj", proj, torch.float32, (cameras, 3, 4))
+    limit = octree_carve_max_cameras()
+    if cameras < 1 or cameras > limit:
+        raise ValueError("octree_carve_select: images_u8 holds %d cameras; 1 .. %d are supported "
+                         "(255 * C must be exact in f32)" % (cameras, limit))
+    if not 1 <= height <= 1 << 24 or not 1 <= width <= 1 << 24:
+        raise ValueError("octree_carve_select: images_u8 must be (C, H, W, 4) with 1 <= H, W <= "
+                         "2^24, got %s" % (tuple(images_u8.shape),))
+    if not bool(torch.isfinite(proj).all()):
+        raise ValueError("octree_carve_select: proj holds a NaN or an infinity")
+    depth, first_code, count = int(depth), int(first_code), int(count)
+    if depth < 1 or depth > octree_max_depth():
+        raise ValueError("octree_carve_select: depth %d is outside what the path codes hold "
+                         "(1 .. %d)" % (depth, octree_max_depth()))
+    if count < 1 or count > octree_max_points():
+        raise ValueError("octree_carve_select: count = %d cells in one chunk; 1 .. %d fit the "
+                         "scan" % (count, octree_max_points()))
+    if first_code < 0 or first_code + count > 8 ** (depth - 1):
+        raise ValueError("octree_carve_select: first_code %d and count %d leave the %d cells of "
+                         "depth %d" % (first_code, count, 8 ** (depth - 1), depth))
+    if not 1 <= int(alpha_u8) <= 255:
+        raise ValueError("octree_carve_select: alpha_u8 must lie in 1 .. 255, got %r" % (alpha_u8,))
+    if not 0 <= int(max_misses) < 2 ** 31 or not 0 <= int(min_views) < 2 ** 31:
+        raise ValueError("octree_carve_select: max_misses and min_views must be >= 0, got %r and "
+                         "%r" % (max_misses, min_views))
+    return cameras, height, width
+
+
+def octree_carve_select(images_u8: torch.Tensor, mask_u8: torch.Tensor, proj: torch.Tensor,
+                        first_code: int, count: int, center, scale: float, depth: int,
+                        alpha_u8: int, max_misses: int, min_views: int, sigma0: float,
+                        want_visited: bool = False):
+    """K23.  images_u8 (C,H,W,4) uint8 RGBA, mask_u8 (C,H,W) uint8 (0 = background), proj (C,3,4)
+    float32 (``cameras.projection_matrices``) -> codes (K) int32 and data (K,4) float32
+    ``[r, g, b, sigma0]`` of the cells among ``first_code .. first_code + count - 1`` of the finest
+    level whose centre (``octree_cell_centers``) falls on the background in at most ``max_misses``
+    of the cameras that see it and that at least ``min_views`` cameras see, in code order.  The
+    colour is the mean of the pixels, with own alpha >= ``alpha_u8``, that the centre projects to
+    (0.5 when there is none).  Reads the count back once.  With ``want_visited`` also (count,)
+    int32: how many cameras each cell's loop looked at.  Bad input is a ``ValueError``
+    (``octree_carve_check``)."""
+    cameras, height, width = octree_carve_check(images_u8, mask_u8, proj, first_code, count,
+                                                depth, alpha_u8, max_misses, min_views)
+    n = int(count)
+    dev = images_u8.device
+    rows = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    codes = torch.empty((n,), dtype=torch.int32, device=dev)
+    data = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    visited = torch.empty((n,), dtype=torch.int32, device=dev) if want_visited else None
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_carve_select", _dev(images_u8, torch.uint8, "images_u8"),
+          _dev(mask_u8, torch.uint8, "mask_u8"), _dev(proj, name="proj"), c_i(cameras),
+          c_i(height), c_i(width), c_i64(int(first_code)), c_i64(n), c_f(center[0]),
+          c_f(center[1]), c_f(center[2]), c_f(scale), c_i(int(depth)), c_i(int(alpha_u8)),
+          c_i(int(max_misses)), c_i(int(min_views)), c_f(sigma0), _dev(flags, torch.uint8),
+          _dev(offsets, torch.int32), _dev(tiles, torch.int32), _dev(rows),
+          _dev(visited, torch.int32), _dev(codes, torch.int32), _dev(data),
+          _dev(total, torch.int32))
+    k = int(total.item())
+    if want_visited:
+        return codes[:k].clone(), data[:k].clone(), visited
+    return codes[:k].clone(), data[:k].clone()

@@ -1193,6 +1193,39 @@ int ffn_mesh_sample(const float* vertices, int64_t num_vertices, const int32_t* 
                     const uint8_t* texture, int height, int width, int channels, float* positions,
                     float* colors, float* sample_uvs, void* stream);
 
+/* K23 (csrc/carve.hip): space carving, an octree's finest cells from the images' silhouettes, one
+ * thread per cell.  No reference counterpart: nothing in the reference builds a tree from a dataset
+ * alone (octree.py builds from a mesh, voxelize_model.py from a trained model's depth renders).
+ * images (cameras, height, width, 4) u8 RGBA, 4-byte aligned; mask (cameras, height, width) u8, a
+ * pixel is background where it is 0; proj (cameras, 3, 4) f32 row-major, world -> homogeneous
+ * pixel, finite (the caller checks).  The cells first_code .. first_code + count - 1 of the finest
+ * level as for ffn_octree_cell_centers, whose centre p (the cube centre included) cell i takes, bit
+ * for bit.  Per cell, camera c = 0 .. cameras-1 in that order, every operation one rounded f32
+ * operation (no fma):
+ *     x = ((P00 p.x + P01 p.y) + P02 p.z) + P03, likewise y (row 1) and w (row 2)
+ *     !(w > 0): not seen (NaN too).  fu = x / w + 0.5f, fv = y / w + 0.5f (IEEE divisions)
+ *     seen iff fu >= 0 && fu < width && fv >= 0 && fv < height;  col = (int)fu, row = (int)fv
+ *     seen += 1;  mask[c, row, col] == 0: misses += 1, and misses > max_misses ends the loop, the
+ *     cell is carved;  otherwise, if the pixel's own alpha >= alpha_u8, its r, g, b are added to
+ *     three uint32 sums and colored += 1
+ * A cell is kept iff it was not carved and seen >= min_views.  Its row is [r, g, b, sigma0],
+ * r = (float)sum_r / (float)(255 colored) (IEEE division), 0.5f for all three when colored == 0.
+ * cameras <= ffn_octree_carve_max_cameras() = 65793, so that 255 cameras is exact in f32.
+ * The kept cells in code order (stable): codes_out (int32) and data_out (count,4), *total (device)
+ * of them, in arrays of count entries.  flags / offsets / tile_sums as for
+ * ffn_octree_density_select, whose scan and scatter this shares; rows (count,4) f32 is scratch;
+ * rows and data_out are 16-byte aligned.  visited (count) int32 or null: how many cameras the
+ * loop of cell i looked at before it ended.  1 <= alpha_u8 <= 255; max_misses, min_views >= 0;
+ * height, width <= 2^24.  No atomics; the same inputs give the same bits. */
+int ffn_octree_carve_max_cameras(void);
+int ffn_octree_carve_select(const uint8_t* images, const uint8_t* mask, const float* proj,
+                            int cameras, int height, int width, int64_t first_code,
+                            int64_t count, float center_x, float center_y, float center_z,
+                            float scale, int depth, int alpha_u8, int max_misses, int min_views,
+                            float sigma0, uint8_t* flags, int* offsets, int* tile_sums,
+                            float* rows, int* visited, int* codes_out, float* data_out,
+                            int* total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
