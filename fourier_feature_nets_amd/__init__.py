@@ -5,7 +5,7 @@ of ``include/ffn_hip.h``; this package is the host-side mirror of the reference'
 for that path.  There is no CPU fallback: using a model or sampler without a GPU raises.
 """
 
-from .cameras import CameraInfo, Resolution, orbit, projection_matrices
+from .cameras import CameraInfo, Resolution, eye_positions, orbit, projection_matrices
 from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
@@ -43,6 +43,6 @@ __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
-           "exponential_lr_decay", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
+           "exponential_lr_decay", "eye_positions", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
            "linspace", "load_model", "load_obj", "normalize_points", "orbit", "procedural_torus",
            "projection_matrices", "refine_actions", "sample_mesh", "triangle_counts"]

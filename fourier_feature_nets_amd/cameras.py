@@ -82,18 +82,38 @@ class CameraInfo(NamedTuple("CameraInfo", [("name", str), ("resolution", Resolut
         return Ray(starts.cpu().numpy(), dirs.cpu().numpy())
 
 
-def projection_matrices(cameras: List[CameraInfo]) -> np.ndarray:
+def projection_matrices(cameras: List[CameraInfo], origin=None) -> np.ndarray:
     """World -> homogeneous pixel, one 3x4 matrix per camera -> (C,3,4) float32:
     ``P = ([[K,0],[0,1]] @ inv(E))[:3]``, the product ``CameraInfo.project`` forms, computed in
     float64 and rounded once.  ``P @ [x, y, z, 1]`` is ``(u w, v w, w)`` with ``w > 0`` in front of
     the camera; pixel ``(u, v)`` is the ray through those coordinates (``CameraInfo.raycast``).
-    What K23 (``ops.octree_carve_select``) takes as ``proj``."""
+    What K23 (``ops.octree_carve_select``) takes as ``proj``.
+
+    With ``origin`` (three floats) the matrices take points RELATIVE to it:
+    ``P @ translate(origin)``, that product formed in float64 too and rounded once -- what K24
+    (``ops.octree_visible_votes``) projects an octree's cube-relative leaf centres with."""
     out = np.empty((len(cameras), 3, 4), np.float32)
+    shift = None
+    if origin is not None:
+        shift = np.eye(4, dtype=np.float64)
+        shift[:3, 3] = np.asarray(origin, np.float64).reshape(3)
     for index, camera in enumerate(cameras):
         proj = np.eye(4, dtype=np.float64)
         proj[:3, :3] = np.asarray(camera.intrinsics, np.float64)
         proj = proj @ np.linalg.inv(np.asarray(camera.extrinsics, np.float64))
+        if shift is not None:
+            proj = proj @ shift
         out[index] = proj[:3]
+    return out
+
+
+def eye_positions(cameras: List[CameraInfo], origin) -> np.ndarray:
+    """The cameras' positions relative to ``origin`` (three floats) -> (C,3) float32: the
+    difference formed in float64 and rounded once.  The ray origins of K24."""
+    origin = np.asarray(origin, np.float64).reshape(3)
+    out = np.empty((len(cameras), 3), np.float32)
+    for index, camera in enumerate(cameras):
+        out[index] = np.asarray(camera.extrinsics, np.float64)[:3, 3] - origin
     return out
 
 

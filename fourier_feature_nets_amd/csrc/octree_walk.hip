@@ -116,6 +116,30 @@
 // Resource report, kLeafWeight: 39 VGPRs, 80 SGPRs, 0 bytes of scratch, 0 spills,
 // 0 bytes of LDS, occupancy 8 waves per SIMD; the nine older instantiations compile to the
 // instructions they had before (38 / 40 / 50 / 53 / 61 / 56 / 72 / 64 / 82 VGPRs).
+//
+// K24  Visible votes: an eleventh mode (kVisible).  A lane is a (leaf, camera) pair -- the leaf from
+// blockIdx.x and the lane, the camera from blockIdx.y, so one launch covers every camera of a call and a
+// small tree still fills the chip with waves -- and the L x C rays exist in registers only.  The lane
+// projects its leaf's centre with K23's operations (csrc/carve.hip) through the camera's block of 16
+// floats (P' for cube-relative points, the eye; the block's address is uniform in a workgroup, so it
+// arrives by scalar loads), and leaves before the first tree lookup when the centre lies behind the
+// camera, off the image, or on a pixel whose alpha is below alpha_u8.  Otherwise the ray o = eye,
+// d = centre - eye (the centre at t = 1) takes K21a's walk with t_min = 0: the taken-leaf rule, t0, the
+// chord, sigma = max(density, 0), a, T and the early end are K21a's operations in K21a's order, and the
+// walk ends "visible" at the lane's own leaf, "occluded" once T <= min_transmittance, and not visible
+// when it runs out.  A visible pair adds the pixel's r, g, b and 1 to its leaf's four uint32 fields as
+// two 64-bit INTEGER atomic adds of two fields each (a sum stays below 2^24 and the count below 2^17,
+// so no carry crosses a field): exact, whatever the order of the cameras and however they are split
+// over calls; no float atomic.  The atomics return nothing and come after the walk.  Contention: the C
+// cameras of a leaf share its two words, the lanes of a wave write 1 KiB of neighbouring words.
+// Divergence: lanes rejected before the walk idle while the wave's longest walk runs; neighbouring
+// lanes are neighbouring leaves of one camera, so their walks are alike.  The idle parameters carry
+// its buffers (see kVisible above the kernel); the kernel's parameter list is unchanged.
+// Resource report, kVisible: 39 VGPRs, 89 SGPRs, 0 bytes of scratch, 0 spills, 0 bytes of LDS,
+// occupancy 8 waves per SIMD.  The ten older instantiations compile to the instructions they had
+// before: their disassembly was compared with the previous commit's, instruction for instruction
+// (758 / 809 / 851 / 887 / 975 / 1002 / 1034 / 1095 / 1132 / 845 instructions, 38 / 40 / 50 / 53 / 61 /
+// 56 / 72 / 64 / 82 / 39 VGPRs).
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
@@ -126,6 +150,8 @@ namespace ffn {
 constexpr int kWalkThreads = 64;
 constexpr int kWalkMaxDepth = 11;     // as K12's path codes: at most 10 levels below the root
 static const int64_t kWalkMaxRays = (int64_t)1 << 31;
+constexpr int kVisibleMaxSide = 1 << 24;              // (float)W and (float)H are exact
+constexpr int kVisibleMaxLaunchCameras = 65535;       // gridDim.y
 
 // is key in the sorted ids?  *at = its position
 __device__ __forceinline__ bool find_id(const int64_t* __restrict__ ids, int64_t n, int64_t key,
@@ -211,7 +237,7 @@ struct FirstHit {
 };
 
 enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
-                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9 };
+                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9, kVisible = 10 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
@@ -229,6 +255,11 @@ enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVo
 // kLeafWeight: K21a.  span_hit the (num_leaves) uint32 weights (f32 bit patterns, raised, never
 //            lowered), first.leaf_data / first.channels rows and their stride, first.shading the
 //            density's offset in a row.  Nothing is written per ray.
+// kVisible:  K24.  n the leaves, blockIdx.y the camera; starts the (num_leaves,3) leaf centres,
+//            directions the per-camera blocks of 16 floats (P' row-major, the eye, one of padding),
+//            t_stops the camera-major uint32 RGBA pixels, leaves the (num_leaves) pairs of 64-bit
+//            vote words, max_length alpha_u8, first.bg_r / first.bg_g the image's width / height as
+//            floats (exact: at most 2^24), first.leaf_data / channels / shading as kLeafWeight.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -243,8 +274,29 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     constexpr int kBasis = kMode == kVolumeSH2 || kMode == kGradSH2 ? 9 : 4;
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= n) return;
-    const float ox = starts[r * 3 + 0], oy = starts[r * 3 + 1], oz = starts[r * 3 + 2];
-    const float dx = directions[r * 3 + 0], dy = directions[r * 3 + 1], dz = directions[r * 3 + 2];
+    const float sx = starts[r * 3 + 0], sy = starts[r * 3 + 1], sz = starts[r * 3 + 2];
+    // K24: the pair's pixel, and the cheap rejects before the first tree lookup
+    const float* camera = directions + (kMode == kVisible ? 16 * (int64_t)blockIdx.y : 0);
+    uint32_t rgba = 0;
+    if (kMode == kVisible) {
+        const float w = ((camera[8] * sx + camera[9] * sy) + camera[10] * sz) + camera[11];
+        if (!(w > 0.0f)) return;                         // behind the camera (NaN too)
+        const float x = ((camera[0] * sx + camera[1] * sy) + camera[2] * sz) + camera[3];
+        const float y = ((camera[4] * sx + camera[5] * sy) + camera[6] * sz) + camera[7];
+        const float fu = x / w + 0.5f, fv = y / w + 0.5f;
+        if (!(fu >= 0.0f && fu < first.bg_r && fv >= 0.0f && fv < first.bg_g)) return;
+        // 0 <= col < width and 0 <= row < height: inside image blockIdx.y
+        const int64_t pixel = ((int64_t)blockIdx.y * (int)first.bg_g + (int)fv) * (int)first.bg_r +
+                              (int)fu;
+        rgba = reinterpret_cast<const uint32_t*>(t_stops)[pixel];   // bytes r, g, b, a from the lowest up
+        if ((rgba >> 24) < (uint32_t)max_length) return;            // background
+    }
+    // K24: from the eye to the leaf's centre, which lies at t = 1
+    const float ox = kMode == kVisible ? camera[12] : sx, oy = kMode == kVisible ? camera[13] : sy,
+                oz = kMode == kVisible ? camera[14] : sz;
+    const float dx = kMode == kVisible ? sx - ox : directions[r * 3 + 0],
+                dy = kMode == kVisible ? sy - oy : directions[r * 3 + 1],
+                dz = kMode == kVisible ? sz - oz : directions[r * 3 + 2];
     const int levels = depth - 1;
     const int cells = 1 << levels;
 
@@ -281,7 +333,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad || kMode == kLeafWeight
+    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad ||
+                               kMode == kLeafWeight || kMode == kVisible
                            ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
@@ -291,6 +344,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int32_t* entry_leaves = reinterpret_cast<int32_t*>(leaves);
     int32_t* entry_rays = reinterpret_cast<int32_t*>(first.leaf);        // K19a
     unsigned* leaf_weights = reinterpret_cast<unsigned*>(span_hit);      // K21a
+    bool visible = false;                                                // K24
     int taken = 0, base = 0, mine = 0;
     float c_r = 0.0f, c_g = 0.0f, c_b = 0.0f, t_end = 0.0f, g_r = 0.0f, g_g = 0.0f, g_b = 0.0f,
           g_a = 0.0f;
@@ -484,6 +538,20 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 trans = trans * (1.0f - a);
                 if (trans <= first.min_transmittance) break;
             }
+        } else if (kMode == kVisible) {
+            if (leaf >= 0 && t_exit > t_min) {
+                if (leaf == r) {                               // nothing opaque came first
+                    visible = true;
+                    break;
+                }
+                const float ls = first.leaf_data[leaf * first.channels + first.shading];
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
         } else if (kSpans) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (!any_leaf) first_in = t > t_min ? t : t_min;
@@ -547,6 +615,15 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         }
     } else if (kMode == kLeafWeight) {
         // nothing per ray
+    } else if (kMode == kVisible) {
+        if (visible) {
+            // [sum_r, sum_g] and [sum_b, count] as two 64-bit words, the first field in the low half:
+            // a sum stays below 2^24 and the count below 2^17, so no carry crosses a field
+            unsigned long long* votes = reinterpret_cast<unsigned long long*>(leaves) + 2 * r;
+            atomicAdd(votes, (unsigned long long)(rgba & 255u) |
+                                 ((unsigned long long)((rgba >> 8) & 255u) << 32));
+            atomicAdd(votes + 1, (unsigned long long)((rgba >> 16) & 255u) | (1ull << 32));
+        }
     } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
         const float side = 2.0f * scale / (float)cells;
@@ -767,6 +844,53 @@ extern "C" int ffn_octree_leaf_weights(const float* starts, const float* directi
     first.shading = sigma_offset;
     return launch_walk<kLeafWeight>(who, walk, first, 0, nullptr, nullptr, 0.0f, nullptr, nullptr,
                                     (uint8_t*)weights);
+}
+
+extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, float scale,
+                                        int depth, const int64_t* node_index, int64_t num_nodes,
+                                        const int64_t* leaf_index, const float* leaf_data,
+                                        int stride, int sigma_offset, const uint8_t* images,
+                                        const float* camera_blocks, int cameras, int height,
+                                        int width, int alpha_u8, float min_transmittance,
+                                        uint32_t* votes, void* stream) {
+    const char* who = "ffn_octree_visible_votes";
+    if (depth < 1 || depth > kWalkMaxDepth) return fail_who(who, "shape (1 <= depth <= 11)");
+    if (num_leaves < 1 || num_leaves > kWalkMaxRays || num_nodes < 0)
+        return fail_who(who, "shape (1 <= num_leaves <= 2^31, num_nodes >= 0)");
+    if (cameras < 1) return fail_who(who, "cameras >= 1");
+    if (height < 1 || width < 1 || height > kVisibleMaxSide || width > kVisibleMaxSide)
+        return fail_who(who, "images (1 <= height, width <= 2^24)");
+    if (alpha_u8 < 1 || alpha_u8 > 255) return fail_who(who, "1 <= alpha_u8 <= 255");
+    if (!(min_transmittance >= 0.0f && min_transmittance < 1.0f))        // NaN fails too
+        return fail_who(who, "0 <= min_transmittance < 1");
+    if (stride < 1 || sigma_offset < 0 || sigma_offset >= stride)
+        return fail_who(who, "stride >= 1, 0 <= sigma_offset < stride");
+    if (!leaf_centers || !leaf_index || (num_nodes > 0 && !node_index) || !leaf_data || !images ||
+        !camera_blocks || !votes)
+        return fail_who(who, "null argument");
+    if (((uintptr_t)images & 3) != 0 || misaligned16(votes))
+        return fail_who(who, "images must be 4-byte aligned, votes 16-byte aligned");
+    // a pixel's index within one launch stays far inside int64
+    const int64_t pixels = (int64_t)height * width;
+    if (pixels > ((int64_t)1 << 46)) return fail_who(who, "images (height * width <= 2^46)");
+    FirstHit first{};
+    first.leaf_data = leaf_data; first.channels = stride; first.shading = sigma_offset;
+    first.bg_r = (float)width; first.bg_g = (float)height;       // exact: at most 2^24
+    first.min_transmittance = min_transmittance;
+    const unsigned blocks = (unsigned)((num_leaves + kWalkThreads - 1) / kWalkThreads);
+    // blockIdx.y is the camera within a launch: at most kVisibleMaxLaunchCameras of them at a time
+    for (int done = 0; done < cameras; done += kVisibleMaxLaunchCameras) {
+        const int now = cameras - done < kVisibleMaxLaunchCameras ? cameras - done
+                                                                  : kVisibleMaxLaunchCameras;
+        hipLaunchKernelGGL(octree_walk_kernel<kVisible>, dim3(blocks, (unsigned)now),
+                           dim3(kWalkThreads), 0, (hipStream_t)stream, leaf_centers,
+                           camera_blocks + 16 * (int64_t)done, num_leaves, scale, depth, node_index,
+                           num_nodes, leaf_index, num_leaves, alpha_u8,
+                           (float*)const_cast<uint8_t*>(images + 4 * pixels * done), (int64_t*)votes, 0.0f, 0.0f,
+                           (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, first);
+        if (int err = check_launch(who)) return err;
+    }
+    return 0;
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

@@ -387,6 +387,14 @@ class OcTree:
             self._cache["geometry"] = (centers.cpu().numpy(), depths.cpu().numpy())
         return self._cache["geometry"]
 
+    def _centers_on_device(self) -> torch.Tensor:
+        """The array behind ``leaf_centers``, on the device (K24 reads it there)."""
+        key = ("leaf_centers", str(self._dev()))
+        if key not in self._cache:
+            self._cache[key] = ops.octree_leaf_geometry(self._on_device("leaf_index"),
+                                                        self._scale)[0]
+        return self._cache[key]
+
     def leaf_centers(self) -> np.ndarray:
         """The Nx3 center coordinates of all leaves."""
         return self._geometry()[0]
@@ -663,6 +671,117 @@ class OcTree:
             self._on_device("leaf_index"), rows, int(rows.shape[1]), offset, float(t_min),
             float(min_transmittance), out)
         return weights.cpu().numpy() if as_numpy else weights
+
+    @staticmethod
+    def _visible_arguments(who, dataset, alpha_threshold):
+        """What ``visible_votes`` checks of its dataset and ``alpha_threshold`` before any device is
+        needed (``_check_volume`` has min_transmittance, the op the camera limit) -> images
+        (C,H,W,4) uint8, cameras, alpha_u8."""
+        alpha_threshold = float(alpha_threshold)
+        if not 0.0 <= alpha_threshold <= 1.0:        # NaN fails too
+            raise ValueError("%s: alpha_threshold must lie in [0, 1], got %r"
+                             % (who, alpha_threshold))
+        images = np.asarray(dataset.images)
+        if images.ndim != 4 or images.shape[-1] != 4 or images.dtype != np.uint8:
+            raise ValueError("%s: dataset.images must be (C,H,W,4) uint8 with an alpha channel, "
+                             "got %s %s" % (who, images.dtype, images.shape))
+        if getattr(dataset, "color_space", "RGB") != "RGB":
+            raise ValueError("%s: dataset.color_space must be RGB, got %r"
+                             % (who, dataset.color_space))
+        cameras = list(dataset.cameras)
+        if len(cameras) != len(images) or not cameras:
+            raise ValueError("%s: dataset has %d cameras for %d images"
+                             % (who, len(cameras), len(images)))
+        return images, cameras, min(max(int(np.ceil(alpha_threshold * 255)), 1), 255)
+
+    def _visible_votes_on_device(self, images, cameras, alpha_u8, center, min_transmittance):
+        from .cameras import eye_positions, projection_matrices
+        dev = self._dev()
+        if self._sh_degree is not None:
+            rows, offset = self._sh_rows_on_device(), 0
+        else:
+            rows, offset = self._colors_on_device(), 3
+        images_u8 = images if torch.is_tensor(images) else \
+            torch.from_numpy(np.ascontiguousarray(images)).to(dev)
+        proj = torch.from_numpy(projection_matrices(cameras, origin=center)).to(dev)
+        eyes = torch.from_numpy(eye_positions(cameras, center)).to(dev)
+        return ops.octree_visible_votes(
+            self._centers_on_device(), self._scale, self.depth, self._on_device("node_index"),
+            self._on_device("leaf_index"), rows, int(rows.shape[1]), offset, images_u8, proj, eyes,
+            alpha_u8, float(min_transmittance))
+
+    def _visible_center(self, who, center):
+        center = self._center if center is None else center
+        if center is None:
+            raise ValueError("%s: a loaded tree does not know its root cube's centre; pass "
+                             "center=(x, y, z)" % who)
+        center = tuple(float(np.float32(c)) for c in center)
+        if len(center) != 3:
+            raise ValueError("%s: center has three components" % who)
+        return center
+
+    def visible_votes(self, dataset, center=None, alpha_threshold: float = 0.5,
+                      min_transmittance: float = 0.3) -> np.ndarray:
+        """Per leaf the pixels of the cameras that can see it (K24; no counterpart in the
+        reference) -> (L,4) uint32 numpy ``[sum_r, sum_g, sum_b, count]``.  ``dataset`` gives
+        ``images`` ((C,H,W,4) uint8 RGBA, colour space RGB) and ``cameras``; ``center`` is the root
+        cube's centre (default: the tree's own, which a loaded tree does not have).  Camera c
+        votes for leaf l when the leaf's centre projects, as ``build_from_silhouettes`` projects a
+        cell, onto a pixel of image c whose own alpha is ``>= ceil(alpha_threshold * 255)``
+        (clamped to 1 .. 255; no grown mask), and the ray from the camera's position to the centre
+        reaches the leaf before its transmittance -- ``render_volume``'s, over the leaves in
+        front, from the tree's own densities -- falls to ``min_transmittance`` or below.  Works on
+        plain and SH trees alike (only the density is read).  Integer sums: the same bits in any
+        order of the cameras."""
+        who = "OcTree.visible_votes"
+        self._check_volume(min_transmittance, who)           # before any device is needed
+        images, cameras, alpha_u8 = OcTree._visible_arguments(who, dataset, alpha_threshold)
+        center = self._visible_center(who, center)
+        return self._visible_votes_on_device(images, cameras, alpha_u8, center,
+                                             min_transmittance).cpu().numpy()
+
+    def color_from_images(self, dataset, center=None, alpha_threshold: float = 0.5,
+                          min_transmittance: float = 0.3) -> Tuple["OcTree", np.ndarray]:
+        """A NEW tree whose leaves take the mean colour of the cameras that can see them (K24,
+        ``visible_votes``) -> ``(tree, counts)``; ``counts`` (L,) uint32 numpy is the number of
+        cameras that voted per leaf.  A leaf with ``count > 0`` gets ``sum / (float)(255 count)``,
+        one f32 division per channel as ``build_from_silhouettes`` divides; a leaf no camera saw
+        keeps its colour.  Structure, densities and any further channels, scale, centre and device
+        carry over; this tree is not modified.  An SH tree is refused: its leaves hold
+        coefficients, not a colour (``visible_votes`` works on it and returns the sums).
+
+        The limits: one ray per (leaf, camera) pair, aimed at the leaf's centre, so a leaf whose
+        centre is hidden counts as hidden however much of it shows.  Opacity is judged from the
+        tree's own densities: a tree that is transparent hides nothing, and one whose cells are
+        opaque where the object is not hides too much.  ``min_transmittance = 0.3`` is an untuned
+        starting value: it lies between the 0.5 and the 0.25 that one and two whole cells of a
+        fresh carve (``cell_opacity = 0.5``) leave, so rays along the lattice do not sit on the
+        threshold."""
+        who = "OcTree.color_from_images"
+        if self._sh_degree is not None:
+            raise ValueError("%s: the leaves of an SH tree hold coefficients, not a colour; "
+                             "OcTree.visible_votes gives the cameras' sums for it" % who)
+        self._check_volume(min_transmittance, who)           # before any device is needed
+        images, cameras, alpha_u8 = OcTree._visible_arguments(who, dataset, alpha_threshold)
+        center = self._visible_center(who, center)
+        votes = self._visible_votes_on_device(images, cameras, alpha_u8, center,
+                                              min_transmittance).cpu().numpy()
+        data = np.array(self._leaf_data, dtype=np.float32, copy=True)
+        data[:, :3] = OcTree._vote_colors(votes, data[:, :3])
+        tree = OcTree(self._scale, self._node_index, self._leaf_index, data)
+        tree._device = self._device
+        tree._center = self._center
+        return tree, votes[:, 3].copy()
+
+    @staticmethod
+    def _vote_colors(votes: np.ndarray, colors: np.ndarray) -> np.ndarray:
+        """(L,3) float32: ``sum / (float)(255 count)`` where ``count > 0`` (both operands exact in
+        f32, one division), ``colors`` elsewhere."""
+        seen = votes[:, 3] > 0
+        out = np.array(colors, dtype=np.float32, copy=True)
+        denominator = (np.uint32(255) * votes[seen, 3]).astype(np.float32)
+        out[seen] = votes[seen, :3].astype(np.float32) / denominator[:, None]
+        return out
 
     def refine(self, action) -> Tuple["OcTree", np.ndarray]:
         """A NEW tree from one decision per leaf (K21b): ``action`` (L,) with 0 drop, 1 keep, 2 split
@@ -1049,7 +1168,9 @@ class OcTree:
     def build_from_silhouettes(dataset, depth: int, center=(0, 0, 0), scale: float = 1.0,
                                alpha_threshold: float = 0.5, dilate: int = 1, max_misses: int = 0,
                                min_views: int = 2, cell_opacity: float = 0.5,
-                               merge_tolerance=None, batch_size: int = 1 << 20) -> "OcTree":
+                               merge_tolerance=None, batch_size: int = 1 << 20,
+                               color: str = "mean",
+                               visible_transmittance: float = 0.3) -> "OcTree":
         """Carves a tree out of the root cube from the images' silhouettes alone (K23; no
         counterpart in the reference): a starting point for ``fit_octree`` that needs neither a
         trained model nor the mesh.
@@ -1072,7 +1193,14 @@ class OcTree:
         colour ignores occlusion: cameras on the far side of the object vote into the mean.  The
         hull of few views is fatter than the object, and concavities that no silhouette shows
         stay filled.  The defaults ``cell_opacity``, ``dilate`` and ``min_views`` are untuned
-        starting values."""
+        starting values.
+
+        ``color="visible"`` answers the second limit (K24): the carved cells, unmerged, form a tree
+        first; every cell that some camera can see through that tree (``visible_votes`` with the
+        same ``alpha_threshold`` and ``min_transmittance = visible_transmittance``) takes the mean
+        of those cameras alone, a cell none sees keeps the mean of all; then the merge passes run
+        as usual.  ``color="mean"`` is the tree described above, bit for bit.  The limits of
+        ``color_from_images`` apply."""
         who = "OcTree.build_from_silhouettes"
         depth, center, scale, batch_size, tolerances = OcTree._grid_arguments(
             who, "center has three components", depth, center, scale, batch_size,
@@ -1083,6 +1211,11 @@ class OcTree:
                              % (who, alpha_threshold))
         if not 0.0 <= cell_opacity < 1.0:
             raise ValueError("%s: cell_opacity must lie in [0, 1), got %r" % (who, cell_opacity))
+        if color not in ("mean", "visible"):
+            raise ValueError("%s: color is 'mean' or 'visible', got %r" % (who, color))
+        if color == "visible" and not 0.0 <= float(visible_transmittance) < 1.0:
+            raise ValueError("%s: visible_transmittance must lie in [0, 1), got %r"
+                             % (who, visible_transmittance))
         dilate, max_misses, min_views = int(dilate), int(max_misses), int(min_views)
         if dilate < 0 or max_misses < 0 or min_views < 0:
             raise ValueError("%s: dilate, max_misses and min_views must be >= 0, got %d, %d and %d"
@@ -1125,8 +1258,16 @@ class OcTree:
         if not kept_codes:
             raise ValueError("%s: no leaf (every cell of depth %d is carved away or seen by fewer "
                              "than %d cameras)" % (who, depth, min_views))
-        return OcTree._from_cells(torch.cat(kept_codes), torch.cat(kept_data), depth, scale,
-                                  center, tolerances, device)
+        codes, data = torch.cat(kept_codes), torch.cat(kept_data)
+        if color == "visible":
+            # the unmerged tree: every leaf on the finest level, where id order is code order
+            hull = OcTree._from_cells(codes, data, depth, scale, center, None, device)
+            votes = hull._visible_votes_on_device(images_u8, cameras, alpha_u8, center,
+                                                  float(visible_transmittance)).cpu().numpy()
+            rows = data.cpu().numpy()
+            rows[:, :3] = OcTree._vote_colors(votes, rows[:, :3])
+            data = torch.from_numpy(rows).to(device)
+        return OcTree._from_cells(codes, data, depth, scale, center, tolerances, device)
 
     @staticmethod
     def build_from_samples(positions, depth: int, min_leaf_size: int, data=None) -> "OcTree":

@@ -1542,3 +1542,98 @@ def octree_carve_select(images_u8: torch.Tensor, mask_u8: torch.Tensor, proj: to
     if want_visited:
         return codes[:k].clone(), data[:k].clone(), visited
     return codes[:k].clone(), data[:k].clone()
+
+
+# --------------------------------------------------------------------------------- K24
+def octree_visible_check(leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj,
+                         eyes, depth, alpha_u8, min_transmittance, out=None):
+    """The refusals of ``octree_visible_votes``, none of which needs a device: shapes, dtypes,
+    contiguity, the camera limit, finite ``proj`` and ``eyes`` (read back once), the scalars'
+    ranges.  Tensors on any device.  -> (L, C, H, W).  Raises ``ValueError`` naming the argument."""
+    who = "octree_visible_votes"
+
+    def want(name, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise ValueError("%s: %s must be a %s tensor, got %s"
+                             % (who, name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise ValueError("%s: %s must be (%s), got %s"
+                             % (who, name, ", ".join("*" if w is None else str(w) for w in shape),
+                                tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+
+    want("leaf_index", leaf_index, torch.int64, (None,))
+    leaves = leaf_index.shape[0]
+    if leaves < 1 or leaves > 1 << 31:
+        raise ValueError("%s: leaf_index holds %d leaves; 1 .. 2^31 are supported" % (who, leaves))
+    want("leaf_centers", leaf_centers, torch.float32, (leaves, 3))
+    stride, sigma_offset = int(stride), int(sigma_offset)
+    if stride < 1 or not 0 <= sigma_offset < stride:
+        raise ValueError("%s: stride >= 1 and 0 <= sigma_offset < stride, got stride %d, "
+                         "sigma_offset %d" % (who, stride, sigma_offset))
+    want("rows", rows, torch.float32, (leaves, stride))
+    want("images_u8", images_u8, torch.uint8, (None, None, None, 4))
+    cameras, height, width = images_u8.shape[:3]
+    limit = octree_carve_max_cameras()
+    if cameras < 1 or cameras > limit:
+        raise ValueError("%s: images_u8 holds %d cameras; 1 .. %d are supported (255 * C must be "
+                         "exact in f32)" % (who, cameras, limit))
+    if not 1 <= height <= 1 << 24 or not 1 <= width <= 1 << 24:
+        raise ValueError("%s: images_u8 must be (C, H, W, 4) with 1 <= H, W <= 2^24, got %s"
+                         % (who, tuple(images_u8.shape)))
+    want("proj", proj, torch.float32, (cameras, 3, 4))
+    want("eyes", eyes, torch.float32, (cameras, 3))
+    if not bool(torch.isfinite(proj).all()) or not bool(torch.isfinite(eyes).all()):
+        raise ValueError("%s: proj or eyes holds a NaN or an infinity" % who)
+    depth = int(depth)
+    if depth < 1 or depth > octree_max_depth():
+        raise ValueError("%s: depth %d is outside what the walk holds (1 .. %d)"
+                         % (who, depth, octree_max_depth()))
+    if not 1 <= int(alpha_u8) <= 255:
+        raise ValueError("%s: alpha_u8 must lie in 1 .. 255, got %r" % (who, alpha_u8))
+    _check_min_transmittance("octree visible_votes", min_transmittance)
+    if out is not None:
+        want("out", out, torch.uint32, (leaves, 4))
+    return leaves, cameras, height, width
+
+
+def octree_visible_votes(leaf_centers: torch.Tensor, scale: float, depth: int,
+                         node_index: torch.Tensor, leaf_index: torch.Tensor, rows: torch.Tensor,
+                         stride: int, sigma_offset: int, images_u8: torch.Tensor,
+                         proj: torch.Tensor, eyes: torch.Tensor, alpha_u8: int,
+                         min_transmittance: float,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K24.  Per leaf the sum of the pixels of the cameras that see it through the tree as it stands
+    -> (L,4) uint32 ``[sum_r, sum_g, sum_b, count]``.  ``leaf_centers`` (L,3) float32 from
+    ``octree_leaf_geometry`` (relative to the root cube's centre); ``rows`` / ``stride`` /
+    ``sigma_offset`` as for ``octree_leaf_weights`` (only the density is read); ``images_u8``
+    (C,H,W,4) uint8 RGBA; ``proj`` (C,3,4) float32 for cube-relative points
+    (``cameras.projection_matrices(cameras, origin=center)``) and ``eyes`` (C,3) float32
+    (``cameras.eye_positions(cameras, center)``).  Camera c votes for leaf l when the leaf's centre
+    projects (K23's operations) onto a pixel of image c whose alpha is ``>= alpha_u8`` and the ray
+    from the eye to the centre reaches the leaf before its transmittance, composited as
+    ``octree_leaf_weights`` does, falls to ``min_transmittance`` or below.  With ``out`` (L,4)
+    uint32 given the votes are ADDED to it (and it is returned): camera subsets folded in several
+    calls give the bits of one call, as long as at most ``octree_carve_max_cameras()`` cameras fold
+    into one buffer (the caller's count to keep).  Bad input is a ``ValueError``
+    (``octree_visible_check``)."""
+    leaves, cameras, height, width = octree_visible_check(
+        leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj, eyes, depth,
+        alpha_u8, min_transmittance, out)
+    dev = leaf_index.device
+    if out is None:
+        out = torch.zeros((leaves, 4), dtype=torch.uint32, device=dev)
+    # per camera 16 floats: P' row-major, the eye, one of padding
+    blocks = torch.cat([proj.reshape(cameras, 12), eyes,
+                        torch.zeros((cameras, 1), dtype=torch.float32, device=proj.device)],
+                       1).contiguous()
+    _call("ffn_octree_visible_votes", _dev(leaf_centers, name="leaf_centers"), c_i64(leaves),
+          c_f(scale), c_i(int(depth)),
+          _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+          c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),
+          _dev(rows, name="rows"), c_i(int(stride)), c_i(int(sigma_offset)),
+          _dev(images_u8, torch.uint8, "images_u8"), _dev(blocks, name="camera blocks"),
+          c_i(cameras), c_i(height), c_i(width), c_i(int(alpha_u8)), c_f(min_transmittance),
+          _dev(out, torch.uint32, "out"))
+    return out

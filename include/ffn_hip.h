@@ -1226,6 +1226,41 @@ int ffn_octree_carve_select(const uint8_t* images, const uint8_t* mask, const fl
                             float* rows, int* visited, int* codes_out, float* data_out,
                             int* total, void* stream);
 
+/* K24 (csrc/octree_walk.hip, an eleventh mode of the K13 kernel): which cameras see a leaf through
+ * the tree as it stands, and the sum of what they see there.  No counterpart in the reference.
+ * One lane per (leaf, camera) pair, the camera in blockIdx.y; no ray is ever stored.
+ * leaf_centers (num_leaves,3) f32 as ffn_octree_leaf_geometry writes them, relative to the root
+ * cube's centre; scale .. leaf_index as for ffn_octree_walk; leaf_data / stride / sigma_offset as
+ * for ffn_octree_leaf_weights (only the density is read).  images (cameras, height, width, 4) u8
+ * RGBA, 4-byte aligned.  camera_blocks (cameras, 16) f32: P' (3x4 row-major, cube-relative point ->
+ * homogeneous pixel), the eye relative to the cube's centre, one float of padding.  Pair (leaf l
+ * with centre p, camera c), every operation one rounded f32 operation (no fma):
+ *     x = ((P00 p.x + P01 p.y) + P02 p.z) + P03, likewise y (row 1) and w (row 2)
+ *     !(w > 0): no vote (NaN too).  fu = x / w + 0.5f, fv = y / w + 0.5f (IEEE divisions)
+ *     no vote unless fu >= 0 && fu < width && fv >= 0 && fv < height;  the pixel is
+ *     images[c, (int)fv, (int)fu], one aligned 4-byte load;  no vote if its alpha < alpha_u8
+ *     o = eye, d = p - o (the centre lies at t = 1), norm = sqrtf(d.x^2 + d.y^2 + d.z^2)
+ *     the K13 walk with t_min = 0 and T = 1; per leaf with t_exit > 0, in order:
+ *         leaf l itself: the pair is visible, the walk ends
+ *         t0 = max(t, 0);  L = (t_exit - t0) * norm;  sigma = fmaxf(density, 0);
+ *         a = 1 - expf(-(sigma * L));  T = T * (1 - a);  T <= min_transmittance: occluded, ends
+ *     a walk that ends without meeting l (a miss of the cube, the trip bound of K13) is not visible
+ * A visible pair adds the pixel's r, g, b and 1 to votes[l] = [sum_r, sum_g, sum_b, count] (uint32),
+ * as two 64-bit integer atomic adds of two fields each: exact, the same bits for the same pairs in
+ * any order, in one call or split over many.  votes (num_leaves,4) is 16-byte aligned; the caller
+ * zeroes it or lets calls fold into it, and keeps the cameras that fold into one buffer at or below
+ * ffn_octree_carve_max_cameras(), so that a sum stays below 2^24, the count below 2^17 and
+ * 255 count exact in f32 (the colour is (float)sum / (float)(255 count), as K23).
+ * 1 <= num_leaves <= 2^31, 1 <= depth <= 11, cameras >= 1 (launched 65535 at a time),
+ * 1 <= height, width <= 2^24, 1 <= alpha_u8 <= 255, 0 <= min_transmittance < 1, stride >= 1,
+ * 0 <= sigma_offset < stride; each refused by name before any launch. */
+int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, float scale, int depth,
+                             const int64_t* node_index, int64_t num_nodes,
+                             const int64_t* leaf_index, const float* leaf_data, int stride,
+                             int sigma_offset, const uint8_t* images, const float* camera_blocks,
+                             int cameras, int height, int width, int alpha_u8,
+                             float min_transmittance, uint32_t* votes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,10 @@ trained model in between.  No counterpart in the reference.
     python scripts/carve_octree.py data.npz tree.npz [--split train] [--voxel-depth 8]
         [--center X Y Z] [--scale S] [--alpha-threshold 0.5] [--dilate 1] [--max-misses 0]
         [--min-views 2] [--cell-opacity 0.5] [--merge-tolerance RGB SIGMA]
+        [--color {mean,visible}] [--visible-transmittance 0.3]
+
+``--color visible`` colours every carved cell from the cameras that can see it through the carved
+hull (kernel K24) instead of from all that look its way.
 """
 
 import os
@@ -36,6 +40,12 @@ CARVE_OCTREE = [
     ("--merge-tolerance", dict(type=float, nargs=2, default=None, metavar=("RGB", "SIGMA"),
                                help="Merge sibling cells that agree within these tolerances")),
     ("--batch-size", dict(type=int, default=1 << 20, help="Cells per kernel launch")),
+    ("--color", dict(choices=["mean", "visible"], default="mean",
+                     help="A cell's colour: the mean of every camera that looks at it, or of "
+                          "those that see it through the carved hull")),
+    ("--visible-transmittance", dict(type=float, default=0.3,
+                                     help="--color visible: a camera sees a cell while the "
+                                          "transmittance in front of it is above this")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -55,7 +65,8 @@ def main():
     print("Carving", 8 ** (args.voxel_depth - 1), "cells with", dataset.num_cameras, "cameras")
     tree = ffn.OcTree.build_from_silhouettes(
         dataset, args.voxel_depth, args.center, args.scale, args.alpha_threshold, args.dilate,
-        args.max_misses, args.min_views, args.cell_opacity, args.merge_tolerance, args.batch_size)
+        args.max_misses, args.min_views, args.cell_opacity, args.merge_tolerance, args.batch_size,
+        args.color, args.visible_transmittance)
     print(tree.num_leaves, "leaves")
     # the file format is the reference's and has no place for the root cube's centre
     print("root cube centre (for train_octree.py / render_octree.py): --center",
