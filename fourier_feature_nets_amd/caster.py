@@ -375,6 +375,10 @@ class Raycaster(nn.Module):
         self.train_occupancy_schedule = None
         self.train_occupancy_resolution = 128
         self.train_occupancy_threshold = 0.01
+        # OPT-IN: an OccupancyGrid that `fit` hands to its training engine before the first step
+        # (one made without a model: OccupancyGrid.from_octree / from_silhouettes, DESIGN K25).  A
+        # schedule, if also set, replaces it at its first rebuild.  None: nothing changes.
+        self.train_occupancy = None
 
     # ------------------------------------------------------------------ rendering
     def _flag(self, device):
@@ -584,10 +588,15 @@ class Raycaster(nn.Module):
         if self.train_occupancy_schedule is not None and isinstance(self.model, Voxels):
             raise NotImplementedError("train_occupancy_schedule (empty-space skipping during "
                                       "training) is not implemented for Voxels models")
+        if self.train_occupancy is not None and isinstance(self.model, Voxels):
+            raise NotImplementedError("train_occupancy (empty-space skipping during training) is "
+                                      "not implemented for Voxels models")
         trainval_dataset = train_dataset.sample_cameras(val_dataset.num_cameras,
                                                         val_dataset.num_samples, False)
         engine = TrainEngine(self.model, weight_decay, self.process_group)
         self.engine = engine
+        if self.train_occupancy is not None:
+            engine.occupancy = self.train_occupancy
         if self.process_group is not None:       # every rank starts from rank 0's weights
             root = torch.distributed.get_global_rank(self.process_group, 0)
             if engine._host_staged:

@@ -12,6 +12,7 @@
 //   K9f scatter_logits       packed logits back to (N,4); skipped samples get sigma logit -100
 //
 // All HBM-streaming, one thread per sample (ballot + popcount for the in-block ranks).
+// K25 (below K9g) makes the same bits from an octree's leaves instead of a density model.
 #include "common.h"
 #include "occupancy_map.h"
 
@@ -160,6 +161,151 @@ gather_logits_kernel(const float4* __restrict__ full, const int32_t* __restrict_
         packed[i] = full[index[i]];
 }
 
+// ---------------------------------------------------------------------------------- K25
+// Occupancy bits from an octree's leaves: the leaves' boxes rasterised into the grid in the
+// coordinate occupied_at truncates (grid_coord).  No counterpart in the reference.
+//
+//   K25a octree_cells_plan   per leaf: box -> index ranges, outside / threshold decision, rows
+//   K25s rows_tile_sums / K9d occupancy_scan / rows_offsets   exclusive scan of the row counts in
+//                            tiles of 4096 leaves, total (one read-back)
+//   K25b octree_cells_rows   per (leaf, iy, iz) row: one mask and one atomicOr per touched word
+//   K25c occupancy_or        dst |= src (folding a dilated raster into the caller's grid)
+constexpr int kOctLevels = 21;        // 8^21 < 2^63: the deepest id an int64 holds (K12k)
+
+// plan[leaf] = (ix0 | ix1 << 16, iy0, iz0, ny); rows[leaf] = ny * nz, 0 for a leaf that marks nothing
+__global__ void __launch_bounds__(256)
+octree_cells_plan_kernel(const int64_t* __restrict__ leaf_index, int64_t num_leaves, float scale,
+                         float ox, float oy, float oz, const float* __restrict__ leaf_data,
+                         int stride, int sigma_offset, float sigma_threshold, int use_threshold,
+                         GridMap map, int4* __restrict__ plan, int32_t* __restrict__ rows) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= num_leaves) return;
+    // the chain of K12k: +-scale / 2^k from 0, level by level from the root, every add rounded
+    int64_t id = leaf_index[i];
+    uint64_t digits = 0u;
+    int d = 0;
+    while (id > 0 && d < kOctLevels) {
+        digits |= (uint64_t)((id - 1) & 7) << (3 * d);
+        id = (id - 1) >> 3;
+        ++d;
+    }
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale;
+    for (int k = d - 1; k >= 0; --k) {
+        const int child = (int)((digits >> (3 * k)) & 7u);
+        half *= 0.5f;
+        cx = (child & 4) ? cx + half : cx - half;
+        cy = (child & 2) ? cy + half : cy - half;
+        cz = (child & 1) ? cz + half : cz - half;
+    }
+    const float c[3] = {cx, cy, cz}, o[3] = {ox, oy, oz};
+    const float lo[3] = {map.min0, map.min1, map.min2}, inv[3] = {map.inv0, map.inv1, map.inv2};
+    const float G = (float)map.G, top = (float)(map.G - 1);
+    bool marks = true;
+    int first[3], last[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float f_lo = grid_coord((c[a] - half) + o[a], lo[a], inv[a]);
+        const float f_hi = grid_coord((c[a] + half) + o[a], lo[a], inv[a]);
+        // [f_lo, f_hi) lies outside [0, G): nothing, where the clamp would mark a border cell
+        if (!(f_hi > 0.0f) || !(f_lo < G)) marks = false;
+        const float i0 = fminf(fmaxf(floorf(f_lo), 0.0f), top);
+        const float i1 = fminf(fmaxf(ceilf(f_hi) - 1.0f, 0.0f), top);
+        first[a] = (int)i0;
+        last[a] = max((int)i0, (int)i1);
+    }
+    // density <= threshold is empty; a NaN density stays occupied, as a NaN position does
+    if (use_threshold && leaf_data[i * stride + sigma_offset] <= sigma_threshold) marks = false;
+    const int ny = last[1] - first[1] + 1, nz = last[2] - first[2] + 1;
+    plan[i] = make_int4(first[0] | (last[0] << 16), first[1], first[2], ny);
+    rows[i] = marks ? ny * nz : 0;
+}
+
+// The scan of the row counts: per tile of 4096 leaves (256 threads x 16) its sum, K9d over the
+// tile sums (int64 total), then the offsets inside each tile.  A leaf has at most 2^20 rows, so a
+// thread's and a wave's sum fit an int32; a tile's may not, and saturates: the total then reaches
+// 2^31 - 1 and the call is refused.
+constexpr int kRowsTile = 4096;
+
+__global__ void __launch_bounds__(256)
+rows_tile_sums_kernel(const int32_t* __restrict__ rows, int64_t n, int32_t* __restrict__ tile_sums) {
+    __shared__ int wave_sums[4];
+    const int64_t first = (int64_t)blockIdx.x * kRowsTile + threadIdx.x * 16;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (first + k < n) s += rows[first + k];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane_id() == 0) wave_sums[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t all = ((int64_t)wave_sums[0] + wave_sums[1]) + ((int64_t)wave_sums[2] + wave_sums[3]);
+        tile_sums[blockIdx.x] = (int32_t)(all < 0x7fffffff ? all : 0x7fffffff);
+    }
+}
+
+// in place: rows[i] becomes the sum of everything before it
+__global__ void __launch_bounds__(256)
+rows_offsets_kernel(int32_t* rows, int64_t n, const int32_t* __restrict__ tile_offsets) {
+    __shared__ int wave_sums[4];
+    const int64_t first = (int64_t)blockIdx.x * kRowsTile + threadIdx.x * 16;
+    int local[16];
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        local[k] = first + k < n ? rows[first + k] : 0;
+        s += local[k];
+    }
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    int inc = s;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == 63) wave_sums[wave] = inc;
+    __syncthreads();
+    int run = tile_offsets[blockIdx.x] + inc - s;
+    for (int w = 0; w < wave; ++w) run += wave_sums[w];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (first + k < n) rows[first + k] = run;
+        run += local[k];
+    }
+}
+
+// one thread per row over all leaves' rows; offsets = the exclusive scan of rows
+__global__ void __launch_bounds__(256)
+octree_cells_rows_kernel(const int4* __restrict__ plan, const int32_t* __restrict__ offsets,
+                         int32_t num_leaves, int32_t total, int G, uint32_t* bits) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= total) return;
+    // the last leaf whose offset is <= r: a leaf without rows shares its offset with the next
+    int32_t lo = 0, hi = num_leaves;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)offsets[mid] <= r) lo = mid; else hi = mid;
+    }
+    const int4 p = plan[lo];
+    const int local = (int)(r - offsets[lo]);
+    const int ix0 = p.x & 0xffff, ix1 = p.x >> 16;
+    const int iy = p.y + local % p.w, iz = p.z + local / p.w;
+    const int64_t begin = ((int64_t)iz * G + iy) * G + ix0, end = begin + (ix1 - ix0);
+    const int64_t w0 = begin >> 5, w1 = end >> 5;
+    for (int64_t w = w0; w <= w1; ++w) {
+        // bits from..to of word w, both in 0..31: no shift by 32 for a whole word
+        const int from = w == w0 ? (int)(begin & 31) : 0, to = w == w1 ? (int)(end & 31) : 31;
+        const uint32_t mask = (0xffffffffu >> (31 - to)) & (0xffffffffu << from);
+        if ((bits[w] & mask) != mask) atomicOr(&bits[w], mask);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+occupancy_or_kernel(const uint32_t* __restrict__ src, int64_t words, uint32_t* __restrict__ dst) {
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words;
+         w += (int64_t)gridDim.x * blockDim.x)
+        dst[w] |= src[w];
+}
+
 }  // namespace ffn
 
 using namespace ffn;
@@ -235,6 +381,94 @@ extern "C" int ffn_gather_logits(const float* full, const int32_t* index, int64_
     hipLaunchKernelGGL(gather_logits_kernel, dim3(stream_grid(m)), dim3(256), 0, (hipStream_t)stream,
                        (const float4*)full, index, m, (float4*)packed);
     return check_launch("ffn_gather_logits");
+}
+
+extern "C" int ffn_occupancy_from_octree(const int64_t* leaf_index, int64_t num_leaves, float scale,
+                                         const float* center, const float* leaf_data, int stride,
+                                         int sigma_offset, float sigma_threshold, int use_threshold,
+                                         const float* box_min, const float* box_size,
+                                         int resolution, int accumulate, int dilate, int32_t* plan,
+                                         int32_t* row_offsets, int32_t* tile_sums,
+                                         int64_t* total, uint32_t* scratch_bits, uint32_t* bits, void* stream) {
+    const char* who = "ffn_occupancy_from_octree";
+    if (resolution < 1 || resolution > 1024) return fail_arg("ffn_occupancy_from_octree: resolution");
+    if (num_leaves < 1 || num_leaves > 0x7fffffff)
+        return fail_arg("ffn_occupancy_from_octree: num_leaves");
+    if (!leaf_index || !center || !box_min || !box_size || !plan || !row_offsets || !tile_sums ||
+        !total || !bits)
+        return fail_arg("ffn_occupancy_from_octree: null argument");
+    if ((uintptr_t)plan & 15) return fail_arg("ffn_occupancy_from_octree: plan is 16-byte aligned");
+    if (!(scale > 0.0f) || !(scale <= 3.402823466e38f))
+        return fail_arg("ffn_occupancy_from_octree: scale");
+    for (int a = 0; a < 3; ++a) {
+        if (!(box_size[a] > 0.0f) || !(box_size[a] <= 3.402823466e38f) ||
+            !(fabsf(box_min[a]) <= 3.402823466e38f))
+            return fail_arg("ffn_occupancy_from_octree: box");
+        if (!(fabsf(center[a]) <= 3.402823466e38f))
+            return fail_arg("ffn_occupancy_from_octree: center");
+    }
+    if (leaf_data && (stride < 1 || sigma_offset < 0 || sigma_offset >= stride))
+        return fail_arg("ffn_occupancy_from_octree: stride >= 1, 0 <= sigma_offset < stride");
+    if (use_threshold && !leaf_data)
+        return fail_arg("ffn_occupancy_from_octree: a threshold needs leaf_data");
+    if (use_threshold && sigma_threshold != sigma_threshold)
+        return fail_arg("ffn_occupancy_from_octree: sigma_threshold");
+    if (dilate < 0) return fail_arg("ffn_occupancy_from_octree: dilate");
+    if (dilate > 0 && !scratch_bits) return fail_arg("ffn_occupancy_from_octree: dilation needs scratch");
+
+    const int64_t cells = (int64_t)resolution * resolution * resolution;
+    const int64_t words = (cells + 31) >> 5;
+    hipStream_t st = (hipStream_t)stream;
+    const GridMap map = make_map(box_min, box_size, resolution);
+    // where the leaves are rasterised: with dilation the passes alternate between two buffers and
+    // must end in `bits` (fresh grid) or beside it, to be folded in (accumulate)
+    uint32_t* raster = bits;
+    uint32_t* other = scratch_bits;
+    if (dilate > 0 && accumulate) {
+        raster = scratch_bits;
+        other = scratch_bits + words;
+    } else if (dilate & 1) {
+        raster = scratch_bits;
+        other = bits;
+    }
+    hipError_t err = hipSuccess;
+    if (raster != bits || !accumulate) err = hipMemsetAsync(raster, 0, (size_t)words * 4, st);
+    if (err != hipSuccess) { set_error(who, err); return (int)err; }
+
+    const unsigned leaf_blocks = (unsigned)((num_leaves + 255) / 256);
+    hipLaunchKernelGGL(octree_cells_plan_kernel, dim3(leaf_blocks), dim3(256), 0, st, leaf_index,
+                       num_leaves, scale, center[0], center[1], center[2], leaf_data, stride,
+                       sigma_offset, sigma_threshold, use_threshold ? 1 : 0, map, (int4*)plan,
+                       row_offsets);
+    const unsigned tiles = (unsigned)((num_leaves + kRowsTile - 1) / kRowsTile);
+    hipLaunchKernelGGL(rows_tile_sums_kernel, dim3(tiles), dim3(256), 0, st, row_offsets, num_leaves,
+                       tile_sums);
+    hipLaunchKernelGGL(occupancy_scan_kernel, dim3(1), dim3(1024), 0, st, tile_sums, (int)tiles,
+                       total);
+    hipLaunchKernelGGL(rows_offsets_kernel, dim3(tiles), dim3(256), 0, st, row_offsets, num_leaves,
+                       tile_sums);
+    int64_t host_total = 0;
+    err = hipMemcpyAsync(&host_total, total, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) { set_error(who, err); return (int)err; }
+    // the scan keeps its offsets in int32 (and a tile sum saturates at 2^31 - 1)
+    if (host_total < 0 || host_total >= 0x7fffffff)
+        return fail_arg("ffn_occupancy_from_octree: too many rows");
+    if (host_total > 0) {
+        const unsigned row_blocks = (unsigned)((host_total + 255) / 256);
+        hipLaunchKernelGGL(octree_cells_rows_kernel, dim3(row_blocks), dim3(256), 0, st,
+                           (const int4*)plan, row_offsets, (int32_t)num_leaves, (int32_t)host_total,
+                           resolution, raster);
+    }
+    for (int pass = 0; pass < dilate; ++pass) {
+        hipLaunchKernelGGL(occupancy_dilate_kernel, dim3(stream_grid(words)), dim3(256), 0, st,
+                           raster, resolution, other);
+        uint32_t* swap = raster; raster = other; other = swap;
+    }
+    if (raster != bits)
+        hipLaunchKernelGGL(occupancy_or_kernel, dim3(stream_grid(words)), dim3(256), 0, st, raster,
+                           words, bits);
+    return check_launch(who);
 }
 
 // ---------------------------------------------------------------------------------- K10

@@ -27,6 +27,15 @@ __device__ __forceinline__ bool occupied_at(const GridMap& m, const uint32_t* __
     return (bits[cell >> 5] >> (cell & 31)) & 1u;
 }
 
+// One axis of the grid coordinate occupied_at truncates: fl(fl(x - min) * inv), each operation
+// rounded on its own.  K25 rasterises leaf boxes in this coordinate, so that a cell it marks is
+// the cell occupied_at looks up.
+__device__ __forceinline__ float grid_coord(float x, float box_min, float inv) {
+#pragma clang fp contract(off)
+    const float shifted = x - box_min;
+    return shifted * inv;
+}
+
 static inline GridMap make_map(const float* box_min, const float* box_size, int G) {
     GridMap m;
     m.min0 = box_min[0]; m.min1 = box_min[1]; m.min2 = box_min[2];

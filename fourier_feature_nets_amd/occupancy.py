@@ -85,6 +85,104 @@ class OccupancyGrid:
         bits = ops.occupancy_build(logits, g, float(sigma_threshold), bool(dilate))
         return cls(bits, lo, size, g)
 
+    @classmethod
+    def from_octree(cls, tree, bounds: np.ndarray, resolution: int = 128, center=None,
+                    sigma_threshold: Optional[float] = None, dilate: int = 1,
+                    out: Optional["OccupancyGrid"] = None) -> "OccupancyGrid":
+        """Grid from an ``OcTree``'s leaves (K25): their boxes rasterised into the bits, no model
+        and no cell-centre sampling involved, so a leaf smaller than a cell still marks its cell.
+
+        ``center`` is the root cube's centre in the frame of ``bounds`` (default ``tree.center``,
+        which a loaded tree does not have).  A leaf marks every cell that meets its half-open box
+        in grid coordinates; every point the lookup of ``compact`` / the fused render places in
+        ``[f(lo), f(hi))`` of a marking leaf is reported occupied (``ffn_occupancy_from_octree`` in
+        include/ffn_hip.h states the rule).  The points left out lie within rounding of a + face:
+        ``dilate`` (n passes of the 26-neighbourhood, default 1) is the slack for those and for
+        structure the tree itself missed.  With ``sigma_threshold`` a leaf whose density is
+        ``<= sigma_threshold`` marks nothing (a NaN density marks); plain ``[r, g, b, sigma]`` and
+        SH trees alike.  A tree without a density column (the 3-channel shells of
+        ``voxelize_model.py``) marks with every leaf and refuses a threshold.  ``out``: an
+        ``OccupancyGrid`` over the same box and resolution to fold into (several trees, or leaf
+        subsets, give the bits of one call); it is returned."""
+        who = "OccupancyGrid.from_octree"
+        center = tree.center if center is None else center
+        if center is None:
+            raise ValueError("%s: a loaded tree does not know its root cube's centre; pass "
+                             "center=(x, y, z)" % who)
+        center = tuple(float(np.float32(c)) for c in center)
+        if len(center) != 3:
+            raise ValueError("%s: center has three components" % who)
+        lo, size = cls.box_of(bounds)
+        g = int(resolution)
+        data = tree.leaf_data()
+        has_density = data is not None and np.ndim(data) == 2 and np.shape(data)[1] >= 4
+        if sigma_threshold is not None and not has_density:
+            raise ValueError("%s: sigma_threshold needs a density, and this tree's leaf_data %s "
+                             "holds none" % (who, None if data is None else np.shape(data)))
+        if out is not None:
+            same = (isinstance(out, OccupancyGrid) and out.resolution == g
+                    and np.array_equal(np.float32(out.box_min), np.float32(lo))
+                    and np.array_equal(np.float32(out.box_size), np.float32(size)))
+            if not same:
+                raise ValueError("%s: out must be an OccupancyGrid over the same box and "
+                                 "resolution (%s + %s at %d)" % (who, list(lo), list(size), g))
+        # refuse bad arguments before any device is needed
+        ops.occupancy_from_octree_check(torch.from_numpy(tree._leaf_index), tree.scale, center, lo,
+                                        size, g, dilate=dilate,
+                                        out=None if out is None else out.bits)
+        if sigma_threshold is not None and np.isnan(float(sigma_threshold)):
+            raise ValueError("%s: sigma_threshold is NaN" % who)
+        rows, stride, offset = None, 4, 3
+        if sigma_threshold is None:
+            pass                                  # nothing of the rows is read
+        elif tree.sh_degree is not None:
+            rows, offset = tree._sh_rows_on_device(), 0
+            stride = int(rows.shape[1])
+        else:
+            rows = tree._colors_on_device()
+            stride = int(rows.shape[1])
+        bits = ops.occupancy_from_octree(tree._on_device("leaf_index"), tree.scale, center, lo, size,
+                                         g, rows, stride, offset, sigma_threshold, dilate,
+                                         None if out is None else out.bits)
+        if out is not None:
+            return out
+        return cls(bits, lo, size, g)
+
+    @classmethod
+    def from_silhouettes(cls, dataset, bounds: Optional[np.ndarray] = None, resolution: int = 128,
+                         depth: int = 8, dilate: int = 1, **carve_kwargs) -> "OccupancyGrid":
+        """Grid from the training images alone: ``OcTree.build_from_silhouettes`` (K23) carves the
+        visual hull, ``from_octree`` rasterises it, no density threshold.  Empty-space skipping
+        from step 0 of a training run then needs nothing but the dataset.
+
+        ``bounds`` defaults to ``dataset.sampler.bounds``; the root cube is the box's centre +-
+        half its longest side.  ``carve_kwargs`` go to ``build_from_silhouettes``
+        (``alpha_threshold``, ``dilate``, ``max_misses``, ``min_views``, ...).
+
+        What a hull is and is not.  It is the intersection of the silhouettes' cones: in the limit
+        of many views it is conservative, it contains the object.  Concavities that no silhouette
+        shows stay filled, which is harmless for skipping: those cells are evaluated and learn
+        density 0.  But the carve samples each cell at its centre only, and can lose structure
+        thinner than a cell or than a pixel's footprint, which is NOT harmless: density in a cell
+        the grid leaves empty is never trained.  ``dilate`` here (grid cells) and ``dilate`` /
+        ``max_misses`` of the carve (pixels, cameras) are the slack."""
+        from .octree import OcTree
+        who = "OccupancyGrid.from_silhouettes"
+        if bounds is None:
+            sampler = getattr(dataset, "sampler", None)
+            bounds = getattr(sampler, "bounds", None)
+            if bounds is None:
+                raise ValueError("%s: the dataset has no sampler.bounds; pass bounds" % who)
+        for taken in ("center", "scale"):
+            if taken in carve_kwargs:
+                raise ValueError("%s: %s comes from bounds (the box's centre, half its longest "
+                                 "side); it cannot be passed" % (who, taken))
+        lo, size = cls.box_of(bounds)
+        center = tuple(float(v) for v in lo + 0.5 * size)
+        scale = 0.5 * float(size.max())
+        tree = OcTree.build_from_silhouettes(dataset, depth, center, scale, **carve_kwargs)
+        return cls.from_octree(tree, bounds, resolution, dilate=dilate)
+
     def fraction_occupied(self) -> float:
         """Share of cells marked occupied (diagnostic; one sync)."""
         cells = self.resolution ** 3

@@ -373,6 +373,93 @@ def occupancy_compact(positions: torch.Tensor, views: Optional[torch.Tensor], bo
     return out_pos, out_view, index
 
 
+def occupancy_from_octree_check(leaf_index, scale, center, box_min, box_size, resolution,
+                                rows=None, stride=4, sigma_offset=3, sigma_threshold=None,
+                                dilate=0, out=None) -> int:
+    """The refusals of ``occupancy_from_octree``, none of which needs a device.  Tensors on any
+    device.  -> the number of int32 words of the grid.  Raises ``ValueError`` naming the argument."""
+    who = "occupancy_from_octree"
+    resolution = int(resolution)
+    if not 1 <= resolution <= 1024:
+        raise ValueError("%s: resolution must lie in 1 .. 1024, got %d" % (who, resolution))
+    if (not torch.is_tensor(leaf_index) or leaf_index.dtype != torch.int64 or leaf_index.dim() != 1
+            or not 1 <= leaf_index.shape[0] < 1 << 31):
+        raise ValueError("%s: leaf_index must be a (L,) int64 tensor of 1 .. 2^31 - 1 leaves" % who)
+    scale = float(np.float32(scale))
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("%s: scale must be finite and positive, got %r" % (who, scale))
+    for name, vec in (("center", center), ("box_min", box_min), ("box_size", box_size)):
+        vec = [float(np.float32(v)) for v in vec]
+        if len(vec) != 3 or not all(math.isfinite(v) for v in vec):
+            raise ValueError("%s: %s must be three finite numbers, got %r" % (who, name, vec))
+        if name == "box_size" and not all(v > 0 for v in vec):
+            raise ValueError("%s: box_size must be positive, got %r" % (who, vec))
+    if rows is None:
+        if sigma_threshold is not None:
+            raise ValueError("%s: sigma_threshold needs the leaves' density (rows); this tree has "
+                             "none" % who)
+    else:
+        stride, sigma_offset = int(stride), int(sigma_offset)
+        if stride < 1 or not 0 <= sigma_offset < stride:
+            raise ValueError("%s: stride >= 1 and 0 <= sigma_offset < stride, got stride %d, "
+                             "sigma_offset %d" % (who, stride, sigma_offset))
+        if (not torch.is_tensor(rows) or rows.dtype != torch.float32
+                or tuple(rows.shape) != (leaf_index.shape[0], stride)):
+            raise ValueError("%s: rows must be (%d, %d) float32, got %s"
+                             % (who, leaf_index.shape[0], stride,
+                                tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__))
+    if sigma_threshold is not None and math.isnan(float(sigma_threshold)):
+        raise ValueError("%s: sigma_threshold is NaN" % who)
+    if int(dilate) != dilate or int(dilate) < 0:
+        raise ValueError("%s: dilate must be an integer >= 0, got %r" % (who, dilate))
+    words = (resolution ** 3 + 31) // 32
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.int32
+                            or tuple(out.shape) != (words,)):
+        raise ValueError("%s: out must be the (%d,) int32 words of a resolution %d grid, got %s"
+                         % (who, words, resolution,
+                            (out.dtype, tuple(out.shape)) if torch.is_tensor(out) else type(out).__name__))
+    return words
+
+
+def occupancy_from_octree(leaf_index: torch.Tensor, scale: float, center, box_min, box_size,
+                          resolution: int, rows: Optional[torch.Tensor] = None, stride: int = 4,
+                          sigma_offset: int = 3, sigma_threshold: Optional[float] = None,
+                          dilate: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K25.  The boxes of an octree's leaves rasterised into a K9 grid -> bit mask
+    (ceil(G^3/32),) int32, as ``occupancy_build`` returns.  ``leaf_index`` (L,) int64 sorted ids,
+    ``scale`` and ``center`` the root cube; ``box_min`` / ``box_size`` the grid's box.  A leaf marks
+    every cell that meets its half-open box in grid coordinates (``ffn_occupancy_from_octree`` in
+    include/ffn_hip.h states the rule and what it guarantees).  ``rows`` (L, stride) float32 with the
+    density at ``sigma_offset`` and ``sigma_threshold``: leaves with density <= threshold mark
+    nothing (NaN marks); without ``rows`` every leaf marks.  ``dilate`` = n passes of the
+    26-neighbourhood dilation over what this call marks.  With ``out`` (a tensor this function
+    returned for the same resolution) the cells are ORed into it and it is returned: leaf subsets
+    or several trees folded over several calls give the bits of one call.  One device-to-host sync
+    (the row count sizes the second launch).  Bad input is a ``ValueError``
+    (``occupancy_from_octree_check``)."""
+    words = occupancy_from_octree_check(leaf_index, scale, center, box_min, box_size, resolution,
+                                        rows, stride, sigma_offset, sigma_threshold, dilate, out)
+    dev = leaf_index.device
+    leaves, dilate = leaf_index.shape[0], int(dilate)
+    bits = out if out is not None else torch.empty((words,), dtype=torch.int32, device=dev)
+    plan = torch.empty((leaves, 4), dtype=torch.int32, device=dev)
+    offsets = torch.empty((leaves,), dtype=torch.int32, device=dev)
+    tiles = torch.empty(((leaves + 4095) // 4096,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int64, device=dev)
+    scratch = None
+    if dilate > 0:
+        scratch = torch.empty((words * (2 if out is not None else 1),), dtype=torch.int32, device=dev)
+    use = sigma_threshold is not None
+    _call("ffn_occupancy_from_octree", _dev(leaf_index, torch.int64, "leaf_index"), c_i64(leaves),
+          c_f(scale), _host3(center), _dev(rows, name="rows"), c_i(int(stride)),
+          c_i(int(sigma_offset)), c_f(float(sigma_threshold) if use else 0.0), c_i(1 if use else 0),
+          _host3(box_min), _host3(box_size), c_i(int(resolution)), c_i(0 if out is None else 1),
+          c_i(dilate), _dev(plan, torch.int32, "plan"), _dev(offsets, torch.int32, "offsets"),
+          _dev(tiles, torch.int32, "tiles"),
+          _dev(total, torch.int64, "total"), _dev(scratch, torch.int32), _dev(bits, torch.int32, "out"))
+    return bits
+
+
 def scatter_logits(packed: torch.Tensor, index: torch.Tensor, n: int,
                    empty_sigma_logit: float = -100.0) -> torch.Tensor:
     """K9f.  (M,4) logits of the evaluated samples -> (N,4), the rest (0,0,0,empty_sigma_logit)."""

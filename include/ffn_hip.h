@@ -1261,6 +1261,53 @@ int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, floa
                              int cameras, int height, int width, int alpha_u8,
                              float min_transmittance, uint32_t* votes, void* stream);
 
+/* K25 (csrc/occupancy.hip, beside K9a / K9b): the occupancy grid of K9 from an octree's leaves, the
+ * leaves' boxes rasterised into the bits.  No counterpart in the reference.
+ * leaf_index (num_leaves) sorted int64 ids, scale as for ffn_octree_leaf_geometry; center, box_min,
+ * box_size are HOST pointers to 3 floats (the root cube's centre; the grid's box as for
+ * ffn_occupancy_count).  Every operation below is one rounded f32 operation (no fma).
+ *   Leaf: centre c and depth d by the chain of ffn_octree_leaf_geometry, h = scale 2^-d (exact);
+ *     per axis lo = (c - h) + center, hi = (c + h) + center.
+ *   Grid coordinate: f(x) = (x - box_min) * inv with inv = (float)G / box_size -- the very number
+ *     the K9 lookup truncates for a sample at x.
+ *   Cells: per axis the leaf covers the half-open interval [f(lo), f(hi)) of grid coordinates and
+ *     marks every cell [i, i + 1) that meets it: i0 = clamp(floor(f(lo)), 0, G - 1),
+ *     i1 = max(i0, clamp(ceil(f(hi)) - 1, 0, G - 1)).  A leaf with !(f(hi) > 0) or !(f(lo) < G) on
+ *     any axis lies outside the box and marks nothing.  Half-open in GRID coordinates: a leaf
+ *     whose + face falls on a cell boundary (every leaf, when the box is the root cube and G a
+ *     power of two) does not mark the neighbour beyond it.
+ *   Density: with leaf_data (num_leaves, stride) given and use_threshold != 0 a leaf whose
+ *     leaf_data[l, sigma_offset] <= sigma_threshold marks nothing; a NaN density marks.
+ *     leaf_data NULL: every leaf marks (use_threshold != 0 is then refused).
+ * Guarantee: f is monotone, so every f32 point p with f(lo) <= f(p) < f(hi) on all three axes, for
+ * a leaf that marks, is reported occupied by the K9 lookup (ffn_occupancy_count / _compact, the
+ * fused render).  The points of a leaf left out are within rounding of a + face; `dilate` is the
+ * slack for those and for what the tree itself missed.
+ * Work: one thread per leaf plans (index ranges; ny nz rows, 0 for a leaf that marks nothing), the
+ * row counts are scanned into offsets (tiles of 4096 leaves round the K9d scan; one read-back of
+ * their sum, refused from 2^31 - 1 on: "too many rows"), then one thread per row ORs the run [(iz G + iy) G + ix0 .. + ix1] into the
+ * grid, one 32-bit mask and at most one integer atomic OR per touched word (<= G / 32 + 2 words a
+ * thread).  Integer OR: the same bits in any order, on every call.
+ * accumulate == 0: bits (ceil(G^3 / 32) words) is zeroed first.  accumulate != 0: the cells are
+ * ORed into what bits holds, so leaf subsets or several trees folded over several calls give the
+ * bits of one call -- also with dilation, which distributes over OR.
+ * dilate = n >= 0: n passes of the 26-neighbourhood dilation of ffn_occupancy_build over what
+ * THIS call rasterised; the result lands in bits for every n.  scratch_bits: NULL for n = 0, else
+ * as many words as bits, twice as many with accumulate.
+ * Workspace (device): plan 4 int32 per leaf, 16-byte aligned; row_offsets 1 int32 per leaf;
+ * tile_sums ceil(num_leaves / 4096) int32; total one int64.  Refused by name before any launch:
+ * resolution outside 1 .. 1024, num_leaves outside 1 .. 2^31 - 1, a null pointer, scale or
+ * box_size not finite and positive, center or box_min not finite, stride < 1 or sigma_offset
+ * outside 0 .. stride - 1, a threshold that is NaN or has no leaf_data, dilate < 0, dilation
+ * without scratch. */
+int ffn_occupancy_from_octree(const int64_t* leaf_index, int64_t num_leaves, float scale,
+                              const float* center, const float* leaf_data, int stride,
+                              int sigma_offset, float sigma_threshold, int use_threshold,
+                              const float* box_min, const float* box_size, int resolution,
+                              int accumulate, int dilate, int32_t* plan, int32_t* row_offsets,
+                              int32_t* tile_sums, int64_t* total, uint32_t* scratch_bits,
+                              uint32_t* bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,17 @@ TRAIN_COMMON = [
     ("--skip-refresh", dict(type=int, default=500)),
     FOCUS_MODE,
 ]
+# not flags of the reference either: a grid that needs no model, imposed from step 0 (DESIGN K25),
+# from a saved octree or carved from the training images' silhouettes at this depth (0 = off).  A
+# table of its own, appended by the two NeRF drivers: TRAIN_COMMON stays what it was
+SKIP_GRID = [
+    ("--skip-tree", dict(help="octree NPZ whose leaves become the occupancy grid")),
+    ("--skip-tree-center", dict(type=float, nargs=3, metavar=("X", "Y", "Z"),
+                                help="the root cube's centre of --skip-tree")),
+    ("--skip-carve-depth", dict(type=int, default=0)),
+    ("--skip-resolution", dict(type=int, default=128)),
+    ("--skip-dilate", dict(type=int, default=1)),
+]
 NERF_ONLY = [
     ("--resolution", dict(type=int, default=400)),
     ("--num-cameras", dict(type=int, default=100)),
@@ -228,10 +239,39 @@ def focus_mode(args) -> str:
     return "live" if mode == "auto" else mode
 
 
-def apply_skipping(caster, args):
-    """--skip-empty-space: the opt-in occupancy-grid schedule of Raycaster.fit."""
+def apply_skipping(caster, args, train=None):
+    """--skip-empty-space: the opt-in occupancy-grid schedule of Raycaster.fit.  --skip-tree /
+    --skip-carve-depth: a grid that needs no model (DESIGN K25), from a saved octree or carved
+    from the training images' silhouettes, imposed from step 0.  Such a grid goes to training AND
+    to rendering: a model trained under a grid has learned nothing about the cells it leaves out,
+    so it must be rendered under the same grid (scripts/skip_training_demo.py)."""
     if getattr(args, "skip_empty_space", False):
         caster.train_occupancy_schedule = (args.skip_warmup, args.skip_refresh)
+    tree_path = getattr(args, "skip_tree", None)
+    carve_depth = getattr(args, "skip_carve_depth", 0)
+    if tree_path is None and not carve_depth:
+        return caster
+    if tree_path is not None and carve_depth:
+        raise SystemExit("--skip-tree and --skip-carve-depth are two sources of one grid: pass one")
+    if train is None:
+        raise SystemExit("--skip-tree / --skip-carve-depth need the training dataset")
+    import fourier_feature_nets_amd as ffn
+    if tree_path is not None:
+        tree = ffn.OcTree.load(tree_path)
+        if tree is None:
+            raise SystemExit("--skip-tree: cannot read %s" % tree_path)
+        if args.skip_tree_center is None:
+            raise SystemExit("--skip-tree needs --skip-tree-center X Y Z: a saved tree does not "
+                             "hold its root cube's centre")
+        grid = ffn.OccupancyGrid.from_octree(tree, train.sampler.bounds, args.skip_resolution,
+                                             center=args.skip_tree_center, dilate=args.skip_dilate)
+    else:
+        grid = ffn.OccupancyGrid.from_silhouettes(train, resolution=args.skip_resolution,
+                                                  depth=carve_depth, dilate=args.skip_dilate)
+    print("empty-space skipping from step 0: %.4f of the %d^3 cells occupied"
+          % (grid.fraction_occupied(), grid.resolution))
+    caster.train_occupancy = grid
+    caster.occupancy = grid
     return caster
 
 

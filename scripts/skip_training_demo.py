@@ -21,7 +21,7 @@ import bench as B  # noqa: E402
 import fourier_feature_nets_amd as ffn  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1200)
     ap.add_argument("--rays", type=int, default=16384)
@@ -29,8 +29,12 @@ def main():
     ap.add_argument("--size", type=int, default=200)
     ap.add_argument("--warm", type=int, default=300, help="recipe C: full steps before the first grid")
     ap.add_argument("--refresh", type=int, default=300, help="recipe C: steps between grid rebuilds")
-    args = ap.parse_args()
-    dev = torch.device("cuda:0")
+    return ap.parse_args(argv)
+
+
+def make_scene(args, dev):
+    """The protocol's scene (also scripts/skip_from_silhouettes_demo.py): the training dataset, the
+    held-out sampler and frames, the valid ray ids and the analytic sphere grid."""
     intr, poses = B.synthetic_rig(args.cameras + 4, args.size)
     cams = [ffn.CameraInfo.create("c%03d" % i, ffn.Resolution(args.size, args.size), intr, p)
             for i, p in enumerate(poses)]
@@ -51,48 +55,73 @@ def main():
     sphere[:, 3] = torch.where(centres.norm(dim=1) < 0.6, 10.0, -30.0)
     analytic = ffn.OccupancyGrid.from_logits(sphere, bounds, 128, 0.01, True)
     del centres, sphere
+    return argparse.Namespace(bounds=bounds, train=train, val_sampler=val_sampler, val_images=val_images,
+                              valid=valid, held=held, train_ids=train_ids, analytic=analytic)
 
-    def psnr(model, grid=None):
-        caster = ffn.Raycaster(model)       # grid None = full render: every sample evaluated
-        caster.occupancy = grid
-        mse = 0.0
-        for f in range(len(held)):
-            frame = caster.render_image(val_sampler, f, 65536).astype(np.float32) / 255
-            mse += float(np.mean((frame - val_images[f]) ** 2))
-        return -10 * np.log10(mse / len(held))
 
-    results = {}
-    for label in ("A_full", "B_analytic_grid", "C_model_grid_refreshed"):
-        torch.manual_seed(20080524)
-        model = ffn.PositionalFourierMLP(3, 4, 5.5).to(dev)
-        engine = ffn.TrainEngine(model, 0.0, None)
-        gen = torch.Generator(device=dev).manual_seed(1)
-        if label == "B_analytic_grid":
-            engine.occupancy = analytic
-        fractions = []
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for step in range(args.steps):
-            if label == "C_model_grid_refreshed" and step >= args.warm and (step - args.warm) % args.refresh == 0:
-                engine.occupancy = ffn.OccupancyGrid.from_model(model, bounds, 128, 0.01, True)
-            pick = torch.randint(0, valid.numel(), (args.rays,), generator=gen, device=dev)
-            lr = 5e-4 * 0.1 ** (step / 25000)
-            engine.train_step(train, valid[pick], step, lr)
-            if engine.occupancy is not None and step % 50 == 0:
-                fractions.append(engine.last_evaluated_fraction)
-        torch.cuda.synchronize()
-        seconds = time.perf_counter() - t0
-        engine.check_finite()
-        results[label] = {"val_psnr_db_full_render": round(psnr(model), 3),
-                          "val_psnr_db_rendered_with_its_grid": (round(psnr(model, engine.occupancy), 3)
-                                                                 if engine.occupancy is not None else None),
-                          "train_seconds": round(seconds, 2),
-                          "ms_per_step": round(1e3 * seconds / args.steps, 3),
-                          "mean_evaluated_sample_fraction": (round(float(np.mean(fractions)), 4)
-                                                             if fractions else 1.0)}
-    out = {"scene": "synthetic shaded sphere r=0.6, %d train / %d held-out cameras %dx%d, 64 samples/ray, "
-                    "%d rays/step, %d steps, tiny NeRF" % (len(train_ids), len(held), args.size, args.size,
-                                                          args.rays, args.steps),
+def psnr(scene, model, grid=None):
+    caster = ffn.Raycaster(model)       # grid None = full render: every sample evaluated
+    caster.occupancy = grid
+    mse = 0.0
+    for f in range(len(scene.held)):
+        frame = caster.render_image(scene.val_sampler, f, 65536).astype(np.float32) / 255
+        mse += float(np.mean((frame - scene.val_images[f]) ** 2))
+    return -10 * np.log10(mse / len(scene.held))
+
+
+def run_arm(scene, args, dev, grid=None, rebuild=None):
+    """One training run of the protocol from the shared seeds.  ``grid``: imposed from step 0;
+    ``rebuild(model, step)``: a grid to switch to before that step, or None."""
+    torch.manual_seed(20080524)
+    model = ffn.PositionalFourierMLP(3, 4, 5.5).to(dev)
+    engine = ffn.TrainEngine(model, 0.0, None)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    if grid is not None:
+        engine.occupancy = grid
+    fractions = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for step in range(args.steps):
+        fresh = rebuild(model, step) if rebuild is not None else None
+        if fresh is not None:
+            engine.occupancy = fresh
+        pick = torch.randint(0, scene.valid.numel(), (args.rays,), generator=gen, device=dev)
+        lr = 5e-4 * 0.1 ** (step / 25000)
+        engine.train_step(scene.train, scene.valid[pick], step, lr)
+        if engine.occupancy is not None and step % 50 == 0:
+            fractions.append(engine.last_evaluated_fraction)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    engine.check_finite()
+    return {"val_psnr_db_full_render": round(psnr(scene, model), 3),
+            "val_psnr_db_rendered_with_its_grid": (round(psnr(scene, model, engine.occupancy), 3)
+                                                   if engine.occupancy is not None else None),
+            "train_seconds": round(seconds, 2),
+            "ms_per_step": round(1e3 * seconds / args.steps, 3),
+            "mean_evaluated_sample_fraction": (round(float(np.mean(fractions)), 4)
+                                               if fractions else 1.0)}
+
+
+def scene_line(scene, args):
+    return ("synthetic shaded sphere r=0.6, %d train / %d held-out cameras %dx%d, 64 samples/ray, "
+            "%d rays/step, %d steps, tiny NeRF" % (len(scene.train_ids), len(scene.held), args.size,
+                                                  args.size, args.rays, args.steps))
+
+
+def main():
+    args = parse_args()
+    dev = torch.device("cuda:0")
+    scene = make_scene(args, dev)
+
+    def refreshed(model, step):
+        if step >= args.warm and (step - args.warm) % args.refresh == 0:
+            return ffn.OccupancyGrid.from_model(model, scene.bounds, 128, 0.01, True)
+        return None
+
+    results = {"A_full": run_arm(scene, args, dev),
+               "B_analytic_grid": run_arm(scene, args, dev, grid=scene.analytic),
+               "C_model_grid_refreshed": run_arm(scene, args, dev, rebuild=refreshed)}
+    out = {"scene": scene_line(scene, args),
            "note": "A = reference-exact optimisation step; B, C = opt-in empty-space skipping during "
                    "training (samples in empty cells are sigma = 0 constants).  A grid that is imposed "
                    "from step 0 (B) leaves the density outside it untrained, so such a model must be "

@@ -12,7 +12,7 @@ from scripts import _cli  # noqa: E402
 
 
 def main():
-    args = _cli.build_parser("NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.NERF_ONLY).parse_args()
+    args = _cli.build_parser("NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.NERF_ONLY, _cli.SKIP_GRID).parse_args()
     args.device, rank, world, group = _cli.setup_device(args.device, True)
     torch.manual_seed(args.seed)
     model = ffn.NeRF(args.num_layers, args.num_channels, args.pos_max_log_scale, args.pos_freq,
@@ -37,7 +37,7 @@ def main():
     if args.mode == "dilate":
         train.mode = ffn.RayDataset.Mode.Dilate
     os.makedirs(args.results_dir, exist_ok=True)
-    caster = _cli.apply_skipping(ffn.Raycaster(_cli.apply_precision(model.to(args.device), args.precision)), args)
+    caster = _cli.apply_skipping(ffn.Raycaster(_cli.apply_precision(model.to(args.device), args.precision)), args, train)
     caster.process_group = group      # data parallel under torch.distributed.run
     if world > 1:                     # distinct jitter streams; weights are broadcast by fit
         torch.cuda.manual_seed(args.seed + rank)

@@ -13,7 +13,7 @@ from scripts import _cli  # noqa: E402
 
 def main():
     kinds = ("nerf_model", dict(choices=["mlp", "basic", "positional", "gaussian"]))
-    args = _cli.build_parser("Tiny NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.TINY_ONLY,
+    args = _cli.build_parser("Tiny NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.TINY_ONLY, _cli.SKIP_GRID,
                              positional_extra=[kinds]).parse_args()
     args.device, rank, world, group = _cli.setup_device(args.device, True)
     torch.manual_seed(args.seed)
@@ -53,7 +53,7 @@ def main():
         print("warning: --make-activations is not supported on the HIP path (the fused kernels "
               "keep hidden activations on the CU); training continues without the activation "
               "video", file=sys.stderr)
-    caster = _cli.apply_skipping(ffn.Raycaster(_cli.apply_precision(model.to(args.device), args.precision)), args)
+    caster = _cli.apply_skipping(ffn.Raycaster(_cli.apply_precision(model.to(args.device), args.precision)), args, train)
     caster.process_group = group      # data parallel under torch.distributed.run
     if world > 1:                     # distinct jitter streams; weights are broadcast by fit
         torch.cuda.manual_seed(args.seed + rank)
