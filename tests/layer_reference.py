@@ -22,6 +22,10 @@ then fail -- one weight scaled by 1 + 1e-3 (layer outputs, logits, dZ; 1 + 1e-2 
 scaled by 1 + 1e-3 (features), one row's contribution removed (weight and bias gradients; one
 32-sample block's above 10^5 samples).  The weight and the row are the ones the comparison is
 most sensitive to, found from the data, so that the check means "a change this small is seen".
+
+Inference launches (no training buffer) leave nothing but logits: ``check_inference`` holds them to
+the bits of the training forward's logits of the same kernel organisation, which the stages above
+tie to float64.
 """
 
 import torch
@@ -335,3 +339,77 @@ def measure_layers(prog, positions, views, saved, dz, d_logits, logits, grads, p
                          "%.3g, kappa %g)" % (s.name, k, r, s.kappa) for k, r in s.teeth.items() if not r > s.kappa]
     report = {s: (st[s].worst, min(st[s].teeth.values(), default=float("inf"))) for s in STAGES}
     return report, problems
+
+
+def _logits_head(prog, saved, n, chunk_blocks=1 << 11):
+    """The logits heads in float64 on the slabs a training forward left in ``saved``: (logits (n, 4),
+    sum|terms| (n, 4)) -- what every kernel organisation that read those slabs may differ by is the
+    order in which it added one head's products."""
+    dev = saved.device
+    acts, _ = prog._split_saved(saved, n)
+    heads = [(i, sp) for i, sp in enumerate(prog.layers) if sp.to_logits is not None]
+    need = set()
+    for i, sp in heads:
+        if sp.act_in > 0:
+            need.add(prog.slot_of[prog.producer_of[i]])
+        if sp.enc_id is not None:
+            need.add(prog.enc_slot[sp.enc_id])
+    ref = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+    terms = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+    blocks = (n + 31) // 32
+    for b0 in range(0, blocks, chunk_blocks):
+        nb = min(chunk_blocks, blocks - b0)
+        r0, rows = 32 * b0, min(32 * nb, n - 32 * b0)
+        slabs = {slot: prog.slot_rows(acts, n, slot, b0, nb).double()[:rows] for slot in need}
+        for i, sp in heads:
+            a = _natural_input(prog, i, slabs)
+            w = sp.weight.detach().double().to(dev)
+            b = sp.bias.detach().double().to(dev)
+            col, cnt = sp.to_logits
+            ref[r0:r0 + rows, col:col + cnt] = a @ w.T + b
+            terms[r0:r0 + rows, col:col + cnt] = a.abs() @ w.abs().T + b.abs()
+    return ref, terms
+
+
+def measure_inference(prog, x, views, logits_train, precision, saved=None):
+    """An inference launch (``saved=None``) of the same samples against the training forward's
+    ``logits_train`` of the same kernel organisation.  Returns (inference logits, rows whose bits
+    differ (bool, n), worst |inference - training| / (2^-24 sum|terms| of the logits head) over those
+    rows -- 0.0 when every bit agrees, NaN when they differ and no ``saved`` was given)."""
+    got = prog.forward(x, views, None, precision=precision)
+    assert got.shape == logits_train.shape and got.dtype == logits_train.dtype
+    differs = (got.view(torch.int32) != logits_train.view(torch.int32)).any(dim=1)
+    if not bool(differs.any()):
+        return got, differs, 0.0
+    if saved is None:
+        return got, differs, float("nan")
+    n = int(x.shape[0])
+    _, terms = _logits_head(prog, saved, n)
+    err = (got.double() - logits_train.double()).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / (U * terms))
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)
+    return got, differs, float(ratio[differs].max())
+
+
+def check_inference(prog, x, views, logits_train, precision, saved=None, reordered_from=None):
+    """Holds an inference launch to the BITS of the training forward's logits of the same kernel
+    organisation (``measure_inference``).  ``reordered_from`` = first row from which the training
+    launch is known, from the code, to add a fused head's products in another order than the
+    inference launch does (the exact-f32 team kernels of a launch's tail): those rows -- and only
+    those -- are held to ``kappa_logits * 2^-24 * sum|terms|`` of the logits head in float64 on the
+    training slabs ``saved`` instead; the hidden layers are the same arithmetic, so anything larger
+    is a bug.  Returns (inference logits, worst ratio of the rows that differ)."""
+    got, differs, worst = measure_inference(prog, x, views, logits_train, precision, saved)
+    n = int(x.shape[0])
+    exact_rows = n if reordered_from is None else int(reordered_from)
+    bad = differs[:exact_rows].nonzero()
+    assert bad.numel() == 0, ("inference logits differ from the training forward's in %d of %d rows, first "
+                              "row %d: %r != %r (worst ratio to 2^-24 sum|terms| of the head: %.3g)"
+                              % (int(bad.numel()), exact_rows, int(bad[0]), got[int(bad[0])].tolist(),
+                                 logits_train[int(bad[0])].tolist(), worst))
+    if reordered_from is not None and bool(differs.any()):
+        assert saved is not None, "the bound on reordered rows needs the training slabs"
+        assert worst <= kappa_of(precision)["logits"], (
+            "reordered rows: |inference - training| is %.3g x 2^-24 sum|terms| of the logits head "
+            "(kappa %g): the hidden layers differ" % (worst, kappa_of(precision)["logits"]))
+    return got, worst

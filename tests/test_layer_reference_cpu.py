@@ -216,3 +216,36 @@ def test_checker_fails_on_one_wrong_value(synthetic, mutate, expect):
     mutate(b, prog)
     _, problems = _measure(prog, b)
     assert problems and any(expect in p for p in problems), problems
+
+
+def test_inference_check_holds_the_bits_and_bounds_only_reordered_rows(synthetic, monkeypatch):
+    """``check_inference`` on a stand-in inference launch: equal bits pass; one last-place change
+    fails; past ``reordered_from`` a change within the logits head's rounding budget passes and is
+    reported, one beyond it (a hidden layer that differs) fails."""
+    prog, b = synthetic
+    if not any(sp.to_logits for sp in prog.layers):
+        return
+    train = b["logits"]
+    out = {}
+    monkeypatch.setattr(prog, "forward", lambda x, views, saved, precision="f32": out["logits"], raising=False)
+    args = (prog, b["positions"], b["views"], train, "f32")
+    out["logits"] = train.clone()
+    got, worst = lr.check_inference(*args)
+    assert torch.equal(got, train) and worst == 0.0
+    _, terms = lr._logits_head(prog, b["saved"], N)
+    row = N - 5
+    col = int(terms[row].argmax())
+    ulp = train.clone()
+    ulp[row, col] = torch.nextafter(ulp[row, col], torch.tensor(float("inf")))
+    out["logits"] = ulp
+    with pytest.raises(AssertionError, match="differ from the training forward"):
+        lr.check_inference(*args, saved=b["saved"])
+    with pytest.raises(AssertionError, match="differ from the training forward"):
+        lr.check_inference(*args, saved=b["saved"], reordered_from=row + 1)
+    _, worst = lr.check_inference(*args, saved=b["saved"], reordered_from=row)
+    assert 0.0 < worst <= lr.KAPPA["f32"]["logits"]
+    far = train.clone()
+    far[row, col] += float(2 * lr.KAPPA["f32"]["logits"] * lr.U * terms[row, col])
+    out["logits"] = far
+    with pytest.raises(AssertionError, match="hidden layers differ"):
+        lr.check_inference(*args, saved=b["saved"], reordered_from=row)

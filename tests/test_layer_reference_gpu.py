@@ -58,18 +58,25 @@ def _model(name):
     return model
 
 
-def _run(name, n, mode, monkeypatch, seed=0):
+def _inputs(model, n, seed=0, radius=1.0):
+    """(positions uniform in [-radius, radius]^3, unit view directions or None, d(loss)/d(logits))
+    of ``n`` samples: what ``_run`` feeds the kernels."""
+    gen = torch.Generator(device=dev()).manual_seed(seed + n)
+    x = (torch.rand(n, 3, device=dev(), generator=gen) * 2 - 1) * radius
+    views = None
+    if model.use_view:
+        views = torch.nn.functional.normalize(torch.randn(n, 3, device=dev(), generator=gen), dim=1)
+    d_logits = torch.randn(n, 4, device=dev(), generator=gen) / math.sqrt(n)
+    return x, views, d_logits
+
+
+def _run(name, n, mode, monkeypatch, seed=0, radius=1.0):
     """One forward / backward pair of ``n`` samples in ``mode``, checked stage by stage."""
     model = _model(name)
     prog = model.program()
     precision = mode.split("+")[0]
     monkeypatch.setenv("FFN_BF16X6_WGRAD", "f32" if mode == "bf16x6+f32wgrad" else "bf16x6")
-    gen = torch.Generator(device=dev()).manual_seed(seed + n)
-    x = torch.rand(n, 3, device=dev(), generator=gen) * 2 - 1
-    views = None
-    if model.use_view:
-        views = torch.nn.functional.normalize(torch.randn(n, 3, device=dev(), generator=gen), dim=1)
-    d_logits = torch.randn(n, 4, device=dev(), generator=gen) / math.sqrt(n)
+    x, views, d_logits = _inputs(model, n, seed, radius)
     saved = torch.full((prog.saved_floats(n),), float("nan"), device=dev())
     if not prog.covers(precision):
         with pytest.raises(NotImplementedError):
@@ -131,7 +138,7 @@ SIZE_LABELS = ["one", "31", "33", "tail-quads", "tail-pairs", "plan-step", "segm
 
 
 @pytest.mark.parametrize("label", SIZE_LABELS)
-@pytest.mark.parametrize("mode", ["f32", "bf16x6"])
+@pytest.mark.parametrize("mode", ["f32", "bf16x6", "bf16x3"])
 @pytest.mark.parametrize("name", ["positional", "nerf_small", "mlp96"])
 def test_batch_sizes_from_the_planner_stage_by_stage(name, mode, label, monkeypatch):
     prog = _model(name).program()
