@@ -147,8 +147,10 @@ class TrainEngine:
     def _can_prefetch(self, sampler) -> bool:
         """Samples of the NEXT step may be drawn before this step's optimiser update only when
         they do not depend on the weights (a live coarse model may be the model in training) and
-        nothing else reshapes the batch (occupancy compaction keeps its own launch order)."""
-        return self.occupancy is None and (not sampler.focus_sampling or sampler.cdfs is not None)
+        nothing else reshapes the batch (occupancy compaction keeps its own launch order).  A
+        sampler focused on an octree (``focus_on_octree``) qualifies: a frozen tree has no weights."""
+        frozen = sampler.cdfs is not None or getattr(sampler, "focus_tree", None) is not None
+        return self.occupancy is None and (not sampler.focus_sampling or frozen)
 
     def _prefetch(self, lookahead):
         """``lookahead`` = (dataset, filtered global ray ids, step) of the NEXT ``train_step``:

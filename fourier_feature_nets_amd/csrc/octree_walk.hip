@@ -140,6 +140,35 @@
 // before: their disassembly was compared with the previous commit's, instruction for instruction
 // (758 / 809 / 851 / 887 / 975 / 1002 / 1034 / 1095 / 1132 / 845 instructions, 38 / 40 / 50 / 53 / 61 /
 // 56 / 72 / 64 / 82 / 39 VGPRs).
+//
+// K26  Focus samples from the tree's own weights: a SIBLING kernel (octree_focus_kernel), not a twelfth
+// mode.  It needs a per-ray id gather, near and far, a loop over two phases around the walk and a merge
+// state of its own, none of which fits the idle parameters, so it takes its arguments as one struct and
+// shares the device functions above (find_id, chain_bits, root_slab, exit_t, step_axis) and K13's loop
+// bounds.  One lane per ray in one-wave workgroups, as the modes.  Per taken leaf (t0 = max(t, near),
+// t1 = min(t_exit, far), t1 > t0) K21a's chain sigma = max(density, 0), a, w = T a, T, and the running
+// sum c of w.  The walk is ONE piece of code run for phase 0 (M = c at the end) and phase 1 (the
+// targets y_j = u_j M are placed where c passes them, linearly inside the leaf), so the second walk
+// repeats the first one's c bit for bit by construction, not by the compiler's grace.  Rays without
+// mass, rays that miss and rays with an empty [near, far] emit the uniform fall-back.
+// The emits: DIRECT per-lane row stores.  A lane owns row r of the (R, S) output and writes it front to
+// back, merging its ascending emits with the row's uniform samples by two pointers (the next uniform
+// sample waits in a register); lanes of a wave write 4 bytes each at a stride of 4 S bytes, so a store
+// instruction touches up to 64 lines, and a line is completed by 16 consecutive emits of one lane while
+// it sits in L2.  Staging a wave's rows through LDS for whole-line stores was not built, so there is no
+// measurement to set against this one; the stores are off the dependent chain of the binary searches
+// that bounds the walk.  No LDS, no atomics, no limit on S.
+// Divergence: as every mode a wave runs as long as its longest ray, here for two walks; the inner emit
+// loop runs as long as the lane with the most targets in the current leaf.
+// Resource report, octree_focus_kernel: 75 VGPRs, 106 SGPRs (6 of them spilled to VGPR lanes, none to
+// memory), 0 bytes of scratch, 0 VGPR spills, 0 bytes of LDS, occupancy 6 waves per SIMD, 1316
+// instructions.  The eleven instantiations of octree_walk_kernel compile to the instructions they had
+// before: their disassembly was compared with the previous commit's, instruction for instruction
+// (758 / 809 / 851 / 887 / 975 / 1002 / 1034 / 1095 / 1132 / 845 / 959 instructions).
+// Measured (MI355X, profiles/r24_octree_focus_microbench.json, S = 128, best of 5): 9.61 ms for 4096 shuffled
+// rays and 16.59 ms for 160 000 rays of one camera in a depth-8 carved tree, 2.1x / 2.2x K15's one walk on the
+// same rays (4.57 / 7.71 ms); depth 10: 37.24 / 71.58 ms, 2.1x.  Latency-bound like every mode: 4096 rays are 64
+// waves.  Kernel times under rocprofv3 and LDS-staged emits were not measured.
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
@@ -709,9 +738,227 @@ int octree_grad_walk(const char* who, const GradWalk& grad, int phase) {
                                     entry_leaves, 0.0f, d_color, d_alpha, slots);
 }
 
+// K26: what ffn_octree_focus_sample passes, one struct by value
+struct FocusWalk {
+    const float* starts;
+    const float* directions;
+    const float* near_far;
+    int64_t num_rays_total;
+    const int64_t* ray_index;
+    int num_rays;
+    float center_x, center_y, center_z, scale;
+    int depth;
+    const int64_t* node_index;
+    int64_t num_nodes;
+    const int64_t* leaf_index;
+    int64_t num_leaves;
+    const float* leaf_rows;
+    int stride, sigma_offset;
+    const float* u;
+    int n_focus;
+    const float* t_uniform;
+    int uniform_stride, n_uniform;
+    float min_mass;
+    float* t_out;
+    float* mass_out;
+};
+
+// K26  The sibling of octree_walk_kernel: K13's stepping (the device functions above, the same loop
+// bounds) walked twice by one lane per ray.  Both walks are ONE piece of code run for phase = 0 and
+// phase = 1, so phase 1 repeats phase 0's c bit for bit by construction.
+__global__ void __launch_bounds__(kWalkThreads) octree_focus_kernel(const FocusWalk f) {
+    const int r = (int)blockIdx.x * kWalkThreads + (int)threadIdx.x;
+    if (r >= f.num_rays) return;
+    const int64_t i = f.ray_index[r];
+    if (i < 0 || i >= f.num_rays_total) return;          // a foreign id: its row is left alone
+    const float ox = f.starts[i * 3 + 0] - f.center_x, oy = f.starts[i * 3 + 1] - f.center_y,
+                oz = f.starts[i * 3 + 2] - f.center_z;
+    const float dx = f.directions[i * 3 + 0], dy = f.directions[i * 3 + 1],
+                dz = f.directions[i * 3 + 2];
+    const float near = f.near_far[i], far = f.near_far[f.num_rays_total + i];
+    const float scale = f.scale;
+    const int depth = f.depth, levels = depth - 1, cells = 1 << levels;
+    const int n_focus = f.n_focus, n_uniform = f.n_uniform;
+
+    float root_in = -__builtin_inff(), root_out = __builtin_inff();
+    int axis_in = 0;
+    bool miss = false;
+    root_slab(ox, dx, scale, 0, root_in, root_out, axis_in, miss);
+    root_slab(oy, dy, scale, 1, root_in, root_out, axis_in, miss);
+    root_slab(oz, dz, scale, 2, root_in, root_out, axis_in, miss);
+    const bool hit = !miss && root_in < root_out && fabsf(root_in) < __builtin_inff() &&
+                     fabsf(root_out) < __builtin_inff();
+    const bool ordered = near < far;                     // false for a NaN end too
+    const int ix0 = axis_in == 0 ? (dx > 0.0f ? 0 : cells - 1) : chain_bits(ox + root_in * dx, 0.0f, scale, levels);
+    const int iy0 = axis_in == 1 ? (dy > 0.0f ? 0 : cells - 1) : chain_bits(oy + root_in * dy, 0.0f, scale, levels);
+    const int iz0 = axis_in == 2 ? (dz > 0.0f ? 0 : cells - 1) : chain_bits(oz + root_in * dz, 0.0f, scale, levels);
+    const int max_stops = 3 * cells + 1;
+    const int max_trips = max_stops * depth;
+    const float norm = sqrtf(dx * dx + dy * dy + dz * dz);
+
+    // the merge: k entries of the row are written, ku of the uniform samples among them; `un` is the
+    // uniform sample that goes next.  put() is called at most n_focus times (every caller holds
+    // j < n_focus) and moves every uniform sample at most once, so k stays below n_uniform + n_focus
+    float* out = f.t_out + (int64_t)r * (n_uniform + n_focus);
+    const float* uniform = n_uniform > 0 ? f.t_uniform + (int64_t)r * f.uniform_stride : nullptr;
+    const float* targets = f.u + (int64_t)r * n_focus;
+    int k = 0, ku = 0, j = 0;
+    float un = n_uniform > 0 ? uniform[0] : 0.0f;
+    auto put = [&](float v) {
+        while (ku < n_uniform && un <= v) {
+            out[k++] = un;
+            ++ku;
+            un = ku < n_uniform ? uniform[ku] : 0.0f;
+        }
+        out[k++] = v;
+    };
+
+    float mass = 0.0f, t_last = near, last = -__builtin_inff();
+    bool use_tree = false;
+    for (int phase = 0; phase < 2; ++phase) {
+        if (phase == 1) {
+            use_tree = mass > 0.0f && mass >= f.min_mass;        // a NaN mass fails
+            if (!use_tree) break;
+        }
+        int64_t id = 0;
+        int level = 0, known = 0, stop = 0, ix = ix0, iy = iy0, iz = iz0;
+        float cx = 0.0f, cy = 0.0f, cz = 0.0f, half = scale, t = root_in;
+        bool inside = hit && ordered;
+        float trans = 1.0f, c = 0.0f;
+        float y = phase == 1 ? targets[0] * mass : 0.0f;
+        for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
+            int64_t at;
+            const bool interior = level < known ||
+                                  (level < levels && find_id(f.node_index, f.num_nodes, id, &at));
+            if (interior) {
+                const int shift = levels - 1 - level;
+                const int bx = (ix >> shift) & 1, by = (iy >> shift) & 1, bz = (iz >> shift) & 1;
+                half *= 0.5f;
+                cx = bx ? cx + half : cx - half;
+                cy = by ? cy + half : cy - half;
+                cz = bz ? cz + half : cz - half;
+                id = 8 * id + 1 + (4 * bx + 2 * by + bz);
+                ++level;
+                continue;
+            }
+            const int64_t leaf = find_id(f.leaf_index, f.num_leaves, id, &at) ? at : -1;
+            const float tx = exit_t(ox, dx, cx, half), ty = exit_t(oy, dy, cy, half),
+                        tz = exit_t(oz, dz, cz, half);
+            int axis_out = 0;
+            float t_exit = tx;
+            if (ty < t_exit) { t_exit = ty; axis_out = 1; }
+            if (tz < t_exit) { t_exit = tz; axis_out = 2; }
+            if (leaf >= 0) {
+                const float t0 = fmaxf(t, near), t1 = fminf(t_exit, far);
+                if (t1 > t0) {
+                    const float ls = f.leaf_rows[leaf * f.stride + f.sigma_offset];
+                    const float length = (t1 - t0) * norm;
+                    const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                    const float a = 1.0f - expf(-(sigma * length));
+                    const float w = trans * a;
+                    const float c_next = c + w;
+                    if (w > 0.0f) {                                // a NaN w fails too
+                        t_last = t1;
+                        if (phase == 1) {
+                            while (j < n_focus && y < c_next) {
+                                const float fr = (y - c) / w;
+                                float v = fminf(fmaxf(t0 + fr * (t1 - t0), t0), t1);
+                                v = fmaxf(v, last);
+                                put(v);
+                                last = v;
+                                ++j;
+                                y = j < n_focus ? targets[j] * mass : 0.0f;
+                            }
+                        }
+                    }
+                    c = c_next;
+                    trans = trans * (1.0f - a);
+                    // every later w is exactly 0; phase 1 has nothing left to place
+                    if (trans == 0.0f || (phase == 1 && j >= n_focus)) break;
+                }
+            }
+            if (!(t_exit < far)) break;          // the next region would begin at or beyond far
+            ++stop;
+            const int span = levels - level;
+            const int nx = step_axis(ix, axis_out == 0, dx, ox + t_exit * dx, cx, half, span);
+            const int ny = step_axis(iy, axis_out == 1, dy, oy + t_exit * dy, cy, half, span);
+            const int nz = step_axis(iz, axis_out == 2, dz, oz + t_exit * dz, cz, half, span);
+            inside = ((nx | ny | nz) >= 0) && nx < cells && ny < cells && nz < cells;
+            const int differ = (ix ^ nx) | (iy ^ ny) | (iz ^ nz);
+            known = inside ? min(level, levels - (32 - __clz(differ)) + 1) : 0;
+            ix = nx; iy = ny; iz = nz;
+            t = t_exit;
+            id = 0; level = 0;
+            cx = 0.0f; cy = 0.0f; cz = 0.0f; half = scale;
+        }
+        if (phase == 0) mass = c;
+    }
+    if (f.mass_out) f.mass_out[r] = mass;
+    if (use_tree) {
+        // u == 1, a target that rounding, a NaN or a broken order left behind: the end of the mass
+        const float v = fmaxf(t_last, last);
+        for (; j < n_focus; ++j) put(v);
+    } else {
+        const float span = far - near;
+        for (; j < n_focus; ++j) put(ordered ? near + targets[j] * span : near);
+    }
+    for (; ku < n_uniform; ++ku) {
+        out[k++] = un;
+        un = ku + 1 < n_uniform ? uniform[ku + 1] : 0.0f;
+    }
+}
+
 }  // namespace ffn
 
 using namespace ffn;
+
+extern "C" int ffn_octree_focus_sample(const float* starts, const float* directions,
+                                       const float* near_far, int64_t num_rays_total,
+                                       const int64_t* ray_index, int num_rays, float center_x,
+                                       float center_y, float center_z, float scale, int depth,
+                                       const int64_t* node_index, int64_t num_nodes,
+                                       const int64_t* leaf_index, int64_t num_leaves,
+                                       const float* leaf_rows, int stride, int sigma_offset,
+                                       const float* u, int n_focus, const float* t_uniform,
+                                       int uniform_stride, int n_uniform, float min_mass,
+                                       float* t_out, float* mass_out, void* stream) {
+    const char* who = "ffn_octree_focus_sample";
+    if (num_rays == 0) return 0;
+    if (num_rays < 0 || num_rays_total < 1) return fail_who(who, "num_rays >= 0, num_rays_total >= 1");
+    if (n_focus < 1) return fail_who(who, "n_focus >= 1");
+    if (n_uniform < 0) return fail_who(who, "n_uniform >= 0");
+    if (n_uniform > 0 && !t_uniform) return fail_who(who, "t_uniform is null with n_uniform > 0");
+    if (n_uniform > 0 && uniform_stride < n_uniform)
+        return fail_who(who, "uniform_stride >= n_uniform");
+    if (depth < 1 || depth > kWalkMaxDepth) return fail_who(who, "depth (1 <= depth <= 11)");
+    if (num_leaves < 1 || num_nodes < 0) return fail_who(who, "num_leaves >= 1, num_nodes >= 0");
+    if (stride < 1 || sigma_offset < 0 || sigma_offset >= stride)
+        return fail_who(who, "stride >= 1, 0 <= sigma_offset < stride");
+    if (!(min_mass >= 0.0f)) return fail_who(who, "min_mass >= 0 (and not NaN)");
+    if ((int64_t)num_rays * ((int64_t)n_uniform + n_focus) >= kWalkMaxRays)
+        return fail_who(who, "num_rays * (n_uniform + n_focus) < 2^31");
+    if (!(center_x == center_x && center_y == center_y && center_z == center_z))
+        return fail_who(who, "center is NaN");
+    if (!starts || !directions || !near_far || !ray_index || !leaf_index ||
+        (num_nodes > 0 && !node_index) || !leaf_rows || !u || !t_out)
+        return fail_who(who, "null argument");
+    if (n_uniform > 0) {
+        // the merge reads uniform samples after it has written entries of the same row
+        const int64_t total = (int64_t)n_uniform + n_focus;
+        const float* out_end = t_out + (int64_t)num_rays * total;
+        const float* uni_end = t_uniform + ((int64_t)num_rays - 1) * uniform_stride + n_uniform;
+        if (t_uniform < out_end && t_out < uni_end)
+            return fail_who(who, "t_out must not alias t_uniform");
+    }
+    const FocusWalk f{starts, directions, near_far, num_rays_total, ray_index, num_rays, center_x,
+                      center_y, center_z, scale, depth, node_index, num_nodes, leaf_index,
+                      num_leaves, leaf_rows, stride, sigma_offset, u, n_focus, t_uniform,
+                      uniform_stride, n_uniform, min_mass, t_out, mass_out};
+    const unsigned blocks = (unsigned)(((int64_t)num_rays + kWalkThreads - 1) / kWalkThreads);
+    hipLaunchKernelGGL(octree_focus_kernel, dim3(blocks), dim3(kWalkThreads), 0,
+                       (hipStream_t)stream, f);
+    return check_launch(who);
+}
 
 extern "C" int ffn_octree_walk(const float* starts, const float* directions, int64_t n, float scale,
                                int depth, const int64_t* node_index, int64_t num_nodes,

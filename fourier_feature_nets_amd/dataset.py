@@ -357,13 +357,20 @@ class ImageDataset(RayDataset):
     # ------------------------------------------------------------------ construction helpers
     def subset(self, cameras: List[int], num_samples: int, stratified: bool,
                label: str) -> "ImageDataset":
-        return ImageDataset(label, self.images[cameras], self.sampler.bounds,
-                            [self.sampler.cameras[i] for i in cameras], num_samples,
-                            self.include_alpha, stratified, self.sampler.opacity_model,
-                            self.sampler.batch_size, self.color_space, self.sparse_size,
-                            self.sampler.anneal_start, self.sampler.num_anneal_steps,
-                            self.alpha_weight,      # unchanged, like image_dataset.py:349-362
-                            device=self.sampler.device, focus_mode=self.sampler.focus_mode)
+        chosen = ImageDataset(label, self.images[cameras], self.sampler.bounds,
+                              [self.sampler.cameras[i] for i in cameras], num_samples,
+                              self.include_alpha, stratified, self.sampler.opacity_model,
+                              self.sampler.batch_size, self.color_space, self.sparse_size,
+                              self.sampler.anneal_start, self.sampler.num_anneal_steps,
+                              self.alpha_weight,      # unchanged, like image_dataset.py:349-362
+                              device=self.sampler.device, focus_mode=self.sampler.focus_mode)
+        # a sampler is re-created from its opacity model; the tree of focus_on_octree is the other
+        # source of focus samples and has to travel the same way
+        if self.sampler.focus_tree is not None:
+            chosen.sampler = chosen.sampler.focus_on_octree(
+                self.sampler.focus_tree, self.sampler.focus_tree_center,
+                self.sampler.focus_min_mass)
+        return chosen
 
     @staticmethod
     def load(path: str, split: str, num_samples: int, include_alpha: bool, stratified: bool,

@@ -672,6 +672,58 @@ class OcTree:
             float(min_transmittance), out)
         return weights.cpu().numpy() if as_numpy else weights
 
+    def _density_rows(self, who):
+        """The device rows and the density's offset in them, for the walks that read the density
+        alone (K21a, K24, K26)."""
+        self._check_volume(0.0, who)
+        if self._sh_degree is not None:
+            return self._sh_rows_on_device(), 0
+        return self._colors_on_device(), 3
+
+    def focus_samples(self, starts, directions, near_far, ray_index, u, t_uniform=None,
+                      center=None, min_mass: float = 1e-3, return_mass: bool = False):
+        """Focus samples from the tree's own compositing weights (K26; the reference has no
+        counterpart: its focus samples come from a coarse model probed at ``n_focus`` points per
+        ray).  ``starts``, ``directions`` (N,3) and ``near_far`` (2,N) are a sampler's per-ray state
+        in WORLD coordinates, float32 device tensors; ``ray_index`` (R,) int64 picks the batch;
+        ``center`` is the root cube's centre (default: the tree's own, which a loaded tree does not
+        have).  ``u`` (R, n_focus) in [0,1] is ASCENDING in every row.  Along ray r, over the
+        leaves it crosses inside ``[near, far]``, the walk forms ``render_volume``'s weights
+        ``w = T * a`` and their running sum, whose total is the ray's mass M; target ``u * M`` lands
+        in the leaf where the sum passes it, linearly between the leaf's two crossings.
+        ``t_uniform`` (R, n_uniform): the rays' ascending uniform samples, merged in.
+        -> t (R, n_uniform + n_focus) float32, every row ascending: ``sort(cat(uniform, focus))``;
+        with ``return_mass`` also M (R,).
+
+        A ray with M < ``min_mass`` (or that misses the cube, or without near < far) gets the
+        uniform fall-back ``near + u * (far - near)``.
+
+        Limits.  The CDF is piecewise linear inside a leaf, and a leaf has ONE density: the samples
+        are as fine as the tree.  Focus samples never land in empty regions -- where the tree has no
+        leaf (or a leaf of density 0) only the uniform half of a sampler still looks.
+        ``min_mass = 1e-3`` is an untuned starting value.  Works for plain and SH trees (only the
+        density is read)."""
+        who = "OcTree.focus_samples"
+        data = self._leaf_data
+        if data is None or np.ndim(data) != 2 or np.shape(data)[1] < 4:
+            raise ValueError("%s: the tree has no density column (leaf_data must be (num_leaves, "
+                             "C >= 4), [r, g, b, sigma] or SH rows; see OcTree.bake, "
+                             "build_from_silhouettes)" % who)
+        if not float(min_mass) >= 0.0:       # NaN fails too
+            raise ValueError("%s: min_mass must be >= 0, got %r" % (who, min_mass))
+        if self.depth > ops.octree_max_depth():
+            raise ValueError("OcTree: a tree of depth %d is deeper than the ray walk's cell "
+                             "coordinates hold (%d)" % (self.depth, ops.octree_max_depth()))
+        center = self._visible_center(who, center)
+        if self._device is None and torch.is_tensor(starts) and starts.is_cuda:
+            self._device = starts.device
+        rows, offset = self._density_rows(who)
+        out = ops.octree_focus_sample(
+            starts, directions, near_far, ray_index, center, self._scale, self.depth,
+            self._on_device("node_index"), self._on_device("leaf_index"), rows,
+            int(rows.shape[1]), offset, u, t_uniform, None, float(min_mass), bool(return_mass))
+        return out
+
     @staticmethod
     def _visible_arguments(who, dataset, alpha_threshold):
         """What ``visible_votes`` checks of its dataset and ``alpha_threshold`` before any device is

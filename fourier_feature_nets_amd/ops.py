@@ -1361,6 +1361,72 @@ def octree_leaf_weights(starts: torch.Tensor, directions: torch.Tensor, scale: f
     return out
 
 
+# --------------------------------------------------------------------------------- K26
+def octree_focus_sample(starts: torch.Tensor, directions: torch.Tensor, near_far: torch.Tensor,
+                        ray_index: torch.Tensor, center, scale: float, depth: int,
+                        node_index: torch.Tensor, leaf_index: torch.Tensor, rows: torch.Tensor,
+                        stride: int, sigma_offset: int, u: torch.Tensor,
+                        t_uniform: Optional[torch.Tensor] = None,
+                        n_uniform: Optional[int] = None, min_mass: float = 1e-3,
+                        want_mass: bool = False):
+    """K26.  Focus samples of the rays ``ray_index`` (R,) int64 drawn from the tree's own compositing
+    weights along each ray, merged with the rays' uniform samples -> t (R, n_uniform + n_focus)
+    float32, every row ascending; with ``want_mass`` also the weight sum M (R,) of every ray.
+    starts, directions (N,3) and near_far (2,N) are the sampler's per-ray state in WORLD coordinates
+    (``center``, three floats, is subtracted from the starts inside the kernel).  ``rows`` / ``stride``
+    / ``sigma_offset`` as for ``octree_leaf_weights``.  ``u`` (R, n_focus) in [0,1], ascending in
+    every row.  ``t_uniform`` (R, >= n_uniform): the first ``n_uniform`` columns of a row are its
+    ascending uniform samples (default: all its columns); None gives the focus samples alone.  A ray
+    whose M is not positive or below ``min_mass``, that misses the cube or has no near < far gets
+    ``near + u * (far - near)``."""
+    who = "octree focus_sample"
+    n = starts.shape[0]
+    if starts.shape != (n, 3) or directions.shape != (n, 3) or near_far.shape != (2, n):
+        raise ValueError("%s: starts and directions must be (N,3) and near_far (2,N)" % who)
+    rays = ray_index.shape[0]
+    if ray_index.dim() != 1 or u.dim() != 2 or u.shape[0] != rays:
+        raise ValueError("%s: ray_index must be (R,) and u (R, n_focus)" % who)
+    n_focus = int(u.shape[1])
+    if n_focus < 1:
+        raise ValueError("%s: n_focus >= 1" % who)
+    stride, sigma_offset = int(stride), int(sigma_offset)
+    if (rows.dim() != 2 or rows.shape[0] != leaf_index.numel() or rows.shape[1] != stride
+            or stride < 1 or not 0 <= sigma_offset < stride):
+        raise ValueError("%s: rows must be (num_leaves, stride) with 0 <= sigma_offset < stride, "
+                         "got %s for %d leaves, stride %d, sigma_offset %d"
+                         % (who, tuple(rows.shape), leaf_index.numel(), stride, sigma_offset))
+    if not float(min_mass) >= 0.0:       # NaN fails too
+        raise ValueError("%s: min_mass must be >= 0, got %r" % (who, min_mass))
+    if t_uniform is None:
+        if n_uniform not in (None, 0):
+            raise ValueError("%s: n_uniform = %d without t_uniform" % (who, n_uniform))
+        n_uniform, uniform_stride = 0, 0
+    else:
+        if t_uniform.dim() != 2 or t_uniform.shape[0] != rays:
+            raise ValueError("%s: t_uniform must be (R, >= n_uniform)" % who)
+        uniform_stride = int(t_uniform.shape[1])
+        n_uniform = uniform_stride if n_uniform is None else int(n_uniform)
+        if not 0 <= n_uniform <= uniform_stride:
+            raise ValueError("%s: 0 <= n_uniform <= t_uniform.shape[1]" % who)
+    if rays * (n_uniform + n_focus) >= 1 << 31:
+        raise ValueError("%s: R * (n_uniform + n_focus) must stay below 2^31" % who)
+    ptrs = (_dev(starts, name="starts"), _dev(directions, name="directions"),
+            _dev(near_far, name="near_far"), _dev(ray_index, torch.int64, "ray_index"),
+            _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+            _dev(leaf_index, torch.int64, "leaf_index"), _dev(rows, name="rows"), _dev(u, name="u"),
+            _dev(t_uniform if n_uniform else None, name="t_uniform"))
+    t = torch.empty((rays, n_uniform + n_focus), dtype=torch.float32, device=starts.device)
+    mass = torch.empty((rays,), dtype=torch.float32, device=starts.device) if want_mass else None
+    if rays > 0:
+        cx, cy, cz = (float(c) for c in center)
+        _call("ffn_octree_focus_sample", ptrs[0], ptrs[1], ptrs[2], c_i64(n), ptrs[3], c_i(rays),
+              c_f(cx), c_f(cy), c_f(cz), c_f(scale), c_i(depth), ptrs[4],
+              c_i64(node_index.numel()), ptrs[5], c_i64(leaf_index.numel()), ptrs[6], c_i(stride),
+              c_i(sigma_offset), ptrs[7], c_i(n_focus), ptrs[8], c_i(uniform_stride),
+              c_i(n_uniform), c_f(min_mass), _dev(t, name="t_out"), _dev(mass, name="mass_out"))
+    return (t, mass) if want_mass else t
+
+
 OCTREE_DROP, OCTREE_KEEP, OCTREE_SPLIT = 0, 1, 2
 
 

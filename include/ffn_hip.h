@@ -1308,6 +1308,59 @@ int ffn_occupancy_from_octree(const int64_t* leaf_index, int64_t num_leaves, flo
                               int32_t* tile_sums, int64_t* total, uint32_t* scratch_bits,
                               uint32_t* bits, void* stream);
 
+/* K26 (csrc/octree_walk.hip, a sibling of the K13 kernel that shares its device functions): a ray's
+ * focus samples drawn from the compositing weights of the octree itself, merged with its uniform
+ * samples.  Stands where the reference probes a coarse model at n_focus points per ray
+ * (ray_sampler.py:234-269, _determine_cdf) and inverts the CDF of the blend weights
+ * (ray_sampler.py:380-392); here the distribution is the tree's own piecewise weights.
+ * starts, directions (num_rays_total,3), near_far (2,num_rays_total) as K1 writes them; ray_index
+ * (num_rays) int64 ids (an id outside 0 .. num_rays_total - 1 leaves its row unwritten); center_x/y/z
+ * the root cube's centre, scale .. num_leaves as for ffn_octree_walk; leaf_rows / stride /
+ * sigma_offset as leaf_data for ffn_octree_leaf_weights (only the density is read: stride 4 and
+ * offset 3 on plain rows, the K18a device stride and offset 0 on SH rows).  u (num_rays,n_focus) in
+ * [0,1], ASCENDING in every row by contract (not checked).  t_uniform: row r's n_uniform ascending
+ * uniform samples at t_uniform + r * uniform_stride (K2a's output), or NULL with n_uniform == 0.
+ * t_out (num_rays, S), S = n_uniform + n_focus, a buffer of its own; mass_out (num_rays) or NULL.
+ * One lane per batch ray r with id i = ray_index[r]; every operation one rounded f32 operation (the
+ * file is compiled with -ffp-contract=off):
+ *     o = starts[i] - center;  d = directions[i];  near, far = near_far[0,i], near_far[1,i]
+ *     norm = sqrtf(dx*dx + dy*dy + dz*dz);  T = 1, c = 0
+ *     for every region of the K13 walk that is a leaf, in walk order (t_entry, t_exit its crossings):
+ *         t0 = fmaxf(t_entry, near);  t1 = fminf(t_exit, far);  taken iff t1 > t0
+ *         L = (t1 - t0) * norm;  sigma = fmaxf(leaf_rows[leaf, sigma_offset], 0)   (NaN counts as 0)
+ *         a = 1 - expf(-(sigma * L));  w = T * a;  c_next = c + w;  T = T * (1 - a)
+ *     the walk ends at the first region whose t_exit >= far, and once T == 0 exactly
+ * Phase 0 walks once: M = c after the last taken leaf.  Phase 1 runs the same code again, so c
+ * repeats bit for bit, with a pointer j into the row's targets:
+ *     y_j = u_j * M;  in a taken leaf with w > 0, while j < n_focus and y_j < c_next:
+ *         f = (y_j - c) / w;  t = fminf(fmaxf(t0 + f * (t1 - t0), t0), t1)
+ *         t = fmaxf(t, last emitted);  emit;  ++j
+ *     after the walk every remaining target (u == 1, rounding, a NaN, a u out of order) is emitted as
+ *     the t1 of the last taken leaf with w > 0 (the end of the mass: every taken leaf after it weighs
+ *     exactly 0, so the value does not depend on where the walk ends), through the same maximum
+ * The uniform fall-back t_j = near + u_j * (far - near) is what a ray emits instead when M > 0 does
+ * not hold or M < min_mass, when it misses the cube or K13 cannot follow it (NaN directions), and
+ * when near < far does not hold -- then t_j = near.  mass_out[r] = M (0 for a ray that did not walk).
+ * Merge: the lane's ascending emits and the row's uniform samples by two pointers, a uniform sample
+ * first where the two are equal: as values and bits row r of t_out is sort(cat(uniform, focus)).
+ * A row of u that breaks the contract may give a poorly ordered row; it never gives a write outside
+ * the row or an unbounded loop: a lane emits exactly n_focus values and moves each uniform sample
+ * once, and its trips are bounded by two K13 walks plus S.  No LDS, no atomics, no S <= 256 limit as
+ * in K2d; a row depends on its own ray alone, so the same inputs give the same bits in any batch.
+ * Refused by name before any launch: n_focus < 1, n_uniform < 0, a null t_uniform with
+ * n_uniform > 0, uniform_stride < n_uniform, depth outside 1 .. ffn_octree_max_depth(), num_leaves
+ * < 1, stride < 1 or sigma_offset outside 0 .. stride - 1, a NaN or negative min_mass,
+ * num_rays * S >= 2^31, a NaN centre, a null pointer, t_out overlapping t_uniform.  num_rays == 0
+ * returns 0 at once. */
+int ffn_octree_focus_sample(const float* starts, const float* directions, const float* near_far,
+                            int64_t num_rays_total, const int64_t* ray_index, int num_rays,
+                            float center_x, float center_y, float center_z, float scale, int depth,
+                            const int64_t* node_index, int64_t num_nodes,
+                            const int64_t* leaf_index, int64_t num_leaves, const float* leaf_rows,
+                            int stride, int sigma_offset, const float* u, int n_focus,
+                            const float* t_uniform, int uniform_stride, int n_uniform,
+                            float min_mass, float* t_out, float* mass_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,18 @@ SKIP_GRID = [
     ("--skip-resolution", dict(type=int, default=128)),
     ("--skip-dilate", dict(type=int, default=1)),
 ]
+# not flags of the reference either: the focus half of every ray's samples drawn from an octree's own
+# weights instead of a coarse model (DESIGN K26), from a saved octree or from one carved out of the
+# training images' silhouettes at this depth (0 = off; colour "visible", no fit).  A table of its own
+# like SKIP_GRID; mutually exclusive with --opacity-model
+FOCUS_TREE = [
+    ("--focus-tree", dict(help="octree NPZ (a density per leaf) the focus samples are drawn from")),
+    ("--focus-tree-center", dict(type=float, nargs=3, metavar=("X", "Y", "Z"),
+                                 help="the root cube's centre of --focus-tree")),
+    ("--focus-carve-depth", dict(type=int, default=0)),
+    ("--focus-min-mass", dict(type=float, default=1e-3,
+                              help="rays whose tree weights sum to less sample uniformly")),
+]
 NERF_ONLY = [
     ("--resolution", dict(type=int, default=400)),
     ("--num-cameras", dict(type=int, default=100)),
@@ -273,6 +285,70 @@ def apply_skipping(caster, args, train=None):
     caster.train_occupancy = grid
     caster.occupancy = grid
     return caster
+
+
+def check_focus_tree(args):
+    """--focus-tree / --focus-carve-depth against each other and against --opacity-model, before
+    anything is loaded."""
+    tree_path = getattr(args, "focus_tree", None)
+    carve_depth = getattr(args, "focus_carve_depth", 0)
+    if tree_path is None and not carve_depth:
+        return False
+    if tree_path is not None and carve_depth:
+        raise SystemExit("--focus-tree and --focus-carve-depth are two sources of one tree: pass one")
+    if getattr(args, "opacity_model", None):
+        raise SystemExit("--focus-tree / --focus-carve-depth and --opacity-model are two sources of "
+                         "one distribution: pass one")
+    if tree_path is not None and args.focus_tree_center is None:
+        raise SystemExit("--focus-tree needs --focus-tree-center X Y Z: a saved tree does not hold "
+                         "its root cube's centre")
+    return True
+
+
+def focus_tree(args, train=None):
+    """The tree and centre of --focus-tree / --focus-carve-depth -> (tree, center), or None when
+    neither is given.  Carving needs the training dataset: the cube is the bounds' box, the colours
+    come from the cameras that see a leaf (``color="visible"``), nothing is fitted."""
+    if not check_focus_tree(args):
+        return None
+    import fourier_feature_nets_amd as ffn
+    if args.focus_tree is not None:
+        tree = ffn.OcTree.load(args.focus_tree)
+        if tree is None:
+            raise SystemExit("--focus-tree: cannot read %s" % args.focus_tree)
+        return tree, tuple(args.focus_tree_center)
+    if train is None:
+        raise SystemExit("--focus-carve-depth needs the training dataset")
+    lo, size = ffn.OccupancyGrid.box_of(train.sampler.bounds)
+    center = tuple(float(v) for v in lo + 0.5 * size)
+    tree = ffn.OcTree.build_from_silhouettes(train, args.focus_carve_depth, center,
+                                             0.5 * float(size.max()), color="visible")
+    return tree, center
+
+
+def apply_focus_tree(args, train, *others):
+    """Points the samplers of ``train`` and of every other dataset at the tree of --focus-tree /
+    --focus-carve-depth (``RaySampler.focus_on_octree``) and prints the share of a camera's rays that
+    will sample from it (mass >= --focus-min-mass); without the options nothing changes."""
+    found = focus_tree(args, train)
+    if found is None:
+        return None
+    tree, center = found
+    for ds in (train,) + others:
+        ds.sampler = ds.sampler.focus_on_octree(tree, center, args.focus_min_mass)
+    report_focus_share(train.sampler)
+    return tree
+
+
+def report_focus_share(sampler, camera: int = 0):
+    rays = sampler._valid_for_camera(camera)
+    if rays.numel() == 0:
+        return
+    mass = sampler.focus_mass(rays)
+    share = float((mass >= sampler.focus_min_mass).float().mean())
+    print("focus samples from an octree of %d leaves: %.4f of camera %d's %d rays have mass >= %g "
+          "(the others sample uniformly)" % (sampler.focus_tree.num_leaves, share, camera,
+                                             rays.numel(), sampler.focus_min_mass))
 
 
 def axis_vector(code):

@@ -14,7 +14,8 @@ from scripts import _cli  # noqa: E402
 
 
 def main():
-    args = _cli.build_parser("Orbit video (MI355X)", _cli.ORBIT).parse_args()
+    args = _cli.build_parser("Orbit video (MI355X)", _cli.ORBIT, _cli.FOCUS_TREE).parse_args()
+    _cli.check_focus_tree(args)
     device, rank, world, _ = _cli.setup_device(args.device, False)
     cameras = ffn.orbit(_cli.axis_vector(args.up_dir), _cli.axis_vector(args.forward_dir),
                         args.num_frames, args.fov_y_degrees,
@@ -27,10 +28,18 @@ def main():
     opacity = model
     if args.opacity_model:
         opacity = ffn.load_model(args.opacity_model).to(device)
+    # --focus-tree: the focus samples come from the octree instead (there are no training images
+    # here to carve from, so --focus-carve-depth is refused)
+    found = _cli.focus_tree(args)
+    if found is not None:
+        opacity = None
     mine = list(range(rank, args.num_frames, world))
     caster = ffn.Raycaster(_cli.apply_precision(model, args.precision))
     sampler = ffn.RaySampler(bounds, [cameras[f] for f in mine], args.num_samples, False, opacity,
                              args.batch_size, device=device, focus_mode=_cli.focus_mode(args))
+    if found is not None:
+        sampler = sampler.focus_on_octree(found[0], found[1], args.focus_min_mass)
+        _cli.report_focus_share(sampler)
     os.makedirs(args.output_dir, exist_ok=True)
     bar = ffn.ETABar("Rendering", max=len(mine))
     # frames stay on the GPU until the sink's side stream copies them out; PNG encoding runs on

@@ -12,8 +12,9 @@ from scripts import _cli  # noqa: E402
 
 
 def main():
-    args = _cli.build_parser("NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.NERF_ONLY, _cli.SKIP_GRID).parse_args()
+    args = _cli.build_parser("NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.NERF_ONLY, _cli.SKIP_GRID, _cli.FOCUS_TREE).parse_args()
     args.device, rank, world, group = _cli.setup_device(args.device, True)
+    _cli.check_focus_tree(args)
     torch.manual_seed(args.seed)
     model = ffn.NeRF(args.num_layers, args.num_channels, args.pos_max_log_scale, args.pos_freq,
                      args.view_max_log_scale, args.view_freq, [4], not args.omit_inputs)
@@ -36,6 +37,7 @@ def main():
         return 1
     if args.mode == "dilate":
         train.mode = ffn.RayDataset.Mode.Dilate
+    _cli.apply_focus_tree(args, train, val)
     os.makedirs(args.results_dir, exist_ok=True)
     caster = _cli.apply_skipping(ffn.Raycaster(_cli.apply_precision(model.to(args.device), args.precision)), args, train)
     caster.process_group = group      # data parallel under torch.distributed.run

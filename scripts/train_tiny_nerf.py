@@ -13,9 +13,10 @@ from scripts import _cli  # noqa: E402
 
 def main():
     kinds = ("nerf_model", dict(choices=["mlp", "basic", "positional", "gaussian"]))
-    args = _cli.build_parser("Tiny NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.TINY_ONLY, _cli.SKIP_GRID,
+    args = _cli.build_parser("Tiny NeRF training (MI355X)", _cli.TRAIN_COMMON, _cli.TINY_ONLY, _cli.SKIP_GRID, _cli.FOCUS_TREE,
                              positional_extra=[kinds]).parse_args()
     args.device, rank, world, group = _cli.setup_device(args.device, True)
+    _cli.check_focus_tree(args)
     torch.manual_seed(args.seed)
     width = dict(num_channels=args.num_channels)
     makers = {
@@ -46,6 +47,7 @@ def main():
         return 1
     if args.mode == "dilate":
         train.mode = ffn.RayDataset.Mode.Dilate
+    _cli.apply_focus_tree(args, train, val)
     os.makedirs(args.results_dir, exist_ok=True)
     if args.make_activations and rank == 0:
         # (train_tiny_nerf.py:137-146 of the reference adds an ActivationVisualizer: a lecture
