@@ -96,29 +96,52 @@ using namespace ffn;
 extern "C" int ffn_fourier_encode(const float* x, int64_t n, const float* b, const float* a,
                                   int num_freq, float scale, int include_input, float* out,
                                   void* stream) {
+    if (n < 0) return fail_arg("ffn_fourier_encode: n < 0");
+    if (num_freq < 0) return fail_arg("ffn_fourier_encode: num_freq < 0");
     if (n == 0) return 0;
-    if (n < 0 || num_freq < 0) return fail_arg("ffn_fourier_encode: shape");
-    if (num_freq == 0) include_input = 1;
+    if (x == nullptr || out == nullptr) return fail_arg("ffn_fourier_encode: null x or out");
     if (num_freq == 0) {                                       // the encoding of no frequencies is x
         if (hipMemcpyAsync(out, x, (size_t)n * 12, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
             return fail_arg("ffn_fourier_encode: copy");
         return 0;
     }
+    if (b == nullptr) return fail_arg("ffn_fourier_encode: null b with num_freq > 0");
     if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail_arg("ffn_fourier_encode: out must be 16-byte aligned");
+    // four rows of at most 64 KB: 4096 columns (the comparison also keeps 2 * num_freq in an int)
+    const int max_width = ENCODE_TILE_BYTES / (4 * 4);
+    if (num_freq > max_width / 2 || 2 * num_freq + (include_input ? 3 : 0) > max_width)
+        return fail_arg("ffn_fourier_encode: a row of 2 * num_freq [+ 3] columns is wider than 4096 "
+                        "(at most 2048 frequencies, 2046 with include_input)");
     const int width = 2 * num_freq + (include_input ? 3 : 0);
     // 32 KB groups measured best (8 KB: 3.3 TB/s, 16 KB: 4.1, 32 KB: 4.4, 48 KB: 4.4)
     int group = ENCODE_GROUP_BYTES / (4 * width) / 4 * 4;     // rows per block pass, a multiple of 4
     if (group > ENCODE_MAX_GROUP) group = ENCODE_MAX_GROUP;
-    if (group < 4) group = ENCODE_TILE_BYTES / (4 * width) / 4 * 4 >= 4 ? 4 : 0;
-    if (group < 4) return fail_arg("ffn_fourier_encode: more than 2046 frequencies");
+    if (group < 4) group = 4;                                  // from the 64 KB tile (width <= 4096)
     const size_t lds = (size_t)group * width * 4;
+    // what the workgroup really takes: the tile plus the kernel's static `points`
+    const size_t need = lds + 3 * ENCODE_MAX_GROUP * sizeof(float);
+    int device = 0, limit = 0;
+    if (hipGetDevice(&device) != hipSuccess ||
+        hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess)
+        return fail_arg("ffn_fourier_encode: the device's LDS limit cannot be read");
+    if (need > (size_t)limit) {
+        char what[160];
+        snprintf(what, sizeof(what), "ffn_fourier_encode: the workgroup needs %zu B of LDS, the device allows %d B",
+                 need, limit);
+        return fail_arg(what);
+    }
     int64_t grid = (n + group - 1) / group;
     if (grid > 256 * 16) grid = 256 * 16;
-    if (include_input)
+    if (include_input) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fourier_encode_kernel<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(fourier_encode_kernel<true>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream,
                            x, n, b, a, num_freq, scale, out, group);
-    else
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fourier_encode_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(fourier_encode_kernel<false>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream,
                            x, n, b, a, num_freq, scale, out, group);
+    }
     return check_launch("ffn_fourier_encode");
 }

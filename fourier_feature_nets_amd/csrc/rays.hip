@@ -314,6 +314,13 @@ extern "C" int ffn_materialise_samples(const float* starts, const float* directi
 
 extern "C" int ffn_to_image(const float* colors, const int64_t* pixel_index, int64_t n,
                             int width, int height, uint8_t* image, void* stream) {
+    // every refusal comes before the clear: a refused call leaves the image as it was
+    if (width <= 0 || height <= 0) return fail_arg("ffn_to_image: width and height must be positive");
+    if (n < 0) return fail_arg("ffn_to_image: n < 0");
+    if (n > (int64_t)width * height) return fail_arg("ffn_to_image: more colours than pixels (n > width * height)");
+    if (image == nullptr) return fail_arg("ffn_to_image: null image");
+    if (n > 0 && (colors == nullptr || pixel_index == nullptr))
+        return fail_arg("ffn_to_image: null colors or pixel_index");
     hipError_t err = hipMemsetAsync(image, 0, (size_t)width * height * 3, (hipStream_t)stream);
     if (err != hipSuccess) { set_error("ffn_to_image: memset", err); return (int)err; }
     if (n == 0) return 0;

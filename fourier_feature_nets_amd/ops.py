@@ -144,8 +144,20 @@ def focus_sample_merge(near_far, cdfs, ray_index, u, unit_focus, t_io, n_focus, 
 
 
 def to_image(colors: torch.Tensor, pixel_index: torch.Tensor, width: int, height: int):
-    """K8.  (n,3) colours + (n,) pixel ids -> (H,W,3) uint8 on the GPU."""
-    img = torch.empty((height, width, 3), dtype=torch.uint8, device=colors.device)
+    """K8.  (n,3) colours + (n,) pixel ids -> (H,W,3) uint8 on the GPU: the byte of a colour
+    ``c`` is ``float32(c) * 255`` truncated, unlisted pixels are 0."""
+    if colors.dim() != 2 or colors.shape[1] != 3:
+        raise ValueError("to_image: colors must be (n, 3), got %s" % (tuple(colors.shape),))
+    if pixel_index.numel() != colors.shape[0]:
+        raise ValueError("to_image: %d pixel ids for %d colours" % (pixel_index.numel(), colors.shape[0]))
+    if width <= 0 or height <= 0:
+        raise ValueError("to_image: width and height must be positive, got %d x %d" % (width, height))
+    if colors.shape[0] > width * height:
+        raise ValueError("to_image: %d colours for a frame of %d x %d pixels" % (colors.shape[0], width, height))
+    if pixel_index.device != colors.device:
+        raise RuntimeError("to_image: tensor arguments live on different devices (%s and %s)"
+                           % (colors.device, pixel_index.device))
+    img =torch.empty((height, width, 3), dtype=torch.uint8, device=colors.device)
     _call("ffn_to_image", _dev(colors), _dev(pixel_index, torch.int64),
               c_i64(colors.shape[0]), c_i(width), c_i(height), _dev(img, torch.uint8))
     return img
@@ -160,9 +172,19 @@ def ycrcb_to_rgb_u8(image: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------- encode
 def fourier_encode(x: torch.Tensor, b: Optional[torch.Tensor], a: Optional[torch.Tensor],
                    scale: float, include_input: bool) -> torch.Tensor:
-    """K3.  (N,3) -> (N, 2F[+3]) with the cos block first."""
+    """K3.  (N,3) -> (N, 2F[+3]) with the cos block first; b (3,F) or None, a (F) or None."""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError("fourier_encode: x must be (N, 3), got %s" % (tuple(x.shape),))
+    if b is not None and (b.dim() != 2 or b.shape[0] != 3):
+        raise ValueError("fourier_encode: b must be (3, F), got %s" % (tuple(b.shape),))
     n = x.shape[0]
     freq = 0 if b is None else b.shape[1]
+    if a is not None and a.numel() != freq:
+        raise ValueError("fourier_encode: a has %d values for %d frequencies" % (a.numel(), freq))
+    for name, t in (("b", b), ("a", a)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError("fourier_encode: tensor arguments live on different devices (x on %s, %s on %s)"
+                               % (x.device, name, t.device))
     width = 2 * freq + (3 if (include_input or freq == 0) else 0)
     out = torch.empty((n, width), dtype=torch.float32, device=x.device)
     _call("ffn_fourier_encode", _dev(x), c_i64(n), _dev(b), _dev(a), c_i(freq),

@@ -121,8 +121,14 @@ int ffn_focus_sample_merge_rows(const float* near_far, int64_t num_rays_total,
  * Replaces fourier_feature_models.py:59-68 (scale = pi, optional a_values) and
  * nerf_model.py:97-102 (scale = 1, include_input appends x).  Output is (N, 2F[+3]),
  * cos block first.  b is (3,F); a is (F) or NULL.  F == 0 copies x (class MLP).
- * `out` must be 16-byte aligned (rows are assembled in LDS and leave as whole float4 lines);
- * F <= 2046.
+ * `out` must be 16-byte aligned (rows are assembled in LDS and leave as whole float4 lines).
+ * A block assembles at least four rows, at most 64 KiB of them: 2F[+3] <= 4096 columns, i.e.
+ * F <= 2048 without and F <= 2046 with include_input.  The workgroup's whole LDS need is those
+ * rows plus 1536 B of staged points; it is stated to the runtime and held against the device's
+ * per-workgroup limit.
+ * Refused by name, before anything is launched or written: n < 0, num_freq < 0; null x or out
+ * (n > 0); null b with F > 0; out not 16-byte aligned (F > 0); a row too wide; an LDS need
+ * above the device's limit (the message carries both figures).  n == 0 does nothing.
  */
 int ffn_fourier_encode(const float* x, int64_t n, const float* b, const float* a,
                        int num_freq, float scale, int include_input, float* out,
@@ -213,6 +219,10 @@ int ffn_loss_value(const float* sums, float colour_count, float alpha_count, flo
 /* ------------------------------------------------------------------------------------
  * K8  image assembly (ray_sampler.py:191-196): zeros, scatter, (x*255) truncated to u8.
  *   colors (n,3); pixel_index (n) int64 pixel id inside the frame; image (H*W*3) u8
+ * A byte is (uint8)(int)(float32(c) * 255.0f): ONE float32 multiply, truncated; defined for
+ * 0 <= c < 256/255.  The whole image is cleared first, also for n == 0; unlisted pixels stay 0.
+ * Refused by name, before the clear: width <= 0 or height <= 0, n < 0, n > width * height, a
+ * null image, null colors or pixel_index with n > 0.  Pixel ids themselves are not checked.
  */
 int ffn_to_image(const float* colors, const int64_t* pixel_index, int64_t n, int width,
                  int height, uint8_t* image, void* stream);

@@ -180,6 +180,11 @@ def test_fourier_encode(ops, golden, name, scale, inc):
     # |angle| reaches ~140 rad (positional) / ~60 rad (gaussian, 3-term dot product whose
     # summation order differs from MKL's): one ulp of the angle is 8e-6 / 4e-6
     np.testing.assert_allclose(got.cpu().numpy(), exp.numpy(), rtol=0, atol=2e-5)
+    # and the float64 budget of tests/encode_reference.py: tighter wherever the angle is small
+    from tests import encode_reference as er
+    ref, terms = er.encode_features(x, b, a, scale, inc)
+    worst, failures = er.check_features(name, got.cpu(), ref, terms)
+    assert not failures, "\n".join(failures)
 
 
 # ----------------------------------------------------------------------------------- K5
