@@ -54,6 +54,8 @@ SOURCES = {
     "mesh.hip": ["-ffp-contract=off"],
     # the projection x = ((P00 px + P01 py) + P02 pz) + P03 rounds every product and sum separately
     "carve.hip": ["-ffp-contract=off"],
+    # the same projection on a cell's centre and eight corners, operation for operation
+    "carve_box.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -26,10 +26,11 @@
 //
 // No atomics, no LDS beyond the scan's, no scratch.  A carved cell leaves the loop at its first
 // max_misses + 1 background pixels, so the cost is about (kept cells x C) + (empty cells x a few
-// cameras); lanes of a wave wait for its longest-lived cell.  There is no hierarchical carve on
-// purpose: the test is a point sample of the cell centre, which is not conservative (a coarse
-// cell whose centre falls on the background can have children whose centres do not), so a coarse
-// level cannot safely reject its children.
+// cameras); lanes of a wave wait for its longest-lived cell.  This test cannot be run coarse to
+// fine: it is a point sample of the cell centre, which is not conservative (a coarse cell whose
+// centre falls on the background can have children whose centres do not), so a coarse level
+// cannot safely reject its children.  The hierarchical carve is K27 (carve_box.hip), which tests
+// a cell's whole projected footprint instead.
 //
 // Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), carve_flags_kernel:
 // 27 VGPRs, 58 SGPRs, 0 bytes of scratch, 0 spills, 0 bytes of LDS, occupancy 8

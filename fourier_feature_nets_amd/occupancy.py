@@ -162,10 +162,14 @@ class OccupancyGrid:
         What a hull is and is not.  It is the intersection of the silhouettes' cones: in the limit
         of many views it is conservative, it contains the object.  Concavities that no silhouette
         shows stay filled, which is harmless for skipping: those cells are evaluated and learn
-        density 0.  But the carve samples each cell at its centre only, and can lose structure
-        thinner than a cell or than a pixel's footprint, which is NOT harmless: density in a cell
-        the grid leaves empty is never trained.  ``dilate`` here (grid cells) and ``dilate`` /
-        ``max_misses`` of the carve (pixels, cameras) are the slack."""
+        density 0.  But the default carve (``footprint="point"``) samples each cell at its centre
+        only, and can lose structure thinner than a cell or than a pixel's footprint, which is NOT
+        harmless: density in a cell the grid leaves empty is never trained.  ``dilate`` here (grid
+        cells) and ``dilate`` / ``max_misses`` of the carve (pixels, cameras) are the slack.
+        ``footprint="box"`` (K27, forwarded like every carve argument) removes that loss instead
+        of padding it: a cell is carved only when a camera sees its whole projected footprint on
+        the background, so every cell holding a point that no camera sees on the background is
+        kept, at the price of a fatter hull; its grid holds every bit of the ``"point"`` grid."""
         from .octree import OcTree
         who = "OccupancyGrid.from_silhouettes"
         if bounds is None:

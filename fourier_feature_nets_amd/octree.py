@@ -107,7 +107,10 @@ public signatures are the reference's, so files and calling code go both ways.  
   depth 8 / 10: 346 484 / 22 177 601 leaves, the build 7.4 / 525 ms wall, K23 with its scan and
   scatter 0.35 / 14.9 ms on the device; carved from 116 cameras at depth 8 and fitted for 300
   steps, 4 held-out cameras go from 24.4 to 27.3 dB (the mesh's own depth-8 tree: 28.0 dB).
-  Kernel times under rocprofv3 are unmeasured.
+  Kernel times under rocprofv3 are unmeasured.  ``footprint="box"`` (K27, ``csrc/carve_box.hip``)
+  is the conservative test beside it: a camera refutes a cell only when the padded rectangle
+  round the cell's projected centre and corners lies on the image and on the background, so thin
+  structure survives, and the carve runs coarse to fine over the children of survivors.
 
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
@@ -1222,7 +1225,8 @@ class OcTree:
                                min_views: int = 2, cell_opacity: float = 0.5,
                                merge_tolerance=None, batch_size: int = 1 << 20,
                                color: str = "mean",
-                               visible_transmittance: float = 0.3) -> "OcTree":
+                               visible_transmittance: float = 0.3,
+                               footprint: str = "point", start_level: int = 4) -> "OcTree":
         """Carves a tree out of the root cube from the images' silhouettes alone (K23; no
         counterpart in the reference): a starting point for ``fit_octree`` that needs neither a
         trained model nor the mesh.
@@ -1252,7 +1256,24 @@ class OcTree:
         same ``alpha_threshold`` and ``min_transmittance = visible_transmittance``) takes the mean
         of those cameras alone, a cell none sees keeps the mean of all; then the merge passes run
         as usual.  ``color="mean"`` is the tree described above, bit for bit.  The limits of
-        ``color_from_images`` apply."""
+        ``color_from_images`` apply.
+
+        ``footprint="box"`` answers the first limit (K27, ``csrc/carve_box.hip``).  A camera
+        refutes a cell only when it sees all of it (centre and eight corners in front) and the
+        bounding rectangle of their nearest pixels, widened by ``1 + (depth - 1 - level)`` pixels,
+        lies wholly inside the image and holds no foreground pixel of the grown mask.  Such a test
+        is conservative, so the carve runs coarse to fine: it starts from every cell of level
+        ``min(start_level, depth - 1)``, tests at most ``batch_size`` candidates per call (one
+        read-back each) and looks only at the children of survivors; ``min_views`` applies at the
+        finest level.  Every ``start_level`` gives the same tree.  Guaranteed: with
+        ``max_misses = 0`` a finest cell is kept if it contains a point that no camera sees on the
+        background of the grown mask (and ``min_views`` cameras see the cell).  Not guaranteed:
+        the hull is fatter than the point carve's by the cell's footprint plus the pad (more than a
+        cell where a pixel is wider than a cell); a cell kept only through its footprint, whose
+        centre projects onto no foreground pixel in any camera, starts grey until
+        ``color="visible"`` or a fit colours it; and a cell that is partly off an image cannot be
+        refuted by that camera at all.  A cell both footprints keep has the same row bit for bit.  ``footprint="point"``
+        (the default) is the carve described first, bit for bit, and ignores ``start_level``."""
         who = "OcTree.build_from_silhouettes"
         depth, center, scale, batch_size, tolerances = OcTree._grid_arguments(
             who, "center has three components", depth, center, scale, batch_size,
@@ -1272,6 +1293,13 @@ class OcTree:
         if dilate < 0 or max_misses < 0 or min_views < 0:
             raise ValueError("%s: dilate, max_misses and min_views must be >= 0, got %d, %d and %d"
                              % (who, dilate, max_misses, min_views))
+        if footprint not in ("point", "box"):
+            raise ValueError("%s: footprint is 'point' or 'box', got %r" % (who, footprint))
+        if footprint == "box":
+            if isinstance(start_level, bool) or int(start_level) != start_level or start_level < 0:
+                raise ValueError("%s: start_level must be an integer >= 0, got %r"
+                                 % (who, start_level))
+            start_level = min(int(start_level), depth - 1)
         images = np.asarray(dataset.images)
         if images.ndim != 4 or images.shape[-1] != 4 or images.dtype != np.uint8:
             raise ValueError("%s: dataset.images must be (C,H,W,4) uint8 with an alpha channel, "
@@ -1299,7 +1327,11 @@ class OcTree:
         mask_u8 = mask.to(torch.uint8).contiguous()
         cells = 8 ** (depth - 1)
         kept_codes, kept_data = [], []
-        for first in range(0, cells, batch_size):
+        if footprint == "box":
+            kept_codes, kept_data = OcTree._carve_box_levels(
+                images_u8, mask_u8, proj, center, scale, depth, alpha_u8, max_misses, min_views,
+                sigma0, start_level, batch_size)
+        for first in range(0, cells if footprint == "point" else 0, batch_size):
             count = min(batch_size, cells - first)
             codes, data = ops.octree_carve_select(images_u8, mask_u8, proj, first, count, center,
                                                   scale, depth, alpha_u8, max_misses, min_views,
@@ -1320,6 +1352,47 @@ class OcTree:
             rows[:, :3] = OcTree._vote_colors(votes, rows[:, :3])
             data = torch.from_numpy(rows).to(device)
         return OcTree._from_cells(codes, data, depth, scale, center, tolerances, device)
+
+    @staticmethod
+    def _carve_box_levels(images_u8, mask_u8, proj, center, scale, depth, alpha_u8, max_misses,
+                          min_views, sigma0, start_level, batch_size, trace=None):
+        """The coarse-to-fine loop of ``build_from_silhouettes(footprint="box")``: every cell of
+        level ``start_level``, then level by level the children of the survivors, at most
+        ``batch_size`` candidates per call of K27.  -> lists of the kept finest cells' codes and
+        rows, chunk by chunk in code order (empty when nothing survives).  ``trace``, a list, gets
+        one ``(level, candidates, survivors)`` per level."""
+        sat = ops.octree_carve_box_tables(mask_u8)
+        device = images_u8.device
+
+        def test(candidates, level, expand):
+            return ops.octree_carve_box_level(images_u8, sat, proj, candidates, level, center,
+                                              scale, depth, alpha_u8, max_misses, min_views,
+                                              sigma0, expand=expand)
+
+        parts, tested = [], 8 ** start_level
+        for first in range(0, tested, batch_size):
+            count = min(batch_size, tested - first)
+            codes = torch.arange(first, first + count, dtype=torch.int32, device=device)
+            parts.append(test(codes, start_level, False))
+        for level in range(start_level, depth):
+            parts = [(c, d) for c, d in parts if c.shape[0] > 0]
+            if trace is not None:
+                trace.append((level, tested, sum(c.shape[0] for c, _ in parts)))
+            if level == depth - 1 or not parts:
+                break
+            parents = torch.cat([c for c, _ in parts])
+            parts, tested = [], 8 * parents.shape[0]
+            if batch_size >= 8:     # the kernel expands eight children per parent itself
+                step = batch_size // 8
+                for first in range(0, parents.shape[0], step):
+                    parts.append(test(parents[first:first + step].contiguous(), level + 1, True))
+            else:
+                children = ((parents[:, None] << 3)
+                            | torch.arange(8, dtype=torch.int32, device=device)).reshape(-1)
+                for first in range(0, tested, batch_size):
+                    parts.append(test(children[first:first + batch_size].contiguous(), level + 1,
+                                      False))
+        return [c for c, _ in parts], [d for _, d in parts]
 
     @staticmethod
     def build_from_samples(positions, depth: int, min_leaf_size: int, data=None) -> "OcTree":

@@ -1719,6 +1719,120 @@ def octree_carve_select(images_u8: torch.Tensor, mask_u8: torch.Tensor, proj: to
     return codes[:k].clone(), data[:k].clone()
 
 
+# --------------------------------------------------------------------------------- K27
+def octree_carve_box_tables(mask_u8: torch.Tensor) -> torch.Tensor:
+    """mask_u8 (C,H,W) uint8 (0 = background) -> the summed-area tables K27 reads, (C,H+1,W+1)
+    int32: ``sat[c, r, q]`` = the foreground pixels of camera c in rows ``< r`` and columns ``< q``.
+    Two int32 ``torch.cumsum``: exact integers, so ``H * W < 2^31``."""
+    if not torch.is_tensor(mask_u8) or mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3:
+        raise ValueError("octree_carve_box_level: mask_u8 must be a (C, H, W) torch.uint8 tensor")
+    cameras, height, width = mask_u8.shape
+    if height * width >= 2 ** 31:
+        raise ValueError("octree_carve_box_level: mask_u8 has H * W = %d pixels; fewer than 2^31 "
+                         "fit the int32 summed-area table" % (height * width))
+    sat = torch.zeros((cameras, height + 1, width + 1), dtype=torch.int32, device=mask_u8.device)
+    inner = (mask_u8 != 0).to(torch.int32)
+    sat[:, 1:, 1:] = torch.cumsum(torch.cumsum(inner, 1, dtype=torch.int32), 2, dtype=torch.int32)
+    return sat
+
+
+def octree_carve_box_check(images_u8, sat, proj, candidates, expand, level, depth, alpha_u8,
+                           max_misses, min_views):
+    """The refusals of ``octree_carve_box_level``, none of which needs a device: shapes, dtypes,
+    contiguity, the camera limit, ``H * W < 2^31``, a finite ``proj`` (read back once), a level
+    inside the tree, a candidate list that fits the scan, and the ranges of the scalars.  Tensors on
+    any device.  -> (C, H, W, count).  Raises ``ValueError`` naming the argument."""
+    who = "octree_carve_box_level"
+
+    def want(name, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise ValueError("%s: %s must be a %s tensor, got %s"
+                             % (who, name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise ValueError("%s: %s must be (%s), got %s"
+                             % (who, name, ", ".join("*" if w is None else str(w) for w in shape),
+                                tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+
+    want("images_u8", images_u8, torch.uint8, (None, None, None, 4))
+    cameras, height, width = images_u8.shape[:3]
+    want("sat", sat, torch.int32, (cameras, height + 1, width + 1))
+    want("proj", proj, torch.float32, (cameras, 3, 4))
+    want("candidates", candidates, torch.int32, (None,))
+    limit = octree_carve_max_cameras()
+    if cameras < 1 or cameras > limit:
+        raise ValueError("%s: images_u8 holds %d cameras; 1 .. %d are supported (255 * C must be "
+                         "exact in f32)" % (who, cameras, limit))
+    if not 1 <= height <= 1 << 24 or not 1 <= width <= 1 << 24:
+        raise ValueError("%s: images_u8 must be (C, H, W, 4) with 1 <= H, W <= 2^24, got %s"
+                         % (who, tuple(images_u8.shape)))
+    if height * width >= 2 ** 31:
+        raise ValueError("%s: images_u8 has H * W = %d pixels; fewer than 2^31 fit the int32 "
+                         "summed-area table" % (who, height * width))
+    if not bool(torch.isfinite(proj).all()):
+        raise ValueError("%s: proj holds a NaN or an infinity" % who)
+    depth, level, expand = int(depth), int(level), bool(expand)
+    if depth < 1 or depth > octree_max_depth():
+        raise ValueError("%s: depth %d is outside what the path codes hold (1 .. %d)"
+                         % (who, depth, octree_max_depth()))
+    if not 0 <= level <= depth - 1:
+        raise ValueError("%s: level %d is outside 0 .. depth - 1 = %d" % (who, level, depth - 1))
+    if expand and level < 1:
+        raise ValueError("%s: expand needs level >= 1 (level 0 has no parent)" % who)
+    count = candidates.shape[0] * (8 if expand else 1)
+    if count < 1 or count > octree_max_points():
+        raise ValueError("%s: candidates gives count = %d cells in one call; 1 .. %d fit the scan"
+                         % (who, count, octree_max_points()))
+    if not 1 <= int(alpha_u8) <= 255:
+        raise ValueError("%s: alpha_u8 must lie in 1 .. 255, got %r" % (who, alpha_u8))
+    if not 0 <= int(max_misses) < 2 ** 31 or not 0 <= int(min_views) < 2 ** 31:
+        raise ValueError("%s: max_misses and min_views must be >= 0, got %r and %r"
+                         % (who, max_misses, min_views))
+    return cameras, height, width, count
+
+
+def octree_carve_box_level(images_u8: torch.Tensor, sat: torch.Tensor, proj: torch.Tensor,
+                           candidates: torch.Tensor, level: int, center, scale: float, depth: int,
+                           alpha_u8: int, max_misses: int, min_views: int, sigma0: float,
+                           expand: bool = False, want_visited: bool = False):
+    """K27.  One level of the conservative carve.  images_u8 (C,H,W,4) uint8 RGBA, sat (C,H+1,W+1)
+    int32 (``octree_carve_box_tables`` of the grown mask), proj (C,3,4) float32, candidates (N,)
+    int32: path codes of level ``level`` in code order, or with ``expand`` the codes of N parents of
+    level ``level - 1`` whose 8 N children are tested (child ``(parent << 3) | j``), never
+    materialised.  -> codes (K) int32 of the survivors in candidate order, and data: (K,4) float32
+    ``[r, g, b, sigma0]`` at the finest level (``level == depth - 1``), None below it.  A camera
+    refutes a cell only if the padded bounding rectangle of the cell's centre and eight corners lies
+    wholly inside the image and holds no foreground pixel; a cell with more than ``max_misses``
+    refutations is dropped, and at the finest level also one that fewer than ``min_views`` cameras
+    see.  A child's rectangle lies inside its parent's, so the children of a dropped cell need no
+    test.  Reads the count back once.  With ``want_visited`` also (count,) int32: how many cameras
+    each candidate's loop looked at.  Bad input is a ``ValueError`` (``octree_carve_box_check``)."""
+    cameras, height, width, n = octree_carve_box_check(images_u8, sat, proj, candidates, expand,
+                                                       level, depth, alpha_u8, max_misses,
+                                                       min_views)
+    dev = images_u8.device
+    rows = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    codes = torch.empty((n,), dtype=torch.int32, device=dev)
+    data = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    visited = torch.empty((n,), dtype=torch.int32, device=dev) if want_visited else None
+    flags, offsets, tiles = _scan_scratch(n, dev)
+    _call("ffn_octree_carve_box_level", _dev(images_u8, torch.uint8, "images_u8"),
+          _dev(sat, torch.int32, "sat"), _dev(proj, name="proj"), c_i(cameras), c_i(height),
+          c_i(width), _dev(candidates, torch.int32, "candidates"), c_i64(n),
+          c_i(1 if expand else 0), c_i(int(level)), c_f(center[0]), c_f(center[1]),
+          c_f(center[2]), c_f(scale), c_i(int(depth)), c_i(int(alpha_u8)), c_i(int(max_misses)),
+          c_i(int(min_views)), c_f(sigma0), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          _dev(tiles, torch.int32), _dev(rows), _dev(visited, torch.int32),
+          _dev(codes, torch.int32), _dev(data), _dev(total, torch.int32))
+    k = int(total.item())
+    kept = data[:k].clone() if int(level) == int(depth) - 1 else None
+    if want_visited:
+        return codes[:k].clone(), kept, visited
+    return codes[:k].clone(), kept
+
+
 # --------------------------------------------------------------------------------- K24
 def octree_visible_check(leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj,
                          eyes, depth, alpha_u8, min_transmittance, out=None):

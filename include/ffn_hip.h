@@ -1236,6 +1236,54 @@ int ffn_octree_carve_select(const uint8_t* images, const uint8_t* mask, const fl
                             float* rows, int* visited, int* codes_out, float* data_out,
                             int* total, void* stream);
 
+/* K27 (csrc/carve_box.hip): one level of a conservative, coarse-to-fine space carve, one thread
+ * per candidate cell of level `level` (0 = the root cube, depth - 1 = the finest).  No reference
+ * counterpart.  images / proj / cameras / height / width / the cube / depth / alpha_u8 / max_misses
+ * / min_views / sigma0 as for ffn_octree_carve_select.  sat (cameras, height + 1, width + 1) int32:
+ * sat[c][r][q] = the foreground pixels of camera c's (grown) mask in rows < r and columns < q, so
+ * height * width < 2^31.  candidates: int32 path codes of level `level`, in [0, 8^level) (only
+ * their low 3 level bits are read; no memory is indexed by a code).  expand == 0: candidate i is
+ * candidates[i], count entries.  expand == 1 (level >= 1): candidate i is
+ * (candidates[i >> 3] << 3) | (i & 7), the children of count / 8 parents of level - 1, count a
+ * multiple of 8; the children are never written out.  Per (candidate, camera c = 0 .. cameras-1
+ * in that order), every operation one rounded f32 operation (no fma):
+ *     q0 = the cell's centre as ffn_octree_cell_centers makes it for depth = level + 1, h = scale
+ *     halved `level` times;  q1 .. q8 = (q0.x -+ h, q0.y -+ h, q0.z -+ h)
+ *     each point: x, y, w as K23;  in front iff w > 0;  fu = x / w + 0.5f, fv = y / w + 0.5f;  a
+ *     non-finite fu or fv of a point in front: the camera is undecided;  col = (int)floorf(fu
+ *     clamped to +-2^30), row likewise
+ *     [c0, c1] x [r0, r1] = min / max over the points in front, widened by
+ *     pad = 1 + (depth - 1 - level) pixels on every side
+ *     inside iff all nine in front, not undecided, 0 <= c0, c1 <= width - 1, 0 <= r0,
+ *     r1 <= height - 1;  miss iff inside and sat counts no foreground pixel in the rectangle
+ *     seen iff some point in front and (undecided or some point not in front or the rectangle
+ *     meets the image)
+ *     misses > max_misses ends the loop, the cell is rejected
+ * A camera that does not see the whole cell never refutes it.  A candidate survives iff it was not
+ * rejected and, at the finest level only, seen >= min_views.  Containment: the padded rectangle of
+ * a child lies inside its parent's (the pad shrinks by one pixel per level, which covers the f32
+ * rounding of the projection as long as that stays below half a pixel), so a cell that survives
+ * at max_misses implies that its parent survives, and testing only the children of survivors
+ * gives the set that testing every finest cell gives.  At the finest level a survivor's row is
+ * [r, g, b, sigma0] with K23's colour from q0's own projection (in front and on the image, the pixel
+ * votes iff its own alpha >= alpha_u8; 0.5f without a vote): a cell K23 keeps too has K23's row
+ * bit for bit.  Below the finest level rows are not written and data_out is undefined.
+ * The survivors in candidate order (stable): codes_out (int32) and data_out (count,4), *total
+ * (device) of them, in arrays of count entries.  flags / offsets / tile_sums / rows / visited as
+ * for ffn_octree_carve_select.  Refused by name before any launch: level outside 0 .. depth - 1,
+ * count outside 1 .. ffn_octree_max_points(), cameras outside 1 .. ffn_octree_carve_max_cameras(),
+ * height or width outside 1 .. 2^24 or height * width >= 2^31, alpha_u8 outside 1 .. 255, negative
+ * max_misses or min_views, a null or misaligned buffer.  No atomics; the same inputs give the same
+ * bits. */
+int ffn_octree_carve_box_level(const uint8_t* images, const int32_t* sat, const float* proj,
+                               int cameras, int height, int width, const int32_t* candidates,
+                               int64_t count, int expand, int level, float center_x,
+                               float center_y, float center_z, float scale, int depth,
+                               int alpha_u8, int max_misses, int min_views, float sigma0,
+                               uint8_t* flags, int* offsets, int* tile_sums, float* rows,
+                               int* visited, int* codes_out, float* data_out, int* total,
+                               void* stream);
+
 /* K24 (csrc/octree_walk.hip, an eleventh mode of the K13 kernel): which cameras see a leaf through
  * the tree as it stands, and the sum of what they see there.  No counterpart in the reference.
  * One lane per (leaf, camera) pair, the camera in blockIdx.y; no ray is ever stored.

@@ -55,6 +55,9 @@ SKIP_GRID = [
     ("--skip-tree-center", dict(type=float, nargs=3, metavar=("X", "Y", "Z"),
                                 help="the root cube's centre of --skip-tree")),
     ("--skip-carve-depth", dict(type=int, default=0)),
+    ("--skip-carve-footprint", dict(choices=["point", "box"], default="point",
+                                    help="--skip-carve-depth: test a cell's centre (K23) or its "
+                                         "whole projected footprint (K27, conservative)")),
     ("--skip-resolution", dict(type=int, default=128)),
     ("--skip-dilate", dict(type=int, default=1)),
 ]
@@ -67,6 +70,9 @@ FOCUS_TREE = [
     ("--focus-tree-center", dict(type=float, nargs=3, metavar=("X", "Y", "Z"),
                                  help="the root cube's centre of --focus-tree")),
     ("--focus-carve-depth", dict(type=int, default=0)),
+    ("--focus-carve-footprint", dict(choices=["point", "box"], default="point",
+                                     help="--focus-carve-depth: test a cell's centre (K23) or its "
+                                          "whole projected footprint (K27, conservative)")),
     ("--focus-min-mass", dict(type=float, default=1e-3,
                               help="rays whose tree weights sum to less sample uniformly")),
 ]
@@ -251,6 +257,13 @@ def focus_mode(args) -> str:
     return "live" if mode == "auto" else mode
 
 
+def carve_footprint(args, prefix):
+    """The carve arguments of --skip-carve-footprint / --focus-carve-footprint (``prefix`` "skip" or
+    "focus"): nothing for "point", so that the default call stays the call it was."""
+    footprint = getattr(args, "%s_carve_footprint" % prefix, "point")
+    return {} if footprint == "point" else {"footprint": footprint}
+
+
 def apply_skipping(caster, args, train=None):
     """--skip-empty-space: the opt-in occupancy-grid schedule of Raycaster.fit.  --skip-tree /
     --skip-carve-depth: a grid that needs no model (DESIGN K25), from a saved octree or carved
@@ -279,7 +292,8 @@ def apply_skipping(caster, args, train=None):
                                              center=args.skip_tree_center, dilate=args.skip_dilate)
     else:
         grid = ffn.OccupancyGrid.from_silhouettes(train, resolution=args.skip_resolution,
-                                                  depth=carve_depth, dilate=args.skip_dilate)
+                                                  depth=carve_depth, dilate=args.skip_dilate,
+                                                  **carve_footprint(args, "skip"))
     print("empty-space skipping from step 0: %.4f of the %d^3 cells occupied"
           % (grid.fraction_occupied(), grid.resolution))
     caster.train_occupancy = grid
@@ -322,7 +336,8 @@ def focus_tree(args, train=None):
     lo, size = ffn.OccupancyGrid.box_of(train.sampler.bounds)
     center = tuple(float(v) for v in lo + 0.5 * size)
     tree = ffn.OcTree.build_from_silhouettes(train, args.focus_carve_depth, center,
-                                             0.5 * float(size.max()), color="visible")
+                                             0.5 * float(size.max()), color="visible",
+                                             **carve_footprint(args, "focus"))
     return tree, center
 
 

@@ -7,9 +7,12 @@ trained model in between.  No counterpart in the reference.
         [--center X Y Z] [--scale S] [--alpha-threshold 0.5] [--dilate 1] [--max-misses 0]
         [--min-views 2] [--cell-opacity 0.5] [--merge-tolerance RGB SIGMA]
         [--color {mean,visible}] [--visible-transmittance 0.3]
+        [--footprint {point,box}] [--start-level 4]
 
 ``--color visible`` colours every carved cell from the cameras that can see it through the carved
-hull (kernel K24) instead of from all that look its way.
+hull (kernel K24) instead of from all that look its way.  ``--footprint box`` carves conservatively
+and coarse to fine from ``--start-level`` (kernel K27): a cell goes only when some camera sees its
+whole projected footprint on the background, so thin structure survives and the hull is fatter.
 """
 
 import os
@@ -46,6 +49,11 @@ CARVE_OCTREE = [
     ("--visible-transmittance", dict(type=float, default=0.3,
                                      help="--color visible: a camera sees a cell while the "
                                           "transmittance in front of it is above this")),
+    ("--footprint", dict(choices=["point", "box"], default="point",
+                         help="What a camera tests of a cell: its centre (K23), or the padded "
+                              "rectangle round its centre and corners (K27, conservative)")),
+    ("--start-level", dict(type=int, default=4,
+                           help="--footprint box: the level the coarse-to-fine carve starts at")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -66,7 +74,7 @@ def main():
     tree = ffn.OcTree.build_from_silhouettes(
         dataset, args.voxel_depth, args.center, args.scale, args.alpha_threshold, args.dilate,
         args.max_misses, args.min_views, args.cell_opacity, args.merge_tolerance, args.batch_size,
-        args.color, args.visible_transmittance)
+        args.color, args.visible_transmittance, args.footprint, args.start_level)
     print(tree.num_leaves, "leaves")
     # the file format is the reference's and has no place for the root cube's centre
     print("root cube centre (for train_octree.py / render_octree.py): --center",
