@@ -10,7 +10,7 @@ from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
-from .octree import OcTree, refine_actions
+from .octree import OcTree, PhotoReport, PhotoSweep, photo_actions, refine_actions
 from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, fit_octree,
                          fit_octree_adaptive, fit_octree_sh, leaf_weights_over)
 from .pixel_dataset import PixelData, PixelDataset
@@ -41,8 +41,8 @@ __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
-           "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
+           "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "eye_positions", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
-           "linspace", "load_model", "load_obj", "normalize_points", "orbit", "procedural_torus",
+           "linspace", "load_model", "load_obj", "normalize_points", "orbit", "photo_actions", "procedural_torus",
            "projection_matrices", "refine_actions", "sample_mesh", "triangle_counts"]

@@ -169,6 +169,24 @@
 // rays and 16.59 ms for 160 000 rays of one camera in a depth-8 carved tree, 2.1x / 2.2x K15's one walk on the
 // same rays (4.57 / 7.71 ms); depth 10: 37.24 / 71.58 ms, 2.1x.  Latency-bound like every mode: 4096 rays are 64
 // waves.  Kernel times under rocprofv3 and LDS-staged emits were not measured.
+//
+// K28a  Visible moments: a twelfth mode (kVisibleMoments), kVisible operation for operation -- the
+// pair, the projection, the early rejects, the walk, the taken-leaf rule, the transmittance and the
+// three endings are the same code (kSees below) -- with a wider write-back: a leaf's row is eight
+// uint32, [sum_r, sum_g, sum_b, count, sq_r, sq_g, sq_b, 0], and a visible pair sends FOUR 64-bit
+// integer atomic adds of two fields each: K24's two words, then [sq_r, sq_g] and [sq_b, 0] with
+// sq_c = c c of the pixel's byte.  The atomics return nothing and come after the walk; no float
+// atomic.  The limit: a square is at most 65025 and 65025 C < 2^32 holds for C <= 66051 cameras folded
+// into one buffer (kMomentsMaxCameras, the caller's to keep), so no carry crosses a field and the
+// sums are exact in any order of the cameras, in one call or split over many.  The lanes of a wave
+// write 2 KiB of neighbouring words.  Not a sibling kernel: it needs nothing that the idle parameters
+// cannot carry (`leaves` is the moments buffer).
+// Resource report, kVisibleMoments: 39 VGPRs, 89 SGPRs, 0 bytes of scratch, 0 spills, 0 bytes of
+// LDS, occupancy 8 waves per SIMD, 966 instructions (kVisible's 959 and seven: the squares, the
+// two further atomics and their operands).  The eleven older instantiations and octree_focus_kernel compile
+// to the instructions they had before: their disassembly was compared with the previous commit's,
+// instruction for instruction (758 / 809 / 851 / 887 / 975 / 1002 / 1034 / 1095 / 1132 / 845 / 959
+// and 1316 instructions; 38 / 40 / 50 / 53 / 61 / 56 / 72 / 64 / 82 / 39 / 39 and 75 VGPRs).
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
@@ -181,6 +199,9 @@ constexpr int kWalkMaxDepth = 11;     // as K12's path codes: at most 10 levels 
 static const int64_t kWalkMaxRays = (int64_t)1 << 31;
 constexpr int kVisibleMaxSide = 1 << 24;              // (float)W and (float)H are exact
 constexpr int kVisibleMaxLaunchCameras = 65535;       // gridDim.y
+constexpr int kMomentsMaxCameras = 66051;             // K28a: 255 * 255 * C < 2^32 (the caller's to keep)
+static_assert(65025ull * kMomentsMaxCameras < (1ull << 32) &&
+              65025ull * (kMomentsMaxCameras + 1) >= (1ull << 32), "the field bound of K28a");
 
 // is key in the sorted ids?  *at = its position
 __device__ __forceinline__ bool find_id(const int64_t* __restrict__ ids, int64_t n, int64_t key,
@@ -266,7 +287,8 @@ struct FirstHit {
 };
 
 enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
-                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9, kVisible = 10 };
+                kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9, kVisible = 10,
+                kVisibleMoments = 11 };
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
@@ -289,6 +311,7 @@ enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVo
 //            t_stops the camera-major uint32 RGBA pixels, leaves the (num_leaves) pairs of 64-bit
 //            vote words, max_length alpha_u8, first.bg_r / first.bg_g the image's width / height as
 //            floats (exact: at most 2^24), first.leaf_data / channels / shading as kLeafWeight.
+// kVisibleMoments: K28a.  kVisible, and leaves the (num_leaves) rows of FOUR 64-bit words.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -298,6 +321,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                    float t_min, float pad, float* __restrict__ span_in,
                    float* __restrict__ span_out, uint8_t* __restrict__ span_hit, FirstHit first) {
     constexpr bool kSpans = kMode == kSpan;
+    constexpr bool kSees = kMode == kVisible || kMode == kVisibleMoments;      // K24, K28a
     constexpr bool kSH = kMode == kVolumeSH1 || kMode == kVolumeSH2;
     constexpr bool kSHGrad = kMode == kGradSH1 || kMode == kGradSH2;
     constexpr int kBasis = kMode == kVolumeSH2 || kMode == kGradSH2 ? 9 : 4;
@@ -305,9 +329,9 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     if (r >= n) return;
     const float sx = starts[r * 3 + 0], sy = starts[r * 3 + 1], sz = starts[r * 3 + 2];
     // K24: the pair's pixel, and the cheap rejects before the first tree lookup
-    const float* camera = directions + (kMode == kVisible ? 16 * (int64_t)blockIdx.y : 0);
+    const float* camera = directions + (kSees ? 16 * (int64_t)blockIdx.y : 0);
     uint32_t rgba = 0;
-    if (kMode == kVisible) {
+    if (kSees) {
         const float w = ((camera[8] * sx + camera[9] * sy) + camera[10] * sz) + camera[11];
         if (!(w > 0.0f)) return;                         // behind the camera (NaN too)
         const float x = ((camera[0] * sx + camera[1] * sy) + camera[2] * sz) + camera[3];
@@ -321,11 +345,11 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         if ((rgba >> 24) < (uint32_t)max_length) return;            // background
     }
     // K24: from the eye to the leaf's centre, which lies at t = 1
-    const float ox = kMode == kVisible ? camera[12] : sx, oy = kMode == kVisible ? camera[13] : sy,
-                oz = kMode == kVisible ? camera[14] : sz;
-    const float dx = kMode == kVisible ? sx - ox : directions[r * 3 + 0],
-                dy = kMode == kVisible ? sy - oy : directions[r * 3 + 1],
-                dz = kMode == kVisible ? sz - oz : directions[r * 3 + 2];
+    const float ox = kSees ? camera[12] : sx, oy = kSees ? camera[13] : sy,
+                oz = kSees ? camera[14] : sz;
+    const float dx = kSees ? sx - ox : directions[r * 3 + 0],
+                dy = kSees ? sy - oy : directions[r * 3 + 1],
+                dz = kSees ? sz - oz : directions[r * 3 + 2];
     const int levels = depth - 1;
     const int cells = 1 << levels;
 
@@ -363,7 +387,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
     const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad ||
-                               kMode == kLeafWeight || kMode == kVisible
+                               kMode == kLeafWeight || kSees
                            ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
@@ -567,7 +591,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 trans = trans * (1.0f - a);
                 if (trans <= first.min_transmittance) break;
             }
-        } else if (kMode == kVisible) {
+        } else if (kSees) {
             if (leaf >= 0 && t_exit > t_min) {
                 if (leaf == r) {                               // nothing opaque came first
                     visible = true;
@@ -644,14 +668,23 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         }
     } else if (kMode == kLeafWeight) {
         // nothing per ray
-    } else if (kMode == kVisible) {
+    } else if (kSees) {
         if (visible) {
             // [sum_r, sum_g] and [sum_b, count] as two 64-bit words, the first field in the low half:
             // a sum stays below 2^24 and the count below 2^17, so no carry crosses a field
-            unsigned long long* votes = reinterpret_cast<unsigned long long*>(leaves) + 2 * r;
+            // K28a: a leaf's row is four words, K24's two and then [sq_r, sq_g] and [sq_b, 0]; a square
+            // is at most 65025 and 65025 C < 2^32 for at most kMomentsMaxCameras cameras per buffer
+            constexpr int kWords = kMode == kVisibleMoments ? 4 : 2;
+            unsigned long long* votes = reinterpret_cast<unsigned long long*>(leaves) + kWords * r;
             atomicAdd(votes, (unsigned long long)(rgba & 255u) |
                                  ((unsigned long long)((rgba >> 8) & 255u) << 32));
             atomicAdd(votes + 1, (unsigned long long)((rgba >> 16) & 255u) | (1ull << 32));
+            if (kMode == kVisibleMoments) {
+                const uint32_t cr = rgba & 255u, cg = (rgba >> 8) & 255u, cb = (rgba >> 16) & 255u;
+                atomicAdd(votes + 2, (unsigned long long)(cr * cr) |
+                                         ((unsigned long long)(cg * cg) << 32));
+                atomicAdd(votes + 3, (unsigned long long)(cb * cb));
+            }
         }
     } else if (kSpans) {
         // pad finest-cell sides along the ray, in t
@@ -1093,14 +1126,15 @@ extern "C" int ffn_octree_leaf_weights(const float* starts, const float* directi
                                     (uint8_t*)weights);
 }
 
-extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, float scale,
-                                        int depth, const int64_t* node_index, int64_t num_nodes,
-                                        const int64_t* leaf_index, const float* leaf_data,
-                                        int stride, int sigma_offset, const uint8_t* images,
-                                        const float* camera_blocks, int cameras, int height,
-                                        int width, int alpha_u8, float min_transmittance,
-                                        uint32_t* votes, void* stream) {
-    const char* who = "ffn_octree_visible_votes";
+// K24 and K28a: one list of arguments and checks, kMode the write-back; `votes` is (num_leaves,4)
+// uint32 for kVisible and (num_leaves,8) for kVisibleMoments
+template <int kMode>
+static int visible_pairs(const char* who, const float* leaf_centers, int64_t num_leaves, float scale,
+                         int depth, const int64_t* node_index, int64_t num_nodes,
+                         const int64_t* leaf_index, const float* leaf_data, int stride,
+                         int sigma_offset, const uint8_t* images, const float* camera_blocks,
+                         int cameras, int height, int width, int alpha_u8, float min_transmittance,
+                         uint32_t* votes, void* stream) {
     if (depth < 1 || depth > kWalkMaxDepth) return fail_who(who, "shape (1 <= depth <= 11)");
     if (num_leaves < 1 || num_leaves > kWalkMaxRays || num_nodes < 0)
         return fail_who(who, "shape (1 <= num_leaves <= 2^31, num_nodes >= 0)");
@@ -1116,7 +1150,9 @@ extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_l
         !camera_blocks || !votes)
         return fail_who(who, "null argument");
     if (((uintptr_t)images & 3) != 0 || misaligned16(votes))
-        return fail_who(who, "images must be 4-byte aligned, votes 16-byte aligned");
+        return fail_who(who, kMode == kVisible
+                                 ? "images must be 4-byte aligned, votes 16-byte aligned"
+                                 : "images must be 4-byte aligned, moments 16-byte aligned");
     // a pixel's index within one launch stays far inside int64
     const int64_t pixels = (int64_t)height * width;
     if (pixels > ((int64_t)1 << 46)) return fail_who(who, "images (height * width <= 2^46)");
@@ -1129,7 +1165,7 @@ extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_l
     for (int done = 0; done < cameras; done += kVisibleMaxLaunchCameras) {
         const int now = cameras - done < kVisibleMaxLaunchCameras ? cameras - done
                                                                   : kVisibleMaxLaunchCameras;
-        hipLaunchKernelGGL(octree_walk_kernel<kVisible>, dim3(blocks, (unsigned)now),
+        hipLaunchKernelGGL(octree_walk_kernel<kMode>, dim3(blocks, (unsigned)now),
                            dim3(kWalkThreads), 0, (hipStream_t)stream, leaf_centers,
                            camera_blocks + 16 * (int64_t)done, num_leaves, scale, depth, node_index,
                            num_nodes, leaf_index, num_leaves, alpha_u8,
@@ -1138,6 +1174,34 @@ extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_l
         if (int err = check_launch(who)) return err;
     }
     return 0;
+}
+
+extern "C" int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, float scale,
+                                        int depth, const int64_t* node_index, int64_t num_nodes,
+                                        const int64_t* leaf_index, const float* leaf_data,
+                                        int stride, int sigma_offset, const uint8_t* images,
+                                        const float* camera_blocks, int cameras, int height,
+                                        int width, int alpha_u8, float min_transmittance,
+                                        uint32_t* votes, void* stream) {
+    return visible_pairs<kVisible>("ffn_octree_visible_votes", leaf_centers, num_leaves, scale,
+                                   depth, node_index, num_nodes, leaf_index, leaf_data, stride,
+                                   sigma_offset, images, camera_blocks, cameras, height, width,
+                                   alpha_u8, min_transmittance, votes, stream);
+}
+
+extern "C" int ffn_octree_visible_moments(const float* leaf_centers, int64_t num_leaves,
+                                          float scale, int depth, const int64_t* node_index,
+                                          int64_t num_nodes, const int64_t* leaf_index,
+                                          const float* leaf_data, int stride, int sigma_offset,
+                                          const uint8_t* images, const float* camera_blocks,
+                                          int cameras, int height, int width, int alpha_u8,
+                                          float min_transmittance, uint32_t* moments,
+                                          void* stream) {
+    return visible_pairs<kVisibleMoments>("ffn_octree_visible_moments", leaf_centers, num_leaves,
+                                          scale, depth, node_index, num_nodes, leaf_index,
+                                          leaf_data, stride, sigma_offset, images, camera_blocks,
+                                          cameras, height, width, alpha_u8, min_transmittance,
+                                          moments, stream);
 }
 
 extern "C" void ffn_octree_face_shade(float* table) {

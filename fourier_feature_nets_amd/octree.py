@@ -112,11 +112,20 @@ public signatures are the reference's, so files and calling code go both ways.  
   round the cell's projected centre and corners lies on the image and on the background, so thin
   structure survives, and the carve runs coarse to fine over the children of survivors.
 
+* ``visible_moments`` / ``carve_photo`` / ``photo_actions`` (K28, a twelfth mode of
+  ``csrc/octree_walk.hip``) have none either: voxel colouring on the sparse tree.  K24's walk with
+  the squares of the seen bytes beside their sums gives every leaf a colour variance over the
+  cameras that see it; ``photo_actions`` is the integer policy that drops a leaf whose cameras
+  disagree; ``carve_photo`` sweeps -- moments, policy, ``refine`` -- until a sweep drops nothing.
+  The one step that removes hull volume no silhouette refutes.  ``build_from_silhouettes(...,
+  photo_threshold=T)`` runs it between the carve and the colouring; off by default.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
 ``bake``, ``bake_sh``, ``build_from_model``, ``build_from_silhouettes``, ``render_volume``,
-``leaf_centers``, ``leaf_depths``, ``neighbors``, ``total_variation``, ``leaf_weights`` and ``refine``
-run on the GPU and raise without one; ``refine_actions`` is numpy.
+``leaf_centers``, ``leaf_depths``, ``neighbors``, ``total_variation``, ``leaf_weights``, ``refine``,
+``visible_votes``, ``visible_moments`` and ``carve_photo`` run on the GPU and raise without one;
+``refine_actions`` and ``photo_actions`` are numpy.
 """
 
 import os
@@ -220,6 +229,64 @@ def refine_actions(weights, depths, prune_below: float = 1e-2, split_above=1e-1,
         action[(weights >= float(split_above)) & (depths < max_depth - 1)] = ops.OCTREE_SPLIT
     action[weights < prune_below] = ops.OCTREE_DROP
     return action
+
+
+def photo_actions(moments, threshold: float, min_views: int = 2) -> np.ndarray:
+    """The photo-consistency policy of K28, pure numpy and integers only: per leaf 0 (drop) where
+    at least ``min_views`` cameras see it and the pixels they see there disagree, 1 (keep)
+    otherwise -> (L,) uint8 for ``OcTree.refine``.  ``moments`` (L,8) uint32 from
+    ``OcTree.visible_moments``: ``[sum_r, sum_g, sum_b, n, sq_r, sq_g, sq_b, 0]``.  With
+    ``Q = sq_r + sq_g + sq_b``, ``S = sum_r^2 + sum_g^2 + sum_b^2`` (int64) and
+    ``limit = ceil(3 (255 threshold)^2)`` (float64, then an integer) a leaf is dropped iff
+    ``n >= min_views`` and ``n Q - S > limit n^2``; equality keeps.  In words: the mean over the
+    three channels of the per-channel variance of the seeing cameras' pixels exceeds
+    ``threshold^2``, colours in [0, 1].  Every product stays below 2^50 for the 66 051 cameras a
+    moments buffer holds.  Raises ``ValueError`` for a ``threshold`` outside [0, 1] (NaN too),
+    ``min_views < 2``, moments of another shape or dtype, a count above 66 051, sums that no ``count``
+    bytes can give and a nonzero eighth field."""
+    threshold = float(threshold)
+    if not 0.0 <= threshold <= 1.0:          # NaN fails too
+        raise ValueError("photo_actions: threshold must lie in [0, 1], got %r" % threshold)
+    if isinstance(min_views, bool) or int(min_views) != min_views or min_views < 2:
+        raise ValueError("photo_actions: min_views must be an integer >= 2 (one camera has no "
+                         "spread), got %r" % (min_views,))
+    moments = np.asarray(moments)
+    if moments.ndim != 2 or moments.shape[1] != 8 or moments.dtype != np.uint32:
+        raise ValueError("photo_actions: moments must be (L, 8) uint32, got %s %s"
+                         % (moments.dtype, moments.shape))
+    if moments[:, 7].any():
+        raise ValueError("photo_actions: the eighth field of moments must be 0 (a carry out of "
+                         "sq_b: more than %d cameras in one buffer?)"
+                         % ops.OCTREE_MOMENTS_MAX_CAMERAS)
+    wide = moments.astype(np.int64)
+    n = wide[:, 3]
+    if n.max(initial=0) > ops.OCTREE_MOMENTS_MAX_CAMERAS:
+        raise ValueError("photo_actions: a count of moments is %d; at most %d cameras fold into "
+                         "one buffer" % (int(n.max()), ops.OCTREE_MOMENTS_MAX_CAMERAS))
+    if (wide[:, :3] > 255 * n[:, None]).any() or (wide[:, 4:7] > 65025 * n[:, None]).any():
+        raise ValueError("photo_actions: a sum of moments exceeds 255 count, or a sum of squares "
+                         "255^2 count: not the moments of bytes")
+    limit = int(np.ceil(3.0 * (255.0 * threshold) ** 2))
+    spread = wide[:, 4:7].sum(1)
+    left, squares, right = n * spread, (wide[:, :3] ** 2).sum(1), limit * n * n
+    assert max(left.max(initial=0), squares.max(initial=0), right.max(initial=0)) < 1 << 50
+    action = np.full(len(moments), ops.OCTREE_KEEP, np.uint8)
+    action[(n >= int(min_views)) & (left - squares > right)] = ops.OCTREE_DROP
+    return action
+
+
+PhotoSweep = NamedTuple("PhotoSweep", [("leaves", int), ("seen", int), ("judged", int),
+                                       ("dropped", int)])
+
+
+class PhotoReport(list):
+    """What ``OcTree.carve_photo`` did: one ``PhotoSweep(leaves, seen, judged, dropped)`` per sweep
+    -- the leaves before it, those some camera saw (``count > 0``), those judged
+    (``count >= min_views``) and those dropped -- and ``converged``: whether the loop ended on a
+    sweep that dropped nothing (``False`` after ``max_sweeps`` sweeps that all dropped, and for
+    ``max_sweeps = 0``)."""
+
+    converged = False
 
 
 Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
@@ -750,6 +817,14 @@ class OcTree:
         return images, cameras, min(max(int(np.ceil(alpha_threshold * 255)), 1), 255)
 
     def _visible_votes_on_device(self, images, cameras, alpha_u8, center, min_transmittance):
+        return self._visible_pairs_on_device(ops.octree_visible_votes, images, cameras, alpha_u8,
+                                             center, min_transmittance)
+
+    def _visible_moments_on_device(self, images, cameras, alpha_u8, center, min_transmittance):
+        return self._visible_pairs_on_device(ops.octree_visible_moments, images, cameras,
+                                             alpha_u8, center, min_transmittance)
+
+    def _visible_pairs_on_device(self, op, images, cameras, alpha_u8, center, min_transmittance):
         from .cameras import eye_positions, projection_matrices
         dev = self._dev()
         if self._sh_degree is not None:
@@ -760,7 +835,7 @@ class OcTree:
             torch.from_numpy(np.ascontiguousarray(images)).to(dev)
         proj = torch.from_numpy(projection_matrices(cameras, origin=center)).to(dev)
         eyes = torch.from_numpy(eye_positions(cameras, center)).to(dev)
-        return ops.octree_visible_votes(
+        return op(
             self._centers_on_device(), self._scale, self.depth, self._on_device("node_index"),
             self._on_device("leaf_index"), rows, int(rows.shape[1]), offset, images_u8, proj, eyes,
             alpha_u8, float(min_transmittance))
@@ -837,6 +912,120 @@ class OcTree:
         denominator = (np.uint32(255) * votes[seen, 3]).astype(np.float32)
         out[seen] = votes[seen, :3].astype(np.float32) / denominator[:, None]
         return out
+
+    def visible_moments(self, dataset, center=None, alpha_threshold: float = 0.5,
+                        min_transmittance: float = 0.3) -> np.ndarray:
+        """``visible_votes`` with the second moments (K28a; no counterpart in the reference) ->
+        (L,8) uint32 numpy ``[sum_r, sum_g, sum_b, count, sq_r, sq_g, sq_b, 0]``: the same
+        arguments and the same (leaf, camera) pairs, the first four fields are the votes bit for
+        bit, and ``sq_c`` is the sum of the squares of the bytes the seeing cameras hold there, so
+        that a leaf has a colour variance as well as a mean (``photo_actions``).  Works on plain
+        and SH trees alike (only the density is read).  Integer sums: the same bits in any order
+        of the cameras.  At most 66 051 cameras (``255^2 C < 2^32``)."""
+        who = "OcTree.visible_moments"
+        self._check_volume(min_transmittance, who)           # before any device is needed
+        images, cameras, alpha_u8 = OcTree._visible_arguments(who, dataset, alpha_threshold)
+        OcTree._check_moments_cameras(who, cameras)
+        center = self._visible_center(who, center)
+        return self._visible_moments_on_device(images, cameras, alpha_u8, center,
+                                               min_transmittance).cpu().numpy()
+
+    @staticmethod
+    def _check_moments_cameras(who, cameras):
+        if len(cameras) > ops.OCTREE_MOMENTS_MAX_CAMERAS:
+            raise ValueError("%s: dataset has %d cameras; at most %d fold into one moments buffer "
+                             "(255^2 * C must stay below 2^32)"
+                             % (who, len(cameras), ops.OCTREE_MOMENTS_MAX_CAMERAS))
+
+    def carve_photo(self, dataset, center=None, threshold: float = 0.1, min_views: int = 2,
+                    max_sweeps: int = 16, alpha_threshold: float = 0.5,
+                    min_transmittance: float = 0.3,
+                    recolor: bool = False) -> Tuple["OcTree", "PhotoReport"]:
+        """Carves by photo-consistency (K28; the classic voxel colouring / space carving, no
+        counterpart in the reference): a NEW tree without the leaves whose seeing cameras disagree
+        on their colour -> ``(tree, report)``, ``report`` a ``PhotoReport``.  Each sweep takes
+        fresh ``visible_moments`` of the tree as it stands over all leaves and all cameras, then
+        ``photo_actions(moments, threshold, min_views)``, then ``refine`` (drops only).  All
+        decisions of a sweep come from one tree, so the result does not depend on the order of the
+        leaves.  A drop can expose leaves behind it, which the next sweep judges; the loop stops
+        after a sweep that drops nothing (``report.converged``) or after ``max_sweeps``.  A sweep
+        that would drop every leaf raises ``ValueError`` (raise ``threshold``).  ``max_sweeps=0``
+        returns a tree equal to this one bit for bit.  ``dataset``, ``center``,
+        ``alpha_threshold`` and ``min_transmittance`` as for ``visible_votes``.
+
+        ``recolor=True`` gives every leaf of the FINAL tree that some camera sees
+        ``sum / (float)(255 count)`` as ``color_from_images`` does (the last sweep's moments when
+        it dropped nothing, one more call otherwise); an SH tree is refused with it, for
+        ``color_from_images``' reason, and accepted without.  Densities, the other channels,
+        scale, centre, ``sh_degree`` and device carry over through ``refine``; this tree is not
+        modified.
+
+        The limits.  One ray per (leaf, camera) pair at the leaf's centre, to the nearest pixel:
+        the colour a camera holds for a leaf is one sample, and a leaf whose centre is hidden
+        counts as hidden.  Opacity is judged from the tree's own densities (``color_from_images``).
+        A smooth or uniform texture cannot refute anything: phantom cells in front of a surface of
+        one colour stay.  Specular or badly exposed views, and colour that changes within a cell's
+        footprint, refute TRUE cells.  The guarantee of the box carve ("a cell containing a point
+        no camera sees on the background is kept") is given up wherever the threshold fires.
+        ``threshold = 0.1`` (the root of the mean channel variance, colours in [0, 1]) is an
+        untuned starting value."""
+        who = "OcTree.carve_photo"
+        if recolor and self._sh_degree is not None:
+            raise ValueError("%s: the leaves of an SH tree hold coefficients, not a colour; "
+                             "recolor=False carves it, OcTree.visible_votes gives the cameras' "
+                             "sums for it" % who)
+        self._check_volume(min_transmittance, who)           # before any device is needed
+        images, cameras, alpha_u8 = OcTree._visible_arguments(who, dataset, alpha_threshold)
+        OcTree._check_moments_cameras(who, cameras)
+        center = self._visible_center(who, center)
+        try:
+            photo_actions(np.zeros((0, 8), np.uint32), threshold, min_views)
+        except ValueError as err:
+            raise ValueError("%s: %s" % (who, str(err).split(": ", 1)[1])) from None
+        if isinstance(max_sweeps, bool) or int(max_sweeps) != max_sweeps or max_sweeps < 0:
+            raise ValueError("%s: max_sweeps must be an integer >= 0, got %r" % (who, max_sweeps))
+        tree, report, moments, _ = self._photo_sweeps(
+            who, images, cameras, alpha_u8, center, threshold, int(min_views), int(max_sweeps),
+            float(min_transmittance), bool(recolor))
+        data = tree._leaf_data
+        if recolor:
+            data = np.array(data, dtype=np.float32, copy=True)
+            data[:, :3] = OcTree._vote_colors(moments[:, :4], data[:, :3])
+        out = OcTree(tree._scale, tree._node_index.copy(), tree._leaf_index.copy(),
+                     np.array(data, copy=True), tree._sh_degree)
+        out._device = self._device
+        out._center = self._center
+        return out, report
+
+    def _photo_sweeps(self, who, images, cameras, alpha_u8, center, threshold, min_views,
+                      max_sweeps, min_transmittance, want_moments=False):
+        """The loop of ``carve_photo`` -> the last tree (this one when nothing was dropped), the
+        report, the last tree's moments (``None`` unless ``want_moments`` or the last sweep was
+        its) and, per leaf of the last tree, the number of the leaf of THIS tree it was."""
+        tree, report, last = self, PhotoReport(), None
+        origin = np.arange(self.num_leaves, dtype=np.int64)
+        if not torch.is_tensor(images):          # once for all sweeps
+            images = torch.from_numpy(np.ascontiguousarray(images)).to(self._dev())
+        for _ in range(max_sweeps):
+            moments = tree._visible_moments_on_device(images, cameras, alpha_u8, center,
+                                                      min_transmittance).cpu().numpy()
+            action = photo_actions(moments, threshold, min_views)
+            dropped = int((action == ops.OCTREE_DROP).sum())
+            report.append(PhotoSweep(tree.num_leaves, int((moments[:, 3] > 0).sum()),
+                                     int((moments[:, 3] >= min_views).sum()), dropped))
+            if dropped == 0:
+                report.converged, last = True, moments
+                break
+            if dropped == tree.num_leaves:
+                raise ValueError("%s: sweep %d would drop every one of the %d leaves: threshold "
+                                 "%r refutes them all, raise it"
+                                 % (who, len(report), tree.num_leaves, threshold))
+            tree, parent = tree.refine(action)
+            origin = origin[parent]
+        if want_moments and last is None:
+            last = tree._visible_moments_on_device(images, cameras, alpha_u8, center,
+                                                   min_transmittance).cpu().numpy()
+        return tree, report, last, origin
 
     def refine(self, action) -> Tuple["OcTree", np.ndarray]:
         """A NEW tree from one decision per leaf (K21b): ``action`` (L,) with 0 drop, 1 keep, 2 split
@@ -1226,7 +1415,10 @@ class OcTree:
                                merge_tolerance=None, batch_size: int = 1 << 20,
                                color: str = "mean",
                                visible_transmittance: float = 0.3,
-                               footprint: str = "point", start_level: int = 4) -> "OcTree":
+                               footprint: str = "point", start_level: int = 4,
+                               photo_threshold: Optional[float] = None,
+                               photo_min_views: int = 2, photo_max_sweeps: int = 16,
+                               photo_report: Optional[list] = None) -> "OcTree":
         """Carves a tree out of the root cube from the images' silhouettes alone (K23; no
         counterpart in the reference): a starting point for ``fit_octree`` that needs neither a
         trained model nor the mesh.
@@ -1273,7 +1465,17 @@ class OcTree:
         centre projects onto no foreground pixel in any camera, starts grey until
         ``color="visible"`` or a fit colours it; and a cell that is partly off an image cannot be
         refuted by that camera at all.  A cell both footprints keep has the same row bit for bit.  ``footprint="point"``
-        (the default) is the carve described first, bit for bit, and ignores ``start_level``."""
+        (the default) is the carve described first, bit for bit, and ignores ``start_level``.
+
+        ``photo_threshold`` answers the third limit (K28).  ``None`` (the default) is the method
+        described so far, bit for bit.  Otherwise the carved cells, unmerged, form a tree and
+        ``carve_photo(dataset, center, photo_threshold, photo_min_views, photo_max_sweeps,
+        alpha_threshold, min_transmittance=visible_transmittance)`` thins it: cells whose seeing
+        cameras disagree on their colour go, sweep by sweep.  That comes before the
+        ``color="visible"`` votes, which are then taken from the thinned tree, and before the merge
+        passes.  ``photo_report``, an empty ``PhotoReport``, receives the sweeps and the
+        ``converged`` flag.  The limits of ``carve_photo`` apply; where the threshold fires, the
+        guarantee of ``footprint="box"`` is given up."""
         who = "OcTree.build_from_silhouettes"
         depth, center, scale, batch_size, tolerances = OcTree._grid_arguments(
             who, "center has three components", depth, center, scale, batch_size,
@@ -1286,9 +1488,19 @@ class OcTree:
             raise ValueError("%s: cell_opacity must lie in [0, 1), got %r" % (who, cell_opacity))
         if color not in ("mean", "visible"):
             raise ValueError("%s: color is 'mean' or 'visible', got %r" % (who, color))
-        if color == "visible" and not 0.0 <= float(visible_transmittance) < 1.0:
+        if (color == "visible" or photo_threshold is not None) and \
+                not 0.0 <= float(visible_transmittance) < 1.0:
             raise ValueError("%s: visible_transmittance must lie in [0, 1), got %r"
                              % (who, visible_transmittance))
+        if photo_threshold is not None:
+            try:
+                photo_actions(np.zeros((0, 8), np.uint32), photo_threshold, photo_min_views)
+            except ValueError as err:
+                raise ValueError("%s: photo_%s" % (who, str(err).split(": ", 1)[1])) from None
+            if isinstance(photo_max_sweeps, bool) or int(photo_max_sweeps) != photo_max_sweeps \
+                    or photo_max_sweeps < 0:
+                raise ValueError("%s: photo_max_sweeps must be an integer >= 0, got %r"
+                                 % (who, photo_max_sweeps))
         dilate, max_misses, min_views = int(dilate), int(max_misses), int(min_views)
         if dilate < 0 or max_misses < 0 or min_views < 0:
             raise ValueError("%s: dilate, max_misses and min_views must be >= 0, got %d, %d and %d"
@@ -1343,6 +1555,18 @@ class OcTree:
             raise ValueError("%s: no leaf (every cell of depth %d is carved away or seen by fewer "
                              "than %d cameras)" % (who, depth, min_views))
         codes, data = torch.cat(kept_codes), torch.cat(kept_data)
+        if photo_threshold is not None:
+            # the unmerged tree again: leaf k is cell k, and `origin` names the cells that are left
+            OcTree._check_moments_cameras(who, cameras)
+            hull = OcTree._from_cells(codes, data, depth, scale, center, None, device)
+            _, report, _, origin = hull._photo_sweeps(
+                who, images_u8, cameras, alpha_u8, center, photo_threshold, int(photo_min_views),
+                int(photo_max_sweeps), float(visible_transmittance))
+            if photo_report is not None:
+                photo_report.extend(report)
+                photo_report.converged = report.converged
+            origin = torch.from_numpy(origin).to(device)
+            codes, data = codes[origin].contiguous(), data[origin].contiguous()
         if color == "visible":
             # the unmerged tree: every leaf on the finest level, where id order is code order
             hull = OcTree._from_cells(codes, data, depth, scale, center, None, device)

@@ -1835,11 +1835,13 @@ def octree_carve_box_level(images_u8: torch.Tensor, sat: torch.Tensor, proj: tor
 
 # --------------------------------------------------------------------------------- K24
 def octree_visible_check(leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj,
-                         eyes, depth, alpha_u8, min_transmittance, out=None):
-    """The refusals of ``octree_visible_votes``, none of which needs a device: shapes, dtypes,
-    contiguity, the camera limit, finite ``proj`` and ``eyes`` (read back once), the scalars'
-    ranges.  Tensors on any device.  -> (L, C, H, W).  Raises ``ValueError`` naming the argument."""
-    who = "octree_visible_votes"
+                         eyes, depth, alpha_u8, min_transmittance, out=None, moments=False):
+    """The refusals of ``octree_visible_votes`` (and, with ``moments``, of
+    ``octree_visible_moments``: its own name, camera limit and eight fields), none of which needs a
+    device: shapes, dtypes, contiguity, the camera limit, finite ``proj`` and ``eyes`` (read back
+    once), the scalars' ranges.  Tensors on any device.  -> (L, C, H, W).  Raises ``ValueError``
+    naming the argument."""
+    who = "octree_visible_moments" if moments else "octree_visible_votes"
 
     def want(name, t, dtype, shape):
         if not torch.is_tensor(t) or t.dtype != dtype:
@@ -1864,10 +1866,11 @@ def octree_visible_check(leaf_centers, leaf_index, rows, stride, sigma_offset, i
     want("rows", rows, torch.float32, (leaves, stride))
     want("images_u8", images_u8, torch.uint8, (None, None, None, 4))
     cameras, height, width = images_u8.shape[:3]
-    limit = octree_carve_max_cameras()
+    limit = OCTREE_MOMENTS_MAX_CAMERAS if moments else octree_carve_max_cameras()
     if cameras < 1 or cameras > limit:
-        raise ValueError("%s: images_u8 holds %d cameras; 1 .. %d are supported (255 * C must be "
-                         "exact in f32)" % (who, cameras, limit))
+        raise ValueError("%s: images_u8 holds %d cameras; 1 .. %d are supported (%s)"
+                         % (who, cameras, limit, "255^2 * C must stay below 2^32" if moments
+                            else "255 * C must be exact in f32"))
     if not 1 <= height <= 1 << 24 or not 1 <= width <= 1 << 24:
         raise ValueError("%s: images_u8 must be (C, H, W, 4) with 1 <= H, W <= 2^24, got %s"
                          % (who, tuple(images_u8.shape)))
@@ -1881,9 +1884,10 @@ def octree_visible_check(leaf_centers, leaf_index, rows, stride, sigma_offset, i
                          % (who, depth, octree_max_depth()))
     if not 1 <= int(alpha_u8) <= 255:
         raise ValueError("%s: alpha_u8 must lie in 1 .. 255, got %r" % (who, alpha_u8))
-    _check_min_transmittance("octree visible_votes", min_transmittance)
+    _check_min_transmittance("octree visible_moments" if moments else "octree visible_votes",
+                             min_transmittance)
     if out is not None:
-        want("out", out, torch.uint32, (leaves, 4))
+        want("out", out, torch.uint32, (leaves, 8 if moments else 4))
     return leaves, cameras, height, width
 
 
@@ -1907,17 +1911,49 @@ def octree_visible_votes(leaf_centers: torch.Tensor, scale: float, depth: int,
     calls give the bits of one call, as long as at most ``octree_carve_max_cameras()`` cameras fold
     into one buffer (the caller's count to keep).  Bad input is a ``ValueError``
     (``octree_visible_check``)."""
+    return _octree_visible_pairs("ffn_octree_visible_votes", False, leaf_centers, scale, depth,
+                                 node_index, leaf_index, rows, stride, sigma_offset, images_u8,
+                                 proj, eyes, alpha_u8, min_transmittance, out)
+
+
+# K28a: 255^2 * C < 2^32 (include/ffn_hip.h); the cameras that may fold into one moments buffer
+OCTREE_MOMENTS_MAX_CAMERAS = 66051
+
+
+def octree_visible_moments(leaf_centers: torch.Tensor, scale: float, depth: int,
+                           node_index: torch.Tensor, leaf_index: torch.Tensor, rows: torch.Tensor,
+                           stride: int, sigma_offset: int, images_u8: torch.Tensor,
+                           proj: torch.Tensor, eyes: torch.Tensor, alpha_u8: int,
+                           min_transmittance: float,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K28a.  ``octree_visible_votes`` with the second moments -> (L,8) uint32 ``[sum_r, sum_g,
+    sum_b, count, sq_r, sq_g, sq_b, 0]``: the same arguments, the same pairs, and the first four
+    fields are the votes bit for bit; ``sq_c`` is the sum of the squares of the seeing cameras'
+    bytes.  With ``out`` (L,8) uint32 given the moments are ADDED to it (and it is returned):
+    camera subsets folded in several calls, in any order, give the bits of one call, as long as at
+    most ``OCTREE_MOMENTS_MAX_CAMERAS`` (66 051: ``255^2 C < 2^32``) cameras fold into one buffer --
+    one call takes no more, several are the caller's count to keep.  Bad input is a ``ValueError``
+    (``octree_visible_check``)."""
+    return _octree_visible_pairs("ffn_octree_visible_moments", True, leaf_centers, scale, depth,
+                                 node_index, leaf_index, rows, stride, sigma_offset, images_u8,
+                                 proj, eyes, alpha_u8, min_transmittance, out)
+
+
+def _octree_visible_pairs(entry, moments, leaf_centers, scale, depth, node_index, leaf_index, rows,
+                          stride, sigma_offset, images_u8, proj, eyes, alpha_u8, min_transmittance,
+                          out):
+    """K24 and K28a share their arguments: one check, one call."""
     leaves, cameras, height, width = octree_visible_check(
         leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj, eyes, depth,
-        alpha_u8, min_transmittance, out)
+        alpha_u8, min_transmittance, out, moments)
     dev = leaf_index.device
     if out is None:
-        out = torch.zeros((leaves, 4), dtype=torch.uint32, device=dev)
+        out = torch.zeros((leaves, 8 if moments else 4), dtype=torch.uint32, device=dev)
     # per camera 16 floats: P' row-major, the eye, one of padding
     blocks = torch.cat([proj.reshape(cameras, 12), eyes,
                         torch.zeros((cameras, 1), dtype=torch.float32, device=proj.device)],
                        1).contiguous()
-    _call("ffn_octree_visible_votes", _dev(leaf_centers, name="leaf_centers"), c_i64(leaves),
+    _call(entry, _dev(leaf_centers, name="leaf_centers"), c_i64(leaves),
           c_f(scale), c_i(int(depth)),
           _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
           c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),

@@ -1319,7 +1319,30 @@ int ffn_octree_visible_votes(const float* leaf_centers, int64_t num_leaves, floa
                              int cameras, int height, int width, int alpha_u8,
                              float min_transmittance, uint32_t* votes, void* stream);
 
-/* K25 (csrc/occupancy.hip, beside K9a / K9b): the occupancy grid of K9 from an octree's leaves, the
+/* K28a (csrc/octree_walk.hip, a twelfth mode of the K13 kernel): K24's votes with their second
+ * moments, so that one walk gives a per-leaf colour variance as well as a mean.  No counterpart in
+ * the reference.  Arguments, checks, pairs and the walk are ffn_octree_visible_votes', operation for
+ * operation; only the write-back differs.  A visible pair adds to
+ *     moments[l] = [sum_r, sum_g, sum_b, count, sq_r, sq_g, sq_b, 0]   (eight uint32, 32 bytes)
+ * with sq_c = c * c of the pixel's byte, as FOUR 64-bit integer atomic adds of two fields each:
+ * [sum_r, sum_g] and [sum_b, count], exactly K24's two words, then [sq_r, sq_g] and [sq_b, 0].
+ * The first four fields are K24's votes bit for bit.  Exact, the same bits for the same pairs in
+ * any order, in one call or split over many, as long as no carry crosses a field: a square is at
+ * most 255^2 = 65025 and 65025 C < 2^32 holds for C <= 66051, so the caller keeps the cameras that
+ * fold into one buffer AT OR BELOW 66051 (the sums and the count are then far below 2^32 too; the
+ * eighth field stays 0).  The f32 colour (float)sum / (float)(255 count) of K24 is exact in both
+ * operands only up to ffn_octree_carve_max_cameras() cameras.  moments (num_leaves,8) is 16-byte
+ * aligned; the caller zeroes it or lets calls fold into it.  Limits and refusals as for
+ * ffn_octree_visible_votes (cameras launched 65535 at a time; each bad argument refused by name
+ * before any launch). */
+int ffn_octree_visible_moments(const float* leaf_centers, int64_t num_leaves, float scale,
+                               int depth, const int64_t* node_index, int64_t num_nodes,
+                               const int64_t* leaf_index, const float* leaf_data, int stride,
+                               int sigma_offset, const uint8_t* images, const float* camera_blocks,
+                               int cameras, int height, int width, int alpha_u8,
+                               float min_transmittance, uint32_t* moments, void* stream);
+
+/* K25(csrc/occupancy.hip, beside K9a / K9b): the occupancy grid of K9 from an octree's leaves, the
  * leaves' boxes rasterised into the bits.  No counterpart in the reference.
  * leaf_index (num_leaves) sorted int64 ids, scale as for ffn_octree_leaf_geometry; center, box_min,
  * box_size are HOST pointers to 3 floats (the root cube's centre; the grid's box as for

@@ -8,11 +8,16 @@ trained model in between.  No counterpart in the reference.
         [--min-views 2] [--cell-opacity 0.5] [--merge-tolerance RGB SIGMA]
         [--color {mean,visible}] [--visible-transmittance 0.3]
         [--footprint {point,box}] [--start-level 4]
+        [--photo-threshold T] [--photo-min-views 2] [--photo-max-sweeps 16]
 
 ``--color visible`` colours every carved cell from the cameras that can see it through the carved
 hull (kernel K24) instead of from all that look its way.  ``--footprint box`` carves conservatively
 and coarse to fine from ``--start-level`` (kernel K27): a cell goes only when some camera sees its
 whole projected footprint on the background, so thin structure survives and the hull is fatter.
+``--photo-threshold T`` then thins the carved hull by photo-consistency (kernel K28a,
+``OcTree.carve_photo``): sweep by sweep a cell goes when the cameras that see it disagree on its
+colour by more than T (the root of the mean channel variance, colours in [0, 1]); the sweeps are
+printed.  Off by default.
 """
 
 import os
@@ -54,8 +59,25 @@ CARVE_OCTREE = [
                               "rectangle round its centre and corners (K27, conservative)")),
     ("--start-level", dict(type=int, default=4,
                            help="--footprint box: the level the coarse-to-fine carve starts at")),
+    ("--photo-threshold", dict(type=float, default=None, metavar="T",
+                               help="Thin the hull by photo-consistency: drop a cell whose seeing "
+                                    "cameras disagree on its colour by more than T (K28; off by "
+                                    "default)")),
+    ("--photo-min-views", dict(type=int, default=2,
+                               help="--photo-threshold: cameras that must see a cell to judge it")),
+    ("--photo-max-sweeps", dict(type=int, default=16,
+                                help="--photo-threshold: sweeps at the most")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
+
+
+def print_report(report):
+    """One line per sweep of ``OcTree.carve_photo``."""
+    for number, sweep in enumerate(report, 1):
+        print("photo sweep %d: %d leaves, %d seen, %d judged, %d dropped"
+              % (number, sweep.leaves, sweep.seen, sweep.judged, sweep.dropped))
+    print("photo carve", "converged" if report.converged else "did not converge", "after",
+          len(report), "sweeps")
 
 
 def build_parser():
@@ -71,10 +93,14 @@ def main():
     if dataset is None:
         return 1
     print("Carving", 8 ** (args.voxel_depth - 1), "cells with", dataset.num_cameras, "cameras")
+    report = ffn.PhotoReport()
     tree = ffn.OcTree.build_from_silhouettes(
         dataset, args.voxel_depth, args.center, args.scale, args.alpha_threshold, args.dilate,
         args.max_misses, args.min_views, args.cell_opacity, args.merge_tolerance, args.batch_size,
-        args.color, args.visible_transmittance, args.footprint, args.start_level)
+        args.color, args.visible_transmittance, args.footprint, args.start_level,
+        args.photo_threshold, args.photo_min_views, args.photo_max_sweeps, report)
+    if args.photo_threshold is not None:
+        print_report(report)
     print(tree.num_leaves, "leaves")
     # the file format is the reference's and has no place for the root cube's centre
     print("root cube centre (for train_octree.py / render_octree.py): --center",
