@@ -46,6 +46,13 @@ struct GradWalk {
     float4* entry_values;
     int32_t* entry_leaves;
     int32_t* entry_rays;
+    // K29b (dist: the walk is one of the three modes with the distortion term): phase 0 also writes
+    // ray_dist[3 r ..] = (W_tot, M_tot, D) and, where it is not null, ray_distortion[r] = D; phase 1
+    // adds dist_scale * dD/dsigma_k to every entry's d sigma
+    bool dist;
+    float dist_scale;
+    float* ray_dist;
+    float* ray_distortion;
 };
 
 // launched by the backward entry points (csrc/octree_grad.hip), which have checked the arguments

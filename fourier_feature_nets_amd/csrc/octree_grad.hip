@@ -422,6 +422,8 @@ struct GradWorkspace {
     int32_t* before;        // num_leaves
     float4* rows[2];        // row_capacity rows of sh_width(degree) floats each
     int64_t row_capacity;
+    // K29b only
+    float* ray_dist;        // 3n: W_tot, M_tot, D per ray
 };
 
 static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
@@ -430,8 +432,10 @@ static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t
 // only) -> the bytes they take; a buffer the kind does not use stays null.  K19b: E / 16 + min(E, L)
 // rows hold every level's partial sums; the second term is taken at L so that the size stays affine
 // in max_entries.
+// K29b: the same buffers at the same offsets and the per-ray triples BEHIND them, so that the sizes
+// and the layout of the entries without the term are what they were.
 static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, int degree,
-                           GradWorkspace* ws, char* base) {
+                           GradWorkspace* ws, char* base, bool dist = false) {
     const bool sh = degree > 0;
     const int64_t tiles = (capacity + kSortTile - 1) / kSortTile;
     int64_t longest = 256 * tiles > n ? 256 * tiles : n;
@@ -452,7 +456,7 @@ static int64_t grad_layout(int64_t n, int64_t num_leaves, int64_t capacity, int 
         {(void**)&w.table, 4 * 256 * tiles, true},      {(void**)&w.seg_lo, 4 * num_leaves, true},
         {(void**)&w.seg_hi, 4 * num_leaves, true},      {(void**)&w.rays, 4 * capacity, sh},
         {(void**)&w.before, 4 * num_leaves, sh},        {(void**)&w.rows[0], rows_bytes, sh},
-        {(void**)&w.rows[1], rows_bytes, sh}};
+        {(void**)&w.rows[1], rows_bytes, sh},           {(void**)&w.ray_dist, 12 * n, dist}};
     int64_t off = 0;
     for (const auto& b : buffers) {
         if (!b.used) continue;
@@ -498,12 +502,12 @@ static inline bool grad_shape(int64_t n, int64_t num_leaves, int64_t max_entries
 }
 
 static int64_t grad_workspace_bytes(const char* who, int64_t n, int64_t num_leaves,
-                                    int64_t max_entries, int degree) {
+                                    int64_t max_entries, int degree, bool dist = false) {
     if (!grad_shape(n, num_leaves, max_entries)) {
         fail_who(who, "shape (1 <= n < 2^31, 1 <= num_leaves < 2^31, 0 <= max_entries < 2^31)");
         return -1;
     }
-    return grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr);
+    return grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr, dist);
 }
 
 // what the front half of a backward leaves for its reduce: the e > 0 entries sorted by leaf
@@ -532,10 +536,11 @@ static int grad_entries(const char* who, GradWalk& grad, void* workspace, int64_
     if (!grad_shape(n, num_leaves, max_entries) ||
         n * (3 * ((int64_t)1 << (grad.walk.depth - 1)) + 1) > kGradMaxEntries)
         return fail_who(who, "shape (n * (3 * 2^(depth-1) + 1) < 2^31: split the rays)");
-    if (workspace_bytes < grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr))
+    if (workspace_bytes < grad_layout(n, num_leaves, max_entries, degree, nullptr, nullptr, grad.dist))
         return fail_who(who, "workspace too small for max_entries");
     GradWorkspace& ws = got->ws;
-    grad_layout(n, num_leaves, max_entries, degree, &ws, (char*)workspace);
+    grad_layout(n, num_leaves, max_entries, degree, &ws, (char*)workspace, grad.dist);
+    grad.ray_dist = ws.ray_dist;
     grad.ray_slots = ws.ray_slots; grad.ray_color = ws.ray_color; grad.ray_trans = ws.ray_trans;
     grad.entry_values = ws.values; grad.entry_leaves = ws.keys[0]; grad.entry_rays = ws.rays;
 
@@ -579,18 +584,31 @@ extern "C" int64_t ffn_octree_grad_workspace_bytes(int64_t n, int64_t num_leaves
     return grad_workspace_bytes("ffn_octree_grad_workspace_bytes", n, num_leaves, max_entries, 0);
 }
 
-extern "C" int ffn_octree_render_volume_backward(
+// K29b: what the two entries with the distortion term refuse before anything else, and the walk's
+// three fields
+static int grad_dist_args(const char* who, GradWalk& grad, float dist_scale, float* ray_distortion) {
+    if (!(dist_scale >= 0.0f && dist_scale < __builtin_inff()))          // NaN fails too
+        return fail_who(who, "dist_scale must be finite and >= 0");
+    grad.dist = true;
+    grad.dist_scale = dist_scale;
+    grad.ray_distortion = ray_distortion;
+    return 0;
+}
+
+// K17a + K17b, and with dist K29b: ffn_octree_render_volume_backward[_dist]
+static int volume_backward(const char* who, bool dist, float dist_scale, float* ray_distortion,
     const float* starts, const float* directions, int64_t n, float scale, int depth,
     const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
     float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
     float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
     int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
     void* stream) {
-    const char* who = "ffn_octree_render_volume_backward";
     GradWalk grad{{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
                    num_leaves, t_min, (hipStream_t)stream},
                   {leaf_data, channels, 0, bg_r, bg_g, bg_b, min_transmittance}, d_color, d_alpha};
     if (entries != nullptr) *entries = -1;
+    if (dist)
+        if (int err = grad_dist_args(who, grad, dist_scale, ray_distortion)) return err;
     if (channels < 4) return fail_who(who, "channels >= 4");
     if (int err = check_volume_args(who, grad.walk, grad.leaves,
                                     !d_color || !d_alpha || !d_leaf_data || !workspace))
@@ -618,6 +636,44 @@ extern "C" int ffn_octree_render_volume_backward(
     return check_launch(who);
 }
 
+extern "C" int ffn_octree_render_volume_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    void* stream) {
+    return volume_backward("ffn_octree_render_volume_backward", false, 0.0f, nullptr, starts,
+                           directions, n, scale, depth, node_index, num_nodes, leaf_index, num_leaves,
+                           t_min, leaf_data, channels, bg_r, bg_g, bg_b, min_transmittance, d_color,
+                           d_alpha, workspace, workspace_bytes, max_entries, d_leaf_data, entries,
+                           stream);
+}
+
+extern "C" int64_t ffn_octree_grad_dist_workspace_bytes(int64_t n, int64_t num_leaves,
+                                                        int64_t max_entries, int degree) {
+    if (degree < 0 || degree > 2) {
+        fail_arg("ffn_octree_grad_dist_workspace_bytes: degree is 0 (plain rows), 1 or 2");
+        return -1;
+    }
+    return grad_workspace_bytes("ffn_octree_grad_dist_workspace_bytes", n, num_leaves, max_entries,
+                                degree, true);
+}
+
+extern "C" int ffn_octree_render_volume_backward_dist(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    float dist_scale, float* ray_distortion, void* stream) {
+    return volume_backward("ffn_octree_render_volume_backward_dist", true, dist_scale,
+                           ray_distortion, starts, directions, n, scale, depth, node_index, num_nodes,
+                           leaf_index, num_leaves, t_min, leaf_data, channels, bg_r, bg_g, bg_b,
+                           min_transmittance, d_color, d_alpha, workspace, workspace_bytes,
+                           max_entries, d_leaf_data, entries, stream);
+}
+
 extern "C" int ffn_octree_project(float* leaf_data, int64_t num_leaves, void* stream) {
     if (!leaf_data) return fail_arg("ffn_octree_project: null argument");
     if (num_leaves < 1) return fail_arg("ffn_octree_project: num_leaves >= 1");
@@ -638,19 +694,21 @@ extern "C" int64_t ffn_octree_grad_sh_workspace_bytes(int64_t n, int64_t num_lea
                                 degree);
 }
 
-extern "C" int ffn_octree_render_volume_sh_backward(
+// K19a + K19b, and with dist K29b: ffn_octree_render_volume_sh_backward[_dist]
+static int volume_sh_backward(const char* who, bool dist, float dist_scale, float* ray_distortion,
     const float* starts, const float* directions, int64_t n, float scale, int depth,
     const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
     float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
     float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
     int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
     int row_stride, void* stream) {
-    const char* who = "ffn_octree_render_volume_sh_backward";
     GradWalk grad{{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
                    num_leaves, t_min, (hipStream_t)stream},
                   {leaf_rows, row_stride, degree, bg_r, bg_g, bg_b, min_transmittance}, d_color,
                   d_alpha};
     if (entries != nullptr) *entries = -1;
+    if (dist)
+        if (int err = grad_dist_args(who, grad, dist_scale, ray_distortion)) return err;
     if (degree != 1 && degree != 2) return fail_who(who, "degree is 1 or 2");
     if (row_stride < 3 * sh_bases(degree) + 1 || row_stride % 4 != 0 || row_stride > 64)
         return fail_who(who, "row_stride is a multiple of 4, 3 * (degree + 1)^2 + 1 <= row_stride "
@@ -695,6 +753,34 @@ extern "C" int ffn_octree_render_volume_sh_backward(
                        src, quads, ws.seg_lo, ws.seg_hi, ws.before, num_leaves, stride_quads,
                        (float4*)d_leaf_rows);
     return check_launch(who);
+}
+
+extern "C" int ffn_octree_render_volume_sh_backward(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
+    int row_stride, void* stream) {
+    return volume_sh_backward("ffn_octree_render_volume_sh_backward", false, 0.0f, nullptr, starts,
+                              directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                              num_leaves, t_min, leaf_rows, bg_r, bg_g, bg_b, min_transmittance,
+                              d_color, d_alpha, workspace, workspace_bytes, max_entries, d_leaf_rows,
+                              entries, degree, row_stride, stream);
+}
+
+extern "C" int ffn_octree_render_volume_sh_backward_dist(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
+    int row_stride, float dist_scale, float* ray_distortion, void* stream) {
+    return volume_sh_backward("ffn_octree_render_volume_sh_backward_dist", true, dist_scale,
+                              ray_distortion, starts, directions, n, scale, depth, node_index,
+                              num_nodes, leaf_index, num_leaves, t_min, leaf_rows, bg_r, bg_g, bg_b,
+                              min_transmittance, d_color, d_alpha, workspace, workspace_bytes,
+                              max_entries, d_leaf_rows, entries, degree, row_stride, stream);
 }
 
 extern "C" int ffn_octree_project_sh(float* leaf_rows, int64_t num_leaves, int row_stride,

@@ -187,6 +187,39 @@
 // to the instructions they had before: their disassembly was compared with the previous commit's,
 // instruction for instruction (758 / 809 / 851 / 887 / 975 / 1002 / 1034 / 1095 / 1132 / 845 / 959
 // and 1316 instructions; 38 / 40 / 50 / 53 / 61 / 56 / 72 / 64 / 82 / 39 / 39 and 75 VGPRs).
+//
+// K29  Per-ray distortion (the distortion loss of Mip-NeRF 360 on the piecewise-constant weights of
+// an octree ray): four more modes.  With the taken leaves of K15 in walk order, their w_k = T_k a_k,
+// L_k and the chord's midpoint m_k = (0.5 (t0_k + t_exit_k)) |d| as a world length, and the running
+// (exclusive) W_k = sum_{j<k} w_j, M_k = sum_{j<k} w_j m_j,
+//     D = sum_k [ (2 w_k) (m_k W_k - M_k) + (w_k w_k) (L_k / 3) ]
+// which is sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 L_i because the leaves are disjoint and
+// ordered along the ray: O(n) per ray, three more registers, no per-lane array.
+// K29a (kDistortion), built as kLeafWeight is: the density alone at first.shading floats into a row of
+// first.channels floats, t0, the chord, sigma, a, w, T and the early end K15's operations in K15's
+// order, dist_step() per taken leaf, and ONE store per ray (first.depth, +0 for a ray that takes no
+// leaf).  Nothing per leaf, no atomics.
+// K29b (kGradDist / kGradSH1Dist / kGradSH2Dist): kGrad / kGradSH1 / kGradSH2 with the term folded into
+// their two walks -- the SAME branches of the loop, with the additions under `if (kDist)`, so that
+// t0, the chord, sigma, a, w, T and the colour arithmetic are the parents' operations in their order.
+// Phase 0 runs dist_step() (the one piece of code K29a runs: D has K29a's bits on the same rays and
+// densities) and also leaves W_tot, M_tot and D per ray (first.depth, n x 3) and D for the caller
+// (first.t_hit, may be null).  Phase 1 keeps the running W, M and P_k = sum_{j<=k} w_j G_j and adds to
+// the d sigma of the entry it writes anyway
+//     pad * L_k [ T_{k+1} G_k - (2 D - P_k) ]          pad carries dist_scale: one multiply, one add
+//     G_k = 2 [ (m_k W_k - M_k) + (M_tot - M_{k+1}) - m_k (W_tot - W_{k+1}) ] + (2/3) (w_k L_k)
+// (sum_j w_j G_j = 2 D, D being homogeneous of degree 2 in w, so the sum over the leaves BEHIND k
+// needs no third walk); 0 where the stored density is negative or NaN, K17a's rule.  The entry list,
+// K17b / K19b and everything behind them are unchanged; no float atomics.  The differences
+// 2 D - P_k and M_tot - M_{k+1} cancel towards the end of a ray: their error is one ulp of D and of
+// the ray's length per step, absolute, which the tests' budget counts.
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), kGradDist / kGradSH1Dist /
+// kGradSH2Dist: 74 / 80 / 91 VGPRs (their parents: 61 / 64 / 82), 106 / 106 / 106 SGPRs, 0 bytes of
+// scratch, 0 spills, 0 bytes of LDS, occupancy 6 / 6 / 5 waves per SIMD (their parents: 8 / 7 / 5).
+// kDistortion: 47 VGPRs, 84 SGPRs, 0 bytes of scratch, 0 spills, 0 bytes of LDS, occupancy 8.
+// The twelve older instantiations and octree_focus_kernel compile to the instructions they had
+// before: their disassembly (hipcc -S, labels renumbered) was compared with the previous commit's,
+// instruction for instruction.
 #include "common.h"
 #include "composite_terms.h"
 #include "octree_grad.h"
@@ -288,7 +321,18 @@ struct FirstHit {
 
 enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVolumeSH1 = 5,
                 kVolumeSH2 = 6, kGradSH1 = 7, kGradSH2 = 8, kLeafWeight = 9, kVisible = 10,
-                kVisibleMoments = 11 };
+                kVisibleMoments = 11, kGradDist = 12, kGradSH1Dist = 13, kGradSH2Dist = 14,
+                kDistortion = 15 };
+
+// K29: what one taken leaf adds to a ray's distortion D and to the running W = sum w, M = sum w m
+// (both exclusive on entry).  ONE piece of code for K29a and for phase 0 of K29b, so that the two
+// form D with the same f32 operations in the same order.
+__device__ __forceinline__ void dist_step(float w, float m, float length, float& run_w, float& run_m,
+                                          float& dist) {
+    dist = dist + ((2.0f * w) * (m * run_w - run_m) + (w * w) * (length * (1.0f / 3.0f)));
+    run_w = run_w + w;
+    run_m = run_m + w * m;
+}
 
 // kPath:     Path rows (t_stops, leaves), max_length entries per ray.
 // kSpan:     per ray t_in / t_out / hit over the leaves that end after t_min.
@@ -312,6 +356,10 @@ enum WalkMode { kPath = 0, kSpan = 1, kFirstHit = 2, kVolume = 3, kGrad = 4, kVo
 //            vote words, max_length alpha_u8, first.bg_r / first.bg_g the image's width / height as
 //            floats (exact: at most 2^24), first.leaf_data / channels / shading as kLeafWeight.
 // kVisibleMoments: K28a.  kVisible, and leaves the (num_leaves) rows of FOUR 64-bit words.
+// kGradDist / kGradSH1Dist / kGradSH2Dist: K29b.  kGrad / kGradSH1 / kGradSH2, and pad carries
+//            dist_scale, first.depth the per-ray (W_tot, M_tot, D) triples (n,3; written in phase 0,
+//            read in phase 1), first.t_hit the caller's (n) ray_distortion (phase 0, may be null).
+// kDistortion: K29a.  first.leaf_data / channels / shading as kLeafWeight, first.depth the (n) D.
 template <int kMode>
 __global__ void __launch_bounds__(kWalkThreads)
 octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ directions,
@@ -323,8 +371,11 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     constexpr bool kSpans = kMode == kSpan;
     constexpr bool kSees = kMode == kVisible || kMode == kVisibleMoments;      // K24, K28a
     constexpr bool kSH = kMode == kVolumeSH1 || kMode == kVolumeSH2;
-    constexpr bool kSHGrad = kMode == kGradSH1 || kMode == kGradSH2;
-    constexpr int kBasis = kMode == kVolumeSH2 || kMode == kGradSH2 ? 9 : 4;
+    constexpr bool kSHGrad = kMode == kGradSH1 || kMode == kGradSH2 || kMode == kGradSH1Dist ||
+                             kMode == kGradSH2Dist;
+    constexpr bool kPlainGrad = kMode == kGrad || kMode == kGradDist;
+    constexpr bool kDist = kMode == kGradDist || kMode == kGradSH1Dist || kMode == kGradSH2Dist;  // K29b
+    constexpr int kBasis = kMode == kVolumeSH2 || kMode == kGradSH2 || kMode == kGradSH2Dist ? 9 : 4;
     const int64_t r = (int64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     if (r >= n) return;
     const float sx = starts[r * 3 + 0], sy = starts[r * 3 + 1], sz = starts[r * 3 + 2];
@@ -386,12 +437,12 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
     int axis_prev = axis_in, hit_face = -1;
     int64_t hit_leaf = -1;
     // volume: world length per unit of t, transmittance, colour, and the heaviest leaf's entry
-    const float norm = kMode == kVolume || kMode == kGrad || kSH || kSHGrad ||
-                               kMode == kLeafWeight || kSees
+    const float norm = kMode == kVolume || kPlainGrad || kSH || kSHGrad ||
+                               kMode == kLeafWeight || kSees || kMode == kDistortion
                            ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     float trans = 1.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, w_best = 0.0f, t_best = 0.0f;
     // gradient walk: the ray's entries [base, base + mine), its C, T_{n+1} and upstream gradients
-    const bool emit = (kMode == kGrad || kSHGrad) && max_length != 0;
+    const bool emit = (kPlainGrad || kSHGrad) && max_length != 0;
     int32_t* ray_slots = reinterpret_cast<int32_t*>(span_hit);
     float4* entry_values = reinterpret_cast<float4*>(t_stops);
     int32_t* entry_leaves = reinterpret_cast<int32_t*>(leaves);
@@ -413,6 +464,14 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         t_end = first.alpha[r];
         g_r = span_in[r * 3 + 0]; g_g = span_in[r * 3 + 1]; g_b = span_in[r * 3 + 2];
         g_a = span_out[r];
+    }
+    // K29: the running W, M (exclusive) and D; phase 1 of K29b: W_tot, M_tot, 2 D and the running
+    // sum of w_j G_j (inclusive)
+    float run_w = 0.0f, run_m = 0.0f, dist = 0.0f, w_tot = 0.0f, m_tot = 0.0f, dist2 = 0.0f,
+          run_wg = 0.0f;
+    if (kDist && emit) {
+        w_tot = first.depth[r * 3 + 0]; m_tot = first.depth[r * 3 + 1];
+        dist2 = 2.0f * first.depth[r * 3 + 2];
     }
     for (int trip = 0; trip < max_trips && stop < max_stops && inside; ++trip) {
         int64_t at;
@@ -499,7 +558,7 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                 trans = trans * (1.0f - a);
                 if (trans <= first.min_transmittance) break;
             }
-        } else if (kMode == kGrad) {
+        } else if (kPlainGrad) {
             if (leaf >= 0 && t_exit > t_min) {
                 float lr, lg, lb, ls;
                 if (first.channels == 4) {
@@ -520,10 +579,24 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                     const float behind = g_r * (trans * lr - (c_r - acc_r)) +
                                          g_g * (trans * lg - (c_g - acc_g)) +
                                          g_b * (trans * lb - (c_b - acc_b));
-                    const float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    if (kDist) {
+                        // G_k, the prefix of w_j G_j, and dD/dsigma_k = L_k [T_{k+1} G_k - sum_{j>k} w_j G_j]
+                        const float m = (0.5f * (t0 + t_exit)) * norm;
+                        const float next_w = run_w + w, next_m = run_m + w * m;
+                        const float g = 2.0f * (((m * run_w - run_m) + (m_tot - next_m)) -
+                                                m * (w_tot - next_w)) +
+                                        (2.0f / 3.0f) * (w * length);
+                        run_wg = run_wg + w * g;
+                        const float dd = length * (trans * g - (dist2 - run_wg));
+                        if (ls >= 0.0f) ds = ds + pad * dd;
+                        run_w = next_w; run_m = next_m;
+                    }
                     entry_values[base + taken] = make_float4(w * g_r, w * g_g, w * g_b, ds);
                     entry_leaves[base + taken] = (int32_t)leaf;
                 }
+                if (kDist && !emit)
+                    dist_step(w, (0.5f * (t0 + t_exit)) * norm, length, run_w, run_m, dist);
                 ++taken;
                 if (trans <= first.min_transmittance) break;
             }
@@ -565,7 +638,19 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                     const float behind = g_r * (trans * lr - (c_r - acc_r)) +
                                          g_g * (trans * lg - (c_g - acc_g)) +
                                          g_b * (trans * lb - (c_b - acc_b));
-                    const float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    float ds = ls >= 0.0f ? length * (behind + g_a * t_end) : 0.0f;
+                    if (kDist) {
+                        // G_k, the prefix of w_j G_j, and dD/dsigma_k = L_k [T_{k+1} G_k - sum_{j>k} w_j G_j]
+                        const float m = (0.5f * (t0 + t_exit)) * norm;
+                        const float next_w = run_w + w, next_m = run_m + w * m;
+                        const float g = 2.0f * (((m * run_w - run_m) + (m_tot - next_m)) -
+                                                m * (w_tot - next_w)) +
+                                        (2.0f / 3.0f) * (w * length);
+                        run_wg = run_wg + w * g;
+                        const float dd = length * (trans * g - (dist2 - run_wg));
+                        if (ls >= 0.0f) ds = ds + pad * dd;
+                        run_w = next_w; run_m = next_m;
+                    }
                     // e_kc = w g_c (c (1 - c)): the factor of Y_b(u) in d k_cb
                     entry_values[base + taken] = make_float4((w * g_r) * (lr * (1.0f - lr)),
                                                              (w * g_g) * (lg * (1.0f - lg)),
@@ -573,6 +658,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                     entry_leaves[base + taken] = (int32_t)leaf;
                     entry_rays[base + taken] = (int32_t)r;
                 }
+                if (kDist && !emit)
+                    dist_step(w, (0.5f * (t0 + t_exit)) * norm, length, run_w, run_m, dist);
                 ++taken;
                 if (trans <= first.min_transmittance) break;
             }
@@ -588,6 +675,18 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
                     const unsigned bits = __float_as_uint(w);
                     if (leaf_weights[leaf] < bits) atomicMax(leaf_weights + leaf, bits);
                 }
+                trans = trans * (1.0f - a);
+                if (trans <= first.min_transmittance) break;
+            }
+        } else if (kMode == kDistortion) {
+            if (leaf >= 0 && t_exit > t_min) {
+                const float ls = first.leaf_data[leaf * first.channels + first.shading];
+                const float t0 = t > t_min ? t : t_min;
+                const float length = (t_exit - t0) * norm;
+                const float sigma = fmaxf(ls, 0.0f);           // NaN -> 0
+                const float a = 1.0f - expf(-(sigma * length));
+                const float w = trans * a;
+                dist_step(w, (0.5f * (t0 + t_exit)) * norm, length, run_w, run_m, dist);
                 trans = trans * (1.0f - a);
                 if (trans <= first.min_transmittance) break;
             }
@@ -658,8 +757,13 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         first.color[r * 3 + 2] = acc_b + trans * first.bg_b;
         first.alpha[r] = 1.0f - trans;
         first.depth[r] = t_best;
-    } else if (kMode == kGrad || kSHGrad) {
+    } else if (kPlainGrad || kSHGrad) {
         if (!emit) {
+            if (kDist) {
+                first.depth[r * 3 + 0] = run_w; first.depth[r * 3 + 1] = run_m;
+                first.depth[r * 3 + 2] = dist;
+                if (first.t_hit) first.t_hit[r] = dist;
+            }
             ray_slots[r] = taken;
             first.color[r * 3 + 0] = acc_r + trans * first.bg_r;
             first.color[r * 3 + 1] = acc_g + trans * first.bg_g;
@@ -668,6 +772,8 @@ octree_walk_kernel(const float* __restrict__ starts, const float* __restrict__ d
         }
     } else if (kMode == kLeafWeight) {
         // nothing per ray
+    } else if (kMode == kDistortion) {
+        first.depth[r] = dist;                               // +0 for a ray that takes no leaf
     } else if (kSees) {
         if (visible) {
             // [sum_r, sum_g] and [sum_b, count] as two 64-bit words, the first field in the low half:
@@ -764,6 +870,17 @@ int octree_grad_walk(const char* who, const GradWalk& grad, int phase) {
     float* d_color = const_cast<float*>(grad.d_color);          // span_in
     float* d_alpha = const_cast<float*>(grad.d_alpha);          // span_out
     uint8_t* slots = (uint8_t*)grad.ray_slots;                  // span_hit; max_length: the phase
+    if (grad.dist) {
+        // K29b: pad carries dist_scale, first.depth the (W_tot, M_tot, D) triples, first.t_hit the
+        // caller's ray_distortion
+        first.depth = grad.ray_dist;
+        first.t_hit = grad.ray_distortion;
+        if (grad.leaves.degree == 0)
+            return launch_walk<kGradDist>(who, grad.walk, first, phase, values, entry_leaves,
+                                          grad.dist_scale, d_color, d_alpha, slots);
+        return launch_walk_sh<kGradSH1Dist>(grad.leaves.degree, who, grad.walk, first, phase, values,
+                                            entry_leaves, grad.dist_scale, d_color, d_alpha, slots);
+    }
     if (grad.leaves.degree == 0)
         return launch_walk<kGrad>(who, grad.walk, first, phase, values, entry_leaves, 0.0f, d_color,
                                   d_alpha, slots);
@@ -1124,6 +1241,24 @@ extern "C" int ffn_octree_leaf_weights(const float* starts, const float* directi
     first.shading = sigma_offset;
     return launch_walk<kLeafWeight>(who, walk, first, 0, nullptr, nullptr, 0.0f, nullptr, nullptr,
                                     (uint8_t*)weights);
+}
+
+extern "C" int ffn_octree_distortion(const float* starts, const float* directions, int64_t n,
+                                     float scale, int depth, const int64_t* node_index,
+                                     int64_t num_nodes, const int64_t* leaf_index,
+                                     int64_t num_leaves, float t_min, const float* rows, int stride,
+                                     int sigma_offset, float min_transmittance, float* distortion,
+                                     void* stream) {
+    const char* who = "ffn_octree_distortion";
+    const Walk walk{starts, directions, n, scale, depth, node_index, num_nodes, leaf_index,
+                    num_leaves, t_min, (hipStream_t)stream};
+    const VolumeLeaves leaves{rows, stride, 0, 0.0f, 0.0f, 0.0f, min_transmittance};
+    if (stride < 1 || sigma_offset < 0 || sigma_offset >= stride)
+        return fail_who(who, "stride >= 1, 0 <= sigma_offset < stride");
+    if (int err = check_volume_args(who, walk, leaves, !distortion)) return err;
+    FirstHit first = volume_first_hit(leaves, nullptr, nullptr, distortion);
+    first.shading = sigma_offset;
+    return launch_walk<kDistortion>(who, walk, first);
 }
 
 // K24 and K28a: one list of arguments and checks, kMode the write-back; `votes` is (num_leaves,4)

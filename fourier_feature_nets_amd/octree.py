@@ -742,6 +742,30 @@ class OcTree:
             float(min_transmittance), out)
         return weights.cpu().numpy() if as_numpy else weights
 
+    def distortion(self, starts, directions, t_min: float = 0.0, min_transmittance: float = 0.0):
+        """Per ray the distortion of its compositing weights (K29a): with the taken leaves of
+        ``render_volume`` in walk order, their weights ``w = T * a``, chord lengths ``L`` and chord
+        midpoints ``m`` (both as world lengths along the ray),
+        ``D = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 L_i`` -- the distortion loss of
+        Mip-NeRF 360 for piecewise-constant weights, small for a ray whose weight sits in one short
+        interval, large for one that spreads it along a chord.  -> (R,) float32, numpy for numpy
+        rays; 0 for a ray that takes no leaf.  Works on plain and SH trees alike (colour does not
+        enter), and the background's share of a ray takes no part.  Inputs as for ``render_volume``.
+
+        Limits.  ``D`` treats a leaf's weight as uniform along its chord, so it depends on the
+        partition: ``refine`` with splits changes it at second order.  It is measured in world
+        lengths, not in units of the cube.  It sees the tree's own densities only.  As a prior
+        (``fit_octree(dist_weight=...)``) it can eat thin true structure behind a strong surface,
+        and ``dist_weight`` has no tuned default."""
+        self._check_volume(min_transmittance, "OcTree.distortion")     # before any device is needed
+        starts, directions, as_numpy = self._rays(starts, directions)
+        rows, offset = self._density_rows("OcTree.distortion")
+        out = ops.octree_distortion(
+            starts, directions, self._scale, self.depth, self._on_device("node_index"),
+            self._on_device("leaf_index"), rows, int(rows.shape[1]), offset, float(t_min),
+            float(min_transmittance))
+        return out.cpu().numpy() if as_numpy else out
+
     def _density_rows(self, who):
         """The device rows and the density's offset in them, for the walks that read the density
         alone (K21a, K24, K26)."""

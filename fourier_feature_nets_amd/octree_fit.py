@@ -22,6 +22,11 @@ term's gradient.  It is off by default, and off means not entered.
 ``leaf_weights_over`` and ``fit_octree_adaptive`` (K21) change the structure between fits: the first
 folds ``OcTree.leaf_weights`` (K21a) over every ray of a dataset, the second alternates a fit with
 measure -> ``refine_actions`` -> ``OcTree.refine`` (K21b).  With ``rounds=0`` it is the plain fit.
+
+Both fields' ``backward`` take ``dist_scale`` and ``ray_distortion`` (K29b): the gradient of the
+rays' distortion (``OcTree.distortion``) folded into the two walks of the backward, and
+``dist_weight`` on the fit loops passes ``dist_weight / batch`` there.  Off by default, and off means
+the entry points without the term.
 """
 
 import time
@@ -166,12 +171,21 @@ class OctreeField(_LeafField):
         super().__init__(tree, values, None, center, device, ops.OctreeGradWorkspace())
 
     def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
-                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
-        """K17a + K17b: d(data) (L,4) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
+                 min_transmittance=0.0, data=None, out=None, dist_scale=0.0,
+                 ray_distortion=None) -> torch.Tensor:
+        """K17a + K17b: d(data) (L,4) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,).  K29b:
+        ``dist_scale > 0`` adds ``dist_scale * d(sum_r D_r)/d sigma`` to the density column, and
+        ``ray_distortion`` (N,) receives ``D`` per ray (``ops.octree_render_volume_backward``);
+        with neither, the call is the one without the term."""
+        if dist_scale == 0.0 and ray_distortion is None:
+            return ops.octree_render_volume_backward(
+                starts, directions, *self._geometry(), self.data.detach() if data is None else data,
+                d_color, d_alpha, float(t_min), background, float(min_transmittance), self.workspace,
+                out)
         return ops.octree_render_volume_backward(
             starts, directions, *self._geometry(), self.data.detach() if data is None else data,
             d_color, d_alpha, float(t_min), background, float(min_transmittance), self.workspace,
-            out)
+            out, dist_scale=dist_scale, ray_distortion=ray_distortion)
 
     def _render(self, data, starts, directions, t_min, background, min_transmittance):
         return ops.octree_render_volume(starts, directions, *self._geometry(), data, t_min,
@@ -203,12 +217,19 @@ class OctreeSHField(_LeafField):
         super().__init__(tree, rows, degree, center, device, ops.OctreeGradSHWorkspace(degree))
 
     def backward(self, starts, directions, d_color, d_alpha, t_min=0.0, background=(0, 0, 0),
-                 min_transmittance=0.0, data=None, out=None) -> torch.Tensor:
-        """K19a + K19b: d(data) (L, stride) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,)."""
+                 min_transmittance=0.0, data=None, out=None, dist_scale=0.0,
+                 ray_distortion=None) -> torch.Tensor:
+        """K19a + K19b: d(data) (L, stride) for upstream ``d_color`` (N,3) and ``d_alpha`` (N,).
+        ``dist_scale`` and ``ray_distortion`` (K29b) as in ``OctreeField.backward``."""
+        if dist_scale == 0.0 and ray_distortion is None:
+            return ops.octree_render_volume_sh_backward(
+                starts, directions, *self._geometry(), self.data.detach() if data is None else data,
+                self.sh_degree, d_color, d_alpha, float(t_min), background,
+                float(min_transmittance), self.workspace, out)
         return ops.octree_render_volume_sh_backward(
             starts, directions, *self._geometry(), self.data.detach() if data is None else data,
             self.sh_degree, d_color, d_alpha, float(t_min), background, float(min_transmittance),
-            self.workspace, out)
+            self.workspace, out, dist_scale=dist_scale, ray_distortion=ray_distortion)
 
     def _render(self, data, starts, directions, t_min, background, min_transmittance):
         return ops.octree_render_volume_sh(starts, directions, *self._geometry(), data,
@@ -254,7 +275,7 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
                min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
                max_norm: float = MAX_NORM, seed: int = 20080524,
                verbose: bool = True, tv_weight=None,
-               tv_eps: float = 1e-2) -> Tuple[OcTree, List[FitLogEntry]]:
+               tv_eps: float = 1e-2, dist_weight: float = 0.0) -> Tuple[OcTree, List[FitLogEntry]]:
     """Optimises the leaf values of a baked ``tree`` against the images of ``train_dataset`` (an
     ``ImageDataset``) through ``render_volume`` with a black background; -> (a new ``OcTree`` of the
     same structure, log).  One step: a batch of ray ids from a seeded shuffle of EVERY ray of every
@@ -274,10 +295,23 @@ def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 
     entered and the result is today's bit for bit (``None``, the default, is all zeros: the two fit
     loops keep one signature).  ``tv_weight`` and ``tv_eps`` are checked like every other argument
     before the first step, whether the prior is on or not: ``tv_eps <= 0`` raises with a zero
-    weight too."""
+    weight too.
+
+    ``dist_weight > 0`` switches the per-ray distortion prior on (K29): the step's loss gains
+    ``dist_weight * (1 / count) * sum_r D_r`` with ``D`` of ``OcTree.distortion`` over the batch's
+    ``count`` rays, and its gradient -- on the densities alone -- is formed inside K17a's two walks
+    (``field.backward(..., dist_scale=dist_weight / count)``): no third walk, no further host sync.
+    It penalises a ray that spreads its weight along a chord, which the data term and TV do not: a
+    fat hull can be thinned.  The logged ``loss`` stays the data term; report lines gain ``dist:``,
+    the batch mean of ``D``.  ``dist_weight`` is checked like every other argument (finite and
+    ``>= 0``); with the default 0 the term's code is not entered and the tree, the log and the
+    printed lines are today's bit for bit.  Limits: ``D`` treats a leaf's weight as uniform along
+    its chord, so it depends on the partition (``refine`` with splits changes it at second order);
+    it is measured in world lengths; it sees the tree's own densities only; it can eat thin true
+    structure behind a strong surface; ``dist_weight`` has no tuned default."""
     return _fit("fit_octree", OctreeField, tree, train_dataset, val_dataset, batch_size,
                 learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
-                clip_value, max_norm, seed, verbose, tv_weight, tv_eps)
+                clip_value, max_norm, seed, verbose, tv_weight, tv_eps, dist_weight)
 
 
 def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 4096,
@@ -286,21 +320,23 @@ def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int
                   min_transmittance: float = 0.0, clip_value: float = CLIP_VALUE,
                   max_norm: float = MAX_NORM, seed: int = 20080524,
                   verbose: bool = True, tv_weight=None,
-                  tv_eps: float = 1e-2) -> Tuple[OcTree, List[FitLogEntry]]:
+                  tv_eps: float = 1e-2,
+                  dist_weight: float = 0.0) -> Tuple[OcTree, List[FitLogEntry]]:
     """``fit_octree`` for a tree with SH leaves (``OcTree.bake_sh``): the same arguments, defaults,
     seeded shuffle, log and report lines; -> (a new SH ``OcTree`` of the same structure and
     ``sh_degree``, log).  One step: K18a, K6, K19a + K19b, K7 on the flat ``(L stride,)`` buffer in
     the device layout, K19c (density ``>= 0``, NaN -> 0; the logit-space coefficients are not
     clamped).  The default learning rate is ``fit_octree``'s.  ``tv_weight = (band0, higher_bands,
-    sigma)`` and ``tv_eps`` as in ``fit_octree`` (K20), on the rows of the device layout."""
+    sigma)`` and ``tv_eps`` as in ``fit_octree`` (K20), on the rows of the device layout;
+    ``dist_weight`` as in ``fit_octree`` (K29), inside K19a's two walks, with the same limits."""
     return _fit("fit_octree_sh", OctreeSHField, tree, train_dataset, val_dataset, batch_size,
                 learning_rate, num_steps, report_interval, center, t_min, min_transmittance,
-                clip_value, max_norm, seed, verbose, tv_weight, tv_eps)
+                clip_value, max_norm, seed, verbose, tv_weight, tv_eps, dist_weight)
 
 
 def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning_rate, num_steps,
          report_interval, center, t_min, min_transmittance, clip_value, max_norm, seed, verbose,
-         tv_weight, tv_eps):
+         tv_weight, tv_eps, dist_weight=0.0):
     """The loop of ``fit_octree`` / ``fit_octree_sh``; the field supplies the render, the backward,
     the TV gradient and the projection."""
     batch_size, num_steps = int(batch_size), int(num_steps)
@@ -314,6 +350,8 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
         raise ValueError("%s: the tree has no SH leaves (sh_degree is None); a plain baked tree is "
                          "fitted by fit_octree" % who)
     tree._check_volume(min_transmittance)
+    dist_weight = ops.octree_check_dist_scale("%s: dist_weight" % who, dist_weight)
+    dist_on = dist_weight > 0.0
     if center is None:
         center = tree.center
     if center is None:
@@ -353,8 +391,14 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
             sums, d_color, d_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas, rays,
                                                   1.0 / (3 * count), aw / count)
             losses.append(ops.loss_value(sums, count, aw))
-            field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
-                           min_transmittance, data=data, out=grads)
+            if dist_on:
+                ray_dist = torch.empty((count,), dtype=torch.float32, device=dev)
+                field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
+                               min_transmittance, data=data, out=grads,
+                               dist_scale=dist_weight / count, ray_distortion=ray_dist)
+            else:
+                field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
+                               min_transmittance, data=data, out=grads)
             if tv_on:
                 field.tv_backward(tv_weight, tv_eps, data=data, out=grads, accumulate=True)
             ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
@@ -374,6 +418,8 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
                           *(["tv: {:2f}".format(float(
                               field.total_variation(tv_weight, tv_eps, data).item()))]
                             if tv_on else []),
+                          *(["dist: {:2f}".format(float(ray_dist.mean().item()))]
+                            if dist_on else []),
                           "lr: {:.2e}".format(learning_rate), "eta:", eta)
             step += 1
     values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)

@@ -911,6 +911,15 @@ def _grad_workspace_bytes(name, *args):
     return int(size)
 
 
+def octree_grad_dist_workspace_bytes(n: int, num_leaves: int, max_entries: int,
+                                     degree: int = 0) -> int:
+    """Bytes of workspace the backwards need with the distortion term (K29b) switched on: those of
+    ``octree_grad_workspace_bytes`` (``degree`` 0) or ``octree_grad_sh_workspace_bytes`` plus three
+    floats per ray."""
+    return _grad_workspace_bytes("ffn_octree_grad_dist_workspace_bytes", c_i64(n),
+                                 c_i64(num_leaves), c_i64(max_entries), c_i(degree))
+
+
 def octree_grad_workspace_bytes(n: int, num_leaves: int, max_entries: int) -> int:
     """Bytes of workspace ``octree_render_volume_backward`` needs for ``n`` rays, ``num_leaves``
     leaves and up to ``max_entries`` (ray, taken leaf) pairs."""
@@ -928,19 +937,24 @@ class OctreeGradWorkspace:
         self.buffer = None
         self.shape = None
         self.entries = 0            # of the last call
+        self.dist = False           # K29b: the buffer also holds the per-ray triples
 
     def _bytes(self, n, num_leaves, want):
         return octree_grad_workspace_bytes(n, num_leaves, want)
 
-    def fit(self, n: int, num_leaves: int, device, at_least: int = 0):
+    def _dist_bytes(self, n, num_leaves, want):
+        return octree_grad_dist_workspace_bytes(n, num_leaves, want, getattr(self, "degree", 0))
+
+    def fit(self, n: int, num_leaves: int, device, at_least: int = 0, dist: bool = False):
         same = (self.buffer is not None and self.shape == (n, num_leaves)
-                and self.buffer.device == device)
+                and self.buffer.device == device and (self.dist or not dist))
         if same and self.max_entries >= max(at_least, 1):
             return
         if at_least > 0:
             self.entries_per_ray = max(self.entries_per_ray, -(-at_least // n))
         want = max(at_least, n * self.entries_per_ray, 1024)
-        need = self._bytes(n, num_leaves, want)
+        need = (self._dist_bytes if dist else self._bytes)(n, num_leaves, want)
+        self.dist = bool(dist)
         if self.buffer is None or self.buffer.numel() * 4 < need or self.buffer.device != device:
             self.buffer = None              # release before the larger one is taken
             self.buffer = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=device)
@@ -948,12 +962,25 @@ class OctreeGradWorkspace:
         self.shape = (n, num_leaves)
 
 
+def octree_check_dist_scale(who, dist_scale) -> float:
+    """A weight of the distortion term (K29): a finite float >= 0, else ``ValueError`` naming it."""
+    try:
+        value = float(dist_scale)
+    except (TypeError, ValueError):
+        value = float("nan")
+    if isinstance(dist_scale, bool) or not (math.isfinite(value) and value >= 0.0):
+        raise ValueError("%s must be finite and >= 0, got %r" % (who, dist_scale))
+    return value
+
+
 def _render_volume_backward(name, walk, t_min, leaf_block, background, min_transmittance, grads,
-                            workspace, out, width, degree=None, tail=()):
+                            workspace, out, width, degree=None, tail=(), dist=None):
     """The backward of a volume render through entry point ``name``: the output (num_leaves,
     ``width``), the call on ``workspace`` and, when the rays take more leaves than it holds, its
     growth and ONE repeat.  ``walk``: the arguments of ``_walk_args``; ``leaf_block()``: the leaf
-    arguments after ``t_min``; ``tail``: those after ``entries``; ``degree``: of SH rows."""
+    arguments after ``t_min``; ``tail``: those after ``entries``; ``degree``: of SH rows.
+    ``dist = (dist_scale, ray_distortion)`` (K29b) calls entry point ``name + "_dist"`` with the two
+    behind ``tail``; ``None`` calls ``name`` as ever."""
     who = "octree " + name[len("ffn_octree_"):]
     starts, leaf_index = walk[0], walk[5]
     d_color, d_alpha = grads
@@ -966,13 +993,21 @@ def _render_volume_backward(name, walk, t_min, leaf_block, background, min_trans
     if out.shape != (leaves, width):
         raise ValueError("%s: %s must be (num_leaves, %d)"
                          % (who, "d_leaf_data" if degree is None else "d_leaf_rows", width))
+    if dist is not None:
+        dist_scale, ray_distortion = dist
+        if ray_distortion is not None and ray_distortion.shape != (n,):
+            raise ValueError("%s: ray_distortion must be (N,) = (%d,), got %s"
+                             % (who, n, tuple(ray_distortion.shape)))
+        if n > 0:
+            name = name + "_dist"
+            tail = tuple(tail) + (c_f(dist_scale), _dev(ray_distortion, name="ray_distortion"))
     if n == 0:
         return out.zero_()
     if degree is not None and getattr(workspace, "degree", None) != degree:
         raise ValueError("%s: the workspace is not one of degree %d" % (who, degree))
     r, g, b = [float(v) for v in background]
     entries = c_i64(-1)
-    workspace.fit(n, leaves, dev)
+    workspace.fit(n, leaves, dev, dist=dist is not None)
     for attempt in range(2):
         try:
             _call(name, *_walk_args(*walk), c_f(t_min), *leaf_block(), c_f(r), c_f(g), c_f(b),
@@ -984,7 +1019,8 @@ def _render_volume_backward(name, walk, t_min, leaf_block, background, min_trans
         except _lib.FfnError:
             if attempt == 1 or entries.value <= workspace.max_entries:
                 raise
-            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4)
+            workspace.fit(n, leaves, dev, at_least=entries.value + entries.value // 4,
+                          dist=dist is not None)
     workspace.entries = int(entries.value)
     return out
 
@@ -995,21 +1031,31 @@ def octree_render_volume_backward(starts: torch.Tensor, directions: torch.Tensor
                                   d_alpha: torch.Tensor, t_min: float = 0.0,
                                   background=(0.0, 0.0, 0.0), min_transmittance: float = 0.0,
                                   workspace: Optional[OctreeGradWorkspace] = None,
-                                  d_leaf_data: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                  d_leaf_data: Optional[torch.Tensor] = None,
+                                  dist_scale: float = 0.0,
+                                  ray_distortion: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K17a + K17b, the backward of ``octree_render_volume``: d_color (N,3), d_alpha (N) ->
     d_leaf_data (L,4) float32 [d r, d g, d b, d sigma], every row written, deterministic (no float
     atomics).  One read-back (the number of (ray, taken leaf) pairs) per call; when the workspace
-    turns out too small for them it is grown and the call repeated."""
+    turns out too small for them it is grown and the call repeated.
+
+    K29b: with ``dist_scale > 0`` the d sigma column also holds ``dist_scale`` times the gradient of
+    the rays' summed distortion (``octree_distortion``), folded into the same two walks, and
+    ``ray_distortion`` (N,) float32, where given, receives ``D`` per ray with the bits of
+    ``octree_distortion``.  With ``dist_scale == 0`` and no ``ray_distortion`` the entry point
+    without the term is called: the bits are those of before the term existed."""
     who = "octree render_volume_backward"
     _check_leaf_data(who, leaf_data, leaf_index)
     _check_min_transmittance(who, min_transmittance)
+    dist_scale = octree_check_dist_scale(who + ": dist_scale", dist_scale)
+    dist = None if dist_scale == 0.0 and ray_distortion is None else (dist_scale, ray_distortion)
     if workspace is None:
         workspace = OctreeGradWorkspace()
     return _render_volume_backward(
         "ffn_octree_render_volume_backward",
         (starts, directions, scale, depth, node_index, leaf_index), t_min,
         lambda: (_dev(leaf_data, name="leaf_data"), c_i(leaf_data.shape[1])), background,
-        min_transmittance, (d_color, d_alpha), workspace, d_leaf_data, 4)
+        min_transmittance, (d_color, d_alpha), workspace, d_leaf_data, 4, dist=dist)
 
 
 def octree_project(leaf_data: torch.Tensor) -> torch.Tensor:
@@ -1062,14 +1108,20 @@ def octree_render_volume_sh_backward(starts: torch.Tensor, directions: torch.Ten
                                      t_min: float = 0.0, background=(0.0, 0.0, 0.0),
                                      min_transmittance: float = 0.0,
                                      workspace: Optional[OctreeGradSHWorkspace] = None,
-                                     d_leaf_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                     d_leaf_rows: Optional[torch.Tensor] = None,
+                                     dist_scale: float = 0.0,
+                                     ray_distortion: Optional[torch.Tensor] = None
+                                     ) -> torch.Tensor:
     """K19a + K19b, the backward of ``octree_render_volume_sh``: d_color (N,3), d_alpha (N) ->
     d_leaf_rows (L, stride) float32 in the device layout of ``leaf_rows`` [d sigma, d k_r..,
     d k_g.., d k_b.., 0 ..], every row written, deterministic (no float atomics).  The read-back and
-    the grow-and-repeat of the workspace are those of ``octree_render_volume_backward``."""
+    the grow-and-repeat of the workspace are those of ``octree_render_volume_backward``, and so are
+    ``dist_scale`` and ``ray_distortion`` (K29b), which act on the d sigma column alone."""
     who = "octree render_volume_sh_backward"
     _check_leaf_rows(who, leaf_rows, leaf_index, degree)
     _check_min_transmittance(who, min_transmittance)
+    dist_scale = octree_check_dist_scale(who + ": dist_scale", dist_scale)
+    dist = None if dist_scale == 0.0 and ray_distortion is None else (dist_scale, ray_distortion)
     if workspace is None:
         workspace = OctreeGradSHWorkspace(degree)
     return _render_volume_backward(
@@ -1077,7 +1129,7 @@ def octree_render_volume_sh_backward(starts: torch.Tensor, directions: torch.Ten
         (starts, directions, scale, depth, node_index, leaf_index), t_min,
         lambda: (_dev(leaf_rows, name="leaf_rows"),), background, min_transmittance,
         (d_color, d_alpha), workspace, d_leaf_rows, leaf_rows.shape[1], degree,
-        (c_i(degree), c_i(leaf_rows.shape[1])))
+        (c_i(degree), c_i(leaf_rows.shape[1])), dist=dist)
 
 
 def octree_project_sh(leaf_rows: torch.Tensor, degree: int) -> torch.Tensor:
@@ -1378,6 +1430,32 @@ def octree_leaf_weights(starts: torch.Tensor, directions: torch.Tensor, scale: f
     if starts.shape[0] > 0:
         _call("ffn_octree_leaf_weights", *_walk_args(starts, directions, scale, depth, node_index,
                                                      leaf_index),
+              c_f(t_min), _dev(rows, name="rows"), c_i(stride), c_i(sigma_offset),
+              c_f(min_transmittance), _dev(out, name="out"))
+    return out
+
+
+# --------------------------------------------------------------------------------- K29
+def octree_distortion(starts: torch.Tensor, directions: torch.Tensor, scale: float, depth: int,
+                      node_index: torch.Tensor, leaf_index: torch.Tensor, rows: torch.Tensor,
+                      stride: int, sigma_offset: int, t_min: float = 0.0,
+                      min_transmittance: float = 0.0) -> torch.Tensor:
+    """K29a.  Per ray the distortion ``D = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 L_i`` of
+    the weights ``w = T * a`` that ``octree_render_volume`` composites with, over the leaves it takes:
+    ``m`` a chord's midpoint and ``L`` its length, both as world lengths along the ray -> (N,)
+    float32, +0 for a ray that takes no leaf.  ``rows``, ``stride`` and ``sigma_offset`` as for
+    ``octree_leaf_weights`` (only the density is read).  No atomics: the same bits on every call."""
+    stride, sigma_offset = int(stride), int(sigma_offset)
+    if (rows.dim() != 2 or rows.shape[0] != leaf_index.numel() or rows.shape[1] != stride
+            or stride < 1 or not 0 <= sigma_offset < stride):
+        raise ValueError("octree distortion: rows must be (num_leaves, stride) with 0 <= "
+                         "sigma_offset < stride, got %s for %d leaves, stride %d, sigma_offset %d"
+                         % (tuple(rows.shape), leaf_index.numel(), stride, sigma_offset))
+    _check_min_transmittance("octree distortion", min_transmittance)
+    out = torch.zeros((starts.shape[0],), dtype=torch.float32, device=starts.device)
+    if starts.shape[0] > 0:
+        _call("ffn_octree_distortion", *_walk_args(starts, directions, scale, depth, node_index,
+                                                   leaf_index),
               c_f(t_min), _dev(rows, name="rows"), c_i(stride), c_i(sigma_offset),
               c_f(min_transmittance), _dev(out, name="out"))
     return out

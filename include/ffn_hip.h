@@ -1071,6 +1071,62 @@ int ffn_octree_project_sh(float* leaf_rows, int64_t num_leaves, int row_stride, 
                           void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K29  a per-ray distortion prior for fitting a tree (csrc/octree_walk.hip: K29a a mode of the K13
+ * kernel built as K21a is, K29b three gradient modes; the entries of K29b: csrc/octree_grad.hip).
+ * The distortion loss of Mip-NeRF 360 on the piecewise-constant weights of an octree ray; no
+ * counterpart in the reference.  For one ray, with the taken leaves k = 1..n of
+ * ffn_octree_render_volume in walk order and its t0_k, L_k, sigma_k, a_k, w_k = T_k a_k, T_{k+1}
+ * (the same f32 operations in the same order), m_k = (0.5 (t0_k + t_exit_k)) |d| the chord's midpoint
+ * as a world length, W_k = sum_{j<k} w_j and M_k = sum_{j<k} w_j m_j:
+ *   D = sum_k [ (2 w_k) (m_k W_k - M_k) + (w_k w_k) (L_k / 3) ]
+ *     = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 L_i      (the leaves are disjoint and ordered)
+ * in f32, summed front to back.  Lengths are world lengths; the background's share takes no part.
+ *
+ * K29a.  Arguments up to min_transmittance as for ffn_octree_leaf_weights (rows of `stride` floats of
+ * which only rows[leaf, sigma_offset] is read; stride >= 1, 0 <= sigma_offset < stride).
+ * distortion (n) f32: D per ray, +0 for a ray that takes no leaf, that misses the cube or that K13
+ * cannot follow.  Nothing is written per leaf, no atomics: the same inputs give the same bits. */
+int ffn_octree_distortion(const float* starts, const float* directions, int64_t n, float scale,
+                          int depth, const int64_t* node_index, int64_t num_nodes,
+                          const int64_t* leaf_index, int64_t num_leaves, float t_min,
+                          const float* rows, int stride, int sigma_offset, float min_transmittance,
+                          float* distortion, void* stream);
+
+/* K29b.  ffn_octree_render_volume_backward / ffn_octree_render_volume_sh_backward with the term
+ * folded into their two walks: the arguments of the parents in their order, then dist_scale and
+ * ray_distortion.  Only densities receive a gradient (m and L are geometry, colours do not enter):
+ *   G_k         = 2 [ (m_k W_k - M_k) + (M_tot - M_{k+1}) - m_k (W_tot - W_{k+1}) ] + (2/3) (w_k L_k)
+ *   dD/dsigma_k = L_k [ T_{k+1} G_k - (2 D - sum_{j<=k} w_j G_j) ]        (sum_j w_j G_j = 2 D)
+ * and every entry's d sigma becomes (parent's d sigma) + dist_scale * dD/dsigma_k: one f32 multiply,
+ * one f32 add, one rounding each; 0 where the stored density is negative or NaN, as in the parent.
+ * The first walk also leaves W_tot, M_tot and D per ray (12 n bytes behind the parent's workspace
+ * layout, which is otherwise unchanged: ffn_octree_grad_dist_workspace_bytes(n, num_leaves,
+ * max_entries, degree) with degree 0 for plain rows is the parent's size plus those bytes, rounded
+ * up to 256) and, where ray_distortion (n) f32 is not null, D there: the bits of
+ * ffn_octree_distortion on the same rays and densities, for plain rows and for SH rows.  The colour
+ * columns, the entry list, the per-leaf sums, *entries and the workspace protocol are the parents'.
+ * dist_scale is the caller's weight / number of rays; finite and >= 0, refused by name before
+ * anything else.  No float atomics: the same inputs give the same bits on every call. */
+int64_t ffn_octree_grad_dist_workspace_bytes(int64_t n, int64_t num_leaves, int64_t max_entries,
+                                             int degree);
+
+int ffn_octree_render_volume_backward_dist(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_data, int channels, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_data, int64_t* entries,
+    float dist_scale, float* ray_distortion, void* stream);
+
+int ffn_octree_render_volume_sh_backward_dist(
+    const float* starts, const float* directions, int64_t n, float scale, int depth,
+    const int64_t* node_index, int64_t num_nodes, const int64_t* leaf_index, int64_t num_leaves,
+    float t_min, const float* leaf_rows, float bg_r, float bg_g, float bg_b,
+    float min_transmittance, const float* d_color, const float* d_alpha, void* workspace,
+    int64_t workspace_bytes, int64_t max_entries, float* d_leaf_rows, int64_t* entries, int degree,
+    int row_stride, float dist_scale, float* ray_distortion, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K20  a total-variation prior between leaves that touch across a face (csrc/octree_tv.hip).  No
  * counterpart in the reference.
  *

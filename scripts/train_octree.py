@@ -4,7 +4,8 @@
 format, ready for ``scripts/render_octree.py --mode volume``.  A tree whose file carries an
 ``sh_degree`` (``OcTree.bake_sh``) is fitted by ``fit_octree_sh`` (K18a, K6, K19a-c, K7) and keeps
 its degree.  ``--tv-weight`` / ``--tv-eps`` switch the total-variation prior between touching
-leaves on (K20).  By default the structure of the tree does not change; ``--refine-rounds N`` makes
+leaves on (K20), ``--dist-weight W`` the per-ray distortion prior (K29), which penalises rays that
+spread their weight along a chord.  By default the structure of the tree does not change; ``--refine-rounds N`` makes
 it ``fit_octree_adaptive`` (K21): N times fit, measure the per-leaf weights over the training rays,
 drop the leaves below ``--prune-below`` and split those at or above ``--split-above``, then a last
 fit; ``--steps`` is the length of every fit.  No counterpart in the reference.
@@ -39,6 +40,9 @@ TRAIN_OCTREE = [
                          help="Weights of the total-variation prior (K20): RGB SIGMA for a plain "
                               "tree, BAND0 HIGHER_BANDS SIGMA for an SH tree (default: off)")),
     ("--tv-eps", dict(type=float, default=1e-2, help="The Charbonnier eps of the prior")),
+    ("--dist-weight", dict(type=float, default=0.0, metavar="W",
+                           help="Weight of the per-ray distortion prior (K29; default 0: off, "
+                                "no tuned value)")),
     ("--refine-rounds", dict(type=int, default=0,
                              help="Rounds of fit -> measure -> prune / split before the last fit "
                                   "(K21; 0: the plain fit)")),
@@ -85,6 +89,9 @@ def main():
             return 1
         prior = dict(tv_weight=tuple(args.tv_weight), tv_eps=args.tv_eps)
         print("total-variation prior:", " ".join("%g" % w for w in args.tv_weight), "eps %g" % args.tv_eps)
+    if args.dist_weight != 0.0:
+        prior["dist_weight"] = args.dist_weight
+        print("distortion prior: %g" % args.dist_weight)
     if args.refine_rounds > 0:
         policy = dict(max_depth=args.max_depth)
         if args.prune_below is not None:
