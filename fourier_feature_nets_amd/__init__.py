@@ -10,13 +10,15 @@ from .caster import LogEntry, Raycaster, TrainEngine
 from .dataset import ImageDataset, RayDataset
 from .frames import FrameSink
 from .occupancy import OccupancyGrid
-from .octree import OcTree, PhotoReport, PhotoSweep, photo_actions, refine_actions
+from .octree import (OcTree, PhotoReport, PhotoSweep, SurfaceMesh, photo_actions,
+                     refine_actions)
 from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, fit_octree,
                          fit_octree_adaptive, fit_octree_sh, leaf_weights_over)
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import load_obj, normalize_points, procedural_torus, sample_mesh, triangle_counts
+from .mesh import (load_obj, normalize_points, procedural_torus, sample_mesh, save_obj,
+                   triangle_counts)
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -42,7 +44,7 @@ __version__ = "0.1.0"
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
-           "RenderResult", "Resolution", "SignalData", "SignalDataset", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "eye_positions", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
            "linspace", "load_model", "load_obj", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "sample_mesh", "triangle_counts"]
+           "projection_matrices", "refine_actions", "sample_mesh", "save_obj", "triangle_counts"]

@@ -56,6 +56,9 @@ SOURCES = {
     "carve.hip": ["-ffp-contract=off"],
     # the same projection on a cell's centre and eight corners, operation for operation
     "carve_box.hip": ["-ffp-contract=off"],
+    # position = centre + ((c - n / 2) + offset) * side and the fixed-order sums of the offsets,
+    # colours and normals, every operation rounded on its own
+    "octree_mesh.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -545,6 +545,12 @@ refine_scatter_kernel(const uint8_t* __restrict__ action, const uint8_t* __restr
 void launch_octree_density_flags(const float* logits, int64_t count, float tau, float side,
                                  float* activated, uint8_t* flags, hipStream_t stream);
 
+// the K12b/c flag scan for the other octree files (octree_cells.h)
+int octree_scan_flags(const uint8_t* flags, int64_t n, int* tile_sums, int* offsets, int* total,
+                      hipStream_t stream) {
+    return scan_flags(flags, n, tile_sums, offsets, total, stream);
+}
+
 // the select tail of K16b and K23 (octree_cells.h)
 int octree_select_flagged(const uint8_t* flags, const float* rows, int64_t first_code,
                           int64_t count, int* offsets, int* tile_sums, int* codes_out,

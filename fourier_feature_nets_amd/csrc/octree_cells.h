@@ -30,6 +30,11 @@ __device__ __forceinline__ void oct_cell_center(int64_t code, float ox, float oy
 // first_code .. first_code + count - 1 -> the K12b/c scan and the stable scatter: codes_out and
 // data_out (count entries each) hold the flagged cells in code order, *total (device) of them.
 // The caller has checked the arguments and checks the launch.
+// octree.hip.  The K12b/c exclusive scan of n u8 flags (n <= ffn_octree_max_points()): offsets (n),
+// *total (device) the number of set flags; tile_sums holds ffn_octree_scan_tiles(n) ints.
+int octree_scan_flags(const uint8_t* flags, int64_t n, int* tile_sums, int* offsets, int* total,
+                      hipStream_t stream);
+
 int octree_select_flagged(const uint8_t* flags, const float* rows, int64_t first_code,
                           int64_t count, int* offsets, int* tile_sums, int* codes_out,
                           float* data_out, int* total, hipStream_t stream);

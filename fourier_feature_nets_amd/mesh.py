@@ -15,7 +15,8 @@ drawing the samples, is a kernel:
   (octree.py:128-129) in O(F), and the same counts for the same seed.
 * ``sample_mesh`` turns the counts into offsets and runs K22; the cloud stays on the GPU.
 
-``OcTree.build_from_triangles`` chains them into a colour octree.
+``OcTree.build_from_triangles`` chains them into a colour octree.  ``save_obj`` is the way back: it
+writes what ``OcTree.extract_mesh`` (K30) returns, with per-vertex colours and normals.
 """
 
 import os
@@ -180,6 +181,45 @@ def _diffuse_map(mtl_path: str) -> Optional[str]:
             if len(words) >= 2 and words[0] == "map_Kd":
                 return os.path.join(os.path.dirname(mtl_path), words[-1])
     return None
+
+
+def save_obj(path: str, vertices, triangles, colors=None, normals=None) -> None:
+    """Writes a Wavefront OBJ: ``v x y z`` per vertex (``v x y z r g b`` with ``colors`` (V,3), the
+    vertex-colour extension most viewers read), ``vn x y z`` per vertex with ``normals`` (V,3), and
+    ``f a b c`` per triangle, 1-based, as ``a//a b//b c//c`` when normals are given.  Floats are
+    written with ``%.9g``: a float32 survives the file bit for bit.  Needs no GPU."""
+    vertices = np.asarray(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError("save_obj: vertices must be (V,3), got %s" % (vertices.shape,))
+    triangles = np.asarray(triangles)
+    if (triangles.ndim != 2 or triangles.shape[1] != 3
+            or not np.issubdtype(triangles.dtype, np.integer)):
+        raise ValueError("save_obj: triangles must be an integer (F,3) array, got %s %s"
+                         % (triangles.dtype, triangles.shape))
+    if len(triangles) and (triangles.min() < 0 or triangles.max() >= len(vertices)):
+        raise ValueError("save_obj: triangles indexes vertices %d .. %d, outside 0 .. %d"
+                         % (triangles.min(), triangles.max(), len(vertices) - 1))
+    columns = [vertices]
+    for name, extra in (("colors", colors), ("normals", normals)):
+        if extra is not None and np.shape(extra) != vertices.shape:
+            raise ValueError("save_obj: %s must be (V,3) = %s, got %s"
+                             % (name, vertices.shape, np.shape(extra)))
+    if colors is not None:
+        columns.append(np.asarray(colors))
+    rows = np.concatenate(columns, 1)
+    lines = ["# %d vertices, %d triangles" % (len(vertices), len(triangles))]
+    lines += ["v " + " ".join("%.9g" % x for x in row) for row in rows.tolist()]
+    if normals is not None:
+        lines += ["vn " + " ".join("%.9g" % x for x in row)
+                  for row in np.asarray(normals).tolist()]
+    corner = "%d//%d" if normals is not None else "%d"
+    for a, b, c in (triangles.astype(np.int64) + 1).tolist():
+        if normals is not None:
+            lines.append("f " + " ".join(corner % (i, i) for i in (a, b, c)))
+        else:
+            lines.append("f %d %d %d" % (a, b, c))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def load_obj(path: str, texture_path: Optional[str] = None) -> Mesh:

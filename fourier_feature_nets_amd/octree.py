@@ -120,11 +120,19 @@ public signatures are the reference's, so files and calling code go both ways.  
   The one step that removes hull volume no silhouette refutes.  ``build_from_silhouettes(...,
   photo_threshold=T)`` runs it between the carve and the colouring; off by default.
 
+* ``extract_mesh`` (K30, ``csrc/octree_mesh.hip``) has none either: the reference hands its leaf
+  cubes to scenepic.  It is the way out of the tree: the boundary between solid and empty finest
+  cells as a closed, consistently wound triangle mesh with per-vertex colours and normals, vertices
+  on the block surface or moved onto the opacity threshold (surface nets).  ``mesh.save_obj`` writes
+  it and ``scripts/octree_to_mesh.py`` is the path-taking entry.  Coplanar quads of a coarse leaf
+  are not merged, there are no UVs, and an SH tree keeps its band-0 colour only.
+
 The tree itself (three small arrays) lives on the host as numpy; ``load`` / ``state_dict`` /
 ``save`` / ``prune`` need no GPU.  Building, ``query``, ``walk``, ``spans``, ``first_hit``, ``render``,
 ``bake``, ``bake_sh``, ``build_from_model``, ``build_from_silhouettes``, ``render_volume``,
 ``leaf_centers``, ``leaf_depths``, ``neighbors``, ``total_variation``, ``leaf_weights``, ``refine``,
-``visible_votes``, ``visible_moments`` and ``carve_photo`` run on the GPU and raise without one;
+``visible_votes``, ``visible_moments``, ``carve_photo`` and ``extract_mesh`` run on the GPU and
+raise without one;
 ``refine_actions`` and ``photo_actions`` are numpy.
 """
 
@@ -291,6 +299,10 @@ class PhotoReport(list):
 
 Path = NamedTuple("Path", [("t_stops", np.ndarray), ("leaves", np.ndarray)])
 Hit = NamedTuple("Hit", [("leaves", np.ndarray), ("t", np.ndarray), ("faces", np.ndarray)])
+SurfaceMesh = NamedTuple("SurfaceMesh", [("vertices", np.ndarray), ("triangles", np.ndarray),
+                                         ("colors", Optional[np.ndarray]),
+                                         ("normals", np.ndarray), ("corners", np.ndarray),
+                                         ("masks", np.ndarray)])
 
 
 class OcTree:
@@ -532,6 +544,117 @@ class OcTree:
         rows = self._tv_rows()
         value, _ = ops.octree_tv(rows, self._tv_plan(), lam, eps)
         return float(value.item())
+
+    def extract_mesh(self, alpha_threshold: float = 0.5, placement: str = "surface_nets",
+                     center=None, solid=None, batch_size: int = 1 << 22) -> SurfaceMesh:
+        """The tree's surface as a coloured triangle mesh (K30, ``csrc/octree_mesh.hip``): the
+        boundary between solid and empty finest cells, closed (it closes at the cube's faces) and
+        wound so that normals point from solid to empty.  No counterpart in the reference, which
+        hands its leaf cubes to scenepic.
+
+        With ``n = 2^(depth-1)`` finest cells per axis and ``side = 2 scale / n``, every finest cell
+        has an opacity ``a``: inside a leaf with a density ``a = 1 - exp(-sigma side)`` (the FINEST
+        side whatever the leaf's level, as in ``build_from_model``; column 3 of a plain tree with
+        ``C >= 4``, the density of an SH tree; 0 for a negative or NaN density), 0 in empty space.
+        A cell is solid when ``a > alpha_threshold``.  A tree whose ``leaf_data`` has exactly 3
+        columns (a voxelized shell, a mesh-built colour tree) or none has ``a = 1`` in every leaf
+        and the threshold 0.5 whatever was passed; so has a call with ``solid``, a bool (L,) array
+        in sorted-leaf order that replaces the rule (``tree.leaf_weights(...) > w``, say): ``a`` is
+        then 1 or 0.
+
+        Vertices are the cell corners ``c = (i, j, k)`` that touch both a solid and an empty cell,
+        ordered by ``(i (n+1) + j)(n+1) + k``; each boundary face of a cell is one quad of two
+        triangles (a coarse leaf's face is ``k^2`` unit quads: coplanar quads are not merged).
+        ``placement="corners"`` puts a vertex at ``center + (c - n/2) side``, the exact block
+        surface; ``"surface_nets"`` moves it by up to half a cell to the mean of the threshold
+        crossings on the twelve edges between its eight cells.  ``center`` defaults to the tree's
+        own, or to zeros.  -> ``SurfaceMesh`` of numpy arrays: ``vertices`` (V,3) f32, ``triangles``
+        (F,3) int32, ``colors`` (V,3) f32 -- the mean ``rgb`` of the solid cells round the vertex --
+        or None for a tree without ``leaf_data``, ``normals`` (V,3) f32 (minus the normalised
+        opacity gradient over the eight cells), ``corners`` (V,3) int32 and ``masks`` (V,) uint8
+        (bit ``4 dx + 2 dy + dz`` set when cell ``c - 1 + (dx, dy, dz)`` is solid).  A tree with no
+        solid leaf gives empty arrays.
+
+        An SH tree is coloured with its band-0 colour ``sigmoid(k_c0 Y_00)``: the view dependence
+        is dropped.  Candidates (the corners on the surfaces of solid leaves) are processed
+        ``batch_size`` at a time, which bounds the memory by the chunk and the output; the result
+        does not depend on it."""
+        who = "OcTree.extract_mesh"
+        try:
+            threshold, surface_nets = ops.octree_mesh_check(alpha_threshold, placement)
+        except ValueError as err:
+            raise ValueError(str(err).replace("octree mesh", who)) from None
+        if isinstance(batch_size, (bool, float)) or int(batch_size) < 1:
+            raise ValueError("%s: batch_size >= 1, got %r" % (who, batch_size))
+        num = self.num_leaves
+        if solid is not None:
+            is_tensor = torch.is_tensor(solid)
+            kind = solid.dtype if is_tensor else np.asarray(solid).dtype
+            if kind != (torch.bool if is_tensor else np.dtype(bool)):
+                raise TypeError("%s: solid must be a bool array, got %s" % (who, kind))
+            if tuple(solid.shape if is_tensor else np.shape(solid)) != (num,):
+                raise ValueError("%s: solid must be (num_leaves,) = (%d,), got %s"
+                                 % (who, num, tuple(np.shape(solid))))
+        data = self._leaf_data
+        has_density = False
+        if data is not None:
+            if np.ndim(data) != 2 or np.shape(data)[0] != num or np.shape(data)[1] < 3:
+                raise ValueError("%s: leaf_data must be (num_leaves, 3) colours or (num_leaves, "
+                                 "C >= 4) with a density, got %s" % (who, np.shape(data),))
+            if self._sh_degree is not None:
+                self._check_volume(0.0, who)
+            has_density = np.shape(data)[1] >= 4
+        if center is None:
+            center = self._center if self._center is not None else (0.0, 0.0, 0.0)
+        center = tuple(float(np.float32(c)) for c in center)
+        if len(center) != 3 or not all(np.isfinite(center)):
+            raise ValueError("%s: center has three finite components" % who)
+        depth = self.depth
+        cells = 1 << (depth - 1)
+        side = float(np.float32(2.0) * np.float32(self._scale) / np.float32(cells))
+
+        dev = self._dev()
+        if depth > ops.octree_mesh_max_depth():
+            raise ValueError("%s: a tree of depth %d is deeper than the corner keys hold (%d)"
+                             % (who, depth, ops.octree_mesh_max_depth()))
+        rows, sigma_offset, color = None, 0, None
+        if data is not None:
+            if self._sh_degree is not None:
+                rows, color = self._sh_rows_on_device(), (1, _sh_bases(self._sh_degree), 1)
+            else:
+                rows, sigma_offset, color = self._colors_on_device(), 3, (0, 1, 0)
+        if solid is not None:
+            solid = (solid if torch.is_tensor(solid) else torch.from_numpy(
+                np.ascontiguousarray(solid))).to(dev).to(torch.uint8).contiguous()
+        if solid is not None or not has_density:
+            threshold = 0.5
+        node_index, leaf_index = self._on_device("node_index"), self._on_device("leaf_index")
+        flags, alpha = ops.octree_mesh_solid(rows if has_density else None, sigma_offset, solid,
+                                             num, side, threshold, dev)
+        offsets, total, top_level = ops.octree_mesh_candidate_offsets(leaf_index, flags, depth)
+        if top_level > depth - 1:          # cannot happen: depth is read off the deepest id
+            raise ValueError("%s: a leaf at level %d in a tree of depth %d"
+                             % (who, top_level, depth))
+        step = min(int(batch_size), ops.octree_max_points())
+        parts = [ops.octree_mesh_candidates(node_index, leaf_index, flags, offsets, first,
+                                            min(step, total - first), depth)
+                 for first in range(0, total, step)]
+        if parts:
+            keys, masks, samples = [torch.cat(p) for p in zip(*parts)]
+        else:
+            keys = torch.empty((0,), dtype=torch.int64, device=dev)
+            masks = torch.empty((0,), dtype=torch.uint8, device=dev)
+            samples = torch.empty((0, 8), dtype=torch.int32, device=dev)
+        # the keys are unique: sorting them, and the payload with them, is integer plumbing
+        keys, order = torch.sort(keys)
+        masks, samples = masks[order].contiguous(), samples[order].contiguous()
+        vertices, colors, normals, corners = ops.octree_mesh_vertices(
+            keys, masks, samples, alpha, rows, color, depth, self._scale, center, threshold,
+            surface_nets)
+        triangles = ops.octree_mesh_faces(keys, masks, depth)
+        return SurfaceMesh(vertices.cpu().numpy(), triangles.cpu().numpy(),
+                           None if colors is None else colors.cpu().numpy(),
+                           normals.cpu().numpy(), corners.cpu().numpy(), masks.cpu().numpy())
 
     def query(self, positions):
         """Index into the sorted leaf ids of the leaf containing each position, -1 outside the

@@ -2040,3 +2040,161 @@ def _octree_visible_pairs(entry, moments, leaf_centers, scale, depth, node_index
           c_i(cameras), c_i(height), c_i(width), c_i(int(alpha_u8)), c_f(min_transmittance),
           _dev(out, torch.uint32, "out"))
     return out
+
+
+# --------------------------------------------------------------------------------- K30
+OCTREE_MESH_PLACEMENTS = ("surface_nets", "corners")
+
+
+def octree_mesh_max_depth() -> int:
+    """The deepest tree whose corner keys ``(i (n+1) + j)(n+1) + k`` an int64 holds."""
+    fn = _lib.load().ffn_octree_mesh_max_depth
+    fn.restype = ctypes.c_int
+    return int(fn())
+
+
+def octree_mesh_check(alpha_threshold, placement):
+    """The refusals of K30 that need no device -> (threshold as a float32 value, surface_nets)."""
+    if placement not in OCTREE_MESH_PLACEMENTS:
+        raise ValueError("octree mesh: placement is 'surface_nets' or 'corners', got %r"
+                         % (placement,))
+    threshold = float(np.float32(alpha_threshold))
+    if not 0.0 < threshold < 1.0:            # NaN fails too
+        raise ValueError("octree mesh: alpha_threshold must lie in (0, 1), got %r"
+                         % (alpha_threshold,))
+    return threshold, placement == "surface_nets"
+
+
+def octree_mesh_solid(rows: Optional[torch.Tensor], sigma_offset: int,
+                      solid: Optional[torch.Tensor], num_leaves: int, side: float,
+                      threshold: float, device):
+    """K30a.  -> (solid (L,) uint8, alpha (L,) float32): per leaf the opacity over one finest side,
+    ``-expm1f(-(sigma * side))`` with ``sigma = rows[:, sigma_offset]`` (0 for a negative or NaN
+    sigma), 1 without ``rows``, 1 / 0 from ``solid`` (L,) uint8 when given; solid iff ``alpha >
+    threshold``."""
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != num_leaves):
+        raise ValueError("octree mesh: rows must be (num_leaves, stride) = (%d, stride), got %s"
+                         % (num_leaves, tuple(rows.shape)))
+    if solid is not None and tuple(solid.shape) != (num_leaves,):
+        raise ValueError("octree mesh: solid must be (num_leaves,) = (%d,), got %s"
+                         % (num_leaves, tuple(solid.shape)))
+    flags = torch.empty((num_leaves,), dtype=torch.uint8, device=device)
+    alpha = torch.empty((num_leaves,), dtype=torch.float32, device=device)
+    _call("ffn_octree_mesh_solid", _dev(rows, name="rows"),
+          c_i(0 if rows is None else int(rows.shape[1])), c_i(int(sigma_offset)),
+          _dev(solid, torch.uint8, "solid"), c_i64(num_leaves), c_f(side), c_f(threshold),
+          _dev(flags, torch.uint8, "flags"), _dev(alpha, name="alpha"))
+    return flags, alpha
+
+
+def octree_mesh_candidate_offsets(leaf_index: torch.Tensor, solid: torch.Tensor, depth: int):
+    """The exclusive int64 scan behind K30b -> (offsets (L+1,) int64 on the device, total, deepest
+    level; one read-back).  A solid leaf of ``k = 2^(depth-1-level)`` cells a side has ``6 k^2 + 2``
+    corners on its closed surface; a leaf that is not solid has none.  Integer plumbing."""
+    dev = leaf_index.device
+    limit = octree_mesh_max_depth()
+    first_id = torch.tensor([(8 ** k - 1) // 7 for k in range(limit + 1)], dtype=torch.int64,
+                            device=dev)
+    levels = torch.searchsorted(first_id, leaf_index, right=True) - 1
+    cells = torch.ones_like(levels) << (depth - 1 - levels).clamp(min=0)
+    counts = torch.where(solid != 0, 6 * cells * cells + 2, torch.zeros_like(cells))
+    offsets = torch.zeros((leaf_index.numel() + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total, top_level = torch.stack([offsets[-1], levels.max()]).cpu().tolist()
+    return offsets, int(total), int(top_level)
+
+
+def octree_mesh_candidates(node_index: torch.Tensor, leaf_index: torch.Tensor,
+                           solid: torch.Tensor, cand_offsets: torch.Tensor, first: int,
+                           count: int, depth: int):
+    """K30b on the candidates ``first .. first + count - 1`` -> (keys (K,) int64, masks (K,) uint8,
+    samples (K,8) int32) of the corners kept, in candidate order.  Reads the count back once."""
+    dev = leaf_index.device
+    num_leaves = leaf_index.numel()
+    if tuple(solid.shape) != (num_leaves,) or tuple(cand_offsets.shape) != (num_leaves + 1,):
+        raise ValueError("octree mesh: solid (num_leaves,) and cand_offsets (num_leaves + 1,) must "
+                         "fit the %d leaves, got %s and %s"
+                         % (num_leaves, tuple(solid.shape), tuple(cand_offsets.shape)))
+    if count < 1 or count > octree_max_points():
+        raise ValueError("octree mesh: 1 <= count <= %d candidates a call, got %d"
+                         % (octree_max_points(), count))
+    flags, offsets, tiles = _scan_scratch(count, dev)
+    keys = torch.empty((2, count), dtype=torch.int64, device=dev)
+    masks = torch.empty((2, count), dtype=torch.uint8, device=dev)
+    samples = torch.empty((2, count, 8), dtype=torch.int32, device=dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    _call("ffn_octree_mesh_candidates",
+          _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
+          c_i64(node_index.numel()), _dev(leaf_index, torch.int64, "leaf_index"),
+          c_i64(num_leaves), _dev(solid, torch.uint8, "solid"),
+          _dev(cand_offsets, torch.int64, "cand_offsets"), c_i64(first), c_i64(count),
+          c_i(int(depth)), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          _dev(tiles, torch.int32), _dev(keys[0], torch.int64), _dev(masks[0], torch.uint8),
+          _dev(samples[0], torch.int32), _dev(keys[1], torch.int64), _dev(masks[1], torch.uint8),
+          _dev(samples[1], torch.int32), _dev(total, torch.int32))
+    k = int(total.item())
+    return keys[1, :k].clone(), masks[1, :k].clone(), samples[1, :k].clone()
+
+
+def octree_mesh_vertices(keys: torch.Tensor, masks: torch.Tensor, samples: torch.Tensor,
+                         alpha: torch.Tensor, rows: Optional[torch.Tensor], color, depth: int,
+                         scale: float, center, threshold: float, surface_nets: bool):
+    """K30c.  ``keys`` (V,) int64 ascending with their ``masks`` (V,) uint8 and ``samples`` (V,8)
+    int32; ``alpha`` (L,) of K30a; ``rows`` (L, stride) and ``color = (offset, step, sh)`` name the
+    three colour columns (``sh``: band-0 SH logits), or ``rows`` None for no colours.
+    -> vertices (V,3) f32, colors (V,3) f32 or None, normals (V,3) f32, corners (V,3) int32."""
+    dev = keys.device
+    count = keys.numel()
+    num_leaves = alpha.numel()
+    if tuple(masks.shape) != (count,) or tuple(samples.shape) != (count, 8):
+        raise ValueError("octree mesh: keys (V,), masks (V,) and samples (V,8) disagree: %s, %s, %s"
+                         % (tuple(keys.shape), tuple(masks.shape), tuple(samples.shape)))
+    if rows is not None and (rows.dim() != 2 or rows.shape[0] != num_leaves):
+        raise ValueError("octree mesh: rows must be (num_leaves, stride) = (%d, stride), got %s"
+                         % (num_leaves, tuple(rows.shape)))
+    vertices = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    corners = torch.empty((count, 3), dtype=torch.int32, device=dev)
+    colors = None if rows is None else torch.empty((count, 3), dtype=torch.float32, device=dev)
+    if count == 0:
+        return vertices, colors, normals, corners
+    offset, step, sh = (0, 1, 0) if rows is None else [int(v) for v in color]
+    _call("ffn_octree_mesh_vertices", _dev(keys, torch.int64, "keys"),
+          _dev(masks, torch.uint8, "masks"), _dev(samples, torch.int32, "samples"), c_i64(count),
+          _dev(alpha, name="alpha"), _dev(rows, name="rows"), c_i64(num_leaves),
+          c_i(0 if rows is None else int(rows.shape[1])), c_i(offset), c_i(step), c_i(sh),
+          c_i(int(depth)), c_f(scale), c_f(center[0]), c_f(center[1]), c_f(center[2]),
+          c_f(threshold), c_i(int(bool(surface_nets))), _dev(vertices), _dev(colors),
+          _dev(normals), _dev(corners, torch.int32))
+    return vertices, colors, normals, corners
+
+
+def octree_mesh_faces(keys: torch.Tensor, masks: torch.Tensor, depth: int) -> torch.Tensor:
+    """K30d.  ``keys`` (V,) int64 ascending and their ``masks`` -> triangles (F,3) int32, two per
+    owned quad, ordered by owner vertex, then axis, wound so that the normal points from solid to
+    empty.  Reads the quad count back once; a quad whose corner is not among the keys raises."""
+    dev = keys.device
+    count = keys.numel()
+    if tuple(masks.shape) != (count,):
+        raise ValueError("octree mesh: keys (V,) and masks (V,) disagree: %s, %s"
+                         % (tuple(keys.shape), tuple(masks.shape)))
+    if count == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=dev)
+    if 3 * count > octree_max_points():
+        raise ValueError("octree mesh: %d vertices are more than one face scan holds (%d)"
+                         % (count, octree_max_points() // 3))
+    flags, offsets, tiles = _scan_scratch(3 * count, dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    _call("ffn_octree_mesh_face_flags", _dev(masks, torch.uint8, "masks"), c_i64(count),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
+          _dev(total, torch.int32))
+    quads = int(total.item())
+    triangles = torch.empty((2 * quads, 3), dtype=torch.int32, device=dev)
+    if quads == 0:
+        return triangles
+    missing = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _call("ffn_octree_mesh_faces", _dev(keys, torch.int64, "keys"),
+          _dev(masks, torch.uint8, "masks"), _dev(flags, torch.uint8), _dev(offsets, torch.int32),
+          c_i64(count), c_i(int(depth)), c_i64(quads), _dev(triangles, torch.int32),
+          _dev(missing, torch.int32))
+    return triangles

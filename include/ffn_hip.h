@@ -1498,6 +1498,94 @@ int ffn_octree_focus_sample(const float* starts, const float* directions, const 
                             const float* t_uniform, int uniform_stride, int n_uniform,
                             float min_mass, float* t_out, float* mass_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K30  a coloured triangle mesh from an octree (csrc/octree_mesh.hip).  No counterpart in the
+ * reference, which hands its leaf cubes to scenepic.
+ *
+ * n = 2^(depth-1) finest cells per axis, side = 2 scale / n.  Vertices sit on the lattice of cell
+ * corners c = (i, j, k), 0 <= i, j, k <= n.  The eight samples of a corner are the cells
+ * c - 1 + (dx, dy, dz) with bit b = 4 dx + 2 dy + dz (the child digit); mask has bit b set when that
+ * cell is solid; cells in empty space or outside the cube are not.  A corner is a vertex when mask is
+ * neither 0 nor 255; its key is (i (n+1) + j)(n+1) + k (int64).  Integers wherever the contract is
+ * integer, f32 sums in a fixed order (the file is compiled with -ffp-contract=off), no float
+ * atomics: the same bits on every call.  Every index read from an input array is held against its
+ * range before use.  Bad shapes and null pointers are refused by name before any launch. */
+int ffn_octree_mesh_max_depth(void);   /* 21: the deepest tree whose keys an int64 holds */
+
+/* K30a.  Per leaf the opacity over one FINEST side and the flag alpha > threshold (strict):
+ *   solid_in (num_leaves) uint8 given: alpha = solid_in ? 1 : 0 (leaf_rows is not read);
+ *   else leaf_rows NULL: alpha = 1;
+ *   else sigma = leaf_rows[l * stride + sigma_offset], alpha = -expm1f(-(sigma * side)), 0 for a
+ *   negative or NaN sigma.
+ * 0 < threshold < 1; side finite and positive. */
+int ffn_octree_mesh_solid(const float* leaf_rows, int stride, int sigma_offset,
+                          const uint8_t* solid_in, int64_t num_leaves, float side, float threshold,
+                          uint8_t* solid, float* alpha, void* stream);
+
+/* K30b.  Only corners on the closed surface of a solid leaf can be vertices; a leaf of k =
+ * 2^(depth-1-level) cells a side has (k+1)^3 - (k-1)^3 = 6 k^2 + 2 of them.  cand_offsets
+ * (num_leaves + 1) int64 is the exclusive scan of that count over the leaves (0 for a leaf that is
+ * not solid), made by the caller.  This call handles the candidates first .. first + count - 1, one
+ * thread each: the leaf by a binary search of cand_offsets, the corner by a closed form of the
+ * remainder (the plane i = 0, the plane i = k, then per i the ring: row j = 0, row j = k, then per j
+ * the ends k = 0 and k = k), the eight cells by integer coordinate from the root down with the
+ * binary searches of ffn_octree_neighbors (a leaf met on the way covers the cell, the root included;
+ * an id in neither index is empty).  A candidate is kept when its mask is active and the first solid
+ * sample in bit order lies in the thread's own leaf: every vertex exactly once.  The kept ones in
+ * candidate order (the K12b/c scan and a stable scatter): keys (int64), masks (uint8) and samples
+ * (.,8) int32 (the eight leaf numbers, -1 for empty), *total (device) of them, in arrays of count
+ * entries; the *_scratch arrays have the same shapes.  flags / offsets / tile_sums as for
+ * ffn_octree_surface_points.  A candidate whose leaf, id or number does not fit depth is dropped.
+ * 1 <= depth <= ffn_octree_mesh_max_depth(); 1 <= count <= ffn_octree_max_points(). */
+int ffn_octree_mesh_candidates(const int64_t* node_index, int64_t num_nodes,
+                               const int64_t* leaf_index, int64_t num_leaves, const uint8_t* solid,
+                               const int64_t* cand_offsets, int64_t first, int64_t count, int depth,
+                               uint8_t* flags, int* offsets, int* tile_sums, int64_t* keys_scratch,
+                               uint8_t* masks_scratch, int32_t* samples_scratch, int64_t* keys,
+                               uint8_t* masks, int32_t* samples, int* total, void* stream);
+
+/* K30c.  Per vertex (keys ascending: the caller sorts them and permutes masks and samples), with
+ * a_b = alpha[samples[v, b]] (0 for -1 or a number outside 0 .. num_leaves - 1), p_b = (dx, dy, dz) -
+ * 0.5 and every operation one rounded f32 operation:
+ *   offset: 0 without surface_nets.  With it, over the 12 sample pairs that differ in one bit -- x
+ *     pairs first, then y, then z, within an axis by ascending lower b -- a pair whose mask bits
+ *     differ contributes p_b0 + t e_ax, t = (threshold - a_b0) / (a_b1 - a_b0); offset = the sum of
+ *     the contributions in that order, divided by their count.
+ *   vertices[v] = center + (((float)c - n / 2) + offset) * side, side = 2 scale / n.
+ *   corners[v] = c (int32).
+ *   normals[v] = -g / |g|, g = sum_b a_b * 2 p_b in bit order, |g| = sqrtf((gx gx + gy gy) + gz gz);
+ *     (0, 0, 0) when |g| is 0.
+ *   colors[v] = the sum over the solid samples, in bit order, of the three columns
+ *     leaf_rows[l * stride + color_offset + c * color_step], divided by their number; with color_sh
+ *     != 0 a column k is first turned into 1 / (1 + expf(-(k * Y_00))), Y_00 = 0.28209479, the
+ *     band-0 colour of an SH leaf (plain rows: offset 0, step 1; K18a device rows of B bases: offset
+ *     1, step B).  leaf_rows and colors are NULL together: no colours. */
+int ffn_octree_mesh_vertices(const int64_t* keys, const uint8_t* masks, const int32_t* samples,
+                             int64_t num_vertices, const float* alpha, const float* leaf_rows,
+                             int64_t num_leaves, int stride, int color_offset, int color_step,
+                             int color_sh, int depth, float scale, float center_x, float center_y,
+                             float center_z, float threshold, int surface_nets, float* vertices,
+                             float* colors, float* normals, int32_t* corners, void* stream);
+
+/* K30d, in two calls around one read-back of the quad count.  Vertex v owns the quad across axis ax
+ * (x, y, z) when cell c (bit 7) and cell c - e_ax (bit 7 ^ (4 >> ax)) differ in solidity.
+ * ffn_octree_mesh_face_flags: flags / offsets (3 num_vertices each, slot 3 v + ax) and tile_sums
+ * (ffn_octree_scan_tiles(3 num_vertices)); *total (device) = the number of quads.
+ * ffn_octree_mesh_faces: with those flags and offsets and num_quads = *total, quad o writes the rows
+ * 2 o and 2 o + 1 of triangles (2 num_quads, 3) int32: its corners q = c, c + e_u, c + e_u + e_v,
+ * c + e_v, (u, v) the next two axes in cyclic order (normal +ax), as written when cell c - e_ax is the
+ * solid one and as c, c + e_v, c + e_u + e_v, c + e_u when cell c is, so that the normal points from
+ * solid to empty; triangles (q0, q1, q2) and (q0, q2, q3).  The three other corners are found by a
+ * binary search of their keys in keys (ascending).  A key that is not found, or an offset outside
+ * 0 .. num_quads - 1, is an error: that quad is not written, missing (one int32 on the device) is
+ * set, and the call -- which waits for the stream to read it -- returns non-zero.
+ * 3 num_vertices <= ffn_octree_max_points(). */
+int ffn_octree_mesh_face_flags(const uint8_t* masks, int64_t num_vertices, uint8_t* flags,
+                               int* offsets, int* tile_sums, int* total, void* stream);
+int ffn_octree_mesh_faces(const int64_t* keys, const uint8_t* masks, const uint8_t* flags,
+                          const int* offsets, int64_t num_vertices, int depth, int64_t num_quads,
+                          int32_t* triangles, int32_t* missing, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
