@@ -485,12 +485,17 @@ class Report:
         return p
 
 
-def depth_candidates(fwd):
-    """(R, S) bool: the samples whose t the kernel may report as depth (module docstring)."""
+def depth_candidates(fwd, inner=None):
+    """(R, S) bool: the samples whose t the kernel may report as depth (module docstring).
+    ``inner`` (R, S) bool: the samples that compete for the pick, by default all but the last (the
+    fused render under an occupancy grid lets only its kept samples compete); a ray none of whose
+    samples competes reports the last sample whatever its alpha."""
     w, a = fwd["wt"]["w"], fwd["alpha"]
     R, S = w.v.shape
     s = torch.arange(S, device=w.v.device)[None]
-    inner = s < S - 1
+    if inner is None:
+        inner = s < S - 1
+    none_inner = ~inner.any(1, keepdim=True)            # (default: S == 1)
     beta = KAPPA["weights"] * U * w.b
     lo = torch.where(inner, w.v - beta, -math.inf)
     hi = torch.where(inner, w.v + beta, -math.inf)
@@ -500,7 +505,7 @@ def depth_candidates(fwd):
     beta_a = KAPPA["alpha"] * U * a.b
     surely_below = (a.v + beta_a < ALPHA_CUT)[:, None]
     surely_above = (a.v - beta_a >= ALPHA_CUT)[:, None]
-    last = (s == S - 1) & (~surely_above | (S == 1))
+    last = (s == S - 1) & (~surely_above | none_inner)
     return (argmax & ~surely_below) | last
 
 
