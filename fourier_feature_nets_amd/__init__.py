@@ -17,8 +17,8 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import (load_obj, normalize_points, procedural_torus, sample_mesh, save_obj,
-                   triangle_counts)
+from .mesh import (load_obj, normalize_points, procedural_torus, render_mesh, render_mesh_image,
+                   sample_mesh, save_obj, triangle_counts)
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -47,4 +47,4 @@ __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo
            "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
            "exponential_lr_decay", "eye_positions", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
            "linspace", "load_model", "load_obj", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "sample_mesh", "save_obj", "triangle_counts"]
+           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_image", "sample_mesh", "save_obj", "triangle_counts"]

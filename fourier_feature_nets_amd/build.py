@@ -59,6 +59,9 @@ SOURCES = {
     # position = centre + ((c - n / 2) + offset) * side and the fixed-order sums of the offsets,
     # colours and normals, every operation rounded on its own
     "octree_mesh.hip": ["-ffp-contract=off"],
+    # K23's projection, the perspective-correct weights and the interpolation of colours, UVs and
+    # positions, every product, sum and quotient rounded on its own
+    "mesh_raster.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -20,8 +20,10 @@
 //   colour     col = u W, row = v H; j0 = floor(col), i0 = floor(row); dj = col - j0,
 //              di = row - i0 BEFORE the indices are clamped to the image; four weights
 //              (1 - di)(1 - dj), (1 - di) dj, di (1 - dj), di dj, each times its texel as f32;
-//              ((v00 + v01) + v10) + v11, then / 255.  Channels 0..2.
+//              ((v00 + v01) + v10) + v11, then / 255.  Channels 0..2.  (mesh_texture_lookup in
+//              mesh_terms.h, which K31c shares)
 #include "common.h"
+#include "mesh_terms.h"
 
 namespace ffn {
 
@@ -40,13 +42,6 @@ __device__ __forceinline__ MeshPoint mesh_pick(int d, MeshPoint v0, MeshPoint v1
                                                MeshPoint v3) {
     const MeshPoint lo = d & 1 ? v1 : v0, hi = d & 1 ? v3 : v2;
     return d & 2 ? hi : lo;
-}
-
-// float index of a texel row or column, clamped to [0, last]; NaN clamps to 0.  Clamping the
-// float keeps the conversion defined for any finite or infinite coordinate; below 2^24 it is the
-// integer clamp of the reference.
-__device__ __forceinline__ int mesh_clamp_index(float index, float last) {
-    return (int)fminf(fmaxf(index, 0.0f), last);
 }
 
 __global__ void __launch_bounds__(kMeshThreads)
@@ -100,24 +95,7 @@ mesh_sample_kernel(const float* __restrict__ vertices, int num_vertices,
         sample_uvs[2 * s + 1] = v;
     }
 
-    const float col = u * (float)width, row = v * (float)height;
-    const float fj = floorf(col), fi = floorf(row);
-    const float dj = col - fj, di = row - fi;
-    const float last_col = (float)(width - 1), last_row = (float)(height - 1);
-    const int j0 = mesh_clamp_index(fj, last_col), j1 = mesh_clamp_index(fj + 1.0f, last_col);
-    const int i0 = mesh_clamp_index(fi, last_row), i1 = mesh_clamp_index(fi + 1.0f, last_row);
-    const float w00 = (1.0f - di) * (1.0f - dj), w01 = (1.0f - di) * dj;
-    const float w10 = di * (1.0f - dj), w11 = di * dj;
-    const uint8_t* t00 = texture + ((int64_t)i0 * width + j0) * channels;
-    const uint8_t* t01 = texture + ((int64_t)i0 * width + j1) * channels;
-    const uint8_t* t10 = texture + ((int64_t)i1 * width + j0) * channels;
-    const uint8_t* t11 = texture + ((int64_t)i1 * width + j1) * channels;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float sum = ((w00 * (float)t00[ch] + w01 * (float)t01[ch]) + w10 * (float)t10[ch])
-                          + w11 * (float)t11[ch];
-        colors[3 * s + ch] = sum / 255.0f;
-    }
+    mesh_texture_lookup(u, v, texture, height, width, channels, colors + 3 * s);
 }
 
 }  // namespace ffn

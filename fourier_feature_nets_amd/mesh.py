@@ -17,6 +17,10 @@ drawing the samples, is a kernel:
 
 ``OcTree.build_from_triangles`` chains them into a colour octree.  ``save_obj`` is the way back: it
 writes what ``OcTree.extract_mesh`` (K30) returns, with per-vertex colours and normals.
+
+``render_mesh`` and ``render_mesh_image`` look at a mesh: a z-buffer rasteriser on the GPU (K31,
+``csrc/mesh_raster.hip``) that draws per-vertex colours or a texture from a ``CameraInfo`` and
+returns what ``OcTree.render`` and ``OcTree.render_image`` return.  No counterpart in the reference.
 """
 
 import os
@@ -222,15 +226,17 @@ def save_obj(path: str, vertices, triangles, colors=None, normals=None) -> None:
         f.write("\n".join(lines) + "\n")
 
 
-def load_obj(path: str, texture_path: Optional[str] = None) -> Mesh:
+def load_obj(path: str, texture_path: Optional[str] = None, return_colors: bool = False):
     """Reads the ``v``, ``vt`` and ``f`` records of a Wavefront OBJ -> ``(vertices, triangles, uvs,
     texture)``.  A face corner is ``v``, ``v/vt``, ``v/vt/vn`` or ``v//vn``, 1-based or negative
     (counted back from the records read so far); polygons become triangle fans; every distinct
     ``(v, vt)`` pair becomes one vertex, in the order the faces first use them.  The texture is
     ``texture_path`` or else the ``map_Kd`` of the ``mtllib`` (read with PIL, row 0 at the top).
     A file with no ``vt``, or with no texture, gives a 1x1 white texture and zero UVs.  Normals,
-    vertex colours, groups and all but the first material are ignored."""
-    positions, coords, corners, library = [], [], [], None
+    groups and all but the first material are ignored, and so are vertex colours unless
+    ``return_colors`` is set: then a fifth value follows, (V,3) float32 per-vertex colours when
+    every ``v`` record reads ``v x y z r g b`` (what ``save_obj`` writes), ``None`` otherwise."""
+    positions, coords, corners, library, tints = [], [], [], None, []
 
     def resolve(text, count, what, number):
         index = int(text)
@@ -250,6 +256,8 @@ def load_obj(path: str, texture_path: Optional[str] = None) -> Mesh:
                     raise ValueError("load_obj: %s line %d: a vertex needs three coordinates"
                                      % (path, number))
                 positions.append([float(w) for w in words[1:4]])
+                if return_colors and len(words) >= 7:
+                    tints.append([float(w) for w in words[4:7]])
             elif words[0] == "vt":
                 values = [float(w) for w in words[1:3]]
                 coords.append((values + [0.0, 0.0])[:2])
@@ -290,4 +298,207 @@ def load_obj(path: str, texture_path: Optional[str] = None) -> Mesh:
             raise ValueError("load_obj: texture %s is not an RGB image" % texture_path)
     else:
         texture = np.full((1, 1, 3), 255, dtype=np.uint8)
-    return vertices, np.asarray(index, dtype=np.int32).reshape(-1, 3), uvs, texture
+    triangles = np.asarray(index, dtype=np.int32).reshape(-1, 3)
+    if not return_colors:
+        return vertices, triangles, uvs, texture
+    colors = None
+    if tints and len(tints) == len(positions):
+        colors = np.asarray(tints, dtype=np.float32)[order[:, 0]]
+    return vertices, triangles, uvs, texture, colors
+
+
+# ------------------------------------------------------------------------------------ K31
+def supersample_projection(camera, supersample: int = 1) -> np.ndarray:
+    """``cameras.projection_matrices([camera])[0]`` for an image of ``k`` times the width and
+    height whose ``k x k`` blocks are centred on the camera's own pixels: ``S @ P`` with ``S``
+    mapping ``u -> k u + (k - 1) / 2`` (and ``v`` likewise), formed in float64 and rounded once.
+    -> (3,4) float32; ``k = 1`` is the plain matrix, bit for bit."""
+    from .cameras import projection_matrices
+    k = int(supersample)
+    if k == 1:
+        return projection_matrices([camera])[0]
+    proj = np.eye(4, dtype=np.float64)
+    proj[:3, :3] = np.asarray(camera.intrinsics, np.float64)
+    proj = (proj @ np.linalg.inv(np.asarray(camera.extrinsics, np.float64)))[:3]
+    grow = np.array([[k, 0.0, 0.5 * (k - 1)], [0.0, k, 0.5 * (k - 1)], [0.0, 0.0, 1.0]])
+    return (grow @ proj).astype(np.float32)
+
+
+def supersample_reduce(color: torch.Tensor, alpha: torch.Tensor, depth: torch.Tensor, width: int,
+                       height: int, supersample: int):
+    """``(k H) x (k W)`` rows of colour, alpha and depth -> ``H x W`` rows: the mean of every
+    ``k x k`` block of colour and alpha, and the mean depth of the block's covered sub-pixels (0
+    when none is).  Plain torch, on whatever device the tensors lie."""
+    k = int(supersample)
+    blocks = (height, k, width, k)
+    color = color.reshape(blocks + (3,)).mean((1, 3)).reshape(-1, 3)
+    hits = alpha.reshape(blocks).sum((1, 3))
+    total = (depth * alpha).reshape(blocks).sum((1, 3))
+    depth = torch.where(hits > 0, total / hits.clamp(min=1), torch.zeros_like(total))
+    return color, (hits / float(k * k)).reshape(-1), depth.reshape(-1)
+
+
+def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, proj, eye, width: int,
+                   height: int, colors=None, uvs=None, texture=None, background=(0, 0, 0),
+                   batch_size: int = 1 << 22):
+    """K31 from set-up to resolve on GPU tensors: ``proj`` (3,4) and ``eye`` (3,) on the host,
+    ``texture`` with the row index growing with ``v`` -> ``(color, alpha, depth, ids, status,
+    box_pixels)``; ``status`` (F,) uint8 indexes ``ops.MESH_RASTER_STATUS``.  One read-back (the
+    number of box pixels); the box pixels are drawn ``batch_size`` at a time, and the image does
+    not depend on that size."""
+    width, height, batch_size = int(width), int(height), int(batch_size)
+    if not 1 <= batch_size <= ops.octree_max_points():
+        raise ValueError("rasterize_mesh: batch_size must lie in 1 .. %d, got %d"
+                         % (ops.octree_max_points(), batch_size))
+    record, status, counts = ops.mesh_raster_setup(vertices, triangles, proj, width, height)
+    offsets, total = ops.mesh_raster_offsets(counts)
+    zbuf = torch.full((width * height,), ops.MESH_RASTER_EMPTY, dtype=torch.int64,
+                      device=vertices.device)
+    for first in range(0, total, batch_size):
+        ops.mesh_raster_draw(record, offsets, first, min(batch_size, total - first), width, height,
+                             zbuf)
+    return ops.mesh_raster_resolve(zbuf, record, vertices, triangles, colors, uvs, texture, eye,
+                                   background, width, height) + (status, total)
+
+
+_warned_clipped = False
+
+
+def _render_mesh_check(who, vertices, triangles, camera, colors, uvs, texture, background,
+                       supersample, batch_size):
+    """The refusals of ``render_mesh`` and ``render_mesh_image``; none needs a device."""
+    shape = tuple(vertices.shape) if hasattr(vertices, "shape") else np.shape(vertices)
+    if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+        raise ValueError("%s: vertices must be (V,3) with V >= 1, got %s" % (who, shape))
+    ids = triangles.cpu().numpy() if torch.is_tensor(triangles) else triangles
+    _check_triangles(who, ids, shape[0])
+    if not hasattr(camera, "intrinsics") or not hasattr(camera, "extrinsics") \
+            or not hasattr(camera, "resolution"):
+        raise ValueError("%s: camera must be a CameraInfo, got %s" % (who, type(camera).__name__))
+    if colors is not None and (uvs is not None or texture is not None):
+        raise ValueError("%s: give either colors, or uvs and texture, not both" % who)
+    if colors is None and (uvs is None or texture is None):
+        raise ValueError("%s: give colors, or both uvs and texture" % who)
+    for name, value, last in (("colors", colors, 3), ("uvs", uvs, 2)):
+        if value is not None and tuple(value.shape if hasattr(value, "shape")
+                                       else np.shape(value)) != (shape[0], last):
+            raise ValueError("%s: %s must be (V,%d) = (%d,%d), got %s"
+                             % (who, name, last, shape[0], last, tuple(np.shape(value))))
+    if texture is not None:
+        tex = tuple(texture.shape) if hasattr(texture, "shape") else np.shape(texture)
+        if len(tex) != 3 or tex[2] < 3 or min(tex) < 1:
+            raise ValueError("%s: texture must be (H,W,C) with C >= 3, got %s" % (who, tex))
+    ground = np.asarray(background, dtype=np.float64).reshape(-1)
+    if ground.shape != (3,) or not np.isfinite(ground).all():
+        raise ValueError("%s: background must be three finite numbers, got %r"
+                         % (who, background))
+    k = int(supersample)
+    width, height = int(camera.resolution.width), int(camera.resolution.height)
+    if k != supersample or k < 1:
+        raise ValueError("%s: supersample must be an integer >= 1, got %r" % (who, supersample))
+    if not 1 <= k * width <= ops.MESH_RASTER_MAX_SIDE \
+            or not 1 <= k * height <= ops.MESH_RASTER_MAX_SIDE:
+        raise ValueError("%s: supersample times the camera's resolution must lie in 1 .. %d a "
+                         "side, got %d x (%d x %d)"
+                         % (who, ops.MESH_RASTER_MAX_SIDE, k, width, height))
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("%s: batch_size must be an integer >= 1, got %r" % (who, batch_size))
+    return k, width, height
+
+
+def render_mesh(vertices, triangles, camera, colors=None, uvs=None, texture=None,
+                background=(0, 0, 0), supersample: int = 1, batch_size: int = 1 << 22,
+                device=None, return_ids: bool = False):
+    """Draws a triangle mesh as ``camera`` (a ``CameraInfo``) sees it, with a z-buffer (K31,
+    ``csrc/mesh_raster.hip``) -> ``(RenderResult, report)``: ``color`` (H W,3), ``alpha`` (H W,) 1
+    where a triangle covers the pixel's centre and 0 elsewhere, ``depth`` (H W,) the distance of
+    the surface from the camera (the ``t`` of ``OcTree.render``; 0 where nothing is), rows in
+    pixel order ``py W + px``.  numpy in gives numpy out; tensors stay tensors.  With
+    ``return_ids`` -> ``(RenderResult, ids, report)``, ``ids`` (H W,) int32 the triangle drawn in
+    every pixel, -1 for none.
+
+    vertices (V,3), triangles (F,3) integers.  Exactly one of ``colors`` (V,3), interpolated
+    perspective-correctly, and ``uvs`` (V,2) + ``texture`` (h,w,C) uint8 with row 0 at the top (as
+    ``load_obj`` and ``procedural_torus`` return it; it is flipped as
+    ``OcTree.build_from_triangles`` flips it for K22, whose bilinear lookup is used).  Both sides
+    of a triangle are drawn; a pixel centre exactly on an edge is covered.
+
+    ``report``: how many triangles were ``drawn``, ``behind`` the camera, ``clipped``,
+    ``degenerate`` after snapping to 1/256 pixel or ``off_image``, and ``box_pixels``.  There is
+    NO near-plane clipping: a triangle with a vertex at or behind the camera plane, or one
+    projected beyond 16384 pixels from the origin, is ``clipped`` -- not drawn -- and a warning
+    says so once.
+
+    ``supersample=k`` draws ``k W x k H`` sub-pixels, ``k x k`` centred on every pixel, and
+    averages colour and alpha over them; the depth is the mean over the covered sub-pixels.
+    ``k = 1`` is the plain image.  ``batch_size``: box pixels per launch; the image does not
+    depend on it."""
+    global _warned_clipped
+    who = "render_mesh"
+    k, width, height = _render_mesh_check(who, vertices, triangles, camera, colors, uvs, texture,
+                                          background, supersample, batch_size)
+    if return_ids and k != 1:
+        raise ValueError("%s: return_ids needs supersample = 1, got %d" % (who, k))
+    from .cameras import eye_positions
+    from .utils import RenderResult
+    as_numpy = not torch.is_tensor(vertices)
+    if device is None:
+        device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+
+    def tensor(x, dtype):
+        if x is None:
+            return None
+        if torch.is_tensor(x):
+            return x.to(device=device, dtype=getattr(torch, dtype)).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(device)
+
+    if texture is not None:
+        texture = texture.flip(0) if torch.is_tensor(texture) else np.asarray(texture)[::-1]
+    color, alpha, depth, ids, status, total = rasterize_mesh(
+        tensor(vertices, "float32"), tensor(triangles, "int32"),
+        supersample_projection(camera, k), eye_positions([camera], (0.0, 0.0, 0.0))[0],
+        k * width, k * height, tensor(colors, "float32"), tensor(uvs, "float32"),
+        tensor(texture, "uint8"), background, batch_size)
+    if k > 1:
+        color, alpha, depth = supersample_reduce(color, alpha, depth, width, height, k)
+    tally = torch.bincount(status.to(torch.int64), minlength=len(ops.MESH_RASTER_STATUS))
+    report = dict(zip(ops.MESH_RASTER_STATUS, [int(v) for v in tally.cpu().tolist()]))
+    report["box_pixels"] = total
+    if report["clipped"] > 0 and not _warned_clipped:
+        _warned_clipped = True
+        import warnings
+        warnings.warn("render_mesh: %d of %d triangles reach the camera plane or leave the guard "
+                      "band and are not drawn (there is no near-plane clipping)"
+                      % (report["clipped"], len(status)))
+    out = RenderResult(color, alpha, depth)
+    if as_numpy:
+        out, ids = out.numpy(), ids.cpu().numpy()
+    return (out, ids, report) if return_ids else (out, report)
+
+
+def render_mesh_image(vertices, triangles, camera, colors=None, uvs=None, texture=None,
+                      background=(0, 0, 0), supersample: int = 1, batch_size: int = 1 << 22,
+                      device=None, include_depth: bool = False):
+    """``render_mesh`` as a frame -> (H,W,3) uint8 numpy (K8's bytes: ``color * 255`` truncated),
+    and with ``include_depth`` also the (H,W) float32 alpha and depth maps: the return shape of
+    ``OcTree.render_image``."""
+    _render_mesh_check("render_mesh_image", vertices, triangles, camera, colors, uvs, texture,
+                       background, supersample, batch_size)
+
+    def on_device(x):
+        if x is None or torch.is_tensor(x):
+            return x
+        return torch.from_numpy(np.ascontiguousarray(x))
+
+    out, _ = render_mesh(on_device(np.asarray(vertices, dtype=np.float32)
+                                   if not torch.is_tensor(vertices) else vertices),
+                         on_device(triangles), camera, on_device(colors), on_device(uvs),
+                         on_device(texture), background, supersample, batch_size, device)
+    width, height = int(camera.resolution.width), int(camera.resolution.height)
+    pixels = torch.arange(width * height, dtype=torch.int64, device=out.color.device)
+    image = ops.to_image(out.color.contiguous(), pixels, width, height).cpu().numpy()
+    if not include_depth:
+        return image
+    return (image, out.alpha.reshape(height, width).cpu().numpy(),
+            out.depth.reshape(height, width).cpu().numpy())

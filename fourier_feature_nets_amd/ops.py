@@ -2198,3 +2198,168 @@ def octree_mesh_faces(keys: torch.Tensor, masks: torch.Tensor, depth: int) -> to
           c_i64(count), c_i(int(depth)), c_i64(quads), _dev(triangles, torch.int32),
           _dev(missing, torch.int32))
     return triangles
+
+
+# --------------------------------------------------------------------------------- K31
+MESH_RASTER_MAX_SIDE = 16384
+MESH_RASTER_STATUS = ("drawn", "behind", "clipped", "degenerate", "off_image")
+MESH_RASTER_EMPTY = -1              # a z-buffer entry of all ones, as the int64 torch holds
+
+
+def _raster_want(who, name, t, dtype, shape):
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise ValueError("%s: %s must be a %s tensor, got %s"
+                         % (who, name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        raise ValueError("%s: %s must be (%s), got %s"
+                         % (who, name, ", ".join("*" if w is None else str(w) for w in shape),
+                            tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def _raster_check_image(who, width, height):
+    if not 1 <= width <= MESH_RASTER_MAX_SIDE or not 1 <= height <= MESH_RASTER_MAX_SIDE:
+        raise ValueError("%s: width and height must lie in 1 .. %d, got %d x %d"
+                         % (who, MESH_RASTER_MAX_SIDE, width, height))
+
+
+def _raster_check_mesh(who, vertices, triangles):
+    _raster_want(who, "vertices", vertices, torch.float32, (None, 3))
+    _raster_want(who, "triangles", triangles, torch.int32, (None, 3))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= vertices.shape[0] <= most:
+        raise ValueError("%s: vertices holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, vertices.shape[0]))
+    if not 1 <= triangles.shape[0] <= most:
+        raise ValueError("%s: triangles holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, triangles.shape[0]))
+
+
+def _raster_host(who, name, values, count):
+    arr = np.asarray(values, dtype=np.float32).reshape(-1)
+    if arr.shape != (count,) or not np.isfinite(arr).all():
+        raise ValueError("%s: %s must be %d finite numbers, got %r" % (who, name, count, values))
+    return (ctypes.c_float * count)(*arr.tolist())
+
+
+def mesh_raster_setup_check(vertices, triangles, proj, width: int, height: int):
+    """The refusals of ``mesh_raster_setup``, none of which needs a device -> ``proj`` as 12 host
+    floats.  Raises ``ValueError`` naming the argument."""
+    who = "mesh_raster_setup"
+    _raster_check_mesh(who, vertices, triangles)
+    _raster_check_image(who, width, height)
+    if np.shape(proj) != (3, 4):
+        raise ValueError("%s: proj must be (3, 4), got %s" % (who, np.shape(proj)))
+    return _raster_host(who, "proj", proj, 12)
+
+
+def mesh_raster_setup(vertices: torch.Tensor, triangles: torch.Tensor, proj, width: int,
+                      height: int):
+    """K31a.  vertices (V,3) f32, triangles (F,3) int32, ``proj`` (3,4) on the host (one matrix of
+    ``cameras.projection_matrices``) -> ``(record (F,16) int32, status (F,) uint8, counts (F,)
+    int64)``: the snapped vertices, ``w`` and pixel box of every triangle, its status (an index
+    into ``MESH_RASTER_STATUS``) and its number of box pixels, 0 unless it is drawn.  There is no
+    near-plane clipping: a triangle that crosses ``w = 0`` or leaves the guard band of 16384
+    pixels has the status ``clipped`` and is not drawn."""
+    width, height = int(width), int(height)
+    matrix = mesh_raster_setup_check(vertices, triangles, proj, width, height)
+    dev = vertices.device
+    num = triangles.shape[0]
+    record = torch.empty((num, 16), dtype=torch.int32, device=dev)
+    status = torch.empty((num,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((num,), dtype=torch.int64, device=dev)
+    _call("ffn_mesh_raster_setup", _dev(vertices, name="vertices"), c_i64(vertices.shape[0]),
+          _dev(triangles, torch.int32, "triangles"), c_i64(num), matrix, c_i(width), c_i(height),
+          _dev(record, torch.int32), _dev(status, torch.uint8), _dev(counts, torch.int64))
+    return record, status, counts
+
+
+def mesh_raster_offsets(counts: torch.Tensor):
+    """The exclusive int64 scan behind K31b -> (offsets (F+1,) int64 on the device, total; one
+    read-back).  Integer plumbing, as ``octree_mesh_candidate_offsets``."""
+    offsets = torch.zeros((counts.numel() + 1,), dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    return offsets, int(offsets[-1].item())
+
+
+def mesh_raster_draw_check(record, offsets, first: int, count: int, width: int, height: int,
+                           zbuf) -> None:
+    """The refusals of ``mesh_raster_draw`` that need no device."""
+    who = "mesh_raster_draw"
+    _raster_want(who, "record", record, torch.int32, (None, 16))
+    _raster_want(who, "offsets", offsets, torch.int64, (record.shape[0] + 1,))
+    _raster_check_image(who, width, height)
+    _raster_want(who, "zbuf", zbuf, torch.int64, (width * height,))
+    if record.shape[0] < 1:
+        raise ValueError("%s: record holds no triangle" % who)
+    if first < 0 or not 1 <= count <= octree_max_points():
+        raise ValueError("%s: first >= 0 and 1 <= count <= %d, got first %d, count %d"
+                         % (who, octree_max_points(), first, count))
+
+
+def mesh_raster_draw(record: torch.Tensor, offsets: torch.Tensor, first: int, count: int,
+                     width: int, height: int, zbuf: torch.Tensor) -> torch.Tensor:
+    """K31b on the box pixels ``first .. first + count - 1`` of the scan ``offsets``: every covered
+    one lowers ``zbuf`` (H W,) int64, ``MESH_RASTER_EMPTY`` where nothing was drawn, to
+    ``bits(depth_w) << 32 | triangle`` when that is less (as unsigned).  The caller keeps
+    ``first + count`` within the scan's total.  -> ``zbuf``."""
+    first, count, width, height = int(first), int(count), int(width), int(height)
+    mesh_raster_draw_check(record, offsets, first, count, width, height, zbuf)
+    _call("ffn_mesh_raster_draw", _dev(record, torch.int32, "record"),
+          _dev(offsets, torch.int64, "offsets"), c_i64(record.shape[0]), c_i64(first),
+          c_i64(count), c_i(width), c_i(height), _dev(zbuf, torch.int64, "zbuf"))
+    return zbuf
+
+
+def mesh_raster_resolve_check(zbuf, record, vertices, triangles, colors, uvs, texture, eye,
+                              background, width: int, height: int):
+    """The refusals of ``mesh_raster_resolve`` that need no device -> (eye, background) as host
+    floats.  Exactly one of ``colors`` and ``uvs`` + ``texture`` is given."""
+    who = "mesh_raster_resolve"
+    _raster_check_mesh(who, vertices, triangles)
+    _raster_check_image(who, width, height)
+    _raster_want(who, "record", record, torch.int32, (triangles.shape[0], 16))
+    _raster_want(who, "zbuf", zbuf, torch.int64, (width * height,))
+    if (colors is None) == (uvs is None and texture is None) or (uvs is None) != (texture is None):
+        raise ValueError("%s: give either colors, or uvs and texture" % who)
+    if colors is not None:
+        _raster_want(who, "colors", colors, torch.float32, (vertices.shape[0], 3))
+    else:
+        _raster_want(who, "uvs", uvs, torch.float32, (vertices.shape[0], 2))
+        _raster_want(who, "texture", texture, torch.uint8, (None, None, None))
+        tex_h, tex_w, channels = texture.shape
+        if (channels < 3 or not 1 <= tex_h <= MESH_MAX_TEXTURE_SIDE
+                or not 1 <= tex_w <= MESH_MAX_TEXTURE_SIDE or tex_h * tex_w * channels >= 2 ** 31):
+            raise ValueError("%s: texture must be (H, W, C) with C >= 3, 1 <= H, W <= 2^24 and "
+                             "fewer than 2^31 bytes, got %s" % (who, tuple(texture.shape)))
+    return _raster_host(who, "eye", eye, 3), _raster_host(who, "background", background, 3)
+
+
+def mesh_raster_resolve(zbuf: torch.Tensor, record: torch.Tensor, vertices: torch.Tensor,
+                        triangles: torch.Tensor, colors: Optional[torch.Tensor],
+                        uvs: Optional[torch.Tensor], texture: Optional[torch.Tensor], eye,
+                        background, width: int, height: int):
+    """K31c.  -> ``(color (H W,3), alpha (H W,), depth (H W,) float32, ids (H W,) int32)``: per
+    pixel the winning triangle's perspective-correct colour (``colors`` (V,3), or ``uvs`` (V,2)
+    through ``texture`` (h,w,C) uint8 with the row index growing with ``v``, K22's lookup), 1, the
+    distance of the surface point from ``eye`` and the triangle's number; ``background``, 0, 0 and
+    -1 where nothing was drawn."""
+    width, height = int(width), int(height)
+    eye_c, background_c = mesh_raster_resolve_check(zbuf, record, vertices, triangles, colors, uvs,
+                                                    texture, eye, background, width, height)
+    dev = vertices.device
+    n = width * height
+    color = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+    depth = torch.empty((n,), dtype=torch.float32, device=dev)
+    ids = torch.empty((n,), dtype=torch.int32, device=dev)
+    tex_h, tex_w, channels = (0, 0, 0) if texture is None else texture.shape
+    _call("ffn_mesh_raster_resolve", _dev(zbuf, torch.int64, "zbuf"),
+          _dev(record, torch.int32, "record"), _dev(vertices, name="vertices"),
+          c_i64(vertices.shape[0]), _dev(triangles, torch.int32, "triangles"),
+          c_i64(triangles.shape[0]), _dev(colors, name="colors"), _dev(uvs, name="uvs"),
+          _dev(texture, torch.uint8, "texture"), c_i(tex_h), c_i(tex_w), c_i(channels), eye_c,
+          background_c, c_i(width), c_i(height), _dev(color), _dev(alpha), _dev(depth),
+          _dev(ids, torch.int32))
+    return color, alpha, depth, ids

@@ -1586,6 +1586,68 @@ int ffn_octree_mesh_faces(const int64_t* keys, const uint8_t* masks, const uint8
                           const int* offsets, int64_t num_vertices, int depth, int64_t num_quads,
                           int32_t* triangles, int32_t* missing, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K31  a z-buffer rasteriser for triangle meshes (csrc/mesh_raster.hip).  No counterpart in the
+ * reference.  vertices (num_vertices,3) f32, triangles (num_triangles,3) i32 (an id is clamped into
+ * 0 .. num_vertices - 1 as in K22: a bad one reads a wrong vertex, not foreign memory), an image of
+ * width x height pixels, pixel (px, py) being the ray through the integer coordinates (px, py).
+ * Coverage is decided on integers; every float operation is one rounded f32 operation in the order
+ * written (no fma; / and sqrtf are IEEE operations): the same inputs give the same bits on every call
+ * and for any split into chunks.  There is NO near-plane clipping: a triangle that crosses w = 0 or
+ * leaves the guard band is not drawn, and its status says so.
+ * 1 <= width, height <= 16384; 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; bad shapes and
+ * null pointers are refused by name before any launch.
+ *
+ * K31a, one thread per triangle.  proj: 12 floats in HOST memory, the 3x4 row-major matrix of K23.
+ *   per vertex p: x = ((P00 p.x + P01 p.y) + P02 p.z) + P03, likewise y (row 1) and w (row 2);
+ *                 sx = x / w, sy = y / w
+ *   status[f]: 1 behind: all three w <= 0;  else 2 clipped: some !(w > 0) or some
+ *              !(fabsf(s) <= 16384.0f) (NaN and infinities fall here);  else
+ *              X = (int)rintf(sx * 256.0f), Y = (int)rintf(sy * 256.0f) (24.8 fixed point) and
+ *              A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) in int64: 3 degenerate when A == 0;  else the box
+ *              x0 = max(0, ceil(minX / 256)), x1 = min(width - 1, floor(maxX / 256)), likewise y
+ *              (integer floor division): 4 off-image when it is empty;  else 0 drawn.
+ *   counts[f] (int64) = (x1-x0+1)(y1-y0+1) when drawn, 0 otherwise.
+ *   record[f] = 16 int32, 16-byte aligned: X0 Y0 X1 Y1 X2 Y2, the bits of w0 w1 w2, x0 y0 x1 y1, three
+ *              zeros.  X and Y are 0 for status 1 and 2; the box is 0 0 -1 -1 unless drawn.
+ *
+ * K31b, one thread per box pixel s = first .. first + count - 1, 1 <= count <= ffn_octree_max_points().
+ * offsets (num_triangles + 1) int64: the exclusive scan of counts, made by the caller.
+ *   f: offsets[f] <= s < offsets[f + 1];  k = s - offsets[f];  bw = x1 - x0 + 1;
+ *   (px, py) = (x0 + k % bw, y0 + k / bw);  Q = (256 px, 256 py);  sgn = sign(A)
+ *   E_i = sgn [(X_k - X_j)(Q_y - Y_j) - (Y_k - Y_j)(Q_x - X_j)], (j, k) = (i+1, i+2) mod 3, in int64
+ *   covered iff E_0, E_1, E_2 >= 0: inclusive and two-sided, so a pixel centre on a shared edge
+ *   belongs to both triangles and there are no cracks
+ *   l_i = (float)E_i / (float)|A|;  q_i = l_i / w_i;  inv_w = (q0 + q1) + q2;  depth_w = 1.0f / inv_w
+ *   skipped unless depth_w is finite and > 0;  key = (uint64)bits(depth_w) << 32 | f
+ *   zbuf[py width + px] = min(itself, key), an unsigned 64-bit atomic behind a plain load that skips
+ *   it when the pixel already holds no more.  zbuf (height width) uint64, all ones where empty (the
+ *   caller fills it).  The minimum does not depend on the order: the nearest depth_w wins, the lower
+ *   triangle id among equal ones.  A pixel outside the image is never written, whatever the record.
+ *
+ * K31c, one thread per pixel.  Exactly one of vertex_colors (num_vertices,3) f32 and uvs
+ * (num_vertices,2) f32 + texture (tex_height, tex_width, tex_channels) u8 (K22's texture and limits,
+ * row index growing with v) is non-null.  eye, background: 3 floats each in HOST memory.
+ *   zbuf all ones: color = background, alpha = 0, depth = 0, ids = -1
+ *   else f = the low word; E_i, l_i, q_i, depth_w as in K31b (the same bits); b_i = q_i * depth_w
+ *   color = (c0 b0 + c1 b1) + c2 b2 per channel, or (u, v) interpolated the same way and looked up
+ *   as in ffn_mesh_sample (bilinear, / 255);  alpha = 1;  ids = f
+ *   p = (v0 b0 + v1 b1) + v2 b2 per component;  d = p - eye;
+ *   depth = sqrtf((d.x d.x + d.y d.y) + d.z d.z): the distance from the eye, OcTree.render's t
+ * color (height width, 3), alpha, depth (height width) f32, ids (height width) int32.  No atomics. */
+int ffn_mesh_raster_setup(const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                          int64_t num_triangles, const float* proj, int width, int height,
+                          int32_t* record, uint8_t* status, int64_t* counts, void* stream);
+int ffn_mesh_raster_draw(const int32_t* record, const int64_t* offsets, int64_t num_triangles,
+                         int64_t first, int64_t count, int width, int height, uint64_t* zbuf,
+                         void* stream);
+int ffn_mesh_raster_resolve(const uint64_t* zbuf, const int32_t* record, const float* vertices,
+                            int64_t num_vertices, const int32_t* triangles, int64_t num_triangles,
+                            const float* vertex_colors, const float* uvs, const uint8_t* texture,
+                            int tex_height, int tex_width, int tex_channels, const float* eye,
+                            const float* background, int width, int height, float* color,
+                            float* alpha, float* depth, int32_t* ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
