@@ -1286,14 +1286,16 @@ def octree_tv_check_eps(eps) -> float:
 
 
 def octree_tv(rows: torch.Tensor, plan: OctreeTVPlan, weights, eps: float,
-              d_rows: Optional[torch.Tensor] = None, accumulate: bool = False):
+              d_rows: Optional[torch.Tensor] = None, accumulate: bool = False,
+              want_grad: bool = True):
     """K20b + K20c.  rows (L, stride) float32, stride a multiple of 4; ``weights`` a (stride,) vector
     of per-column weights (``octree_tv_weights``), finite and >= 0; -> (value, d_rows): the
     Charbonnier energy ``(1/E) sum_e sum_c w_c (sqrt(d^2 + eps^2) - eps)`` over the plan's edges as a
     device scalar, and its gradient (L, stride), every row written (``accumulate``: added to the
     content of the ``d_rows`` passed in).  Deterministic, no float atomics, no host sync.  No
     geometric weight: every face counts the same whatever its area or the distance of the
-    centres."""
+    centres.  ``want_grad=False`` (and no ``d_rows``) computes the value alone: the entry point gets a
+    null ``d_rows``, skips the reduction and ``(value, None)`` comes back."""
     if not isinstance(plan, OctreeTVPlan):
         raise TypeError("octree tv: plan must be an OctreeTVPlan (ops.octree_tv_plan)")
     eps = octree_tv_check_eps(eps)
@@ -1313,12 +1315,14 @@ def octree_tv(rows: torch.Tensor, plan: OctreeTVPlan, weights, eps: float,
         raise ValueError("octree tv: rows must be 16-byte aligned")
     if accumulate and d_rows is None:
         raise ValueError("octree tv: accumulate needs the d_rows to add to")
-    if d_rows is None:
+    if not want_grad and d_rows is not None:
+        raise ValueError("octree tv: want_grad=False takes no d_rows")
+    if d_rows is None and want_grad:
         d_rows = torch.empty_like(rows)
-    if d_rows.shape != rows.shape:
+    if d_rows is not None and d_rows.shape != rows.shape:
         raise ValueError("octree tv: d_rows must be %s, got %s" % (tuple(rows.shape),
                                                                    tuple(d_rows.shape)))
-    if d_rows.data_ptr() % 16 != 0:
+    if d_rows is not None and d_rows.data_ptr() % 16 != 0:
         raise ValueError("octree tv: d_rows must be 16-byte aligned")
     value = torch.empty((), dtype=torch.float32, device=rows.device)
     workspace = plan.workspace(stride)
@@ -1548,6 +1552,33 @@ def octree_refine_check_action(action, num_leaves: int) -> None:
                          "the limit of 2^31" % (num_leaves, 8 * num_leaves))
 
 
+def _octree_refine_count(action_c: torch.Tensor):
+    """K21b's first launch on the actions in code order -> (flags, offsets, total): the scan of the
+    8 L slots and, as a device scalar, the new leaf count.  No read-back."""
+    num, dev = action_c.shape[0], action_c.device
+    flags, offsets, tiles = _scan_scratch(8 * num, dev)
+    total = torch.zeros((), dtype=torch.int32, device=dev)
+    _call("ffn_octree_refine_count", _dev(action_c, torch.uint8, "action"), c_i64(num),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
+          _dev(total, torch.int32))
+    return flags, offsets, total
+
+
+def _octree_refine_scatter(action_c, flags, offsets, ids_c, rows_c, with_rows: bool, channels: int,
+                           count: int):
+    """K21b's second launch for the ``count`` new leaves of ``_octree_refine_count``'s scan, all
+    arrays in code order -> (new_ids, new_rows or None, parent).  No read-back."""
+    num, dev = ids_c.shape[0], ids_c.device
+    new_ids = torch.empty((count,), dtype=torch.int64, device=dev)
+    parent = torch.empty((count,), dtype=torch.int32, device=dev)
+    new_rows = torch.empty((count, channels), dtype=torch.float32, device=dev) if with_rows else None
+    _call("ffn_octree_refine_scatter", _dev(action_c, torch.uint8, "action"),
+          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(ids_c, torch.int64, "leaf_ids"),
+          _dev(rows_c, name="rows"), c_i64(num), c_i(channels), c_i64(count),
+          _dev(new_ids, torch.int64), _dev(new_rows if channels else None), _dev(parent, torch.int32))
+    return new_ids, new_rows, parent
+
+
 def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: torch.Tensor,
                   depth: int):
     """K21b.  ``leaf_ids`` (L,) int64 sorted (a tree's ``leaf_index``), ``rows`` (L,C) float32 or
@@ -1580,13 +1611,9 @@ def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: 
     ids_c = leaf_ids[order].contiguous()
     action_c = action[order].contiguous()
     rows_c = None if rows is None or channels == 0 else rows[order].contiguous()
-    flags, offsets, tiles = _scan_scratch(8 * num, dev)
-    total = torch.zeros((), dtype=torch.int32, device=dev)
     # the scan runs before the action's values and the levels are judged, so that the new count and
     # what the refusals need come back in ONE read-back; a value above 2 sets no flag in the kernel
-    _call("ffn_octree_refine_count", _dev(action_c, torch.uint8, "action"), c_i64(num),
-          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(tiles, torch.int32),
-          _dev(total, torch.int32))
+    flags, offsets, total = _octree_refine_count(action_c)
     split = action == OCTREE_SPLIT
     stats = torch.stack([total.to(torch.int64), action.max().to(torch.int64), levels.max(),
                          torch.where(split, levels, -1).max(),
@@ -1604,14 +1631,8 @@ def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: 
                          % (top_split, limit))
     if count < 1:
         raise ValueError("octree refine: the action leaves no leaf; a tree needs at least one")
-    new_ids = torch.empty((count,), dtype=torch.int64, device=dev)
-    parent = torch.empty((count,), dtype=torch.int32, device=dev)
-    new_rows = None if rows is None else torch.empty((count, channels), dtype=torch.float32,
-                                                     device=dev)
-    _call("ffn_octree_refine_scatter", _dev(action_c, torch.uint8, "action"),
-          _dev(flags, torch.uint8), _dev(offsets, torch.int32), _dev(ids_c, torch.int64, "leaf_ids"),
-          _dev(rows_c, name="rows"), c_i64(num), c_i(channels), c_i64(count),
-          _dev(new_ids, torch.int64), _dev(new_rows if channels else None), _dev(parent, torch.int32))
+    new_ids, new_rows, parent = _octree_refine_scatter(action_c, flags, offsets, ids_c, rows_c,
+                                                       rows is not None, channels, count)
     new_depth = max(top_kept, top_split + 1) + 1
     node_ids = octree_interior_nodes(new_ids, new_depth)      # wants code order
     new_ids, back = torch.sort(new_ids)                       # code order -> id order
@@ -1689,6 +1710,12 @@ def mesh_sample(vertices: torch.Tensor, triangles: torch.Tensor, uvs: torch.Tens
     triangle is the Basu-Owen point ``k + 1``; the same inputs give the same bits.  Bad input is a
     ``ValueError`` (``mesh_sample_check``: the ids, the UVs and the offsets are read back once)."""
     n = mesh_sample_check(vertices, triangles, uvs, offsets, texture)
+    return _mesh_sample_launch(vertices, triangles, uvs, offsets, texture, n, want_uvs)
+
+
+def _mesh_sample_launch(vertices, triangles, uvs, offsets, texture, n: int, want_uvs: bool):
+    """The launch of ``mesh_sample`` for ``n = offsets[F]`` samples of checked arguments: the
+    outputs and the call, no read-back."""
     dev = vertices.device
     positions = torch.empty((n, 3), dtype=torch.float32, device=dev)
     colors = torch.empty((n, 3), dtype=torch.float32, device=dev)
