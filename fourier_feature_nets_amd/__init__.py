@@ -17,8 +17,9 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import (load_obj, normalize_points, procedural_torus, render_mesh, render_mesh_image,
-                   sample_mesh, save_obj, triangle_counts)
+from .mesh import (color_mesh_from_images, fit_mesh_colors, load_obj, normalize_points,
+                   procedural_torus, render_mesh, render_mesh_backward, render_mesh_image,
+                   sample_mesh, save_obj, triangle_counts, vertex_adjacency)
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -44,7 +45,7 @@ __version__ = "0.1.0"
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
-           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights",
-           "exponential_lr_decay", "eye_positions", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights", "color_mesh_from_images",
+           "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
            "linspace", "load_model", "load_obj", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_image", "sample_mesh", "save_obj", "triangle_counts"]
+           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_image", "sample_mesh", "save_obj", "triangle_counts", "vertex_adjacency"]

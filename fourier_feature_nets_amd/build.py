@@ -62,6 +62,8 @@ SOURCES = {
     # K23's projection, the perspective-correct weights and the interpolation of colours, UVs and
     # positions, every product, sum and quotient rounded on its own
     "mesh_raster.hip": ["-ffp-contract=off"],
+    # K31c's b_i = q_i * depth_w and the sums of b_i * g over pixels, every product and add rounded
+    "mesh_raster_grad.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -21,6 +21,11 @@ writes what ``OcTree.extract_mesh`` (K30) returns, with per-vertex colours and n
 ``render_mesh`` and ``render_mesh_image`` look at a mesh: a z-buffer rasteriser on the GPU (K31,
 ``csrc/mesh_raster.hip``) that draws per-vertex colours or a texture from a ``CameraInfo`` and
 returns what ``OcTree.render`` and ``OcTree.render_image`` return.  No counterpart in the reference.
+
+``render_mesh_backward`` is the transpose of that picture in the per-vertex colours (K32,
+``csrc/mesh_raster_grad.hip``); ``color_mesh_from_images`` uses it to give every vertex the mean
+colour of the pixels that see it, ``fit_mesh_colors`` to optimise the colours against a dataset's
+images, and ``vertex_adjacency`` makes the corner lists both need.  No counterpart either.
 """
 
 import os
@@ -346,6 +351,13 @@ def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, proj, eye, w
     box_pixels)``; ``status`` (F,) uint8 indexes ``ops.MESH_RASTER_STATUS``.  One read-back (the
     number of box pixels); the box pixels are drawn ``batch_size`` at a time, and the image does
     not depend on that size."""
+    return _rasterize(vertices, triangles, proj, eye, width, height, colors, uvs, texture,
+                      background, batch_size)[1:]
+
+
+def _rasterize(vertices, triangles, proj, eye, width, height, colors=None, uvs=None, texture=None,
+               background=(0, 0, 0), batch_size=1 << 22):
+    """``rasterize_mesh`` with K31a's ``record`` in front of its results (K32a reads it)."""
     width, height, batch_size = int(width), int(height), int(batch_size)
     if not 1 <= batch_size <= ops.octree_max_points():
         raise ValueError("rasterize_mesh: batch_size must lie in 1 .. %d, got %d"
@@ -357,8 +369,9 @@ def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, proj, eye, w
     for first in range(0, total, batch_size):
         ops.mesh_raster_draw(record, offsets, first, min(batch_size, total - first), width, height,
                              zbuf)
-    return ops.mesh_raster_resolve(zbuf, record, vertices, triangles, colors, uvs, texture, eye,
-                                   background, width, height) + (status, total)
+    return (record,) + ops.mesh_raster_resolve(zbuf, record, vertices, triangles, colors, uvs,
+                                               texture, eye, background, width, height) \
+        + (status, total)
 
 
 _warned_clipped = False
@@ -502,3 +515,372 @@ def render_mesh_image(vertices, triangles, camera, colors=None, uvs=None, textur
         return image
     return (image, out.alpha.reshape(height, width).cpu().numpy(),
             out.depth.reshape(height, width).cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------ K32
+# ops.clip_adam's defaults, as fit_octree has them
+CLIP_VALUE = 0.1
+MAX_NORM = 0.1
+_MOST = (2 ** 31 - 1) // 3
+
+
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _on(x, dtype, device):
+    if torch.is_tensor(x):
+        return x.to(device=device, dtype=getattr(torch, dtype)).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(device)
+
+
+def vertex_adjacency(triangles, num_vertices: int, device=None):
+    """Which corners use every vertex -> ``(corner_order (3F,) int32, vertex_starts (V+1,) int32)``
+    tensors on ``device`` (default: the tensor's own, or the GPU for a numpy array):
+    ``corner_order`` holds the flat corner indices ``3 f + i`` stably sorted by vertex id -- the
+    corners of one vertex in the order of the faces -- and ``vertex_starts`` the CSR rows, so that
+    vertex ``v`` owns ``corner_order[vertex_starts[v] : vertex_starts[v + 1]]``.  The ids are
+    clamped into ``0 .. V - 1`` as K31 clamps them.  A torch stable sort and a bincount: integer
+    plumbing, as the key sort of ``OcTree.extract_mesh``; it depends on the triangles alone and
+    can be made once for many calls of ``render_mesh_backward``."""
+    who = "vertex_adjacency"
+    shape = _shape_of(triangles)
+    if torch.is_tensor(triangles):
+        integer = not (triangles.dtype.is_floating_point or triangles.dtype.is_complex
+                       or triangles.dtype == torch.bool)
+    else:
+        integer = np.issubdtype(np.asarray(triangles).dtype, np.integer)
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= _MOST or not integer:
+        raise ValueError("%s: triangles must be an integer (F,3) array with 1 <= F <= "
+                         "(2^31 - 1) / 3, got %s" % (who, shape))
+    if int(num_vertices) != num_vertices or not 1 <= int(num_vertices) <= _MOST:
+        raise ValueError("%s: num_vertices must be an integer in 1 .. (2^31 - 1) / 3, got %r"
+                         % (who, num_vertices))
+    num_vertices = int(num_vertices)
+    if device is None:
+        device = triangles.device if torch.is_tensor(triangles) else "cuda"
+    flat = _on(triangles, "int64", torch.device(device)).reshape(-1).clamp(0, num_vertices - 1)
+    order = torch.sort(flat, stable=True)[1].to(torch.int32).contiguous()
+    starts = torch.zeros((num_vertices + 1,), dtype=torch.int64, device=flat.device)
+    torch.cumsum(torch.bincount(flat, minlength=num_vertices), 0, out=starts[1:])
+    return order, starts.to(torch.int32)
+
+
+def _mesh_colors_check(who, vertices, colors=None, uvs=None, texture=None,
+                       supersample=1, batch_size=1):
+    """What every K32 function refuses of its mesh from shapes and types alone -> V.  The vertex
+    ids themselves are looked at last (``_mesh_ids_check``): for a tensor on the GPU that is a
+    read-back, and every refusal that needs none comes before it."""
+    shape = _shape_of(vertices)
+    if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+        raise ValueError("%s: vertices must be (V,3) with V >= 1, got %s" % (who, shape))
+    if uvs is not None or texture is not None:
+        raise ValueError("%s: uvs and texture are not supported: the textured path of render_mesh "
+                         "has no backward, only per-vertex colors have" % who)
+    if colors is not None:
+        if _shape_of(colors) != (shape[0], 3):
+            raise ValueError("%s: colors must be (V,3) = (%d,3), got %s"
+                             % (who, shape[0], _shape_of(colors)))
+        kind = colors.dtype
+        floating = kind.is_floating_point if torch.is_tensor(colors) \
+            else np.issubdtype(np.asarray(colors).dtype, np.floating)
+        if not floating:
+            raise ValueError("%s: colors must be floating point, got %s" % (who, kind))
+    if supersample != 1:
+        raise ValueError("%s: supersample must be 1 (the backward of the k x k mean is not "
+                         "built), got %r" % (who, supersample))
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("%s: batch_size must be an integer >= 1, got %r" % (who, batch_size))
+    return shape[0]
+
+
+def _mesh_ids_check(who, triangles, num_vertices):
+    """The shape, type and range of the vertex ids, as ``render_mesh`` checks them: the last of a
+    function's refusals."""
+    _check_triangles(who, triangles.cpu().numpy() if torch.is_tensor(triangles) else triangles,
+                     num_vertices)
+
+
+def _camera_size(who, camera):
+    if not hasattr(camera, "intrinsics") or not hasattr(camera, "extrinsics") \
+            or not hasattr(camera, "resolution"):
+        raise ValueError("%s: camera must be a CameraInfo, got %s" % (who, type(camera).__name__))
+    width, height = int(camera.resolution.width), int(camera.resolution.height)
+    if not 1 <= width <= ops.MESH_RASTER_MAX_SIDE or not 1 <= height <= ops.MESH_RASTER_MAX_SIDE:
+        raise ValueError("%s: the camera's resolution must lie in 1 .. %d a side, got %d x %d"
+                         % (who, ops.MESH_RASTER_MAX_SIDE, width, height))
+    return width, height
+
+
+def _alpha_byte(who, alpha_threshold):
+    """K24's threshold byte: ``ceil(alpha_threshold * 255)`` clamped into 1 .. 255."""
+    alpha_threshold = float(alpha_threshold)
+    if not 0.0 <= alpha_threshold <= 1.0:        # NaN fails too
+        raise ValueError("%s: alpha_threshold must lie in [0, 1], got %r" % (who, alpha_threshold))
+    return min(max(int(np.ceil(alpha_threshold * 255)), 1), 255)
+
+
+def _mesh_dataset_check(who, name, dataset):
+    """``dataset.images`` (C,H,W,3 or 4) uint8 and ``dataset.cameras`` of that one resolution, RGB
+    -> (images, cameras, width, height).  No device."""
+    images = np.asarray(getattr(dataset, "images", None))
+    if images.ndim != 4 or images.shape[-1] not in (3, 4) or images.dtype != np.uint8:
+        raise ValueError("%s: %s.images must be (C,H,W,3) or (C,H,W,4) uint8, got %s %s"
+                         % (who, name, images.dtype, images.shape))
+    if getattr(dataset, "color_space", "RGB") != "RGB":
+        raise ValueError("%s: %s.color_space must be RGB, got %r"
+                         % (who, name, dataset.color_space))
+    cameras = list(dataset.cameras)
+    if len(cameras) != len(images) or not cameras:
+        raise ValueError("%s: %s has %d cameras for %d images"
+                         % (who, name, len(cameras), len(images)))
+    height, width = images.shape[1:3]
+    for camera in cameras:
+        if _camera_size(who, camera) != (width, height):
+            raise ValueError("%s: a camera of %s is %d x %d, its image %d x %d"
+                             % ((who, name) + _camera_size(who, camera) + (width, height)))
+    return images, cameras, width, height
+
+
+def _raster_ids(vertices, triangles, proj, width, height, batch_size):
+    """K31a-c for the ids alone -> (record, ids).  The resolve needs some colours and an eye: the
+    vertices and the origin serve, the image they make is dropped."""
+    out = _rasterize(vertices, triangles, proj, (0.0, 0.0, 0.0), width, height, vertices,
+                     batch_size=batch_size)
+    return out[0], out[4]
+
+
+def render_mesh_backward(vertices, triangles, camera, d_color, adjacency=None, grad=None,
+                         weight=None, accumulate: bool = False, batch_size: int = 1 << 22,
+                         supersample: int = 1, uvs=None, texture=None):
+    """The transpose of ``render_mesh``'s colours in the per-vertex ``colors`` (K32,
+    ``csrc/mesh_raster_grad.hip``) -> ``(grad (V,3), weight (V,))`` float32: with ``d_color``
+    (H W,3) the gradient of a loss in the image's colours, ``grad`` is its gradient in the vertex
+    colours, ``grad[v] = sum b_i d_color[p]`` over the pixels ``p`` won by a triangle with ``v``
+    as its corner ``i``, and ``weight[v] = sum b_i`` over the same pixels; ``b_i`` are K31's
+    perspective-correct barycentric weights, the bits the forward used.  It runs K31a-c for the
+    camera (the ids of the z-buffer decide which triangle owns a pixel: occlusion is the mesh's
+    own), then K32a and K32b: fixed orders, no float atomics, the same bits on every call and for
+    every ``batch_size``.  The background has no gradient here; positions get none.
+
+    numpy in gives numpy out; tensors stay tensors.  ``adjacency``: what ``vertex_adjacency``
+    returns for these triangles (made here when None).  ``grad`` and ``weight`` (GPU tensors) are
+    written in place when given, and added to with ``accumulate``.  ``supersample`` must be 1 and
+    ``uvs`` / ``texture`` None: the mean over sub-pixels and the textured path have no
+    backward."""
+    who = "render_mesh_backward"
+    num_vertices = _mesh_colors_check(who, vertices, None, uvs, texture, supersample,
+                                      batch_size)
+    width, height = _camera_size(who, camera)
+    if _shape_of(d_color) != (width * height, 3):
+        raise ValueError("%s: d_color must be (H W,3) = (%d,3), got %s"
+                         % (who, width * height, _shape_of(d_color)))
+    if (grad is None) != (weight is None) or (accumulate and grad is None):
+        raise ValueError("%s: give both grad and weight, or neither; accumulate needs them" % who)
+    _mesh_ids_check(who, triangles, num_vertices)
+    as_numpy = not torch.is_tensor(vertices)
+    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    if adjacency is None:
+        adjacency = vertex_adjacency(triangles, num_vertices, device)
+    record, ids = _raster_ids(vertices, triangles, supersample_projection(camera, 1), width,
+                              height, batch_size)
+    face_sums = ops.mesh_raster_face_sums(record, ids, _on(d_color, "float32", device), width,
+                                          height)
+    grad, weight = ops.mesh_vertex_gather(face_sums, adjacency[0], adjacency[1], grad, weight,
+                                          accumulate)
+    if as_numpy:
+        return grad.cpu().numpy(), weight.cpu().numpy()
+    return grad, weight
+
+
+def _mean_vertex_colors(sums: np.ndarray, weights: np.ndarray, colors: np.ndarray):
+    """``sums / weights`` (float32, one division per channel) where ``weights > 0``, ``colors``
+    elsewhere -> (colors (V,3) float32, weights)."""
+    out = np.array(colors, dtype=np.float32, copy=True)
+    seen = weights > 0
+    out[seen] = sums[seen].astype(np.float32) / weights[seen].astype(np.float32)[:, None]
+    return out, weights
+
+
+def color_mesh_from_images(vertices, triangles, dataset, colors=None,
+                           alpha_threshold: float = 0.5):
+    """Gives every vertex the mean colour of the pixels that see it -> ``(colors (V,3), weights
+    (V,))`` float32 (numpy in gives numpy out; tensors stay tensors).  Over the cameras of
+    ``dataset`` (an ``ImageDataset``: ``images`` (C,H,W,4) uint8 and ``cameras``) in order, K32
+    accumulates ``sum b_i rgb[p] / 255`` and ``sum b_i`` per vertex; a pixel whose own alpha byte
+    is below ``ceil(alpha_threshold * 255)`` (clamped into 1 .. 255, as
+    ``OcTree.color_from_images`` clamps it) is left out of both sums.  A vertex with
+    ``weight > 0`` gets ``sum / weight``, one f32 division per channel; any other keeps
+    ``colors[v]``, or 0.5 grey when ``colors`` is None.  What K24 does for the leaves of a tree.
+
+    The limits: the weights are the perspective-correct barycentric weights of the pixels, not
+    areas, so a camera that sees a triangle large counts for more; a vertex seen only at grazing
+    angles still counts, with whatever those few pixels hold; visibility is the mesh's own
+    z-buffer, so a hole in the mesh lets the far side be coloured from the front."""
+    who = "color_mesh_from_images"
+    num_vertices = _mesh_colors_check(who, vertices, colors)
+    alpha_u8 = _alpha_byte(who, alpha_threshold)
+    images, cameras, width, height = _mesh_dataset_check(who, "dataset", dataset)
+    _mesh_ids_check(who, triangles, num_vertices)
+    as_numpy = not torch.is_tensor(vertices)
+    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    order, starts = vertex_adjacency(triangles, num_vertices, device)
+    total = torch.zeros((num_vertices, 3), dtype=torch.float32, device=device)
+    weights = torch.zeros((num_vertices,), dtype=torch.float32, device=device)
+    for number, camera in enumerate(cameras):
+        record, ids = _raster_ids(vertices, triangles, supersample_projection(camera, 1), width,
+                                  height, 1 << 22)
+        frame = images[number]
+        if frame.shape[-1] == 4:
+            hidden = torch.from_numpy(frame[..., 3].reshape(-1) < alpha_u8).to(device)
+            ids = ids.masked_fill(hidden, -1)
+        rgb = (frame[..., :3].astype(np.float32) / 255).reshape(-1, 3)      # as ImageDataset
+        face_sums = ops.mesh_raster_face_sums(record, ids, torch.from_numpy(rgb).to(device),
+                                              width, height)
+        ops.mesh_vertex_gather(face_sums, order, starts, total, weights, accumulate=number > 0)
+    # (the division on the host: one IEEE f32 division per channel, whatever the device's is)
+    base = np.full((num_vertices, 3), 0.5, dtype=np.float32) if colors is None else \
+        np.array(colors.detach().cpu().numpy() if torch.is_tensor(colors) else colors,
+                 dtype=np.float32)
+    out, weights_host = _mean_vertex_colors(total.cpu().numpy(), weights.cpu().numpy(), base)
+    if as_numpy:
+        return out, weights_host
+    return torch.from_numpy(out).to(device), weights
+
+
+def _mesh_psnr(vertices, triangles, data, dataset, cameras, width, height) -> float:
+    """-10 log10 of the mean colour-MSE over every pixel of the dataset's cameras."""
+    from .cameras import eye_positions
+    per = width * height
+    device = vertices.device
+    alphas = dataset._gt_alphas()
+    total = torch.zeros((2,), dtype=torch.float32, device=device)
+    pixels = torch.arange(per, dtype=torch.int64, device=device)
+    eyes = eye_positions(cameras, (0.0, 0.0, 0.0))
+    for number, camera in enumerate(cameras):
+        color, alpha = rasterize_mesh(vertices, triangles, supersample_projection(camera, 1),
+                                      eyes[number], width, height, data)[:2]
+        sums, _, _ = ops.mse_loss(color, alpha, dataset.colors, alphas, pixels + number * per,
+                                  0.0, 0.0, want_grad=False)
+        total += sums
+    mean = float(total.cpu().numpy().astype(np.float64)[0]) / (3 * per * len(cameras))
+    return float(-10.0 * np.log10(max(mean, 1e-12)))
+
+
+def fit_mesh_colors(vertices, triangles, colors, train_dataset, val_dataset=None,
+                    num_steps: int = 500, learning_rate: float = 1e-2, cameras_per_step: int = 1,
+                    report_interval: int = 100, alpha_threshold=None,
+                    clip_value: float = CLIP_VALUE, max_norm: float = MAX_NORM,
+                    seed: int = 20080524, verbose: bool = True):
+    """Optimises the per-vertex ``colors`` (V,3) of a mesh against the images of ``train_dataset``
+    (an ``ImageDataset``) through ``render_mesh`` with a black background -> ``(colors, log)``;
+    the geometry is not changed.  numpy in gives numpy out; tensors stay tensors, and the given
+    ``colors`` are not modified.  The loop is ``fit_octree``'s on a (V,3) buffer, with whole
+    cameras for batches: a seeded permutation of the cameras is dealt ``cameras_per_step`` at a
+    time, and one step is, for each of its cameras, the K31 frame, K6 (``ops.mse_loss``) on that
+    camera's pixels with ``color_scale = 1 / (3 count)`` (``count`` the pixels of the step) and
+    no alpha term, the optional alpha mask, and K32 accumulated over the step's cameras; then K7
+    (``ops.clip_adam`` with ``clip_value`` / ``max_norm``, defaults those of ``fit_octree``) and
+    ``clamp_(0, 1)``.  With ``alpha_threshold`` the gradient of a pixel whose own alpha byte is
+    below ``ceil(alpha_threshold * 255)`` (clamped into 1 .. 255) is set to zero; None, the
+    default, masks nothing.  The dataset's colours count as black where its alpha is 0, as in
+    every fit here.
+
+    The log holds ``FitLogEntry(step, loss, val_psnr)``: every step's training loss (the mean
+    squared colour error of the step's pixels), ``val_psnr`` over all pixels of ``val_dataset``'s
+    cameras at steps below 10 and multiples of ``report_interval``, else NaN; report steps are
+    printed as ``fit_octree`` prints them.  The only host synchronisation of a step is the
+    read-back inside ``ops.mesh_raster_offsets`` (one per camera), as K17b has one; the losses are
+    fetched at the end.  ``learning_rate`` has NO tuned default: 1e-2 is ``fit_octree``'s."""
+    who = "fit_mesh_colors"
+    num_vertices = _mesh_colors_check(who, vertices, colors)
+    if colors is None:
+        raise ValueError("%s: colors must be (V,3), got None (color_mesh_from_images makes a "
+                         "start)" % who)
+    num_steps, cameras_per_step = int(num_steps), int(cameras_per_step)
+    if num_steps < 0 or cameras_per_step < 1 or int(report_interval) < 1:
+        raise ValueError("%s: num_steps >= 0, cameras_per_step >= 1, report_interval >= 1" % who)
+    if not learning_rate > 0:
+        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
+    alpha_u8 = None if alpha_threshold is None else _alpha_byte(who, alpha_threshold)
+    images, cameras, width, height = _mesh_dataset_check(who, "train_dataset", train_dataset)
+    if alpha_u8 is not None and images.shape[-1] != 4:
+        raise ValueError("%s: alpha_threshold needs train_dataset.images with an alpha channel, "
+                         "got %s" % (who, images.shape))
+    if val_dataset is not None:
+        _, val_cameras, val_width, val_height = _mesh_dataset_check(who, "val_dataset",
+                                                                    val_dataset)
+    _mesh_ids_check(who, triangles, num_vertices)
+    from .cameras import eye_positions
+    from .octree_fit import FitLogEntry
+    import time
+
+    as_numpy = not torch.is_tensor(vertices)
+    device = train_dataset.colors.device
+    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    data = _on(colors, "float32", device).clone()
+    flat = data.view(-1)
+    grads = torch.empty_like(data)
+    weight = torch.empty((num_vertices,), dtype=torch.float32, device=device)
+    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
+    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=device)
+    order, starts = vertex_adjacency(triangles, num_vertices, device)
+    projections = [supersample_projection(camera, 1) for camera in cameras]
+    eyes = eye_positions(cameras, (0.0, 0.0, 0.0))
+    per = width * height
+    pixels = torch.arange(per, dtype=torch.int64, device=device)
+    alphas = train_dataset._gt_alphas()
+    kept = {}
+    generator = torch.Generator()
+    generator.manual_seed(int(seed))
+    losses, reports = [], {}
+    start_time = time.time()
+    step = 0
+    while step < num_steps:
+        deal = torch.randperm(len(cameras), generator=generator).tolist()
+        for start in range(0, len(deal), cameras_per_step):
+            if step >= num_steps:
+                break
+            chosen = deal[start:start + cameras_per_step]
+            count = len(chosen) * per
+            total = None
+            for number, camera in enumerate(chosen):
+                record, color, alpha, _, ids, _, _ = _rasterize(
+                    vertices, triangles, projections[camera], eyes[camera], width, height, data)
+                sums, d_color, _ = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
+                                                pixels + camera * per, 1.0 / (3 * count), 0.0)
+                if alpha_u8 is not None:
+                    if camera not in kept:
+                        kept[camera] = torch.from_numpy(
+                            images[camera][..., 3].reshape(-1, 1) >= alpha_u8).to(device)
+                    d_color = torch.where(kept[camera], d_color, torch.zeros_like(d_color))
+                face_sums = ops.mesh_raster_face_sums(record, ids, d_color, width, height)
+                ops.mesh_vertex_gather(face_sums, order, starts, grads, weight,
+                                       accumulate=number > 0)
+                total = sums if total is None else total + sums
+            losses.append(ops.loss_value(total, count, 0.0))
+            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
+                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
+            data.clamp_(0, 1)
+            if val_dataset is not None and (step < 10 or step % report_interval == 0):
+                reports[step] = _mesh_psnr(vertices, triangles, data, val_dataset, val_cameras,
+                                           val_width, val_height)
+                if verbose:
+                    now = time.time()
+                    per_step = (now - start_time) / step if step >= report_interval else 0
+                    eta = "N/A" if not per_step else time.strftime(
+                        "%a, %d %b %Y %H:%M:%S +0000",
+                        time.gmtime(now + (num_steps - step) * per_step))
+                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
+                          "loss: {:2f}".format(float(losses[-1].item())),
+                          "val_psnr: {:2f}".format(reports[step]),
+                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
+            step += 1
+    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
+    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
+           for k in range(len(values))]
+    return (data.cpu().numpy() if as_numpy else data), log

@@ -2390,3 +2390,77 @@ def mesh_raster_resolve(zbuf: torch.Tensor, record: torch.Tensor, vertices: torc
           background_c, c_i(width), c_i(height), _dev(color), _dev(alpha), _dev(depth),
           _dev(ids, torch.int32))
     return color, alpha, depth, ids
+
+
+# --------------------------------------------------------------------------------- K32
+def mesh_raster_face_sums_check(record, ids, d_color, width: int, height: int) -> None:
+    """The refusals of ``mesh_raster_face_sums`` that need no device."""
+    who = "mesh_raster_face_sums"
+    _raster_want(who, "record", record, torch.int32, (None, 16))
+    _raster_check_image(who, width, height)
+    _raster_want(who, "ids", ids, torch.int32, (width * height,))
+    _raster_want(who, "d_color", d_color, torch.float32, (width * height, 3))
+    if not 1 <= record.shape[0] <= (2 ** 31 - 1) // 3:
+        raise ValueError("%s: record holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, record.shape[0]))
+
+
+def mesh_raster_face_sums(record: torch.Tensor, ids: torch.Tensor, d_color: torch.Tensor,
+                          width: int, height: int) -> torch.Tensor:
+    """K32a.  record (F,16) int32 of K31a, ids (H W,) int32 of K31c, d_color (H W,3) f32 ->
+    ``face_sums`` (F,12) f32: per triangle, over the pixels ``ids`` gives it, the sums of
+    ``b_i * d_color[p][j]`` (columns ``3 i + j``) and of ``b_i`` (columns ``9 + i``), ``b_i`` the
+    barycentric weights of K31c; one wavefront per triangle, a fixed order, no atomics.  A pixel
+    whose id is another triangle's (or -1) is not read: a NaN there reaches nothing."""
+    width, height = int(width), int(height)
+    mesh_raster_face_sums_check(record, ids, d_color, width, height)
+    face_sums = torch.empty((record.shape[0], 12), dtype=torch.float32, device=record.device)
+    _call("ffn_mesh_raster_face_sums", _dev(record, torch.int32, "record"),
+          _dev(ids, torch.int32, "ids"), _dev(d_color, name="d_color"), c_i64(record.shape[0]),
+          c_i(width), c_i(height), _dev(face_sums))
+    return face_sums
+
+
+def mesh_vertex_gather_check(face_sums, corner_order, vertex_starts, grad=None, weight=None,
+                             accumulate: bool = False) -> int:
+    """The refusals of ``mesh_vertex_gather`` that need no device -> the number of vertices."""
+    who = "mesh_vertex_gather"
+    _raster_want(who, "face_sums", face_sums, torch.float32, (None, 12))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= face_sums.shape[0] <= most:
+        raise ValueError("%s: face_sums holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, face_sums.shape[0]))
+    _raster_want(who, "corner_order", corner_order, torch.int32, (3 * face_sums.shape[0],))
+    _raster_want(who, "vertex_starts", vertex_starts, torch.int32, (None,))
+    num_vertices = vertex_starts.shape[0] - 1
+    if not 1 <= num_vertices <= most:
+        raise ValueError("%s: vertex_starts must be (V + 1,) with 1 <= V <= (2^31 - 1) / 3, got "
+                         "%s" % (who, tuple(vertex_starts.shape)))
+    if (grad is None) != (weight is None):
+        raise ValueError("%s: give both grad and weight, or neither" % who)
+    if accumulate and grad is None:
+        raise ValueError("%s: accumulate needs grad and weight to add to" % who)
+    if grad is not None:
+        _raster_want(who, "grad", grad, torch.float32, (num_vertices, 3))
+        _raster_want(who, "weight", weight, torch.float32, (num_vertices,))
+    return num_vertices
+
+
+def mesh_vertex_gather(face_sums: torch.Tensor, corner_order: torch.Tensor,
+                       vertex_starts: torch.Tensor, grad: Optional[torch.Tensor] = None,
+                       weight: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """K32b.  face_sums (F,12) of K32a, ``corner_order`` (3F,) int32 and ``vertex_starts`` (V+1,)
+    int32 of ``mesh.vertex_adjacency`` -> ``(grad (V,3), weight (V,))`` f32: per vertex the sums of
+    its corners' rows of ``face_sums`` in CSR order, one thread per vertex.  ``grad`` and ``weight``
+    are written in place when given, and with ``accumulate`` added to (``out = out + value``)."""
+    num_vertices = mesh_vertex_gather_check(face_sums, corner_order, vertex_starts, grad, weight,
+                                            accumulate)
+    if grad is None:
+        grad = torch.empty((num_vertices, 3), dtype=torch.float32, device=face_sums.device)
+        weight = torch.empty((num_vertices,), dtype=torch.float32, device=face_sums.device)
+    _call("ffn_mesh_vertex_gather", _dev(face_sums, name="face_sums"),
+          _dev(corner_order, torch.int32, "corner_order"),
+          _dev(vertex_starts, torch.int32, "vertex_starts"), c_i64(face_sums.shape[0]),
+          c_i64(num_vertices), _dev(grad, name="grad"), _dev(weight, name="weight"),
+          c_i(1 if accumulate else 0))
+    return grad, weight

@@ -1648,6 +1648,48 @@ int ffn_mesh_raster_resolve(const uint64_t* zbuf, const int32_t* record, const f
                             const float* background, int width, int height, float* color,
                             float* alpha, float* depth, int32_t* ids, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K32  the adjoint of K31c's colour interpolation (csrc/mesh_raster_grad.hip).  No counterpart in
+ * the reference.  K31's colour is (c_v0 b0 + c_v1 b1) + c_v2 b2 with b_i from the geometry alone:
+ * the image is a linear map of the vertex colours, and these two launches are its transpose, for
+ * the per-vertex colours only (the textured path has no backward, the geometry no gradient).  No
+ * float atomics and no LDS; every float operation is one rounded f32 operation in the order
+ * written: the same inputs give the same bits on every call.  Limits as in K31: 1 <= width, height
+ * <= 16384; 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; bad shapes and null pointers are
+ * refused by name before any launch.
+ *
+ * K32a, one wavefront (64 lanes) per triangle f.  record (num_triangles,16) int32, 16-byte aligned,
+ * from K31a; ids (height width) int32 from K31c; d_color (height width,3) f32.
+ *   the box x0 y0 x1 y1 of record[f];  bw = x1 - x0 + 1;  n = bw (y1 - y0 + 1)
+ *   a box that is empty, not inside the image, or has n > 2^28 contributes nothing: a pixel outside
+ *   the image is never read, whatever the record
+ *   box pixel k = 0 .. n - 1 is (px, py) = (x0 + k % bw, y0 + k / bw), p = py width + px; it is
+ *   SELECTED iff ids[p] == f.  ids is compared and never used as an index.  A pixel that is not
+ *   selected is skipped by selection, not multiplied by zero: d_color[p] is not read
+ *   a selected pixel: E_i, l_i, q_i, depth_w as in K31b (the same bits); b_i = q_i * depth_w;
+ *     t[3 i + j] = b_i * d_color[p][j] (one rounded product each), t[9 + i] = b_i
+ *   segment s holds k = 64 s .. 64 s + 63, lane l the pixel k = 64 s + l; a lane that is not selected
+ *   or past n holds +0.0f; the 64 lane values are folded by x += shfl_xor(x, off), off = 32, 16, 8,
+ *   4, 2, 1 -- an IEEE add commutes bit for bit, so this is the fold of halves a[:h] + a[h:2h],
+ *   h = 32 .. 1;  acc = 0.0f, then acc = acc + segment_s for s = 0, 1, .. in order
+ * face_sums (num_triangles,12) f32 = the twelve acc.  Every row is written; the row of a triangle
+ * that is not drawn, or wins no pixel, is +0.
+ *
+ * K32b, one thread per vertex v.  corner_order (3 num_triangles) int32: the corners 3 f + i stably
+ * sorted by vertex id; vertex_starts (num_vertices + 1) int32: the rows of v are
+ * corner_order[vertex_starts[v] .. vertex_starts[v + 1] - 1] (CSR; the range is clamped into the
+ * array).  From 0.0f and in that order, for the corner 3 f + i:
+ *   g[j] = g[j] + face_sums[f][3 i + j], j = 0 .. 2;  w = w + face_sums[f][9 + i]
+ * a corner outside 0 .. 3 num_triangles - 1 is skipped.  grad (num_vertices,3) = g and weight
+ * (num_vertices) = w, or with accumulate != 0 out = out + value, one add each. */
+int ffn_mesh_raster_face_sums(const int32_t* record, const int32_t* ids, const float* d_color,
+                              int64_t num_triangles, int width, int height, float* face_sums,
+                              void* stream);
+int ffn_mesh_vertex_gather(const float* face_sums, const int32_t* corner_order,
+                           const int32_t* vertex_starts, int64_t num_triangles,
+                           int64_t num_vertices, float* grad, float* weight, int accumulate,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
