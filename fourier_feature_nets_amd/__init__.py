@@ -17,9 +17,12 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import (color_mesh_from_images, fit_mesh_colors, load_obj, normalize_points,
+from .mesh import (MeshTaps, bake_vertex_colors, color_mesh_from_images, fit_mesh_colors,
+                   fit_mesh_texture, load_obj, mesh_texture_taps, normalize_points,
                    procedural_torus, render_mesh, render_mesh_backward, render_mesh_image,
-                   sample_mesh, save_obj, triangle_counts, vertex_adjacency)
+                   render_mesh_texture, render_mesh_texture_backward, sample_mesh, save_obj,
+                   texture_mesh_from_images, texture_to_uint8, triangle_counts, unwrap_mesh,
+                   vertex_adjacency)
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -43,9 +46,10 @@ from .voxels import VoxelProgram, Voxels
 __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
-           "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "NeRF",
+           "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "MeshTaps", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
-           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "calculate_blend_weights", "color_mesh_from_images",
-           "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
-           "linspace", "load_model", "load_obj", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_image", "sample_mesh", "save_obj", "triangle_counts", "vertex_adjacency"]
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "bake_vertex_colors", "calculate_blend_weights", "color_mesh_from_images",
+           "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_mesh_texture", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
+           "linspace", "load_model", "load_obj", "mesh_texture_taps", "normalize_points", "orbit", "photo_actions", "procedural_torus",
+           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_image", "render_mesh_texture", "render_mesh_texture_backward", "sample_mesh", "save_obj",
+           "texture_mesh_from_images", "texture_to_uint8", "triangle_counts", "unwrap_mesh", "vertex_adjacency"]

@@ -64,6 +64,9 @@ SOURCES = {
     "mesh_raster.hip": ["-ffp-contract=off"],
     # K31c's b_i = q_i * depth_w and the sums of b_i * g over pixels, every product and add rounded
     "mesh_raster_grad.hip": ["-ffp-contract=off"],
+    # K31c's UV interpolation and K22's bilinear weights again, and the sums of w * texel and
+    # w * g in a fixed order, every product and add rounded
+    "mesh_texture.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -1,7 +1,8 @@
 // The bilinear texture lookup of K22 (mesh.hip), shared with K31c (mesh_raster.hip): the
 // reference's interpolate_bilinear (utils.py:197-241) followed by the / 255 of octree.py:849.
-// Every operation is one rounded f32 operation in the order written; both including files are
-// compiled with -ffp-contract=off.
+// Every operation is one rounded f32 operation in the order written; every including file is
+// compiled with -ffp-contract=off.  mesh_texture_taps() is the same lookup without the texture, for
+// K33a (mesh_texture.hip).
 #pragma once
 #include "common.h"
 
@@ -39,6 +40,30 @@ __device__ __forceinline__ void mesh_texture_lookup(float u, float v,
                           + w11 * (float)t11[ch];
         rgb[ch] = sum / 255.0f;
     }
+}
+
+// The four texels and weights mesh_texture_lookup blends at (u, v), without the texture: the same
+// operations in the same order, so the same bits (K33a, mesh_texture.hip).  texel[k] = i width + j
+// and weight[k] in the order 00, 01, 10, 11; height width < 2^31.
+struct MeshTextureTaps {
+    int texel[4];
+    float weight[4];
+};
+
+__device__ __forceinline__ MeshTextureTaps mesh_texture_taps(float u, float v, int height,
+                                                             int width) {
+    const float col = u * (float)width, row = v * (float)height;
+    const float fj = floorf(col), fi = floorf(row);
+    const float dj = col - fj, di = row - fi;
+    const float last_col = (float)(width - 1), last_row = (float)(height - 1);
+    const int j0 = mesh_clamp_index(fj, last_col), j1 = mesh_clamp_index(fj + 1.0f, last_col);
+    const int i0 = mesh_clamp_index(fi, last_row), i1 = mesh_clamp_index(fi + 1.0f, last_row);
+    MeshTextureTaps t;
+    t.weight[0] = (1.0f - di) * (1.0f - dj), t.weight[1] = (1.0f - di) * dj;
+    t.weight[2] = di * (1.0f - dj), t.weight[3] = di * dj;
+    t.texel[0] = i0 * width + j0, t.texel[1] = i0 * width + j1;
+    t.texel[2] = i1 * width + j0, t.texel[3] = i1 * width + j1;
+    return t;
 }
 
 }  // namespace ffn

@@ -26,10 +26,17 @@ returns what ``OcTree.render`` and ``OcTree.render_image`` return.  No counterpa
 ``csrc/mesh_raster_grad.hip``); ``color_mesh_from_images`` uses it to give every vertex the mean
 colour of the pixels that see it, ``fit_mesh_colors`` to optimise the colours against a dataset's
 images, and ``vertex_adjacency`` makes the corner lists both need.  No counterpart either.
+
+``mesh_texture_taps`` writes the textured picture of one camera as a sparse matrix in the texture
+(K33, ``csrc/mesh_texture.hip``); ``render_mesh_texture`` and ``render_mesh_texture_backward``
+are its two products, ``texture_mesh_from_images`` and ``fit_mesh_texture`` what
+``color_mesh_from_images`` and ``fit_mesh_colors`` are for vertices.  ``unwrap_mesh`` makes a
+texture atlas for a mesh that has no UVs, ``bake_vertex_colors`` fills it from per-vertex colours,
+and ``texture_to_uint8`` + ``save_obj(uvs=, texture=)`` write the result out.
 """
 
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -192,11 +199,20 @@ def _diffuse_map(mtl_path: str) -> Optional[str]:
     return None
 
 
-def save_obj(path: str, vertices, triangles, colors=None, normals=None) -> None:
+def save_obj(path: str, vertices, triangles, colors=None, normals=None, uvs=None,
+             texture=None) -> None:
     """Writes a Wavefront OBJ: ``v x y z`` per vertex (``v x y z r g b`` with ``colors`` (V,3), the
     vertex-colour extension most viewers read), ``vn x y z`` per vertex with ``normals`` (V,3), and
     ``f a b c`` per triangle, 1-based, as ``a//a b//b c//c`` when normals are given.  Floats are
-    written with ``%.9g``: a float32 survives the file bit for bit.  Needs no GPU."""
+    written with ``%.9g``: a float32 survives the file bit for bit.  Needs no GPU.
+
+    With ``uvs`` (V,2) and ``texture`` (H,W,3 or 4) uint8 with row 0 at the top (what ``load_obj``
+    returns and ``texture_to_uint8`` makes) -- both or neither -- it also writes ``vt u v`` per
+    vertex, the faces as ``a/a b/b c/c`` (``a/a/a`` with normals), the texture as a PNG and a
+    material library with its ``map_Kd`` beside the OBJ (``name.png``, ``name.mtl`` for
+    ``name.obj``): ``load_obj`` reads the same arrays back when the triangles use the vertices in
+    the order of their numbers, as those of ``unwrap_mesh`` do.  Without them the file is byte for
+    byte what it was."""
     vertices = np.asarray(vertices)
     if vertices.ndim != 2 or vertices.shape[1] != 3:
         raise ValueError("save_obj: vertices must be (V,3), got %s" % (vertices.shape,))
@@ -213,22 +229,52 @@ def save_obj(path: str, vertices, triangles, colors=None, normals=None) -> None:
         if extra is not None and np.shape(extra) != vertices.shape:
             raise ValueError("save_obj: %s must be (V,3) = %s, got %s"
                              % (name, vertices.shape, np.shape(extra)))
+    if (uvs is None) != (texture is None):
+        raise ValueError("save_obj: give both uvs and texture, or neither")
+    if uvs is not None:
+        if np.shape(uvs) != (len(vertices), 2):
+            raise ValueError("save_obj: uvs must be (V,2) = (%d,2), got %s"
+                             % (len(vertices), np.shape(uvs)))
+        texture = np.asarray(texture)
+        if texture.ndim != 3 or texture.shape[2] not in (3, 4) or texture.dtype != np.uint8 \
+                or min(texture.shape) < 1:
+            raise ValueError("save_obj: texture must be (H,W,3) or (H,W,4) uint8 with row 0 at the "
+                             "top (texture_to_uint8 makes one), got %s %s"
+                             % (texture.dtype, texture.shape))
     if colors is not None:
         columns.append(np.asarray(colors))
     rows = np.concatenate(columns, 1)
     lines = ["# %d vertices, %d triangles" % (len(vertices), len(triangles))]
+    stem = os.path.splitext(os.path.basename(path))[0]
+    if uvs is not None:
+        lines.append("mtllib %s.mtl" % stem)
     lines += ["v " + " ".join("%.9g" % x for x in row) for row in rows.tolist()]
+    if uvs is not None:
+        lines += ["vt " + " ".join("%.9g" % x for x in row) for row in np.asarray(uvs).tolist()]
     if normals is not None:
         lines += ["vn " + " ".join("%.9g" % x for x in row)
                   for row in np.asarray(normals).tolist()]
-    corner = "%d//%d" if normals is not None else "%d"
-    for a, b, c in (triangles.astype(np.int64) + 1).tolist():
-        if normals is not None:
-            lines.append("f " + " ".join(corner % (i, i) for i in (a, b, c)))
-        else:
-            lines.append("f %d %d %d" % (a, b, c))
+    if uvs is not None:
+        lines.append("usemtl atlas")
+        corner = "%d/%d/%d" if normals is not None else "%d/%d"
+        copies = 3 if normals is not None else 2
+        for face in (triangles.astype(np.int64) + 1).tolist():
+            lines.append("f " + " ".join(corner % ((i,) * copies) for i in face))
+    else:
+        corner = "%d//%d" if normals is not None else "%d"
+        for a, b, c in (triangles.astype(np.int64) + 1).tolist():
+            if normals is not None:
+                lines.append("f " + " ".join(corner % (i, i) for i in (a, b, c)))
+            else:
+                lines.append("f %d %d %d" % (a, b, c))
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+    if uvs is not None:
+        from PIL import Image      # only a textured OBJ needs it
+        folder = os.path.dirname(os.path.abspath(path))
+        Image.fromarray(texture).save(os.path.join(folder, stem + ".png"))
+        with open(os.path.join(folder, stem + ".mtl"), "w") as f:
+            f.write("newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nmap_Kd %s.png\n" % stem)
 
 
 def load_obj(path: str, texture_path: Optional[str] = None, return_colors: bool = False):
@@ -575,8 +621,8 @@ def _mesh_colors_check(who, vertices, colors=None, uvs=None, texture=None,
     if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
         raise ValueError("%s: vertices must be (V,3) with V >= 1, got %s" % (who, shape))
     if uvs is not None or texture is not None:
-        raise ValueError("%s: uvs and texture are not supported: the textured path of render_mesh "
-                         "has no backward, only per-vertex colors have" % who)
+        raise ValueError("%s: uvs and texture are not supported here, only per-vertex colors: the "
+                         "textured path's transpose is render_mesh_texture_backward" % who)
     if colors is not None:
         if _shape_of(colors) != (shape[0], 3):
             raise ValueError("%s: colors must be (V,3) = (%d,3), got %s"
@@ -883,4 +929,502 @@ def fit_mesh_colors(vertices, triangles, colors, train_dataset, val_dataset=None
     values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
     log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
            for k in range(len(values))]
+    return (data.cpu().numpy() if as_numpy else data), log
+
+
+# ------------------------------------------------------------------------------------ K33
+class MeshTaps(NamedTuple("MeshTaps", [("tap_texel", torch.Tensor), ("tap_weight", torch.Tensor),
+                                       ("sorted_texels", torch.Tensor),
+                                       ("tap_order", torch.Tensor), ("width", int),
+                                       ("height", int)])):
+    """K31c's textured picture of one camera as a sparse matrix (K33a and a sort): per pixel the
+    four texels ``tap_texel`` (P,4) int32 (``row * width + column``, -1 where nothing is drawn) and
+    weights ``tap_weight`` (P,4) float32 of the bilinear lookup; ``sorted_texels`` and
+    ``tap_order`` (4P,) int32, the tap slots ``4 p + k`` stably sorted by texel, which K33c reads;
+    ``width`` and ``height`` of the TEXTURE.  64 bytes per pixel."""
+
+    @property
+    def num_texels(self) -> int:
+        return self.width * self.height
+
+
+def _power_of_two(n: int) -> int:
+    return 1 << max(int(n) - 1, 0).bit_length()
+
+
+def _atlas_size(num_tiles: int, tile: int):
+    """The smallest powers of two (width, height), width = height or 2 height, whose
+    ``(width // tile) * (height // tile)`` tiles hold ``num_tiles``."""
+    width = height = _power_of_two(tile)
+    while (width // tile) * (height // tile) < num_tiles:
+        if width == height:
+            width *= 2
+        else:
+            height *= 2
+    return width, height
+
+
+def unwrap_mesh(vertices, triangles, tile: int = 4):
+    """A texture atlas for a mesh without UVs -> ``(vertices', triangles', uvs, vertex_map,
+    (height, width))``: one ``tile x tile`` square of texels per quad.  Host-only, integer work.
+
+    Triangles ``2k`` and ``2k + 1`` share a tile when both have three distinct vertex ids and they
+    share exactly two of them (``OcTree.extract_mesh`` writes every quad as ``(q0, q1, q2), (q0,
+    q2, q3)``); the shared edge lies on the tile's diagonal.  Every other triangle gets a tile of
+    its own and uses its lower-left half.  The corners sit at the tile-local texel coordinates 0.5
+    and ``tile - 1.5``: a lone triangle's at ``(0.5, 0.5), (tile - 1.5, 0.5), (0.5, tile - 1.5)`` in
+    the order of its corners; of a pair the first triangle's unshared corner at ``(0.5, 0.5)``, the
+    next two (in its winding) at ``(tile - 1.5, 0.5)`` and ``(0.5, tile - 1.5)``, and the partner's
+    unshared corner at ``(tile - 1.5, tile - 1.5)``.  A bilinear lookup at texel coordinate ``x``
+    reads the texels ``floor(x)`` and ``floor(x) + 1``, so every tap of every pixel of a triangle
+    stays inside its own tile, whatever the roundings of the interpolated ``u``: neighbouring tiles
+    never bleed into each other.  ``tile >= 3``.
+
+    The tiles are laid out row-major, in the order of the triangles, in a texture whose ``width``
+    and ``height`` are the smallest powers of two that hold them (``width`` = ``height`` or twice
+    it): ``u * width`` is exact in float32.  ``v`` grows with the row index, the kernels'
+    orientation.  Vertices are duplicated per tile, 4 per pair and 3 per lone triangle, numbered in
+    the order the triangles first use them (so ``load_obj`` of a saved atlas returns these arrays);
+    ``vertex_map`` (V',) int32 names the original vertex: ``vertices' = vertices[vertex_map]``,
+    ``vertex_map[triangles'] = triangles``, and colours and normals follow the same way."""
+    who = "unwrap_mesh"
+    points = np.asarray(vertices)
+    if points.ndim != 2 or points.shape[1] != 3 or len(points) == 0:
+        raise ValueError("%s: vertices must be (V,3) with V >= 1, got %s" % (who, points.shape))
+    tri = _check_triangles(who, triangles, len(points)).astype(np.int64)
+    if int(tile) != tile or tile < 3:
+        raise ValueError("%s: tile must be an integer >= 3, got %r" % (who, tile))
+    tile = int(tile)
+    count = len(tri)
+    pairs = count // 2
+    first, second = tri[0:2 * pairs:2], tri[1:2 * pairs:2]
+
+    def distinct(t):
+        return (t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 0] != t[:, 2])
+
+    equal = first[:, :, None] == second[:, None, :]              # [pair, corner of 2k, of 2k+1]
+    in_second, in_first = equal.any(2), equal.any(1)
+    paired = distinct(first) & distinct(second) & (in_second.sum(1) == 2)
+    joined = np.zeros(count, dtype=bool)                          # the second triangle of a pair
+    joined[1:2 * pairs:2] = paired
+    opens = np.zeros(count, dtype=bool)                           # the first triangle of a pair
+    opens[0:2 * pairs:2] = paired
+    tile_of = np.cumsum(~joined) - 1
+    num_tiles = int(tile_of[-1]) + 1
+    width, height = _atlas_size(num_tiles, tile)
+    if width * height > ops.MESH_TEXTURE_MAX_TEXELS:
+        raise ValueError("%s: %d tiles of %d x %d need a %d x %d texture; at most (2^31 - 1) / 3 "
+                         "texels are supported" % (who, num_tiles, tile, tile, width, height))
+    # the vertices a tile owns: 3 for its first triangle, one more for a partner
+    owned = np.where(joined, 1, 3)
+    base = np.cumsum(owned) - owned                               # the first new vertex of a triangle
+    new_tri = base[:, None] + np.arange(3)
+    lo, hi = 0.5, tile - 1.5
+    spots = np.array([[lo, lo], [hi, lo], [lo, hi], [hi, hi]])    # P0 P1 P2 and the partner's P3
+    local = np.zeros((count, 3, 2))
+    local[:] = spots[:3]
+    vertex_map = np.empty(int(owned.sum()), dtype=np.int64)
+    vertex_map[new_tri[~joined].reshape(-1)] = tri[~joined].reshape(-1)
+    if paired.any():
+        a, b = np.flatnonzero(opens), np.flatnonzero(joined)
+        alone = np.argmin(in_second[paired], 1)                   # the first's unshared corner
+        other = np.argmin(in_first[paired], 1)                    # the partner's unshared corner
+        turn = (np.arange(3)[None, :] - alone[:, None]) % 3       # corner -> P0, P1, P2
+        local[a] = spots[turn]
+        # the partner: its shared corners are the first's, its own gets the tile's fourth vertex
+        match = np.argmax(equal[paired], 1)                       # [pair, corner of 2k+1] -> of 2k
+        new_tri[b] = np.take_along_axis(new_tri[a], match, 1)
+        local[b] = np.take_along_axis(local[a], match[:, :, None], 1)
+        new_tri[b, other] = base[b]
+        local[b, other] = spots[3]
+        vertex_map[base[b]] = tri[b, other]
+    tiles_per_row = width // tile
+    origin = np.stack([tile_of % tiles_per_row, tile_of // tiles_per_row], 1) * tile
+    texel = origin[:, None, :] + local                            # (F,3,2) in texel coordinates
+    uvs = np.zeros((len(vertex_map), 2), dtype=np.float64)
+    uvs[new_tri.reshape(-1)] = texel.reshape(-1, 2) / np.array([width, height], dtype=np.float64)
+    return (points[vertex_map], new_tri.astype(np.int32), uvs.astype(np.float32),
+            vertex_map.astype(np.int32), (height, width))
+
+
+def bake_vertex_colors(colors, triangles, uvs, size, tile: int):
+    """Per-vertex colours of an ``unwrap_mesh`` atlas as a texture -> (H,W,3) float32 in the
+    kernels' orientation.  Host-only.  Every texel of a tile takes the barycentric blend of its
+    triangle's corner colours at the texel's own position (texel ``j`` lies at texel coordinate
+    ``j``); in a pair's tile the texels beyond the diagonal take the partner's.  Texels outside the
+    corners extrapolate and are clamped to [0, 1]; texels of no tile get the mean colour.  A fit
+    that starts here starts from what K30 or K32 produced, and texels that no camera sees keep a
+    sensible colour."""
+    who = "bake_vertex_colors"
+    colors = np.asarray(colors, dtype=np.float64)
+    if colors.ndim != 2 or colors.shape[1] != 3 or len(colors) == 0:
+        raise ValueError("%s: colors must be (V,3) with V >= 1, got %s" % (who, colors.shape))
+    tri = _check_triangles(who, triangles, len(colors)).astype(np.int64)
+    if np.shape(uvs) != (len(colors), 2):
+        raise ValueError("%s: uvs must be (V,2) = (%d,2), got %s"
+                         % (who, len(colors), np.shape(uvs)))
+    if int(tile) != tile or tile < 3:
+        raise ValueError("%s: tile must be an integer >= 3, got %r" % (who, tile))
+    tile = int(tile)
+    height, width = (int(s) for s in size)
+    if height < tile or width < tile:
+        raise ValueError("%s: size must be (height, width) of at least one tile, got %r"
+                         % (who, size))
+    texture = np.empty((height, width, 3), dtype=np.float64)
+    texture[:] = colors.mean(0)
+    texel = np.asarray(uvs, dtype=np.float64)[tri] * np.array([width, height], dtype=np.float64)
+    origin = np.floor(texel.min(1) / tile).astype(np.int64) * tile          # (F,2) column, row
+    if (origin < 0).any() or (origin[:, 0] + tile > width).any() \
+            or (origin[:, 1] + tile > height).any():
+        raise ValueError("%s: a triangle's uvs lie outside the %d x %d texture" % (who, width,
+                                                                                    height))
+    local = texel - origin[:, None, :]
+    upper = local.sum(2).max(1) > tile - 1 + 0.25           # it owns the corner (tile-1.5, tile-1.5)
+    edge1, edge2 = local[:, 1] - local[:, 0], local[:, 2] - local[:, 0]
+    det = edge1[:, 0] * edge2[:, 1] - edge1[:, 1] * edge2[:, 0]
+    if (det == 0).any():
+        raise ValueError("%s: a triangle's uvs are collinear" % who)
+    ly, lx = np.meshgrid(np.arange(tile), np.arange(tile), indexing="ij")
+    dx = lx[None] - local[:, 0, 0, None, None]
+    dy = ly[None] - local[:, 0, 1, None, None]
+    w1 = (dx * edge2[:, 1, None, None] - dy * edge2[:, 0, None, None]) / det[:, None, None]
+    w2 = (dy * edge1[:, 0, None, None] - dx * edge1[:, 1, None, None]) / det[:, None, None]
+    c0, c1, c2 = (colors[tri[:, i]][:, None, None, :] for i in range(3))
+    blend = c0 + w1[..., None] * (c1 - c0) + w2[..., None] * (c2 - c0)       # (F,tile,tile,3)
+    rows = origin[:, 1, None, None] + ly[None]
+    cols = origin[:, 0, None, None] + lx[None]
+    beyond = (lx + ly > tile - 1)[None]
+    for chosen, mask in ((~upper, np.ones_like(beyond)), (upper, beyond)):
+        keep = np.broadcast_to(mask, rows.shape)[chosen]
+        texture[rows[chosen][keep], cols[chosen][keep]] = blend[chosen][keep]
+    return np.clip(texture, 0.0, 1.0).astype(np.float32)
+
+
+def texture_to_uint8(texture) -> np.ndarray:
+    """A float (H,W,3) texture in the kernels' orientation -> (H,W,3) uint8 with row 0 at the top,
+    as ``load_obj`` returns one and ``render_mesh`` and ``save_obj`` take it:
+    ``floor(x * 255 + 0.5)`` in float32, clamped into 0 .. 255 (NaN gives 0)."""
+    values = texture.detach().cpu().numpy() if torch.is_tensor(texture) else np.asarray(texture)
+    if values.ndim != 3 or values.shape[2] != 3 or not np.issubdtype(values.dtype, np.floating):
+        raise ValueError("texture_to_uint8: texture must be a float (H,W,3) array, got %s %s"
+                         % (values.dtype, values.shape))
+    with np.errstate(invalid="ignore"):
+        scaled = np.floor(values.astype(np.float32) * np.float32(255.0) + np.float32(0.5))
+        scaled = np.fmin(np.fmax(np.nan_to_num(scaled, nan=0.0), 0.0), 255.0)
+    return np.ascontiguousarray(scaled.astype(np.uint8)[::-1])
+
+
+def _texture_check(who, texture):
+    """A float (H,W,3) texture within K33's limits -> (height, width).  No device."""
+    shape = _shape_of(texture)
+    floating = hasattr(texture, "dtype") and (
+        texture.dtype.is_floating_point if torch.is_tensor(texture)
+        else np.issubdtype(texture.dtype, np.floating))
+    if len(shape) != 3 or shape[2] != 3 or min(shape) < 1 or not floating:
+        raise ValueError("%s: texture must be a float (H,W,3) array in the kernels' orientation, "
+                         "got %s %s" % (who, getattr(texture, "dtype", type(texture).__name__),
+                                        shape))
+    _texture_size_check(who, shape[:2])
+    return int(shape[0]), int(shape[1])
+
+
+def _texture_size_check(who, size):
+    try:
+        height, width = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError("%s: size must be (height, width), got %r" % (who, size)) from None
+    if (not 1 <= height <= ops.MESH_MAX_TEXTURE_SIDE or not 1 <= width <= ops.MESH_MAX_TEXTURE_SIDE
+            or height * width > ops.MESH_TEXTURE_MAX_TEXELS):
+        raise ValueError("%s: the texture must be 1 .. 2^24 a side with at most (2^31 - 1) / 3 "
+                         "texels, got %r" % (who, tuple(size)))
+    return height, width
+
+
+def _mesh_uvs_check(who, vertices, uvs, supersample=1, batch_size=1) -> int:
+    """What every K33 function refuses of its mesh from shapes alone -> V."""
+    shape = _shape_of(vertices)
+    if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+        raise ValueError("%s: vertices must be (V,3) with V >= 1, got %s" % (who, shape))
+    if uvs is None or _shape_of(uvs) != (shape[0], 2):
+        raise ValueError("%s: uvs must be (V,2) = (%d,2), got %s (unwrap_mesh makes an atlas)"
+                         % (who, shape[0], None if uvs is None else _shape_of(uvs)))
+    if supersample != 1:
+        raise ValueError("%s: supersample must be 1 (the backward of the k x k mean is not "
+                         "built), got %r" % (who, supersample))
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("%s: batch_size must be an integer >= 1, got %r" % (who, batch_size))
+    return shape[0]
+
+
+def _taps(vertices, triangles, uvs, proj, width, height, size, batch_size=1 << 22, hidden=None):
+    """K31a-c for the ids, K33a, and the stable sort of the tap slots by texel -> MeshTaps.
+    ``hidden`` (H W,) bool marks pixels that count as uncovered."""
+    record, ids = _raster_ids(vertices, triangles, proj, width, height, batch_size)
+    if hidden is not None:
+        ids = ids.masked_fill(hidden, -1)
+    tap_texel, tap_weight = ops.mesh_texture_taps(record, ids, triangles, uvs, size[0], size[1],
+                                                  width, height)
+    # integer plumbing, as the key sort of OcTree.extract_mesh and vertex_adjacency
+    sorted_texels, order = torch.sort(tap_texel.reshape(-1), stable=True)
+    return MeshTaps(tap_texel, tap_weight, sorted_texels.contiguous(),
+                    order.to(torch.int32).contiguous(), int(size[1]), int(size[0]))
+
+
+def mesh_texture_taps(vertices, triangles, uvs, camera, size, batch_size: int = 1 << 22,
+                      supersample: int = 1) -> MeshTaps:
+    """The picture ``render_mesh(uvs=, texture=)`` draws from ``camera`` as a sparse matrix in the
+    texture -> ``MeshTaps`` of GPU tensors, for a texture of ``size = (height, width)``: K31a-c for
+    the ids of the z-buffer, K33a for the four texels and weights of every pixel (the bits K31c
+    uses), and a torch stable sort of the tap slots by texel for K33c.  It depends on the geometry,
+    the camera and the UVs alone: made once per camera, it serves every step of a fit.  64 bytes
+    per pixel.  The read-backs of K31 (one per call) are the only host synchronisation."""
+    who = "mesh_texture_taps"
+    num_vertices = _mesh_uvs_check(who, vertices, uvs, supersample, batch_size)
+    width, height = _camera_size(who, camera)
+    size = _texture_size_check(who, size)
+    _mesh_ids_check(who, triangles, num_vertices)
+    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+    return _taps(_on(vertices, "float32", device), _on(triangles, "int32", device),
+                 _on(uvs, "float32", device), supersample_projection(camera, 1), width, height,
+                 size, int(batch_size))
+
+
+def _taps_check(who, taps):
+    if not isinstance(taps, MeshTaps):
+        raise ValueError("%s: taps must be a MeshTaps (mesh_texture_taps makes one), got %s"
+                         % (who, type(taps).__name__))
+
+
+def render_mesh_texture(taps: MeshTaps, texture, background=(0, 0, 0)):
+    """K33b: the picture of ``taps`` for a float ``texture`` (H,W,3) in the kernels' orientation
+    (the row index growing with ``v``; plain floats, no ``/ 255``) -> ``RenderResult(color (P,3),
+    alpha (P,), None)``: the depth is not recomputed here.  A numpy texture gives numpy results.
+    With ``texture = uint8 / 255`` the colours are K31c's within a rounding or two (K31c divides
+    after the blend)."""
+    who = "render_mesh_texture"
+    _taps_check(who, taps)
+    if _texture_check(who, texture) != (taps.height, taps.width):
+        raise ValueError("%s: texture must be (%d,%d,3) as the taps were made for, got %s"
+                         % (who, taps.height, taps.width, _shape_of(texture)))
+    from .utils import RenderResult
+    as_numpy = not torch.is_tensor(texture)
+    flat = _on(texture, "float32", taps.tap_texel.device).reshape(-1, 3)
+    color, alpha = ops.mesh_texture_gather(taps.tap_texel, taps.tap_weight, flat, background)
+    out = RenderResult(color, alpha, None)
+    return out.numpy() if as_numpy else out
+
+
+def render_mesh_texture_backward(taps: MeshTaps, d_color, grad=None, weight=None,
+                                 accumulate: bool = False):
+    """K33c: the transpose of ``render_mesh_texture`` -> ``(grad (H,W,3), weight (H,W))`` float32
+    of the texture: ``grad[t] = sum w d_color[p]`` over the taps of texel ``t`` and ``weight[t] =
+    sum w``, in the fixed order of the sorted slots, no float atomics.  ``grad`` and ``weight`` (GPU
+    tensors of those shapes, or flat (T,3) and (T,)) are written in place when given, and added to
+    with ``accumulate``: how several cameras fold into one buffer.  A numpy ``d_color`` gives numpy
+    results."""
+    who = "render_mesh_texture_backward"
+    _taps_check(who, taps)
+    num_pixels = taps.tap_texel.shape[0]
+    if _shape_of(d_color) != (num_pixels, 3):
+        raise ValueError("%s: d_color must be (H W,3) = (%d,3), got %s"
+                         % (who, num_pixels, _shape_of(d_color)))
+    if (grad is None) != (weight is None) or (accumulate and grad is None):
+        raise ValueError("%s: give both grad and weight, or neither; accumulate needs them" % who)
+    as_numpy = not torch.is_tensor(d_color)
+    shaped = (taps.height, taps.width)
+    if grad is not None:
+        if not torch.is_tensor(grad) or not torch.is_tensor(weight) \
+                or grad.numel() != 3 * taps.num_texels or weight.numel() != taps.num_texels:
+            raise ValueError("%s: grad must be a (%d,%d,3) and weight a (%d,%d) tensor"
+                             % ((who,) + shaped + shaped))
+    flat_grad = None if grad is None else grad.view(-1, 3)
+    flat_weight = None if weight is None else weight.view(-1)
+    out_grad, out_weight = ops.mesh_texture_grad(
+        taps.sorted_texels, taps.tap_order, taps.tap_weight,
+        _on(d_color, "float32", taps.tap_texel.device), taps.num_texels, flat_grad, flat_weight,
+        accumulate)
+    if grad is None:
+        grad, weight = out_grad.view(shaped + (3,)), out_weight.view(shaped)
+    if as_numpy:
+        return grad.cpu().numpy(), weight.cpu().numpy()
+    return grad, weight
+
+
+def texture_mesh_from_images(vertices, triangles, uvs, dataset, size, texture=None,
+                             alpha_threshold: float = 0.5):
+    """Gives every texel the weighted mean colour of the pixels that see it -> ``(texture (H,W,3),
+    weights (H,W))`` float32 in the kernels' orientation (numpy in gives numpy out; tensors stay
+    tensors): ``color_mesh_from_images`` for texels.  Over the cameras of ``dataset`` in order, K33c
+    accumulates ``sum w rgb[p] / 255`` and ``sum w`` per texel, ``w`` the bilinear weights of K31c;
+    a pixel whose own alpha byte is below ``ceil(alpha_threshold * 255)`` (clamped into 1 .. 255)
+    counts as uncovered.  A texel with ``weight > 0`` gets ``sum / weight``, one f32 division per
+    channel on the host; any other keeps ``texture[t]``, or 0.5 grey when ``texture`` is None."""
+    who = "texture_mesh_from_images"
+    num_vertices = _mesh_uvs_check(who, vertices, uvs)
+    size = _texture_size_check(who, size)
+    if texture is not None and _texture_check(who, texture) != size:
+        raise ValueError("%s: texture must be (%d,%d,3), got %s"
+                         % (who, size[0], size[1], _shape_of(texture)))
+    alpha_u8 = _alpha_byte(who, alpha_threshold)
+    images, cameras, width, height = _mesh_dataset_check(who, "dataset", dataset)
+    _mesh_ids_check(who, triangles, num_vertices)
+    as_numpy = not torch.is_tensor(vertices)
+    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    uvs = _on(uvs, "float32", device)
+    num_texels = size[0] * size[1]
+    total = torch.zeros((num_texels, 3), dtype=torch.float32, device=device)
+    weights = torch.zeros((num_texels,), dtype=torch.float32, device=device)
+    for number, camera in enumerate(cameras):
+        frame = images[number]
+        hidden = None
+        if frame.shape[-1] == 4:
+            hidden = torch.from_numpy(frame[..., 3].reshape(-1) < alpha_u8).to(device)
+        taps = _taps(vertices, triangles, uvs, supersample_projection(camera, 1), width, height,
+                     size, hidden=hidden)
+        rgb = (frame[..., :3].astype(np.float32) / 255).reshape(-1, 3)      # as ImageDataset
+        ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight,
+                              torch.from_numpy(rgb).to(device), num_texels, total, weights,
+                              accumulate=number > 0)
+    base = np.full((num_texels, 3), 0.5, dtype=np.float32) if texture is None else \
+        np.array(texture.detach().cpu().numpy() if torch.is_tensor(texture) else texture,
+                 dtype=np.float32).reshape(-1, 3)
+    out, weights_host = _mean_vertex_colors(total.cpu().numpy(), weights.cpu().numpy(), base)
+    out, weights_host = out.reshape(size + (3,)), weights_host.reshape(size)
+    if as_numpy:
+        return out, weights_host
+    return torch.from_numpy(out).to(device), weights.view(size)
+
+
+def _texture_psnr(taps, flat, dataset, width, height) -> float:
+    """-10 log10 of the mean colour-MSE over every pixel of the dataset's cameras."""
+    per = width * height
+    alphas = dataset._gt_alphas()
+    total = torch.zeros((2,), dtype=torch.float32, device=flat.device)
+    pixels = torch.arange(per, dtype=torch.int64, device=flat.device)
+    for number, camera_taps in enumerate(taps):
+        color, alpha = ops.mesh_texture_gather(camera_taps.tap_texel, camera_taps.tap_weight, flat)
+        sums, _, _ = ops.mse_loss(color, alpha, dataset.colors, alphas, pixels + number * per,
+                                  0.0, 0.0, want_grad=False)
+        total += sums
+    mean = float(total.cpu().numpy().astype(np.float64)[0]) / (3 * per * len(taps))
+    return float(-10.0 * np.log10(max(mean, 1e-12)))
+
+
+def fit_mesh_texture(vertices, triangles, uvs, texture, train_dataset, val_dataset=None,
+                     num_steps: int = 500, learning_rate: float = 1e-2, cameras_per_step: int = 1,
+                     report_interval: int = 100, alpha_threshold=None,
+                     clip_value: float = CLIP_VALUE, max_norm: float = MAX_NORM,
+                     seed: int = 20080524, cache_taps: bool = True, verbose: bool = True):
+    """Optimises the float ``texture`` (H,W,3, the kernels' orientation) of a mesh with ``uvs``
+    against the images of ``train_dataset`` with a black background -> ``(texture, log)``; the
+    geometry and the UVs are not changed.  numpy in gives numpy out; tensors stay tensors, and the
+    given ``texture`` is not modified.  ``fit_mesh_colors``' loop on a (T,3) buffer: the same
+    seeded deal of the cameras, ``cameras_per_step`` at a time, and one step is, for each of its
+    cameras, the taps (from the cache, or K31a-c + K33a + the sort when ``cache_taps`` is off), the
+    K33b frame, K6 (``ops.mse_loss``) on that camera's pixels with ``color_scale = 1 / (3 count)``
+    and no alpha term, the optional alpha mask (``alpha_threshold``, as in ``fit_mesh_colors``),
+    and K33c accumulated over the step's cameras; then K7 (``ops.clip_adam``) and ``clamp_(0, 1)``.
+
+    The log holds ``FitLogEntry(step, loss, val_psnr)`` as ``fit_mesh_colors``' does, and report
+    steps are printed the same way.  With the cache (64 bytes per pixel and camera) a step has no
+    host synchronisation at all: the only ones are the read-backs of K31 when a camera's taps are
+    first built; without it every camera of every step pays them.  The bits do not depend on
+    ``cache_taps``.  ``learning_rate`` has NO tuned default: 1e-2 is ``fit_octree``'s."""
+    who = "fit_mesh_texture"
+    num_vertices = _mesh_uvs_check(who, vertices, uvs)
+    if texture is None:
+        raise ValueError("%s: texture must be a float (H,W,3) array, got None "
+                         "(texture_mesh_from_images or bake_vertex_colors makes a start)" % who)
+    size = _texture_check(who, texture)
+    num_steps, cameras_per_step = int(num_steps), int(cameras_per_step)
+    if num_steps < 0 or cameras_per_step < 1 or int(report_interval) < 1:
+        raise ValueError("%s: num_steps >= 0, cameras_per_step >= 1, report_interval >= 1" % who)
+    if not learning_rate > 0:
+        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
+    alpha_u8 = None if alpha_threshold is None else _alpha_byte(who, alpha_threshold)
+    images, cameras, width, height = _mesh_dataset_check(who, "train_dataset", train_dataset)
+    if alpha_u8 is not None and images.shape[-1] != 4:
+        raise ValueError("%s: alpha_threshold needs train_dataset.images with an alpha channel, "
+                         "got %s" % (who, images.shape))
+    if val_dataset is not None:
+        _, val_cameras, val_width, val_height = _mesh_dataset_check(who, "val_dataset",
+                                                                    val_dataset)
+    _mesh_ids_check(who, triangles, num_vertices)
+    from .octree_fit import FitLogEntry
+    import time
+
+    as_numpy = not torch.is_tensor(texture)
+    device = train_dataset.colors.device
+    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    uvs = _on(uvs, "float32", device)
+    data = _on(texture, "float32", device).reshape(-1, 3).clone()
+    num_texels = data.shape[0]
+    flat = data.view(-1)
+    grads = torch.empty_like(data)
+    weight = torch.empty((num_texels,), dtype=torch.float32, device=device)
+    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
+    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=device)
+    projections = [supersample_projection(camera, 1) for camera in cameras]
+    per = width * height
+    pixels = torch.arange(per, dtype=torch.int64, device=device)
+    alphas = train_dataset._gt_alphas()
+    kept, cache, val_taps = {}, {}, None
+    generator = torch.Generator()
+    generator.manual_seed(int(seed))
+    losses, reports = [], {}
+    start_time = time.time()
+    step = 0
+    while step < num_steps:
+        deal = torch.randperm(len(cameras), generator=generator).tolist()
+        for start in range(0, len(deal), cameras_per_step):
+            if step >= num_steps:
+                break
+            chosen = deal[start:start + cameras_per_step]
+            count = len(chosen) * per
+            total = None
+            for number, camera in enumerate(chosen):
+                taps = cache.get(camera)
+                if taps is None:
+                    taps = _taps(vertices, triangles, uvs, projections[camera], width, height,
+                                 size)
+                    if cache_taps:
+                        cache[camera] = taps
+                color, alpha = ops.mesh_texture_gather(taps.tap_texel, taps.tap_weight, data)
+                sums, d_color, _ = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
+                                                pixels + camera * per, 1.0 / (3 * count), 0.0)
+                if alpha_u8 is not None:
+                    if camera not in kept:
+                        kept[camera] = torch.from_numpy(
+                            images[camera][..., 3].reshape(-1, 1) >= alpha_u8).to(device)
+                    d_color = torch.where(kept[camera], d_color, torch.zeros_like(d_color))
+                ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight,
+                                      d_color, num_texels, grads, weight, accumulate=number > 0)
+                total = sums if total is None else total + sums
+            losses.append(ops.loss_value(total, count, 0.0))
+            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
+                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
+            data.clamp_(0, 1)
+            if val_dataset is not None and (step < 10 or step % report_interval == 0):
+                if val_taps is None:
+                    val_taps = [_taps(vertices, triangles, uvs, supersample_projection(camera, 1),
+                                      val_width, val_height, size) for camera in val_cameras]
+                reports[step] = _texture_psnr(val_taps, data, val_dataset, val_width, val_height)
+                if verbose:
+                    now = time.time()
+                    per_step = (now - start_time) / step if step >= report_interval else 0
+                    eta = "N/A" if not per_step else time.strftime(
+                        "%a, %d %b %Y %H:%M:%S +0000",
+                        time.gmtime(now + (num_steps - step) * per_step))
+                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
+                          "loss: {:2f}".format(float(losses[-1].item())),
+                          "val_psnr: {:2f}".format(reports[step]),
+                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
+            step += 1
+    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
+    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
+           for k in range(len(values))]
+    data = data.view(size + (3,))
     return (data.cpu().numpy() if as_numpy else data), log

@@ -2464,3 +2464,140 @@ def mesh_vertex_gather(face_sums: torch.Tensor, corner_order: torch.Tensor,
           c_i64(num_vertices), _dev(grad, name="grad"), _dev(weight, name="weight"),
           c_i(1 if accumulate else 0))
     return grad, weight
+
+
+# --------------------------------------------------------------------------------- K33
+MESH_TEXTURE_MAX_TEXELS = (2 ** 31 - 1) // 3    # 3 T floats index in an int32
+MESH_TEXTURE_MAX_PIXELS = 1 << 28               # 4 P tap slots index in an int32
+
+
+def _texture_check_size(who, tex_height, tex_width):
+    if (not 1 <= tex_height <= MESH_MAX_TEXTURE_SIDE or not 1 <= tex_width <= MESH_MAX_TEXTURE_SIDE
+            or tex_height * tex_width > MESH_TEXTURE_MAX_TEXELS):
+        raise ValueError("%s: the texture must be 1 .. 2^24 a side with at most (2^31 - 1) / 3 "
+                         "texels, got %d x %d" % (who, tex_height, tex_width))
+
+
+def _texture_check_taps(who, tap_texel, tap_weight) -> int:
+    _raster_want(who, "tap_texel", tap_texel, torch.int32, (None, 4))
+    num_pixels = tap_texel.shape[0]
+    if not 1 <= num_pixels <= MESH_TEXTURE_MAX_PIXELS:
+        raise ValueError("%s: tap_texel holds %d pixels; 1 .. 2^28 are supported"
+                         % (who, num_pixels))
+    _raster_want(who, "tap_weight", tap_weight, torch.float32, (num_pixels, 4))
+    return num_pixels
+
+
+def mesh_texture_taps_check(record, ids, triangles, uvs, tex_height: int, tex_width: int,
+                            width: int, height: int) -> None:
+    """The refusals of ``mesh_texture_taps`` that need no device."""
+    who = "mesh_texture_taps"
+    _raster_want(who, "triangles", triangles, torch.int32, (None, 3))
+    _raster_want(who, "uvs", uvs, torch.float32, (None, 2))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= triangles.shape[0] <= most:
+        raise ValueError("%s: triangles holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, triangles.shape[0]))
+    if not 1 <= uvs.shape[0] <= most:
+        raise ValueError("%s: uvs holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, uvs.shape[0]))
+    _raster_want(who, "record", record, torch.int32, (triangles.shape[0], 16))
+    _raster_check_image(who, width, height)
+    _raster_want(who, "ids", ids, torch.int32, (width * height,))
+    _texture_check_size(who, tex_height, tex_width)
+
+
+def mesh_texture_taps(record: torch.Tensor, ids: torch.Tensor, triangles: torch.Tensor,
+                      uvs: torch.Tensor, tex_height: int, tex_width: int, width: int, height: int):
+    """K33a.  record (F,16) int32 of K31a, ids (H W,) int32 of K31c, triangles (F,3) int32, uvs
+    (V,2) f32 and the size of the texture -> ``(tap_texel (H W,4) int32, tap_weight (H W,4) f32)``:
+    per pixel the four texels ``i * tex_width + j`` K31c's bilinear lookup blends, in the order 00,
+    01, 10, 11, and their weights, the bits K31c uses.  A pixel whose id is outside ``0 .. F - 1``
+    is uncovered: texels -1, weights +0."""
+    tex_height, tex_width = int(tex_height), int(tex_width)
+    width, height = int(width), int(height)
+    mesh_texture_taps_check(record, ids, triangles, uvs, tex_height, tex_width, width, height)
+    tap_texel = torch.empty((width * height, 4), dtype=torch.int32, device=record.device)
+    tap_weight = torch.empty((width * height, 4), dtype=torch.float32, device=record.device)
+    _call("ffn_mesh_texture_taps", _dev(record, torch.int32, "record"),
+          _dev(ids, torch.int32, "ids"), _dev(triangles, torch.int32, "triangles"),
+          c_i64(triangles.shape[0]), _dev(uvs, name="uvs"), c_i64(uvs.shape[0]), c_i(tex_height),
+          c_i(tex_width), c_i(width), c_i(height), _dev(tap_texel, torch.int32),
+          _dev(tap_weight))
+    return tap_texel, tap_weight
+
+
+def mesh_texture_gather_check(tap_texel, tap_weight, texture, background):
+    """The refusals of ``mesh_texture_gather`` that need no device -> ``background`` as 3 host
+    floats."""
+    who = "mesh_texture_gather"
+    _texture_check_taps(who, tap_texel, tap_weight)
+    _raster_want(who, "texture", texture, torch.float32, (None, 3))
+    if not 1 <= texture.shape[0] <= MESH_TEXTURE_MAX_TEXELS:
+        raise ValueError("%s: texture holds %d texels; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, texture.shape[0]))
+    return _raster_host(who, "background", background, 3)
+
+
+def mesh_texture_gather(tap_texel: torch.Tensor, tap_weight: torch.Tensor, texture: torch.Tensor,
+                        background=(0, 0, 0)):
+    """K33b.  The taps of K33a and ``texture`` (T,3) f32, plain floats -> ``(color (P,3), alpha
+    (P,))`` f32: ``((w00 t00 + w01 t01) + w10 t10) + w11 t11`` per channel and 1 for a covered
+    pixel, ``background`` and 0 for an uncovered one (``tap_texel[p][0] < 0``).  A tap whose texel
+    is outside ``0 .. T - 1`` contributes +0."""
+    background_c = mesh_texture_gather_check(tap_texel, tap_weight, texture, background)
+    num_pixels = tap_texel.shape[0]
+    color = torch.empty((num_pixels, 3), dtype=torch.float32, device=tap_texel.device)
+    alpha = torch.empty((num_pixels,), dtype=torch.float32, device=tap_texel.device)
+    _call("ffn_mesh_texture_gather", _dev(tap_texel, torch.int32, "tap_texel"),
+          _dev(tap_weight, name="tap_weight"), _dev(texture, name="texture"),
+          c_i64(texture.shape[0]), background_c, c_i64(num_pixels), _dev(color), _dev(alpha))
+    return color, alpha
+
+
+def mesh_texture_grad_check(sorted_texels, tap_order, tap_weight, d_color, num_texels: int,
+                            grad=None, weight=None, accumulate: bool = False) -> int:
+    """The refusals of ``mesh_texture_grad`` that need no device -> the number of pixels."""
+    who = "mesh_texture_grad"
+    _raster_want(who, "tap_weight", tap_weight, torch.float32, (None, 4))
+    num_pixels = tap_weight.shape[0]
+    if not 1 <= num_pixels <= MESH_TEXTURE_MAX_PIXELS:
+        raise ValueError("%s: tap_weight holds %d pixels; 1 .. 2^28 are supported"
+                         % (who, num_pixels))
+    _raster_want(who, "sorted_texels", sorted_texels, torch.int32, (4 * num_pixels,))
+    _raster_want(who, "tap_order", tap_order, torch.int32, (4 * num_pixels,))
+    _raster_want(who, "d_color", d_color, torch.float32, (num_pixels, 3))
+    if int(num_texels) != num_texels or not 1 <= num_texels <= MESH_TEXTURE_MAX_TEXELS:
+        raise ValueError("%s: num_texels must be an integer in 1 .. (2^31 - 1) / 3, got %r"
+                         % (who, num_texels))
+    if (grad is None) != (weight is None):
+        raise ValueError("%s: give both grad and weight, or neither" % who)
+    if accumulate and grad is None:
+        raise ValueError("%s: accumulate needs grad and weight to add to" % who)
+    if grad is not None:
+        _raster_want(who, "grad", grad, torch.float32, (int(num_texels), 3))
+        _raster_want(who, "weight", weight, torch.float32, (int(num_texels),))
+    return num_pixels
+
+
+def mesh_texture_grad(sorted_texels: torch.Tensor, tap_order: torch.Tensor,
+                      tap_weight: torch.Tensor, d_color: torch.Tensor, num_texels: int,
+                      grad: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                      accumulate: bool = False):
+    """K33c.  ``sorted_texels`` and ``tap_order`` (4P,) int32: the tap slots ``4 p + k`` stably
+    sorted by ``tap_texel`` (``mesh.mesh_texture_taps`` makes them); ``tap_weight`` (P,4) and
+    ``d_color`` (P,3) f32 -> ``(grad (T,3), weight (T,))`` f32: per texel, over its taps in sorted
+    order, the sums of ``w * d_color[p]`` and of ``w``; a tap with ``!(w > 0)`` is skipped, so a NaN
+    weight reaches no texel.  One thread per texel, no atomics.  ``grad`` and ``weight`` are written
+    in place when given, and with ``accumulate`` added to (``out = out + value``)."""
+    num_pixels = mesh_texture_grad_check(sorted_texels, tap_order, tap_weight, d_color,
+                                         num_texels, grad, weight, accumulate)
+    num_texels = int(num_texels)
+    if grad is None:
+        grad = torch.empty((num_texels, 3), dtype=torch.float32, device=tap_weight.device)
+        weight = torch.empty((num_texels,), dtype=torch.float32, device=tap_weight.device)
+    _call("ffn_mesh_texture_grad", _dev(sorted_texels, torch.int32, "sorted_texels"),
+          _dev(tap_order, torch.int32, "tap_order"), _dev(tap_weight, name="tap_weight"),
+          _dev(d_color, name="d_color"), c_i64(num_pixels), c_i64(num_texels),
+          _dev(grad, name="grad"), _dev(weight, name="weight"), c_i(1 if accumulate else 0))
+    return grad, weight

@@ -1652,7 +1652,7 @@ int ffn_mesh_raster_resolve(const uint64_t* zbuf, const int32_t* record, const f
  * K32  the adjoint of K31c's colour interpolation (csrc/mesh_raster_grad.hip).  No counterpart in
  * the reference.  K31's colour is (c_v0 b0 + c_v1 b1) + c_v2 b2 with b_i from the geometry alone:
  * the image is a linear map of the vertex colours, and these two launches are its transpose, for
- * the per-vertex colours only (the textured path has no backward, the geometry no gradient).  No
+ * the per-vertex colours only (the textured path's transpose is K33, the geometry has no gradient).  No
  * float atomics and no LDS; every float operation is one rounded f32 operation in the order
  * written: the same inputs give the same bits on every call.  Limits as in K31: 1 <= width, height
  * <= 16384; 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; bad shapes and null pointers are
@@ -1689,6 +1689,64 @@ int ffn_mesh_vertex_gather(const float* face_sums, const int32_t* corner_order,
                            const int32_t* vertex_starts, int64_t num_triangles,
                            int64_t num_vertices, float* grad, float* weight, int accumulate,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K33  K31c's textured colour as a sparse matrix and its two products (csrc/mesh_texture.hip).  No
+ * counterpart in the reference.  K31c's textured colour is a bilinear blend of four texels whose
+ * indices and weights come from the geometry, the camera and the UVs alone: the image is a linear
+ * map of the texture with four entries (taps) per covered pixel.  K33a makes the taps, K33b applies
+ * them to a float texture and K33c their transpose to an image.  No float atomics and no LDS; every
+ * float operation is one rounded f32 operation in the order written: the same inputs give the same
+ * bits on every call.  Every index read from an input array is held against its range before it is
+ * used: foreign ids, taps or orders give wrong numbers, never an access outside the buffers.
+ * Limits: 1 <= width, height <= 16384 and 1 <= num_pixels <= 2^28; 1 <= num_vertices,
+ * num_triangles <= (2^31 - 1) / 3; 1 <= tex_height, tex_width <= 2^24 and num_texels =
+ * tex_height tex_width <= (2^31 - 1) / 3; bad shapes and null pointers are refused by name before
+ * any launch.  tap_texel and tap_weight are 16-byte aligned.
+ *
+ * K33a, one thread per pixel p.  record (num_triangles,16) int32, 16-byte aligned, from K31a; ids
+ * (height width) int32 from K31c; triangles (num_triangles,3) int32; uvs (num_vertices,2) f32.
+ *   f = ids[p] outside 0 .. num_triangles - 1: the pixel is uncovered, tap_texel[p][0..3] = -1 and
+ *   tap_weight[p][0..3] = +0
+ *   else E_i, l_i, q_i, depth_w as in K31b (the same bits); b_i = q_i * depth_w; the vertex ids
+ *   clamped into 0 .. num_vertices - 1; u = (u0 b0 + u1 b1) + u2 b2, v likewise; then the index and
+ *   weight arithmetic of ffn_mesh_sample's lookup: col = u tex_width, row = v tex_height,
+ *   fj = floorf(col), fi = floorf(row), dj = col - fj, di = row - fi (before clamping),
+ *   j0 = clamp(fj), j1 = clamp(fj + 1) into 0 .. tex_width - 1 (as floats; NaN clamps to 0), i0 and
+ *   i1 likewise, w00 = (1 - di)(1 - dj), w01 = (1 - di) dj, w10 = di (1 - dj), w11 = di dj
+ * tap_texel (height width,4) int32 = i tex_width + j in the order 00, 01, 10, 11 (i0 j0, i0 j1,
+ * i1 j0, i1 j1); tap_weight (height width,4) f32 the weights in that order.
+ *
+ * K33b, one thread per pixel p.  texture (num_texels,3) f32, plain floats (no / 255); background: 3
+ * floats in HOST memory.
+ *   tap_texel[p][0] < 0: color[p] = background, alpha[p] = 0
+ *   else term_k = tap_weight[p][k] * texture[tap_texel[p][k]][ch], or +0.0f by selection when the
+ *   texel is outside 0 .. num_texels - 1 (it is not read);
+ *   color[p][ch] = ((term_0 + term_1) + term_2) + term_3;  alpha[p] = 1
+ * color (num_pixels,3), alpha (num_pixels) f32.
+ *
+ * K33c, one thread per texel t.  sorted_texels (4 num_pixels) int32, ascending, and tap_order
+ * (4 num_pixels) int32: the tap slots 4 p + k stably sorted by tap_texel, made by the caller (the -1
+ * slots sort first and belong to no texel).  d_color (num_pixels,3) f32.
+ *   the row of t is [lower_bound(t), lower_bound(t + 1)) of sorted_texels (binary searches; both
+ *   ends lie in 0 .. 4 num_pixels whatever the array holds).  From 0.0f and in that order, for the
+ *   slot s = tap_order[at] and w = tap_weight[s]:
+ *     skipped by selection, not multiplied by zero, when s is outside 0 .. 4 num_pixels - 1 or
+ *     !(w > 0.0f): a NaN weight, or a zero weight over a non-finite d_color, reaches no texel
+ *     else g[ch] = g[ch] + w * d_color[s / 4][ch], ch = 0 .. 2;  wsum = wsum + w
+ * grad (num_texels,3) = g and weight (num_texels) = wsum, or with accumulate != 0 out = out +
+ * value, one add each.  The loop is linear in the length of the row. */
+int ffn_mesh_texture_taps(const int32_t* record, const int32_t* ids, const int32_t* triangles,
+                          int64_t num_triangles, const float* uvs, int64_t num_vertices,
+                          int tex_height, int tex_width, int width, int height,
+                          int32_t* tap_texel, float* tap_weight, void* stream);
+int ffn_mesh_texture_gather(const int32_t* tap_texel, const float* tap_weight,
+                            const float* texture, int64_t num_texels, const float* background,
+                            int64_t num_pixels, float* color, float* alpha, void* stream);
+int ffn_mesh_texture_grad(const int32_t* sorted_texels, const int32_t* tap_order,
+                          const float* tap_weight, const float* d_color, int64_t num_pixels,
+                          int64_t num_texels, float* grad, float* weight, int accumulate,
+                          void* stream);
 
 #ifdef __cplusplus
 }
