@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import ops
 from .dataset import RayDataset
+from .fit_loop import report_line
 from .occupancy import OccupancyGrid
 from .sampler import RaySampler, RaySamples
 from .utils import RenderResult, check_color_space, learning_rate_at
@@ -662,18 +663,10 @@ class Raycaster(nn.Module):
                     train_psnr = self._validate(engine, trainval_dataset, batch_size, step)
                     val_psnr = self._validate(engine, val_dataset, batch_size, step)
                     now = time.time()
-                    if step >= report_interval:
-                        per_step = (now - start_time) / step
-                        eta = time.strftime("%a, %d %b %Y %H:%M:%S +0000",
-                                            time.gmtime(now + (num_steps - step) * per_step))
-                    else:
-                        per_step = 0
-                        eta = "N/A"
                     if is_main:
-                        print("{:07}".format(step), "{:2f} s/step".format(per_step),
-                              "psnr_train: {:2f}".format(train_psnr),
-                              "val_psnr: {:2f}".format(val_psnr), "lr: {:.2e}".format(lr),
-                              "eta:", eta)
+                        print(report_line(step, num_steps, report_interval, start_time, now,
+                                          [("psnr_train", train_psnr), ("val_psnr", val_psnr)],
+                                          lr))
                     if step % report_interval == 0:
                         state = copy.deepcopy(self.model.state_dict())
                         log.append(LogEntry(step, now - start_time, state, train_psnr, val_psnr))

@@ -41,7 +41,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import fit_loop, ops
 
 Mesh = Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]
 
@@ -580,6 +580,17 @@ def _on(x, dtype, device):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(device)
 
 
+def _mesh_on(vertices, triangles, device=None):
+    """numpy in, numpy out -> (whether ``vertices`` came as numpy, the device, ``vertices`` float32
+    and ``triangles`` int32 as tensors on it).  ``device`` defaults to that of ``vertices`` when
+    they are a GPU tensor, else the GPU."""
+    if device is None:
+        device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
+    device = torch.device(device)
+    return (not torch.is_tensor(vertices), device, _on(vertices, "float32", device),
+            _on(triangles, "int32", device))
+
+
 def vertex_adjacency(triangles, num_vertices: int, device=None):
     """Which corners use every vertex -> ``(corner_order (3F,) int32, vertex_starts (V+1,) int32)``
     tensors on ``device`` (default: the tensor's own, or the GPU for a numpy array):
@@ -724,10 +735,7 @@ def render_mesh_backward(vertices, triangles, camera, d_color, adjacency=None, g
     if (grad is None) != (weight is None) or (accumulate and grad is None):
         raise ValueError("%s: give both grad and weight, or neither; accumulate needs them" % who)
     _mesh_ids_check(who, triangles, num_vertices)
-    as_numpy = not torch.is_tensor(vertices)
-    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
-    device = torch.device(device)
-    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    as_numpy, device, vertices, triangles = _mesh_on(vertices, triangles)
     if adjacency is None:
         adjacency = vertex_adjacency(triangles, num_vertices, device)
     record, ids = _raster_ids(vertices, triangles, supersample_projection(camera, 1), width,
@@ -739,15 +747,6 @@ def render_mesh_backward(vertices, triangles, camera, d_color, adjacency=None, g
     if as_numpy:
         return grad.cpu().numpy(), weight.cpu().numpy()
     return grad, weight
-
-
-def _mean_vertex_colors(sums: np.ndarray, weights: np.ndarray, colors: np.ndarray):
-    """``sums / weights`` (float32, one division per channel) where ``weights > 0``, ``colors``
-    elsewhere -> (colors (V,3) float32, weights)."""
-    out = np.array(colors, dtype=np.float32, copy=True)
-    seen = weights > 0
-    out[seen] = sums[seen].astype(np.float32) / weights[seen].astype(np.float32)[:, None]
-    return out, weights
 
 
 def color_mesh_from_images(vertices, triangles, dataset, colors=None,
@@ -770,51 +769,125 @@ def color_mesh_from_images(vertices, triangles, dataset, colors=None,
     alpha_u8 = _alpha_byte(who, alpha_threshold)
     images, cameras, width, height = _mesh_dataset_check(who, "dataset", dataset)
     _mesh_ids_check(who, triangles, num_vertices)
-    as_numpy = not torch.is_tensor(vertices)
-    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
-    device = torch.device(device)
-    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    as_numpy, device, vertices, triangles = _mesh_on(vertices, triangles)
     order, starts = vertex_adjacency(triangles, num_vertices, device)
-    total = torch.zeros((num_vertices, 3), dtype=torch.float32, device=device)
-    weights = torch.zeros((num_vertices,), dtype=torch.float32, device=device)
-    for number, camera in enumerate(cameras):
+
+    def splat(camera, hidden, rgb, total, weights, accumulate):
         record, ids = _raster_ids(vertices, triangles, supersample_projection(camera, 1), width,
                                   height, 1 << 22)
+        if hidden is not None:
+            ids = ids.masked_fill(hidden, -1)
+        face_sums = ops.mesh_raster_face_sums(record, ids, rgb, width, height)
+        ops.mesh_vertex_gather(face_sums, order, starts, total, weights, accumulate)
+
+    return _mean_from_images(images, cameras, alpha_u8, colors, num_vertices, splat, device,
+                             as_numpy)
+
+
+def _mean_from_images(images, cameras, alpha_u8, given, count, splat, device, as_numpy):
+    """What ``color_mesh_from_images`` and ``texture_mesh_from_images`` share -> ``(colors
+    (count,3), weights (count,))``.  Over the cameras in order, ``splat(camera, hidden, rgb, total,
+    weights, accumulate)`` adds the camera's weighted colours and weights to the two buffers:
+    ``hidden`` (H W,) bool marks the pixels whose alpha byte is below ``alpha_u8`` (None for images
+    without alpha).  A row nobody saw keeps ``given``'s, or 0.5 grey when ``given`` is None."""
+    total = torch.zeros((count, 3), dtype=torch.float32, device=device)
+    weights = torch.zeros((count,), dtype=torch.float32, device=device)
+    for number, camera in enumerate(cameras):
         frame = images[number]
+        hidden = None
         if frame.shape[-1] == 4:
             hidden = torch.from_numpy(frame[..., 3].reshape(-1) < alpha_u8).to(device)
-            ids = ids.masked_fill(hidden, -1)
         rgb = (frame[..., :3].astype(np.float32) / 255).reshape(-1, 3)      # as ImageDataset
-        face_sums = ops.mesh_raster_face_sums(record, ids, torch.from_numpy(rgb).to(device),
-                                              width, height)
-        ops.mesh_vertex_gather(face_sums, order, starts, total, weights, accumulate=number > 0)
+        splat(camera, hidden, torch.from_numpy(rgb).to(device), total, weights, number > 0)
+    out = np.full((count, 3), 0.5, dtype=np.float32) if given is None else \
+        np.array(given.detach().cpu().numpy() if torch.is_tensor(given) else given,
+                 dtype=np.float32).reshape(-1, 3)
     # (the division on the host: one IEEE f32 division per channel, whatever the device's is)
-    base = np.full((num_vertices, 3), 0.5, dtype=np.float32) if colors is None else \
-        np.array(colors.detach().cpu().numpy() if torch.is_tensor(colors) else colors,
-                 dtype=np.float32)
-    out, weights_host = _mean_vertex_colors(total.cpu().numpy(), weights.cpu().numpy(), base)
+    sums, weights_host = total.cpu().numpy(), weights.cpu().numpy()
+    seen = weights_host > 0
+    out[seen] = sums[seen] / weights_host[seen][:, None]
     if as_numpy:
         return out, weights_host
     return torch.from_numpy(out).to(device), weights
 
 
-def _mesh_psnr(vertices, triangles, data, dataset, cameras, width, height) -> float:
-    """-10 log10 of the mean colour-MSE over every pixel of the dataset's cameras."""
-    from .cameras import eye_positions
+def _fit_mesh(who, num_vertices, vertices, triangles, start, setup, train_dataset, val_dataset,
+              num_steps, learning_rate, cameras_per_step, report_interval, alpha_threshold,
+              clip_value, max_norm, seed, verbose):
+    """What ``fit_mesh_colors`` and ``fit_mesh_texture`` do alike, after the refusals of their own
+    buffer ``start``: the other refusals (the vertex ids last; none touches the device), then
+    ``fit_loop.run`` on a copy of ``start`` as an (n,3) buffer on the dataset's device ->
+    ``(data, log)``, with the step their docstrings describe.  ``setup(vertices, triangles, data,
+    view, val_view)`` gets the mesh on the device and ``(cameras, width, height)`` of the two
+    datasets (``val_view`` None without one) and returns ``(frame, val_frame, transpose)``:
+    ``frame(camera) -> (color, alpha, ctx)`` and ``transpose(ctx, d_color, grads, weight,
+    accumulate)``, which accumulates from a step's second camera on."""
+    fit_loop.check_schedule(who, "num_steps >= 0, cameras_per_step >= 1, report_interval >= 1",
+                            cameras_per_step, num_steps, report_interval, learning_rate)
+    cameras_per_step = int(cameras_per_step)
+    alpha_u8 = None if alpha_threshold is None else _alpha_byte(who, alpha_threshold)
+    images, *view = _mesh_dataset_check(who, "train_dataset", train_dataset)
+    if alpha_u8 is not None and images.shape[-1] != 4:
+        raise ValueError("%s: alpha_threshold needs train_dataset.images with an alpha channel, "
+                         "got %s" % (who, images.shape))
+    val_view = None if val_dataset is None else \
+        _mesh_dataset_check(who, "val_dataset", val_dataset)[1:]
+    _mesh_ids_check(who, triangles, num_vertices)
+    _, device, vertices, triangles = _mesh_on(vertices, triangles, train_dataset.colors.device)
+    data = _on(start, "float32", device).reshape(-1, 3).clone()
+    frame, val_frame, transpose = setup(vertices, triangles, data, view, val_view)
+    cameras, width, height = view
     per = width * height
-    device = vertices.device
-    alphas = dataset._gt_alphas()
-    total = torch.zeros((2,), dtype=torch.float32, device=device)
+    weight = torch.empty((data.shape[0],), dtype=torch.float32, device=device)
     pixels = torch.arange(per, dtype=torch.int64, device=device)
+    alphas = train_dataset._gt_alphas()
+    kept = {}
+    generator = torch.Generator()
+    generator.manual_seed(int(seed))
+
+    def epoch():
+        deal = torch.randperm(len(cameras), generator=generator).tolist()
+        return [deal[first:first + cameras_per_step]
+                for first in range(0, len(deal), cameras_per_step)]
+
+    def step(chosen, grads):
+        count = len(chosen) * per
+        total = None
+        for number, camera in enumerate(chosen):
+            color, alpha, ctx = frame(camera)
+            sums, d_color, _ = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
+                                            pixels + camera * per, 1.0 / (3 * count), 0.0)
+            if alpha_u8 is not None:
+                if camera not in kept:
+                    kept[camera] = torch.from_numpy(
+                        images[camera][..., 3].reshape(-1, 1) >= alpha_u8).to(device)
+                d_color = torch.where(kept[camera], d_color, torch.zeros_like(d_color))
+            transpose(ctx, d_color, grads, weight, number > 0)
+            total = sums if total is None else total + sums
+        return ops.loss_value(total, count, 0.0)
+
+    def validate():
+        return fit_loop.camera_psnr(val_frame, len(val_view[0]), val_view[1] * val_view[2],
+                                    val_dataset)
+
+    log = fit_loop.run(data, epoch, step, lambda rows: rows.clamp_(0, 1),
+                       validate if val_dataset is not None else None, int(num_steps),
+                       learning_rate, report_interval, clip_value, max_norm, verbose)
+    return data, log
+
+
+def _color_frames(vertices, triangles, data, cameras, width, height):
+    """-> ``frame(number)``: K31's picture of ``cameras[number]`` with the vertex colours ``data`` as
+    they are at the call -> (color, alpha, (record, ids)).  One read-back per frame."""
+    from .cameras import eye_positions
+    projections = [supersample_projection(camera, 1) for camera in cameras]
     eyes = eye_positions(cameras, (0.0, 0.0, 0.0))
-    for number, camera in enumerate(cameras):
-        color, alpha = rasterize_mesh(vertices, triangles, supersample_projection(camera, 1),
-                                      eyes[number], width, height, data)[:2]
-        sums, _, _ = ops.mse_loss(color, alpha, dataset.colors, alphas, pixels + number * per,
-                                  0.0, 0.0, want_grad=False)
-        total += sums
-    mean = float(total.cpu().numpy().astype(np.float64)[0]) / (3 * per * len(cameras))
-    return float(-10.0 * np.log10(max(mean, 1e-12)))
+
+    def frame(number):
+        record, color, alpha, _, ids, _, _ = _rasterize(
+            vertices, triangles, projections[number], eyes[number], width, height, data)
+        return color, alpha, (record, ids)
+    return frame
 
 
 def fit_mesh_colors(vertices, triangles, colors, train_dataset, val_dataset=None,
@@ -847,89 +920,22 @@ def fit_mesh_colors(vertices, triangles, colors, train_dataset, val_dataset=None
     if colors is None:
         raise ValueError("%s: colors must be (V,3), got None (color_mesh_from_images makes a "
                          "start)" % who)
-    num_steps, cameras_per_step = int(num_steps), int(cameras_per_step)
-    if num_steps < 0 or cameras_per_step < 1 or int(report_interval) < 1:
-        raise ValueError("%s: num_steps >= 0, cameras_per_step >= 1, report_interval >= 1" % who)
-    if not learning_rate > 0:
-        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
-    alpha_u8 = None if alpha_threshold is None else _alpha_byte(who, alpha_threshold)
-    images, cameras, width, height = _mesh_dataset_check(who, "train_dataset", train_dataset)
-    if alpha_u8 is not None and images.shape[-1] != 4:
-        raise ValueError("%s: alpha_threshold needs train_dataset.images with an alpha channel, "
-                         "got %s" % (who, images.shape))
-    if val_dataset is not None:
-        _, val_cameras, val_width, val_height = _mesh_dataset_check(who, "val_dataset",
-                                                                    val_dataset)
-    _mesh_ids_check(who, triangles, num_vertices)
-    from .cameras import eye_positions
-    from .octree_fit import FitLogEntry
-    import time
 
-    as_numpy = not torch.is_tensor(vertices)
-    device = train_dataset.colors.device
-    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
-    data = _on(colors, "float32", device).clone()
-    flat = data.view(-1)
-    grads = torch.empty_like(data)
-    weight = torch.empty((num_vertices,), dtype=torch.float32, device=device)
-    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
-    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=device)
-    order, starts = vertex_adjacency(triangles, num_vertices, device)
-    projections = [supersample_projection(camera, 1) for camera in cameras]
-    eyes = eye_positions(cameras, (0.0, 0.0, 0.0))
-    per = width * height
-    pixels = torch.arange(per, dtype=torch.int64, device=device)
-    alphas = train_dataset._gt_alphas()
-    kept = {}
-    generator = torch.Generator()
-    generator.manual_seed(int(seed))
-    losses, reports = [], {}
-    start_time = time.time()
-    step = 0
-    while step < num_steps:
-        deal = torch.randperm(len(cameras), generator=generator).tolist()
-        for start in range(0, len(deal), cameras_per_step):
-            if step >= num_steps:
-                break
-            chosen = deal[start:start + cameras_per_step]
-            count = len(chosen) * per
-            total = None
-            for number, camera in enumerate(chosen):
-                record, color, alpha, _, ids, _, _ = _rasterize(
-                    vertices, triangles, projections[camera], eyes[camera], width, height, data)
-                sums, d_color, _ = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
-                                                pixels + camera * per, 1.0 / (3 * count), 0.0)
-                if alpha_u8 is not None:
-                    if camera not in kept:
-                        kept[camera] = torch.from_numpy(
-                            images[camera][..., 3].reshape(-1, 1) >= alpha_u8).to(device)
-                    d_color = torch.where(kept[camera], d_color, torch.zeros_like(d_color))
-                face_sums = ops.mesh_raster_face_sums(record, ids, d_color, width, height)
-                ops.mesh_vertex_gather(face_sums, order, starts, grads, weight,
-                                       accumulate=number > 0)
-                total = sums if total is None else total + sums
-            losses.append(ops.loss_value(total, count, 0.0))
-            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
-                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
-            data.clamp_(0, 1)
-            if val_dataset is not None and (step < 10 or step % report_interval == 0):
-                reports[step] = _mesh_psnr(vertices, triangles, data, val_dataset, val_cameras,
-                                           val_width, val_height)
-                if verbose:
-                    now = time.time()
-                    per_step = (now - start_time) / step if step >= report_interval else 0
-                    eta = "N/A" if not per_step else time.strftime(
-                        "%a, %d %b %Y %H:%M:%S +0000",
-                        time.gmtime(now + (num_steps - step) * per_step))
-                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
-                          "loss: {:2f}".format(float(losses[-1].item())),
-                          "val_psnr: {:2f}".format(reports[step]),
-                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
-            step += 1
-    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
-    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
-           for k in range(len(values))]
-    return (data.cpu().numpy() if as_numpy else data), log
+    def setup(vertices, triangles, data, view, val_view):
+        order, starts = vertex_adjacency(triangles, num_vertices, data.device)
+
+        def transpose(ctx, d_color, grads, weight, accumulate):
+            face_sums = ops.mesh_raster_face_sums(ctx[0], ctx[1], d_color, view[1], view[2])
+            ops.mesh_vertex_gather(face_sums, order, starts, grads, weight, accumulate=accumulate)
+        # (validation rasterises anew at each report: the colours have changed)
+        val_frame = None if val_view is None else \
+            _color_frames(vertices, triangles, data, *val_view)
+        return _color_frames(vertices, triangles, data, *view), val_frame, transpose
+
+    data, log = _fit_mesh(who, num_vertices, vertices, triangles, colors, setup, train_dataset,
+                          val_dataset, num_steps, learning_rate, cameras_per_step, report_interval,
+                          alpha_threshold, clip_value, max_norm, seed, verbose)
+    return (data if torch.is_tensor(vertices) else data.cpu().numpy()), log
 
 
 # ------------------------------------------------------------------------------------ K33
@@ -1183,11 +1189,9 @@ def mesh_texture_taps(vertices, triangles, uvs, camera, size, batch_size: int = 
     width, height = _camera_size(who, camera)
     size = _texture_size_check(who, size)
     _mesh_ids_check(who, triangles, num_vertices)
-    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
-    device = torch.device(device)
-    return _taps(_on(vertices, "float32", device), _on(triangles, "int32", device),
-                 _on(uvs, "float32", device), supersample_projection(camera, 1), width, height,
-                 size, int(batch_size))
+    _, device, vertices, triangles = _mesh_on(vertices, triangles)
+    return _taps(vertices, triangles, _on(uvs, "float32", device),
+                 supersample_projection(camera, 1), width, height, size, int(batch_size))
 
 
 def _taps_check(who, taps):
@@ -1269,48 +1273,38 @@ def texture_mesh_from_images(vertices, triangles, uvs, dataset, size, texture=No
     alpha_u8 = _alpha_byte(who, alpha_threshold)
     images, cameras, width, height = _mesh_dataset_check(who, "dataset", dataset)
     _mesh_ids_check(who, triangles, num_vertices)
-    as_numpy = not torch.is_tensor(vertices)
-    device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else "cuda"
-    device = torch.device(device)
-    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
+    as_numpy, device, vertices, triangles = _mesh_on(vertices, triangles)
     uvs = _on(uvs, "float32", device)
     num_texels = size[0] * size[1]
-    total = torch.zeros((num_texels, 3), dtype=torch.float32, device=device)
-    weights = torch.zeros((num_texels,), dtype=torch.float32, device=device)
-    for number, camera in enumerate(cameras):
-        frame = images[number]
-        hidden = None
-        if frame.shape[-1] == 4:
-            hidden = torch.from_numpy(frame[..., 3].reshape(-1) < alpha_u8).to(device)
+
+    def splat(camera, hidden, rgb, total, weights, accumulate):
         taps = _taps(vertices, triangles, uvs, supersample_projection(camera, 1), width, height,
                      size, hidden=hidden)
-        rgb = (frame[..., :3].astype(np.float32) / 255).reshape(-1, 3)      # as ImageDataset
-        ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight,
-                              torch.from_numpy(rgb).to(device), num_texels, total, weights,
-                              accumulate=number > 0)
-    base = np.full((num_texels, 3), 0.5, dtype=np.float32) if texture is None else \
-        np.array(texture.detach().cpu().numpy() if torch.is_tensor(texture) else texture,
-                 dtype=np.float32).reshape(-1, 3)
-    out, weights_host = _mean_vertex_colors(total.cpu().numpy(), weights.cpu().numpy(), base)
-    out, weights_host = out.reshape(size + (3,)), weights_host.reshape(size)
-    if as_numpy:
-        return out, weights_host
-    return torch.from_numpy(out).to(device), weights.view(size)
+        ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight, rgb,
+                              num_texels, total, weights, accumulate=accumulate)
+
+    out, weights = _mean_from_images(images, cameras, alpha_u8, texture, num_texels, splat,
+                                     device, as_numpy)
+    return out.reshape(size + (3,)), weights.reshape(size)
 
 
-def _texture_psnr(taps, flat, dataset, width, height) -> float:
-    """-10 log10 of the mean colour-MSE over every pixel of the dataset's cameras."""
-    per = width * height
-    alphas = dataset._gt_alphas()
-    total = torch.zeros((2,), dtype=torch.float32, device=flat.device)
-    pixels = torch.arange(per, dtype=torch.int64, device=flat.device)
-    for number, camera_taps in enumerate(taps):
-        color, alpha = ops.mesh_texture_gather(camera_taps.tap_texel, camera_taps.tap_weight, flat)
-        sums, _, _ = ops.mse_loss(color, alpha, dataset.colors, alphas, pixels + number * per,
-                                  0.0, 0.0, want_grad=False)
-        total += sums
-    mean = float(total.cpu().numpy().astype(np.float64)[0]) / (3 * per * len(taps))
-    return float(-10.0 * np.log10(max(mean, 1e-12)))
+def _texture_frames(vertices, triangles, uvs, data, cameras, width, height, size, keep=True):
+    """-> ``frame(number)``: K33b's picture of ``cameras[number]`` with the texels ``data`` (T,3) as
+    they are at the call -> (color, alpha, taps).  A camera's taps are built when its frame is first
+    asked for (K31a-c + K33a + the sort, with K31's read-backs) and, with ``keep``, kept: a later
+    frame of that camera has no host synchronisation."""
+    projections = [supersample_projection(camera, 1) for camera in cameras]
+    cache = {}
+
+    def frame(number):
+        taps = cache.get(number)
+        if taps is None:
+            taps = _taps(vertices, triangles, uvs, projections[number], width, height, size)
+            if keep:
+                cache[number] = taps
+        color, alpha = ops.mesh_texture_gather(taps.tap_texel, taps.tap_weight, data)
+        return color, alpha, taps
+    return frame
 
 
 def fit_mesh_texture(vertices, triangles, uvs, texture, train_dataset, val_dataset=None,
@@ -1339,92 +1333,19 @@ def fit_mesh_texture(vertices, triangles, uvs, texture, train_dataset, val_datas
         raise ValueError("%s: texture must be a float (H,W,3) array, got None "
                          "(texture_mesh_from_images or bake_vertex_colors makes a start)" % who)
     size = _texture_check(who, texture)
-    num_steps, cameras_per_step = int(num_steps), int(cameras_per_step)
-    if num_steps < 0 or cameras_per_step < 1 or int(report_interval) < 1:
-        raise ValueError("%s: num_steps >= 0, cameras_per_step >= 1, report_interval >= 1" % who)
-    if not learning_rate > 0:
-        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
-    alpha_u8 = None if alpha_threshold is None else _alpha_byte(who, alpha_threshold)
-    images, cameras, width, height = _mesh_dataset_check(who, "train_dataset", train_dataset)
-    if alpha_u8 is not None and images.shape[-1] != 4:
-        raise ValueError("%s: alpha_threshold needs train_dataset.images with an alpha channel, "
-                         "got %s" % (who, images.shape))
-    if val_dataset is not None:
-        _, val_cameras, val_width, val_height = _mesh_dataset_check(who, "val_dataset",
-                                                                    val_dataset)
-    _mesh_ids_check(who, triangles, num_vertices)
-    from .octree_fit import FitLogEntry
-    import time
 
-    as_numpy = not torch.is_tensor(texture)
-    device = train_dataset.colors.device
-    vertices, triangles = _on(vertices, "float32", device), _on(triangles, "int32", device)
-    uvs = _on(uvs, "float32", device)
-    data = _on(texture, "float32", device).reshape(-1, 3).clone()
-    num_texels = data.shape[0]
-    flat = data.view(-1)
-    grads = torch.empty_like(data)
-    weight = torch.empty((num_texels,), dtype=torch.float32, device=device)
-    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
-    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=device)
-    projections = [supersample_projection(camera, 1) for camera in cameras]
-    per = width * height
-    pixels = torch.arange(per, dtype=torch.int64, device=device)
-    alphas = train_dataset._gt_alphas()
-    kept, cache, val_taps = {}, {}, None
-    generator = torch.Generator()
-    generator.manual_seed(int(seed))
-    losses, reports = [], {}
-    start_time = time.time()
-    step = 0
-    while step < num_steps:
-        deal = torch.randperm(len(cameras), generator=generator).tolist()
-        for start in range(0, len(deal), cameras_per_step):
-            if step >= num_steps:
-                break
-            chosen = deal[start:start + cameras_per_step]
-            count = len(chosen) * per
-            total = None
-            for number, camera in enumerate(chosen):
-                taps = cache.get(camera)
-                if taps is None:
-                    taps = _taps(vertices, triangles, uvs, projections[camera], width, height,
-                                 size)
-                    if cache_taps:
-                        cache[camera] = taps
-                color, alpha = ops.mesh_texture_gather(taps.tap_texel, taps.tap_weight, data)
-                sums, d_color, _ = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
-                                                pixels + camera * per, 1.0 / (3 * count), 0.0)
-                if alpha_u8 is not None:
-                    if camera not in kept:
-                        kept[camera] = torch.from_numpy(
-                            images[camera][..., 3].reshape(-1, 1) >= alpha_u8).to(device)
-                    d_color = torch.where(kept[camera], d_color, torch.zeros_like(d_color))
-                ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight,
-                                      d_color, num_texels, grads, weight, accumulate=number > 0)
-                total = sums if total is None else total + sums
-            losses.append(ops.loss_value(total, count, 0.0))
-            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
-                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
-            data.clamp_(0, 1)
-            if val_dataset is not None and (step < 10 or step % report_interval == 0):
-                if val_taps is None:
-                    val_taps = [_taps(vertices, triangles, uvs, supersample_projection(camera, 1),
-                                      val_width, val_height, size) for camera in val_cameras]
-                reports[step] = _texture_psnr(val_taps, data, val_dataset, val_width, val_height)
-                if verbose:
-                    now = time.time()
-                    per_step = (now - start_time) / step if step >= report_interval else 0
-                    eta = "N/A" if not per_step else time.strftime(
-                        "%a, %d %b %Y %H:%M:%S +0000",
-                        time.gmtime(now + (num_steps - step) * per_step))
-                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
-                          "loss: {:2f}".format(float(losses[-1].item())),
-                          "val_psnr: {:2f}".format(reports[step]),
-                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
-            step += 1
-    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
-    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
-           for k in range(len(values))]
+    def setup(vertices, triangles, data, view, val_view):
+        mesh = (vertices, triangles, _on(uvs, "float32", data.device), data)
+
+        def transpose(taps, d_color, grads, weight, accumulate):
+            ops.mesh_texture_grad(taps.sorted_texels, taps.tap_order, taps.tap_weight, d_color,
+                                  data.shape[0], grads, weight, accumulate=accumulate)
+        # (the validation taps are built once, at the first report)
+        val_frame = None if val_view is None else _texture_frames(*mesh, *val_view, size)
+        return _texture_frames(*mesh, *view, size, keep=cache_taps), val_frame, transpose
+
+    data, log = _fit_mesh(who, num_vertices, vertices, triangles, texture, setup, train_dataset,
+                          val_dataset, num_steps, learning_rate, cameras_per_step, report_interval,
+                          alpha_threshold, clip_value, max_norm, seed, verbose)
     data = data.view(size + (3,))
-    return (data.cpu().numpy() if as_numpy else data), log
+    return (data if torch.is_tensor(texture) else data.cpu().numpy()), log

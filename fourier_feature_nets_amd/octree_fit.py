@@ -7,7 +7,9 @@ leaf.  ``OctreeField`` makes the leaf values a parameter: its forward is ``OcTre
 ``fit_octree`` is the training loop on the kernels of the NeRF path: K6 (loss and its gradient),
 K17a + K17b, K7 (clip and Adam) on the flat ``(4 L,)`` buffer, K17c (projection onto
 ``0 <= rgb <= 1``, ``sigma >= 0``).  A fit does not change the structure of the tree.  No counterpart
-in the reference.
+in the reference.  The loop is ``fit_loop.run``, which the mesh fits use too; ``_fit`` supplies the
+seeded shuffle of the rays, one step's forward and gradient, the projection, the validation and the
+``tv:`` / ``dist:`` fields of the report line.
 
 ``OctreeSHField`` and ``fit_octree_sh`` (K19) are the same for a tree with spherical-harmonic leaves
 (``OcTree.bake_sh``): the parameter is the ``(L, stride)`` buffer in the device layout K18a reads,
@@ -29,17 +31,16 @@ rays' distortion (``OcTree.distortion``) folded into the two walks of the backwa
 the entry points without the term.
 """
 
-import time
 from typing import List, NamedTuple, Tuple
 
 import numpy as np
 import torch
 
-from . import ops
+from . import fit_loop, ops
+from .fit_loop import FitLogEntry
 from .octree import OcTree, refine_actions
 from .utils import RenderResult
 
-FitLogEntry = NamedTuple("FitLogEntry", [("step", int), ("loss", float), ("val_psnr", float)])
 # one round of fit_octree_adaptive: leaves_before = dropped + split + kept, leaves_after = kept +
 # 8 split; weight_quantiles the (min, 25 %, 50 %, 75 %, max) of the measured per-leaf weights
 RefineReport = NamedTuple("RefineReport", [("round", int), ("leaves_before", int), ("dropped", int),
@@ -249,24 +250,18 @@ def _validation_psnr(field, dataset, t_min, min_transmittance) -> float:
     """-10 log10 of the mean colour-MSE + alpha_weight * alpha-MSE over every ray of the
     dataset's cameras, camera by camera."""
     sampler = dataset.sampler
-    shift = torch.tensor(field.center, dtype=torch.float32, device=sampler.starts.device)
-    alphas = dataset._gt_alphas()
-    aw = float(dataset.alpha_weight) if alphas is not None else 0.0
     per = sampler.rays_per_camera
-    total = torch.zeros((2,), dtype=torch.float32, device=sampler.starts.device)
-    with torch.no_grad():
-        for camera in range(sampler.num_cameras):
-            rays = torch.arange(camera * per, (camera + 1) * per, dtype=torch.int64,
-                                device=sampler.starts.device)
-            out = field(sampler.starts[rays] - shift, sampler.directions[rays], t_min, (0, 0, 0),
-                        min_transmittance)
-            sums, _, _ = ops.mse_loss(out.color, out.alpha, dataset.colors, alphas, rays, 0.0, 0.0,
-                                      want_grad=False)
-            total += sums
-    count = per * sampler.num_cameras
-    total = total.cpu().numpy().astype(np.float64)
-    mean = total[0] / (3 * count) + aw * total[1] / count
-    return float(-10.0 * np.log10(max(mean, 1e-12)))
+    shift = torch.tensor(field.center, dtype=torch.float32, device=sampler.starts.device)
+
+    def frame(camera):
+        rays = torch.arange(camera * per, (camera + 1) * per, dtype=torch.int64,
+                            device=sampler.starts.device)
+        with torch.no_grad():
+            return field(sampler.starts[rays] - shift, sampler.directions[rays], t_min, (0, 0, 0),
+                         min_transmittance)
+
+    aw = float(dataset.alpha_weight) if dataset._gt_alphas() is not None else 0.0
+    return fit_loop.camera_psnr(frame, sampler.num_cameras, per, dataset, aw)
 
 
 def fit_octree(tree: OcTree, train_dataset, val_dataset=None, batch_size: int = 4096,
@@ -337,13 +332,12 @@ def fit_octree_sh(tree: OcTree, train_dataset, val_dataset=None, batch_size: int
 def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning_rate, num_steps,
          report_interval, center, t_min, min_transmittance, clip_value, max_norm, seed, verbose,
          tv_weight, tv_eps, dist_weight=0.0):
-    """The loop of ``fit_octree`` / ``fit_octree_sh``; the field supplies the render, the backward,
-    the TV gradient and the projection."""
+    """``fit_octree`` / ``fit_octree_sh`` on ``fit_loop.run``: the checks, the seeded shuffle of all
+    rays, one step's forward and gradient, the validation and the ``tv:`` / ``dist:`` report fields
+    are here; the field supplies the render, the backward, the TV gradient and the projection."""
+    fit_loop.check_schedule(who, "batch_size >= 1, num_steps >= 0, report_interval >= 1",
+                            batch_size, num_steps, report_interval, learning_rate)
     batch_size, num_steps = int(batch_size), int(num_steps)
-    if batch_size < 1 or num_steps < 0 or int(report_interval) < 1:
-        raise ValueError("%s: batch_size >= 1, num_steps >= 0, report_interval >= 1" % who)
-    if not learning_rate > 0:
-        raise ValueError("%s: learning_rate must be positive, got %r" % (who, learning_rate))
     if field_type is OctreeField:
         _refuse_sh(tree, who)
     elif not isinstance(tree, OcTree) or tree.sh_degree is None:
@@ -364,67 +358,54 @@ def _fit(who, field_type, tree, train_dataset, val_dataset, batch_size, learning
     # (refuses a tuple of the wrong shape; None is off, as the default of all zeros)
     tv_on = tv_weight is not None and bool(field._tv_weights(tv_weight).any())
     data = field.data.detach()
-    flat = data.view(-1)
-    grads = torch.empty_like(data)
-    exp_avg, exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
-    scratch = torch.empty(((flat.numel() + 1023) // 1024,), dtype=torch.float32, device=dev)
     shift = torch.tensor(field.center, dtype=torch.float32, device=dev)
     alphas = train_dataset._gt_alphas()
     aw = float(train_dataset.alpha_weight) if alphas is not None else 0.0
     num_rays = sampler.num_cameras * sampler.rays_per_camera
     generator = torch.Generator(device=dev)
     generator.manual_seed(int(seed))
-    losses, reports = [], {}
-    start_time = time.time()
-    step = 0
-    while step < num_steps:
+    ray_dist = None                          # the last step's per-ray distortion, for the report
+
+    def epoch():
         order = torch.randperm(num_rays, generator=generator, device=dev)
-        for start in range(0, num_rays, batch_size):
-            if step >= num_steps:
-                break
-            rays = order[start:start + batch_size]
-            count = int(rays.numel())
-            starts = (sampler.starts[rays] - shift).contiguous()
-            directions = sampler.directions[rays].contiguous()
-            color, alpha, _ = field._render(data, starts, directions, float(t_min),
-                                            (0.0, 0.0, 0.0), float(min_transmittance))
-            sums, d_color, d_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas, rays,
-                                                  1.0 / (3 * count), aw / count)
-            losses.append(ops.loss_value(sums, count, aw))
-            if dist_on:
-                ray_dist = torch.empty((count,), dtype=torch.float32, device=dev)
-                field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
-                               min_transmittance, data=data, out=grads,
-                               dist_scale=dist_weight / count, ray_distortion=ray_dist)
-            else:
-                field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
-                               min_transmittance, data=data, out=grads)
-            if tv_on:
-                field.tv_backward(tv_weight, tv_eps, data=data, out=grads, accumulate=True)
-            ops.clip_adam(flat, grads.view(-1), exp_avg, exp_avg_sq, step + 1, learning_rate,
-                          clip_value=clip_value, max_norm=max_norm, scratch=scratch)
-            field._project(data)
-            if val_dataset is not None and (step < 10 or step % report_interval == 0):
-                reports[step] = _validation_psnr(field, val_dataset, t_min, min_transmittance)
-                if verbose:
-                    now = time.time()
-                    per_step = (now - start_time) / step if step >= report_interval else 0
-                    eta = "N/A" if not per_step else time.strftime(
-                        "%a, %d %b %Y %H:%M:%S +0000",
-                        time.gmtime(now + (num_steps - step) * per_step))
-                    print("{:07}".format(step), "{:2f} s/step".format(per_step),
-                          "loss: {:2f}".format(float(losses[-1].item())),
-                          "val_psnr: {:2f}".format(reports[step]),
-                          *(["tv: {:2f}".format(float(
-                              field.total_variation(tv_weight, tv_eps, data).item()))]
-                            if tv_on else []),
-                          *(["dist: {:2f}".format(float(ray_dist.mean().item()))]
-                            if dist_on else []),
-                          "lr: {:.2e}".format(learning_rate), "eta:", eta)
-            step += 1
-    values = torch.stack(losses).cpu().numpy() if losses else np.zeros(0, np.float32)
-    log = [FitLogEntry(k, float(values[k]), reports.get(k, float("nan")))
-           for k in range(len(values))]
+        return (order[start:start + batch_size] for start in range(0, num_rays, batch_size))
+
+    def step(rays, grads):
+        nonlocal ray_dist
+        count = int(rays.numel())
+        starts = (sampler.starts[rays] - shift).contiguous()
+        directions = sampler.directions[rays].contiguous()
+        color, alpha, _ = field._render(data, starts, directions, float(t_min), (0.0, 0.0, 0.0),
+                                        float(min_transmittance))
+        sums, d_color, d_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas, rays,
+                                              1.0 / (3 * count), aw / count)
+        loss = ops.loss_value(sums, count, aw)
+        if dist_on:
+            ray_dist = torch.empty((count,), dtype=torch.float32, device=dev)
+            field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
+                           min_transmittance, data=data, out=grads,
+                           dist_scale=dist_weight / count, ray_distortion=ray_dist)
+        else:
+            field.backward(starts, directions, d_color, d_alpha, t_min, (0.0, 0.0, 0.0),
+                           min_transmittance, data=data, out=grads)
+        if tv_on:
+            field.tv_backward(tv_weight, tv_eps, data=data, out=grads, accumulate=True)
+        return loss
+
+    def fields():
+        shown = []
+        if tv_on:
+            shown.append(("tv", float(field.total_variation(tv_weight, tv_eps, data).item())))
+        if dist_on:
+            shown.append(("dist", float(ray_dist.mean().item())))
+        return shown
+
+    def validate():
+        return _validation_psnr(field, val_dataset, t_min, min_transmittance)
+
+    log = fit_loop.run(data, epoch, step, field._project,
+                       validate if val_dataset is not None else None, num_steps, learning_rate,
+                       report_interval, clip_value, max_norm, verbose, fields)
     return field.tree(), log
 
 

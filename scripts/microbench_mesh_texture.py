@@ -34,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 import fourier_feature_nets_amd as ffn  # noqa: E402
+from fourier_feature_nets_amd import fit_loop  # noqa: E402
 from fourier_feature_nets_amd import mesh as mesh_module  # noqa: E402
 from fourier_feature_nets_amd import ops  # noqa: E402
 from scripts.microbench_mesh_fit import frames_of  # noqa: E402
@@ -129,7 +130,8 @@ def quality(args):
     c = on_gpu(surface.colors, "float32")
 
     def vertex_psnr(colors):
-        return mesh_module._mesh_psnr(v, t, colors, held, held_cameras, args.size, args.size)
+        frame = mesh_module._color_frames(v, t, colors, held_cameras, args.size, args.size)
+        return fit_loop.camera_psnr(frame, len(held_cameras), args.size * args.size, held)
     out["a_k30_colors_psnr"] = vertex_psnr(c)
     colors, _ = ffn.color_mesh_from_images(v, t, train, c)
     out["b_color_mesh_from_images_psnr"] = vertex_psnr(colors)
@@ -147,8 +149,12 @@ def quality(args):
         held_taps = [ffn.mesh_texture_taps(tv, tt, tuv, camera, size) for camera in held_cameras]
 
         def texture_psnr(texture):
-            return mesh_module._texture_psnr(held_taps, texture.reshape(-1, 3), held, args.size,
-                                             args.size)
+            flat = texture.reshape(-1, 3)
+
+            def frame(number):
+                return ops.mesh_texture_gather(held_taps[number].tap_texel,
+                                               held_taps[number].tap_weight, flat)
+            return fit_loop.camera_psnr(frame, len(held_taps), args.size * args.size, held)
         start = on_gpu(ffn.bake_vertex_colors(surface.colors[vertex_map], triangles, uvs, size,
                                               tile), "float32")
         key = "c_tile_%d" % tile
