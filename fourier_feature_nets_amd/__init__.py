@@ -17,12 +17,13 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import (MeshTaps, bake_vertex_colors, color_mesh_from_images, fit_mesh_colors,
-                   fit_mesh_texture, load_obj, mesh_texture_taps, normalize_points,
-                   procedural_torus, render_mesh, render_mesh_backward, render_mesh_image,
+from .mesh import (MeshTaps, bake_vertex_colors, color_mesh_from_images, edge_opposites,
+                   fit_mesh_colors, fit_mesh_geometry, fit_mesh_texture, load_obj,
+                   mesh_texture_taps, normalize_points, procedural_torus, render_mesh,
+                   render_mesh_backward, render_mesh_geometry_backward, render_mesh_image,
                    render_mesh_texture, render_mesh_texture_backward, sample_mesh, save_obj,
                    texture_mesh_from_images, texture_to_uint8, triangle_counts, unwrap_mesh,
-                   vertex_adjacency)
+                   vertex_adjacency, vertex_neighbors)
 from .models import (
     BasicFourierMLP,
     FourierFeatureMLP,
@@ -48,8 +49,8 @@ __version__ = "0.1.0"
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
            "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "MeshTaps", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
-           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "bake_vertex_colors", "calculate_blend_weights", "color_mesh_from_images",
-           "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_mesh_texture", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "bake_vertex_colors", "calculate_blend_weights", "color_mesh_from_images", "edge_opposites",
+           "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_mesh_geometry", "fit_mesh_texture", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
            "linspace", "load_model", "load_obj", "mesh_texture_taps", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_image", "render_mesh_texture", "render_mesh_texture_backward", "sample_mesh", "save_obj",
-           "texture_mesh_from_images", "texture_to_uint8", "triangle_counts", "unwrap_mesh", "vertex_adjacency"]
+           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_geometry_backward", "render_mesh_image", "render_mesh_texture", "render_mesh_texture_backward", "sample_mesh", "save_obj",
+           "texture_mesh_from_images", "texture_to_uint8", "triangle_counts", "unwrap_mesh", "vertex_adjacency", "vertex_neighbors"]

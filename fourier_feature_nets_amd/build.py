@@ -67,6 +67,9 @@ SOURCES = {
     # K31c's UV interpolation and K22's bilinear weights again, and the sums of w * texel and
     # w * g in a fixed order, every product and add rounded
     "mesh_texture.hip": ["-ffp-contract=off"],
+    # the edge crossing alpha = E(a) / (E(a) - E(b)), the blends out + m * (in[s] - in[p]) and the
+    # sums of the vertex entries in a fixed order, every product, add and quotient rounded
+    "mesh_aa.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -1,7 +1,7 @@
 """The training loop of the explicit-buffer fits: ``fit_octree`` / ``fit_octree_sh`` (K17, K19),
-``fit_mesh_colors`` (K32) and ``fit_mesh_texture`` (K33) all optimise one plain float32 buffer
-against an ``ImageDataset`` with K7 (``ops.clip_adam``), and ``run`` is that loop once; a fit
-supplies what is its own as plain callables.  ``report_line`` is the line a report step prints,
+``fit_mesh_colors`` (K32), ``fit_mesh_texture`` (K33) and ``fit_mesh_geometry`` (K34) all optimise
+one plain float32 buffer against an ``ImageDataset`` with K7 (``ops.clip_adam``), and ``run`` is
+that loop once; a fit supplies what is its own as plain callables.  ``report_line`` is the line a report step prints,
 shared with ``Raycaster.fit``; ``check_schedule`` the refusals the fits have in common, made before
 a fit touches the device; ``camera_psnr`` their validation.  Host code only: no kernel of its own.
 """

@@ -33,6 +33,12 @@ are its two products, ``texture_mesh_from_images`` and ``fit_mesh_texture`` what
 ``color_mesh_from_images`` and ``fit_mesh_colors`` are for vertices.  ``unwrap_mesh`` makes a
 texture atlas for a mesh that has no UVs, ``bake_vertex_colors`` fills it from per-vertex colours,
 and ``texture_to_uint8`` + ``save_obj(uvs=, texture=)`` write the result out.
+
+``render_mesh(..., antialias=True)`` blends the silhouette edges analytically (K34,
+``csrc/mesh_aa.hip``, nvdiffrast's edge antialiasing), which makes the picture a smooth function of
+the vertex positions; ``render_mesh_geometry_backward`` is its transpose in the positions,
+``fit_mesh_geometry`` optimises them against a dataset's images, and ``edge_opposites`` and
+``vertex_neighbors`` make the edge and neighbour lists they need.
 """
 
 import os
@@ -404,6 +410,13 @@ def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, proj, eye, w
 def _rasterize(vertices, triangles, proj, eye, width, height, colors=None, uvs=None, texture=None,
                background=(0, 0, 0), batch_size=1 << 22):
     """``rasterize_mesh`` with K31a's ``record`` in front of its results (K32a reads it)."""
+    return _rasterize_z(vertices, triangles, proj, eye, width, height, colors, uvs, texture,
+                        background, batch_size)[:-1]
+
+
+def _rasterize_z(vertices, triangles, proj, eye, width, height, colors=None, uvs=None,
+                 texture=None, background=(0, 0, 0), batch_size=1 << 22):
+    """``_rasterize`` with K31b's ``zbuf`` behind its results (K34 reads it)."""
     width, height, batch_size = int(width), int(height), int(batch_size)
     if not 1 <= batch_size <= ops.octree_max_points():
         raise ValueError("rasterize_mesh: batch_size must lie in 1 .. %d, got %d"
@@ -417,7 +430,7 @@ def _rasterize(vertices, triangles, proj, eye, width, height, colors=None, uvs=N
                              zbuf)
     return (record,) + ops.mesh_raster_resolve(zbuf, record, vertices, triangles, colors, uvs,
                                                texture, eye, background, width, height) \
-        + (status, total)
+        + (status, total, zbuf)
 
 
 _warned_clipped = False
@@ -467,7 +480,7 @@ def _render_mesh_check(who, vertices, triangles, camera, colors, uvs, texture, b
 
 def render_mesh(vertices, triangles, camera, colors=None, uvs=None, texture=None,
                 background=(0, 0, 0), supersample: int = 1, batch_size: int = 1 << 22,
-                device=None, return_ids: bool = False):
+                device=None, return_ids: bool = False, antialias: bool = False):
     """Draws a triangle mesh as ``camera`` (a ``CameraInfo``) sees it, with a z-buffer (K31,
     ``csrc/mesh_raster.hip``) -> ``(RenderResult, report)``: ``color`` (H W,3), ``alpha`` (H W,) 1
     where a triangle covers the pixel's centre and 0 elsewhere, ``depth`` (H W,) the distance of
@@ -491,7 +504,17 @@ def render_mesh(vertices, triangles, camera, colors=None, uvs=None, texture=None
     ``supersample=k`` draws ``k W x k H`` sub-pixels, ``k x k`` centred on every pixel, and
     averages colour and alpha over them; the depth is the mean over the covered sub-pixels.
     ``k = 1`` is the plain image.  ``batch_size``: box pixels per launch; the image does not
-    depend on it."""
+    depend on it.
+
+    ``antialias=True`` puts colour and alpha through K34a (``csrc/mesh_aa.hip``, nvdiffrast's
+    analytic edge antialiasing): two neighbouring pixels that a silhouette edge separates are
+    blended by how far the edge reaches between their centres, so alpha takes values between 0
+    and 1 along the outline, on the vertex-colour and the textured path alike; ``depth`` and
+    ``ids`` stay K31's.  With ``supersample > 1`` the pass runs on the sub-pixel image, before the
+    reduction.  With False, the default, nothing of K34 is called and the bits are K31's.  The
+    limits: only silhouette, fold, boundary and non-manifold edges are blended (an edge between
+    two triangles that continue the surface is not); a silhouette that falls between two pixel
+    centres of the same id is not seen."""
     global _warned_clipped
     who = "render_mesh"
     k, width, height = _render_mesh_check(who, vertices, triangles, camera, colors, uvs, texture,
@@ -514,11 +537,17 @@ def render_mesh(vertices, triangles, camera, colors=None, uvs=None, texture=None
 
     if texture is not None:
         texture = texture.flip(0) if torch.is_tensor(texture) else np.asarray(texture)[::-1]
-    color, alpha, depth, ids, status, total = rasterize_mesh(
-        tensor(vertices, "float32"), tensor(triangles, "int32"),
-        supersample_projection(camera, k), eye_positions([camera], (0.0, 0.0, 0.0))[0],
-        k * width, k * height, tensor(colors, "float32"), tensor(uvs, "float32"),
-        tensor(texture, "uint8"), background, batch_size)
+    frame = (tensor(vertices, "float32"), tensor(triangles, "int32"),
+             supersample_projection(camera, k), eye_positions([camera], (0.0, 0.0, 0.0))[0],
+             k * width, k * height, tensor(colors, "float32"), tensor(uvs, "float32"),
+             tensor(texture, "uint8"), background, batch_size)
+    if antialias:
+        record, color, alpha, depth, ids, status, total, zbuf = _rasterize_z(*frame)
+        color, alpha = ops.mesh_aa_forward(
+            record, zbuf, ids, edge_opposites(frame[1], frame[0].shape[0], device), frame[0],
+            frame[2], color, alpha, k * width, k * height)
+    else:
+        color, alpha, depth, ids, status, total = rasterize_mesh(*frame)
     if k > 1:
         color, alpha, depth = supersample_reduce(color, alpha, depth, width, height, k)
     tally = torch.bincount(status.to(torch.int64), minlength=len(ops.MESH_RASTER_STATUS))
@@ -538,10 +567,10 @@ def render_mesh(vertices, triangles, camera, colors=None, uvs=None, texture=None
 
 def render_mesh_image(vertices, triangles, camera, colors=None, uvs=None, texture=None,
                       background=(0, 0, 0), supersample: int = 1, batch_size: int = 1 << 22,
-                      device=None, include_depth: bool = False):
+                      device=None, include_depth: bool = False, antialias: bool = False):
     """``render_mesh`` as a frame -> (H,W,3) uint8 numpy (K8's bytes: ``color * 255`` truncated),
     and with ``include_depth`` also the (H,W) float32 alpha and depth maps: the return shape of
-    ``OcTree.render_image``."""
+    ``OcTree.render_image``.  ``antialias`` is ``render_mesh``'s."""
     _render_mesh_check("render_mesh_image", vertices, triangles, camera, colors, uvs, texture,
                        background, supersample, batch_size)
 
@@ -553,7 +582,8 @@ def render_mesh_image(vertices, triangles, camera, colors=None, uvs=None, textur
     out, _ = render_mesh(on_device(np.asarray(vertices, dtype=np.float32)
                                    if not torch.is_tensor(vertices) else vertices),
                          on_device(triangles), camera, on_device(colors), on_device(uvs),
-                         on_device(texture), background, supersample, batch_size, device)
+                         on_device(texture), background, supersample, batch_size, device,
+                         antialias=bool(antialias))
     width, height = int(camera.resolution.width), int(camera.resolution.height)
     pixels = torch.arange(width * height, dtype=torch.int64, device=out.color.device)
     image = ops.to_image(out.color.contiguous(), pixels, width, height).cpu().numpy()
@@ -1349,3 +1379,284 @@ def fit_mesh_texture(vertices, triangles, uvs, texture, train_dataset, val_datas
                           alpha_threshold, clip_value, max_norm, seed, verbose)
     data = data.view(size + (3,))
     return (data if torch.is_tensor(texture) else data.cpu().numpy()), log
+
+
+# ------------------------------------------------------------------------------------ K34
+def _triangle_ids(who, triangles, num_vertices) -> np.ndarray:
+    """(F,3) int64 on the host, clamped into ``0 .. V - 1`` as K31 clamps them."""
+    shape = _shape_of(triangles)
+    if torch.is_tensor(triangles):
+        integer = not (triangles.dtype.is_floating_point or triangles.dtype.is_complex
+                       or triangles.dtype == torch.bool)
+    else:
+        integer = np.issubdtype(np.asarray(triangles).dtype, np.integer)
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= _MOST or not integer:
+        raise ValueError("%s: triangles must be an integer (F,3) array with 1 <= F <= "
+                         "(2^31 - 1) / 3, got %s" % (who, shape))
+    if int(num_vertices) != num_vertices or not 1 <= int(num_vertices) <= _MOST:
+        raise ValueError("%s: num_vertices must be an integer in 1 .. (2^31 - 1) / 3, got %r"
+                         % (who, num_vertices))
+    ids = triangles.cpu().numpy() if torch.is_tensor(triangles) else np.asarray(triangles)
+    return np.clip(ids.astype(np.int64), 0, int(num_vertices) - 1)
+
+
+def _plumbing_device(triangles, device):
+    if device is None:
+        device = triangles.device if torch.is_tensor(triangles) else "cuda"
+    return torch.device(device)
+
+
+def edge_opposites(triangles, num_vertices: int, device=None) -> torch.Tensor:
+    """Which vertex lies across every edge -> ``opposite`` (3F,) int32 on ``device`` (default: the
+    tensor's own, or the GPU for a numpy array), what K34 takes.  Edge ``i`` of triangle ``f`` joins
+    its corners ``i + 1`` and ``i + 2`` (mod 3), K31b's numbering.  ``opposite[3 f + i]`` is the
+    vertex of the neighbouring triangle that is not on the edge when the undirected edge is used
+    by exactly two corners of two different triangles, and -1 otherwise: a boundary edge, an edge
+    shared by three or more triangles, an edge a degenerate triangle uses twice.  The ids are
+    clamped into ``0 .. V - 1`` as K31 clamps them.  A numpy sort on the host, integer plumbing
+    as ``vertex_adjacency``; it depends on the triangles alone and is made once per mesh."""
+    ids = _triangle_ids("edge_opposites", triangles, num_vertices)
+    j, k = ids[:, [1, 2, 0]].reshape(-1), ids[:, [2, 0, 1]].reshape(-1)      # corner 3 f + i
+    keys = np.minimum(j, k) * int(num_vertices) + np.maximum(j, k)
+    order = np.argsort(keys, kind="stable")
+    ranked = keys[order]
+    first = np.ones(len(ranked), dtype=bool)
+    first[1:] = ranked[1:] != ranked[:-1]
+    starts = np.flatnonzero(first)
+    sizes = np.diff(np.append(starts, len(ranked)))
+    opposite = np.full(len(keys), -1, dtype=np.int32)
+    two = starts[sizes == 2]
+    a, b = order[two], order[two + 1]
+    apart = a // 3 != b // 3
+    a, b = a[apart], b[apart]
+    flat = ids.reshape(-1)
+    opposite[a], opposite[b] = flat[b], flat[a]
+    return torch.from_numpy(opposite).to(_plumbing_device(triangles, device))
+
+
+def vertex_neighbors(triangles, num_vertices: int, device=None):
+    """The vertices every vertex shares an edge with -> ``(starts (V+1,) int32, neighbors int32)``
+    on ``device``, the CSR K34d takes: ``neighbors[starts[v] : starts[v + 1]]`` in ascending
+    order, every undirected edge once per end, an edge from a vertex to itself left out.  The ids
+    are clamped as K31 clamps them.  Integer plumbing on the host, made once per mesh."""
+    ids = _triangle_ids("vertex_neighbors", triangles, num_vertices)
+    num_vertices = int(num_vertices)
+    j, k = ids[:, [1, 2, 0]].reshape(-1), ids[:, [2, 0, 1]].reshape(-1)
+    keep = j != k
+    keys = np.unique(np.concatenate([j[keep] * num_vertices + k[keep],
+                                     k[keep] * num_vertices + j[keep]]))
+    if len(keys) >= 2 ** 31:
+        raise ValueError("vertex_neighbors: %d neighbour ids; fewer than 2^31 are supported"
+                         % len(keys))
+    starts = np.zeros(num_vertices + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys // num_vertices, minlength=num_vertices), out=starts[1:])
+    device = _plumbing_device(triangles, device)
+    return (torch.from_numpy(starts.astype(np.int32)).to(device),
+            torch.from_numpy((keys % num_vertices).astype(np.int32)).to(device))
+
+
+def _geometry_backward(frame, opposites, vertices, triangles, proj, width, height, g_color,
+                       g_alpha, grad, accumulate):
+    """K34b, the stable sort of its entries and K34c on one K31 frame ``(record, color, alpha,
+    ids, zbuf)`` -> (grad, d_color, d_alpha).  No read-back."""
+    record, color, alpha, ids, zbuf = frame
+    d_color, d_alpha, entry_vertex, entry_grad = ops.mesh_aa_backward(
+        record, zbuf, ids, opposites, vertices, triangles, proj, color, alpha, g_color, g_alpha,
+        width, height)
+    sorted_vertex, order = torch.sort(entry_vertex, stable=True)
+    grad = ops.mesh_aa_vertex_grad(sorted_vertex.contiguous(), order.to(torch.int32).contiguous(),
+                                   entry_grad, vertices, proj, grad, accumulate)
+    return grad, d_color, d_alpha
+
+
+def render_mesh_geometry_backward(vertices, triangles, camera, colors, d_color, d_alpha,
+                                  opposites=None, grad=None, accumulate: bool = False,
+                                  background=(0, 0, 0), batch_size: int = 1 << 22):
+    """The transpose of ``render_mesh(..., colors=colors, antialias=True)`` in the vertex
+    POSITIONS (K34, ``csrc/mesh_aa.hip``) -> ``(grad (V,3), d_color_plain (H W,3))`` float32.
+    ``d_color`` (H W,3) and ``d_alpha`` (H W,) are the gradient of a loss in the antialiased colour
+    and alpha; ``grad`` is its gradient in the positions, and ``d_color_plain`` the gradient in
+    K31's own colours, which is what ``render_mesh_backward`` (K32) takes: colours and geometry
+    can share one backward.  It runs K31 for the camera, then K34b, a stable sort of its vertex
+    entries and K34c: fixed orders, no float atomics, the same bits on every call and for every
+    ``batch_size``.
+
+    numpy in gives numpy out; tensors stay tensors.  ``opposites``: what ``edge_opposites``
+    returns for these triangles (made here when None).  ``grad`` (a GPU tensor) is written in
+    place when given, and added to with ``accumulate``.
+
+    The limits: only silhouette and fold edges (and boundary and non-manifold ones) carry a
+    gradient -- the interior term, colour through the barycentric weights, is not built; the
+    topology never changes; the snap to 1/256 pixel is passed straight through; a silhouette that
+    falls between two pixel centres of the same id is not seen; self-intersections are not
+    prevented."""
+    who = "render_mesh_geometry_backward"
+    num_vertices = _mesh_colors_check(who, vertices, colors, batch_size=batch_size)
+    if colors is None:
+        raise ValueError("%s: colors must be (V,3), got None" % who)
+    width, height = _camera_size(who, camera)
+    if _shape_of(d_color) != (width * height, 3):
+        raise ValueError("%s: d_color must be (H W,3) = (%d,3), got %s"
+                         % (who, width * height, _shape_of(d_color)))
+    if _shape_of(d_alpha) != (width * height,):
+        raise ValueError("%s: d_alpha must be (H W,) = (%d,), got %s"
+                         % (who, width * height, _shape_of(d_alpha)))
+    if accumulate and grad is None:
+        raise ValueError("%s: accumulate needs grad to add to" % who)
+    ground = np.asarray(background, dtype=np.float64).reshape(-1)
+    if ground.shape != (3,) or not np.isfinite(ground).all():
+        raise ValueError("%s: background must be three finite numbers, got %r"
+                         % (who, background))
+    _mesh_ids_check(who, triangles, num_vertices)
+    from .cameras import eye_positions
+    as_numpy, device, vertices, triangles = _mesh_on(vertices, triangles)
+    if opposites is None:
+        opposites = edge_opposites(triangles, num_vertices, device)
+    proj = supersample_projection(camera, 1)
+    record, color, alpha, _, ids, _, _, zbuf = _rasterize_z(
+        vertices, triangles, proj, eye_positions([camera], (0.0, 0.0, 0.0))[0], width, height,
+        _on(colors, "float32", device), background=background, batch_size=batch_size)
+    grad, plain, _ = _geometry_backward(
+        (record, color, alpha, ids, zbuf), opposites, vertices, triangles, proj, width, height,
+        _on(d_color, "float32", device), _on(d_alpha, "float32", device), grad, accumulate)
+    if as_numpy:
+        return grad.cpu().numpy(), plain.cpu().numpy()
+    return grad, plain
+
+
+def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=None,
+                      num_steps: int = 500, learning_rate: float = 1e-3,
+                      cameras_per_step: int = 1, report_interval: int = 100, alpha_weight=None,
+                      laplacian_weight: float = 0.0, max_displacement=None,
+                      clip_value: float = CLIP_VALUE, max_norm: float = MAX_NORM,
+                      seed: int = 20080524, verbose: bool = True):
+    """Optimises the vertex POSITIONS (V,3) of a mesh against the images of ``train_dataset`` (an
+    ``ImageDataset``) through ``render_mesh(..., antialias=True)`` with a black background ->
+    ``(vertices, log)``; the per-vertex ``colors`` and the triangles are held fixed.  numpy in gives
+    numpy out; tensors stay tensors, and the given ``vertices`` are not modified.  The loop is
+    ``fit_mesh_colors``' (``fit_loop.run``) on the (V,3) positions: a seeded permutation of the
+    cameras is dealt ``cameras_per_step`` at a time, and one step is, for each of its cameras, the
+    K31 frame, K34a, K6 (``ops.mse_loss``) on colour and alpha with ``color_scale = 1 / (3 count)``
+    and ``alpha_scale = alpha_weight / count`` (``count`` the pixels of the step; ``alpha_weight``
+    None takes the dataset's, as ``fit_octree`` does, and 0 for a dataset without alpha), K34b, the
+    stable sort of its entries and K34c accumulated over the step's cameras.  Then, with
+    ``laplacian_weight > 0``, K34d on the displacement ``d = v - v0`` adds the gradient of
+    ``laplacian_weight * (1 / V) * 1/2 sum_edges |d_i - d_j|^2`` (report lines gain ``lap:``, the
+    value of that term; with 0 the kernel is not entered); then K7 (``ops.clip_adam``) and, with
+    ``max_displacement``, every component of ``v`` is clamped into ``v0 -+ max_displacement``.
+
+    The log holds ``FitLogEntry(step, loss, val_psnr)`` as ``fit_mesh_colors``' does -- the loss is
+    K6's, colour plus ``alpha_weight`` times alpha, without the smoothness term; ``val_psnr`` is
+    the colour PSNR of the antialiased pictures of ``val_dataset``'s cameras -- and report steps
+    are printed the same way.  The only host synchronisation of a step is K31's one read-back per
+    camera.  ``learning_rate``, ``laplacian_weight`` and ``max_displacement`` have NO tuned
+    defaults: 1e-3 is a guess in scene units per step, 0 and None switch the two off.
+
+    The limits: only silhouette and fold edges (and boundary and non-manifold ones) carry a
+    gradient -- the interior term, colour through the barycentric weights, is not built, so a
+    vertex that no camera sees on an outline does not move; the topology never changes; the snap
+    to 1/256 pixel is passed straight through; a silhouette that falls between two pixel centres
+    of the same id is not seen; self-intersections are not prevented."""
+    who = "fit_mesh_geometry"
+    num_vertices = _mesh_colors_check(who, vertices, colors)
+    if colors is None:
+        raise ValueError("%s: colors must be (V,3), got None (color_mesh_from_images makes them)"
+                         % who)
+    fit_loop.check_schedule(who, "num_steps >= 0, cameras_per_step >= 1, report_interval >= 1",
+                            cameras_per_step, num_steps, report_interval, learning_rate)
+    cameras_per_step = int(cameras_per_step)
+    if alpha_weight is not None and not float(alpha_weight) >= 0:
+        raise ValueError("%s: alpha_weight must be None or >= 0, got %r" % (who, alpha_weight))
+    laplacian_weight = float(laplacian_weight)
+    if not 0 <= laplacian_weight < float("inf"):
+        raise ValueError("%s: laplacian_weight must be finite and >= 0, got %r"
+                         % (who, laplacian_weight))
+    if max_displacement is not None and not float(max_displacement) > 0:
+        raise ValueError("%s: max_displacement must be None or positive, got %r"
+                         % (who, max_displacement))
+    _, cameras, width, height = _mesh_dataset_check(who, "train_dataset", train_dataset)
+    val_view = None if val_dataset is None else \
+        _mesh_dataset_check(who, "val_dataset", val_dataset)[1:]
+    _mesh_ids_check(who, triangles, num_vertices)
+    from .cameras import eye_positions
+    _, device, start, triangles = _mesh_on(vertices, triangles, train_dataset.colors.device)
+    colors = _on(colors, "float32", device)
+    data = start.clone()
+    opposites = edge_opposites(triangles, num_vertices, device)
+    per = width * height
+    pixels = torch.arange(per, dtype=torch.int64, device=device)
+    alphas = train_dataset._gt_alphas()
+    if alphas is None:
+        aw = 0.0
+    else:
+        aw = float(train_dataset.alpha_weight if alpha_weight is None else alpha_weight)
+    displacement = neighbor_starts = neighbors = None
+    if laplacian_weight > 0:
+        neighbor_starts, neighbors = vertex_neighbors(triangles, num_vertices, device)
+        displacement = torch.empty_like(data)
+    if max_displacement is not None:
+        low, high = start - float(max_displacement), start + float(max_displacement)
+
+    def frames(view_cameras, width, height):
+        projections = [supersample_projection(camera, 1) for camera in view_cameras]
+        eyes = eye_positions(view_cameras, (0.0, 0.0, 0.0))
+
+        def frame(number):
+            record, color, alpha, _, ids, _, _, zbuf = _rasterize_z(
+                data, triangles, projections[number], eyes[number], width, height, colors)
+            smooth = ops.mesh_aa_forward(record, zbuf, ids, opposites, data, projections[number],
+                                         color, alpha, width, height)
+            return smooth + ((record, color, alpha, ids, zbuf), projections[number])
+        return frame
+
+    frame = frames(cameras, width, height)
+    val_frame = None if val_view is None else frames(*val_view)
+    generator = torch.Generator()
+    generator.manual_seed(int(seed))
+
+    def epoch():
+        deal = torch.randperm(len(cameras), generator=generator).tolist()
+        return [deal[first:first + cameras_per_step]
+                for first in range(0, len(deal), cameras_per_step)]
+
+    def step(chosen, grads):
+        count = len(chosen) * per
+        total = None
+        for number, camera in enumerate(chosen):
+            color, alpha, plain, proj = frame(camera)
+            sums, g_color, g_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
+                                                  pixels + camera * per, 1.0 / (3 * count),
+                                                  aw / count)
+            _geometry_backward(plain, opposites, data, triangles, proj, width, height, g_color,
+                               g_alpha, grads, number > 0)
+            total = sums if total is None else total + sums
+        if laplacian_weight > 0:
+            torch.sub(data, start, out=displacement)
+            ops.mesh_laplacian(displacement, neighbor_starts, neighbors,
+                               laplacian_weight / num_vertices, grads, accumulate=True)
+        return ops.loss_value(total, count, aw)
+
+    def project(rows):
+        if max_displacement is not None:
+            torch.minimum(rows, high, out=rows)
+            torch.maximum(rows, low, out=rows)
+
+    def fields():
+        if not laplacian_weight > 0:
+            return []
+        moved = data - start
+        rows = torch.repeat_interleave(
+            torch.arange(num_vertices, device=device),
+            (neighbor_starts[1:] - neighbor_starts[:-1]).to(torch.int64))
+        # (every edge is listed once per end: a quarter of the sum over the ends)
+        term = 0.25 * ((moved[rows] - moved[neighbors.to(torch.int64)]) ** 2).sum()
+        return [("lap", float(term.item()) * laplacian_weight / num_vertices)]
+
+    def validate():
+        return fit_loop.camera_psnr(val_frame, len(val_view[0]), val_view[1] * val_view[2],
+                                    val_dataset)
+
+    log = fit_loop.run(data, epoch, step, project,
+                       validate if val_dataset is not None else None, int(num_steps),
+                       learning_rate, report_interval, clip_value, max_norm, verbose, fields)
+    return (data if torch.is_tensor(vertices) else data.cpu().numpy()), log

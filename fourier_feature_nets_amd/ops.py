@@ -2601,3 +2601,185 @@ def mesh_texture_grad(sorted_texels: torch.Tensor, tap_order: torch.Tensor,
           _dev(d_color, name="d_color"), c_i64(num_pixels), c_i64(num_texels),
           _dev(grad, name="grad"), _dev(weight, name="weight"), c_i(1 if accumulate else 0))
     return grad, weight
+
+
+# --------------------------------------------------------------------------------- K34
+MESH_AA_MAX_PIXELS = 1 << 28                    # 4 P entries index in an int32
+
+
+def _aa_check_frame(who, record, zbuf, ids, opposite, vertices, proj, color, alpha, width, height):
+    """What K34a and K34b refuse alike -> ``proj`` as 12 host floats."""
+    _raster_want(who, "vertices", vertices, torch.float32, (None, 3))
+    _raster_want(who, "record", record, torch.int32, (None, 16))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= vertices.shape[0] <= most:
+        raise ValueError("%s: vertices holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, vertices.shape[0]))
+    if not 1 <= record.shape[0] <= most:
+        raise ValueError("%s: record holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, record.shape[0]))
+    _raster_check_image(who, width, height)
+    if width * height > MESH_AA_MAX_PIXELS:
+        raise ValueError("%s: the image holds %d pixels; at most 2^28 are supported"
+                         % (who, width * height))
+    _raster_want(who, "zbuf", zbuf, torch.int64, (width * height,))
+    _raster_want(who, "ids", ids, torch.int32, (width * height,))
+    _raster_want(who, "opposite", opposite, torch.int32, (3 * record.shape[0],))
+    _raster_want(who, "color", color, torch.float32, (width * height, 3))
+    _raster_want(who, "alpha", alpha, torch.float32, (width * height,))
+    if np.shape(proj) != (3, 4):
+        raise ValueError("%s: proj must be (3, 4), got %s" % (who, np.shape(proj)))
+    return _raster_host(who, "proj", proj, 12)
+
+
+def mesh_aa_forward_check(record, zbuf, ids, opposite, vertices, proj, color, alpha, width: int,
+                          height: int):
+    """The refusals of ``mesh_aa_forward`` that need no device -> ``proj`` as 12 host floats."""
+    return _aa_check_frame("mesh_aa_forward", record, zbuf, ids, opposite, vertices, proj, color,
+                           alpha, width, height)
+
+
+def mesh_aa_forward(record: torch.Tensor, zbuf: torch.Tensor, ids: torch.Tensor,
+                    opposite: torch.Tensor, vertices: torch.Tensor, proj, color: torch.Tensor,
+                    alpha: torch.Tensor, width: int, height: int):
+    """K34a.  record (F,16) of K31a, zbuf (H W,) int64 of K31b, ids, color (H W,3) and alpha (H W,)
+    of K31c, ``opposite`` (3F,) int32 of ``mesh.edge_opposites``, vertices (V,3) f32 and ``proj``
+    (3,4) on the host -> ``(out_color (H W,3), out_alpha (H W,))`` f32: every pair of 4-neighbours
+    with different ids that a silhouette edge separates is blended by how far the edge reaches
+    between the two centres, ``out = out + m * (in[source] - in[p])`` at the pair's target.  A pixel
+    in no such pair is copied bit for bit."""
+    width, height = int(width), int(height)
+    matrix = mesh_aa_forward_check(record, zbuf, ids, opposite, vertices, proj, color, alpha,
+                                   width, height)
+    out_color, out_alpha = torch.empty_like(color), torch.empty_like(alpha)
+    _call("ffn_mesh_aa_forward", _dev(record, torch.int32, "record"),
+          _dev(zbuf, torch.int64, "zbuf"), _dev(ids, torch.int32, "ids"),
+          _dev(opposite, torch.int32, "opposite"), _dev(vertices, name="vertices"),
+          c_i64(vertices.shape[0]), c_i64(record.shape[0]), matrix, _dev(color, name="color"),
+          _dev(alpha, name="alpha"), c_i(width), c_i(height), _dev(out_color), _dev(out_alpha))
+    return out_color, out_alpha
+
+
+def mesh_aa_backward_check(record, zbuf, ids, opposite, vertices, triangles, proj, color, alpha,
+                           g_color, g_alpha, width: int, height: int):
+    """The refusals of ``mesh_aa_backward`` that need no device -> ``proj`` as 12 host floats."""
+    who = "mesh_aa_backward"
+    matrix = _aa_check_frame(who, record, zbuf, ids, opposite, vertices, proj, color, alpha, width,
+                             height)
+    _raster_want(who, "triangles", triangles, torch.int32, (record.shape[0], 3))
+    _raster_want(who, "g_color", g_color, torch.float32, (width * height, 3))
+    _raster_want(who, "g_alpha", g_alpha, torch.float32, (width * height,))
+    return matrix
+
+
+def mesh_aa_backward(record: torch.Tensor, zbuf: torch.Tensor, ids: torch.Tensor,
+                     opposite: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, proj,
+                     color: torch.Tensor, alpha: torch.Tensor, g_color: torch.Tensor,
+                     g_alpha: torch.Tensor, width: int, height: int):
+    """K34b.  The inputs of ``mesh_aa_forward``, ``triangles`` (F,3) int32 and the gradient
+    ``g_color`` (H W,3), ``g_alpha`` (H W,) in its outputs -> ``(d_color (H W,3), d_alpha (H W,),
+    entry_vertex (4 H W,) int32, entry_grad (4 H W,2) f32)``: the gradient in K31c's colour and
+    alpha (the transpose of the blend), and per slot ``(p, axis)`` the two entries ``4 p + 2 axis +
+    {0, 1}``: the two vertices of the pair's silhouette edge and the gradient in their screen
+    positions, ``num_vertices`` and zeros for a slot without an active pair.  Every entry is
+    written.  A ``g`` at a pixel in no active pair reaches only its own ``d``."""
+    width, height = int(width), int(height)
+    matrix = mesh_aa_backward_check(record, zbuf, ids, opposite, vertices, triangles, proj, color,
+                                    alpha, g_color, g_alpha, width, height)
+    dev = record.device
+    d_color, d_alpha = torch.empty_like(color), torch.empty_like(alpha)
+    entry_vertex = torch.empty((4 * width * height,), dtype=torch.int32, device=dev)
+    entry_grad = torch.empty((4 * width * height, 2), dtype=torch.float32, device=dev)
+    _call("ffn_mesh_aa_backward", _dev(record, torch.int32, "record"),
+          _dev(zbuf, torch.int64, "zbuf"), _dev(ids, torch.int32, "ids"),
+          _dev(opposite, torch.int32, "opposite"), _dev(vertices, name="vertices"),
+          c_i64(vertices.shape[0]), _dev(triangles, torch.int32, "triangles"),
+          c_i64(record.shape[0]), matrix, _dev(color, name="color"), _dev(alpha, name="alpha"),
+          _dev(g_color, name="g_color"), _dev(g_alpha, name="g_alpha"), c_i(width), c_i(height),
+          _dev(d_color), _dev(d_alpha), _dev(entry_vertex, torch.int32), _dev(entry_grad))
+    return d_color, d_alpha, entry_vertex, entry_grad
+
+
+def mesh_aa_vertex_grad_check(sorted_vertex, order, entry_grad, vertices, proj, grad=None,
+                              accumulate: bool = False):
+    """The refusals of ``mesh_aa_vertex_grad`` that need no device -> ``proj`` as 12 host
+    floats."""
+    who = "mesh_aa_vertex_grad"
+    _raster_want(who, "entry_grad", entry_grad, torch.float32, (None, 2))
+    entries = entry_grad.shape[0]
+    if entries % 4 != 0 or not 1 <= entries // 4 <= MESH_AA_MAX_PIXELS:
+        raise ValueError("%s: entry_grad holds %d entries; 4 per pixel of 1 .. 2^28 pixels are "
+                         "supported" % (who, entries))
+    _raster_want(who, "sorted_vertex", sorted_vertex, torch.int32, (entries,))
+    _raster_want(who, "order", order, torch.int32, (entries,))
+    _raster_want(who, "vertices", vertices, torch.float32, (None, 3))
+    if not 1 <= vertices.shape[0] <= (2 ** 31 - 1) // 3:
+        raise ValueError("%s: vertices holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, vertices.shape[0]))
+    if accumulate and grad is None:
+        raise ValueError("%s: accumulate needs grad to add to" % who)
+    if grad is not None:
+        _raster_want(who, "grad", grad, torch.float32, (vertices.shape[0], 3))
+    if np.shape(proj) != (3, 4):
+        raise ValueError("%s: proj must be (3, 4), got %s" % (who, np.shape(proj)))
+    return _raster_host(who, "proj", proj, 12)
+
+
+def mesh_aa_vertex_grad(sorted_vertex: torch.Tensor, order: torch.Tensor,
+                        entry_grad: torch.Tensor, vertices: torch.Tensor, proj,
+                        grad: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """K34c.  ``sorted_vertex`` and ``order`` (4 H W,) int32: K34b's ``entry_vertex`` stably sorted
+    and the entries in that order; ``entry_grad`` (4 H W,2) -> ``grad`` (V,3) f32: per vertex the
+    sum of its entries in sorted order, put through the Jacobian of K31a's projection, a zero row
+    when ``!(w > 0)``.  One thread per vertex, no atomics; the loop is linear in the vertex's run.
+    ``grad`` is written in place when given, and with ``accumulate`` added to."""
+    matrix = mesh_aa_vertex_grad_check(sorted_vertex, order, entry_grad, vertices, proj, grad,
+                                       accumulate)
+    if grad is None:
+        grad = torch.empty((vertices.shape[0], 3), dtype=torch.float32, device=vertices.device)
+    _call("ffn_mesh_aa_vertex_grad", _dev(sorted_vertex, torch.int32, "sorted_vertex"),
+          _dev(order, torch.int32, "order"), _dev(entry_grad, name="entry_grad"),
+          c_i64(entry_grad.shape[0] // 4), _dev(vertices, name="vertices"),
+          c_i64(vertices.shape[0]), matrix, _dev(grad, name="grad"), c_i(1 if accumulate else 0))
+    return grad
+
+
+def mesh_laplacian_check(values, neighbor_starts, neighbors, scale, out=None,
+                         accumulate: bool = False) -> float:
+    """The refusals of ``mesh_laplacian`` that need no device -> ``scale`` as a float."""
+    who = "mesh_laplacian"
+    _raster_want(who, "values", values, torch.float32, (None, 3))
+    if not 1 <= values.shape[0] <= (2 ** 31 - 1) // 3:
+        raise ValueError("%s: values holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, values.shape[0]))
+    _raster_want(who, "neighbor_starts", neighbor_starts, torch.int32, (values.shape[0] + 1,))
+    _raster_want(who, "neighbors", neighbors, torch.int32, (None,))
+    if neighbors.shape[0] >= 2 ** 31:
+        raise ValueError("%s: neighbors holds %d ids; fewer than 2^31 are supported"
+                         % (who, neighbors.shape[0]))
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("%s: scale must be finite, got %r" % (who, scale))
+    if accumulate and out is None:
+        raise ValueError("%s: accumulate needs out to add to" % who)
+    if out is not None:
+        _raster_want(who, "out", out, torch.float32, (values.shape[0], 3))
+    return scale
+
+
+def mesh_laplacian(values: torch.Tensor, neighbor_starts: torch.Tensor, neighbors: torch.Tensor,
+                   scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+    """K34d.  ``values`` (V,3) f32 and the CSR ``neighbor_starts`` (V+1,), ``neighbors`` int32 of
+    ``mesh.vertex_neighbors`` -> (V,3) f32: ``scale * sum_n (x[v] - x[n])`` over the row in order,
+    ``scale`` times the gradient of ``1/2 sum_edges |x_i - x_j|^2``.  ``out`` is written in place
+    when given, and with ``accumulate`` added to (``out = out + scale * acc``)."""
+    scale = mesh_laplacian_check(values, neighbor_starts, neighbors, scale, out, accumulate)
+    if out is None:
+        out = torch.empty_like(values)
+    _call("ffn_mesh_laplacian", _dev(values, name="values"),
+          _dev(neighbor_starts, torch.int32, "neighbor_starts"),
+          _dev(neighbors, torch.int32, "neighbors") if neighbors.numel() else _dev(None),
+          c_i64(values.shape[0]), c_i64(neighbors.shape[0]), c_f(scale), _dev(out, name="out"),
+          c_i(1 if accumulate else 0))
+    return out

@@ -1748,6 +1748,108 @@ int ffn_mesh_texture_grad(const int32_t* sorted_texels, const int32_t* tap_order
                           int64_t num_texels, float* grad, float* weight, int accumulate,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K34  analytic edge antialiasing behind K31, its transposes in the image and in the vertex
+ * positions, and a smoothness term for vertex displacements (csrc/mesh_aa.hip).  No counterpart in
+ * the reference; the method is nvdiffrast's (Laine et al. 2020).  K31's image is piecewise constant in
+ * the positions.  Here two 4-neighbour pixels whose ids differ are blended by how far the silhouette
+ * edge between their centres reaches, a smooth function of the edge's two vertices.  Decisions are
+ * made on integers; every float operation is one rounded f32 operation in the order written (no fma;
+ * / is the IEEE division; -x is the sign flip); no float atomics and no LDS: the same inputs give the
+ * same bits on every call.  Every index read from an input array is held against its range before it
+ * is used.  Limits as in K31: 1 <= width, height <= 16384, and width height <= 2^28 (the 4 width
+ * height entries index in an int32); 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; bad shapes
+ * and null pointers are refused by name before any launch.  record is 16-byte, zbuf and entry_grad
+ * are 8-byte aligned.
+ *
+ * Notation.  Pixel p = py width + px, centres at integer coordinates.  A PAIR is two 4-neighbours:
+ * slot (p, axis) pairs p with q = p + 1 (axis 0, only when px + 1 < width) or q = p + width (axis 1,
+ * only when py + 1 < height).  record (num_triangles,16) from K31a, zbuf (height width) uint64 from
+ * K31b (all ones where empty), ids (height width) int32 from K31c.  opposite (3 num_triangles) int32:
+ * for corner 3 f + i the vertex across edge i of triangle f (edge i joins the corners j = (i+1) mod 3
+ * and k = (i+2) mod 3, K31b's numbering) when exactly one other triangle shares the undirected edge,
+ * else -1 (boundary and non-manifold edges).  proj: 12 floats in HOST memory, as in K31a.
+ *
+ * The pair decision of (p, q), the same function in every kernel:
+ *   inactive when ids[p] == ids[q].  near = q when zbuf[q] < zbuf[p] (unsigned), else p; far the other.
+ *   attempt(near -> far); when it fails and ids[far] >= 0, attempt(far -> near); the first success
+ *   decides; with none the pair is inactive.
+ *   attempt(a -> b): f = ids[a]; fails when f is outside 0 .. num_triangles - 1.  X, Y, A, sgn =
+ *     sign(A) from record[f]; fails when A == 0.  E_i(Q_a), E_i(Q_b), i = 0 .. 2, as in K31b (int64,
+ *     sgn applied), Q = 256 (x, y) of the pixel.  Fails when some E_i(Q_a) < 0, and when no
+ *     E_i(Q_b) < 0.  For every i with E_i(Q_b) < 0: D_i = E_i(Q_a) - E_i(Q_b) (int64, > 0),
+ *     alpha_i = (float)E_i(Q_a) / (float)D_i.  i* = the smallest alpha_i, the lowest i among equal
+ *     ones (a later i replaces the best only when its alpha is less).
+ *     o = opposite[3 f + i*].  o < 0 passes.  Else o is clamped to num_vertices - 1 and projected as
+ *     in K31a: x, y, w, sx = x / w, sy = y / w; fails when !(w > 0) or !(fabsf(sx) <= 16384.0f) or
+ *     !(fabsf(sy) <= 16384.0f); O = ((int)rintf(sx * 256.0f), (int)rintf(sy * 256.0f));
+ *     side = sgn [(X_k - X_j)(O_y - Y_j) - (Y_k - Y_j)(O_x - X_j)] in int64, E_i* at O; passes iff
+ *     side >= 0 (the neighbour folds back onto f's own side), fails otherwise (an interior edge).
+ *   On success alpha = alpha_i*, D = D_i*;  s = alpha - 0.5f;  s >= 0: target = b, source = a (f
+ *   reaches past the midpoint into b's pixel); else target = a, source = b;  m = fabsf(s).
+ *
+ * K34a, one thread per pixel p.  The channels c are r, g, b of color (height width,3) and alpha
+ * (height width), K31c's.  out_c = in[p]_c; then for the pairs left (slot (p - 1, 0)), right
+ * (slot (p, 0)), up (slot (p - width, 1)), down (slot (p, 1)) that exist, in that order, each active
+ * one whose target is p:  out_c = out_c + m * (in[source]_c - in[p]_c).  out_color (height width,3),
+ * out_alpha (height width).  A pixel in no active pair is copied bit for bit.
+ *
+ * K34b, one thread per pixel p.  g_color, g_alpha: the gradient in K34a's outputs.
+ *   image: d_c = g[p]_c; the same four pairs in the same order; an active pair with target p:
+ *   d_c = d_c - m * g[p]_c; with source p: d_c = d_c + m * g[target]_c.  A g at a pixel that is
+ *   neither p nor the target of one of p's pairs is not read.  d_color (height width,3), d_alpha.
+ *   entries: the thread owns the slots (p, 0) and (p, 1); slot (p, axis) has the entries
+ *   e = 4 p + 2 axis + {0, 1}.  Inactive or non-existent: entry_vertex[e] = num_vertices,
+ *   entry_grad[e] = (+0, +0), both entries.  Active, with t = target:
+ *     delta_c = in[source]_c - in[t]_c;
+ *     G = ((g[t]_r delta_r + g[t]_g delta_g) + g[t]_b delta_b) + g[t]_a delta_a;
+ *     d_alpha_pair = s >= 0 ? G : -G;   V_j, V_k = (float)(X, Y) of the corners j, k of f;
+ *     C = ((float)Q_a.x + alpha * (float)(Q_b.x - Q_a.x), likewise y);  c_j = C - V_j, c_k = C - V_k;
+ *     r = (sgn > 0 ? d_alpha_pair : -d_alpha_pair) / (float)D;   r256 = 256.0f * r;
+ *     entry 0: vertex triangles[f][k], (r256 * c_j.y, -(r256 * c_j.x));
+ *     entry 1: vertex triangles[f][j], (-(r256 * c_k.y), r256 * c_k.x);  ids clamped as in K31.
+ *   These are d loss / d (sx, sy) of the two vertices: alpha's derivative in V_k is
+ *   (sgn / D)(c_j.y, -c_j.x), in V_j it is -(sgn / D)(c_k.y, -c_k.x), and the snap V = 256 s is
+ *   passed straight through.  entry_vertex (4 height width) int32, entry_grad (4 height width,2)
+ *   f32; every entry is written on every call.
+ *
+ * K34c, one thread per vertex v.  sorted_vertex (4 num_pixels) int32: entry_vertex stably sorted,
+ * ascending; order (4 num_pixels) int32: the entries in that order; both made by the caller (the
+ * sentinel num_vertices sorts behind every vertex and belongs to none).  The run of v is
+ * [lower_bound(v), lower_bound(v + 1)) of sorted_vertex (binary searches; both ends lie in
+ * 0 .. 4 num_pixels whatever the array holds).  From 0.0f and in that order, e = order[at]:
+ * gx = gx + entry_grad[e][0], gy = gy + entry_grad[e][1]; an e outside 0 .. 4 num_pixels - 1 is
+ * skipped.  v projected as in K31a to x, y, w, sx = x / w, sy = y / w.  !(w > 0): the row is +0.
+ * Else, per component c of the position, with P the rows of proj:
+ *   grad[v][c] = ((gx * (P0c - sx * P2c)) + (gy * (P1c - sy * P2c))) / w
+ * grad (num_vertices,3) = the row, or with accumulate != 0 out = out + row, one add each.  The loop
+ * is linear in the run: a vertex on a long silhouette is one thread's loop, K33c's limit.
+ *
+ * K34d, one thread per vertex v.  values (num_vertices,3) f32; neighbor_starts (num_vertices + 1)
+ * int32 and neighbors (num_neighbors) int32: a CSR with every undirected edge listed once per end
+ * (the range of a row is clamped into the array).  From 0.0f and in the row's order, per component:
+ * acc_c = acc_c + (x[v]_c - x[n]_c); an n outside 0 .. num_vertices - 1 is skipped.
+ * out[v]_c = scale * acc_c, or with accumulate != 0 out = out + scale * acc.  With scale = 1 this
+ * is the gradient of 1/2 sum_edges |x_i - x_j|^2.  0 <= num_neighbors < 2^31. */
+int ffn_mesh_aa_forward(const int32_t* record, const uint64_t* zbuf, const int32_t* ids,
+                        const int32_t* opposite, const float* vertices, int64_t num_vertices,
+                        int64_t num_triangles, const float* proj, const float* color,
+                        const float* alpha, int width, int height, float* out_color,
+                        float* out_alpha, void* stream);
+int ffn_mesh_aa_backward(const int32_t* record, const uint64_t* zbuf, const int32_t* ids,
+                         const int32_t* opposite, const float* vertices, int64_t num_vertices,
+                         const int32_t* triangles, int64_t num_triangles, const float* proj,
+                         const float* color, const float* alpha, const float* g_color,
+                         const float* g_alpha, int width, int height, float* d_color,
+                         float* d_alpha, int32_t* entry_vertex, float* entry_grad, void* stream);
+int ffn_mesh_aa_vertex_grad(const int32_t* sorted_vertex, const int32_t* order,
+                            const float* entry_grad, int64_t num_pixels, const float* vertices,
+                            int64_t num_vertices, const float* proj, float* grad, int accumulate,
+                            void* stream);
+int ffn_mesh_laplacian(const float* values, const int32_t* neighbor_starts,
+                       const int32_t* neighbors, int64_t num_vertices, int64_t num_neighbors,
+                       float scale, float* out, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ with its vertex colours, any other with its texture (``--texture``, or the ``map
 ``mtllib``; white without one).  ``--normalize`` puts the mesh where
 ``scripts/make_mesh_npz.py`` put it when it made the dataset from the same file.
 
-    python scripts/render_mesh.py mesh.obj data.npz out_dir [--normalize] [--supersample 4]
+    python scripts/render_mesh.py mesh.obj data.npz out_dir [--normalize] [--supersample 4] [--antialias]
 """
 
 import os
@@ -33,6 +33,8 @@ RENDER_MESH = [
     ("--background", dict(type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("R", "G", "B"))),
     ("--supersample", dict(type=int, default=1,
                            help="sub-pixels a side that every pixel averages")),
+    ("--antialias", dict(action="store_true",
+                         help="blend the silhouette edges analytically (kernel K34a)")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -65,7 +67,7 @@ def main():
     for camera in range(sampler.num_cameras):
         image = ffn.render_mesh_image(vertices, triangles, sampler.cameras[camera],
                                       background=args.background, supersample=args.supersample,
-                                      device=device, **paint)
+                                      device=device, antialias=args.antialias, **paint)
         _cli.save_png(os.path.join(args.output_dir, "frame_{:05d}.png".format(camera)), image)
         truth = ground_truth(dataset.images[camera], resolution, args.background)
         values.append(psnr(image, truth))
