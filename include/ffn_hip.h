@@ -15,6 +15,12 @@
  *     contiguous row-major float32 unless the comment says otherwise
  *   - no hidden allocation, no hidden synchronisation; kernels are enqueued on
  *     `stream` (a hipStream_t passed as void*; NULL = the default stream)
+ *   - memory: an entry point writes only through its non-const pointers (or, for
+ *     ffn_mlp_pack_jobs and ffn_render_fused_fwd, through the output pointers that its job
+ *     table or ffn_render_out names) and only within the extents documented for them; on
+ *     success it writes every output word that the comment does not call undefined; it
+ *     reads its inputs only within their extents.  tests/test_memory_bounds_gpu.py holds
+ *     every entry point that takes a `stream` to this, between red zones
  *   - functions are re-entrant and keep no mutable global state
  *   - one device per call: the device that is current on the calling thread
  */

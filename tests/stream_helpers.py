@@ -249,19 +249,30 @@ class Hook:
 
 
 # ------------------------------------------------------------------------------------ one case
+def take_extras(live):
+    """Takes what is not a tensor out of a builder's ``live`` -> (decoys, kept, check_reference)
+    (tests/stream_order_cases.py, module docstring)."""
+    return live.pop("_decoys", {}), live.pop("_kept", {}), live.pop("_check_reference", None)
+
+
+def keep_answers(patch, kept):
+    """The wrappers' host-side checks named in ``kept`` give their recorded answers (``_keep_answer``
+    of tests/stream_order_cases.py) to the end of ``patch``."""
+    from fourier_feature_nets_amd import ops
+    for name, answer in kept.items():
+        patch.setattr(ops, name, lambda *args, _answer=answer, **kwargs: _answer)
+
+
 def run_case(case, scenario, hook, monkeypatch):
     """Runs ``case`` (tests/stream_order_cases.py) in ``scenario`` "A" or "B" -> the entry points
     it reached.  Raises AssertionError naming the outputs that differ and the call sequence."""
     import torch
-    from fourier_feature_nets_amd import ops
     assert scenario in ("A", "B")
     delay()
     null, side = torch.cuda.default_stream(), side_stream()
     assert null.cuda_stream == 0 and side.cuda_stream != 0
     live, run = case.build(torch.device("cuda:0"))
-    custom = live.pop("_decoys", {})
-    kept = live.pop("_kept", {})
-    check_reference = live.pop("_check_reference", None)
+    custom, kept, check_reference = take_extras(live)
     real = {k: live[k].clone() for k in case.decoy}
     decoy = {k: (custom[k] if k in custom else real[k].flip(0)).contiguous() for k in case.decoy}
     for k in case.decoy:
@@ -273,8 +284,7 @@ def run_case(case, scenario, hook, monkeypatch):
 
     with monkeypatch.context() as patch:
         mark_empties(patch)
-        for name, answer in kept.items():
-            patch.setattr(ops, name, lambda *args, _answer=answer, **kwargs: _answer)
+        keep_answers(patch, kept)
         put(real)
         want = clones(run(live))
         torch.cuda.synchronize()
