@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import c_i, c_i64
-from .ops import _call, _dev
+from .ops import _call, _dev, _want, _want_numel
 
 MAX_STEPS = 16
 BIAS_LDS_FLOATS = 4096      # csrc/mlp.hip kBiasLdsFloats: the LDS copy of the bias buffer's head
@@ -301,6 +301,7 @@ class MlpProgram:
         self.device = device
         self.encodings = list(encodings)
         self.layers = list(layers)
+        self.uses_views = any(spec.enc_id == 1 for spec in self.layers)
         self._workspaces: Dict[int, Workspace] = {}
         self._build_forward()
         self._build_backward()
@@ -893,14 +894,35 @@ class MlpProgram:
         if self._packed_x6_dirty:
             self.pack16(parts=3)
 
+    def _want_samples(self, who, positions, views) -> int:
+        """The argument contract of a launch over samples: positions (n,3), and views (n,3)
+        exactly when a layer of the chain reads the view encoding -> n."""
+        try:        # the good case on plain ints (``_want`` below repeats it with the dtypes)
+            if (positions.dim() == 2 and positions.shape[1] == 3
+                    and positions.dtype == torch.float32 and positions.is_contiguous()
+                    and ((views is None and not self.uses_views)
+                         or (self.uses_views and views.shape == positions.shape
+                             and views.dtype == torch.float32 and views.is_contiguous()))):
+                return positions.shape[0]
+        except AttributeError:
+            pass
+        _want(who, "positions", positions, (None, 3))
+        n = positions.shape[0]
+        if self.uses_views:
+            _want(who, "views", views, (n, 3))
+        elif views is not None:
+            raise ValueError("%s: views given, but no layer of this chain reads a view encoding"
+                             % who)
+        return n
+
     def forward16(self, positions: torch.Tensor, views: Optional[torch.Tensor]) -> torch.Tensor:
         """Inference in the opt-in split-bf16 mode (3 bf16 matrix products per f32 product):
         positions (N,3) [views (N,3)] -> raw logits (N,4)."""
+        n = self._want_samples("MlpProgram.forward16", positions, views)
         if self.fwd16 is None:
             raise NotImplementedError("the split-bf16 kernels cover chains whose logits heads are fused")
         if self._packed16_dirty:
             self.pack16()
-        n = positions.shape[0]
         logits = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         _call("ffn_mlp_forward_bf16x3", ctypes.byref(self.fwd16), _dev(self.packed16, torch.int16),
               _dev(self.bias_buf), _dev(positions, name="positions"), _dev(views, name="views"),
@@ -1070,7 +1092,9 @@ class MlpProgram:
         buffer of ``saved_floats(N)`` elements) receives what the backward pass needs.
         ``precision="bf16x3"`` (opt-in) runs the split-bf16 kernel, ``"bf16x6"`` (opt-in) the
         f32-accurate three-part split (six bf16 matrix products per f32 product)."""
-        n = positions.shape[0]
+        n = self._want_samples("MlpProgram.forward", positions, views)
+        if saved is not None:
+            _want_numel("MlpProgram.forward", "saved", saved, self.saved_floats(n), at_least=True)
         logits = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         acts, masks = (None, None) if saved is None else self._split_saved(saved, n)
         if saved is not None:
@@ -1155,6 +1179,7 @@ class MlpProgram:
             base, rays, valid = int(ray_index[0]), int(ray_index[1]), ray_index[2]
             ray_index = None
         else:
+            _want("MlpProgram.render", "ray_index", ray_index, (None,), torch.int64)
             rays = int(ray_index.shape[0])
         dev = self.device
         color = torch.empty((rays, 3), dtype=torch.float32, device=dev) if want_color else None
@@ -1162,8 +1187,40 @@ class MlpProgram:
         depth = torch.empty((rays,), dtype=torch.float32, device=dev) if want_depth else None
         if rays == 0:
             return color, alpha, depth
+        who = "MlpProgram.render"
         if t_values is not None and tuple(t_values.shape) != (rays, num_samples):
             raise ValueError("t_values must be (num_rays, num_samples)")
+        _want(who, "starts", starts, (None, 3))
+        _want(who, "directions", directions, (starts.shape[0], 3))
+        _want(who, "near_far", near_far, (2, None))
+        total = near_far.shape[1]           # the kernel's num_rays_total
+        if starts.shape[0] < total:
+            raise ValueError("%s: starts holds %d rays, fewer than the %d of near_far"
+                             % (who, starts.shape[0], total))
+        if ray_index is None:
+            if base < 0 or base + rays > total:
+                raise ValueError("%s: ray_index = (first id %d, count %d) leaves the %d rays of "
+                                 "near_far" % (who, base, rays, total))
+            if valid is not None:
+                _want(who, "valid", valid, (None,), torch.uint8)
+                if valid.shape[0] < base + rays:
+                    raise ValueError("%s: the valid mask of ray_index holds %d rays, fewer than "
+                                     "first id + count = %d" % (who, valid.shape[0], base + rays))
+        if unit is not None and 1 <= num_samples <= 256:    # (the entry point refuses the rest)
+            _want(who, "unit", unit, (num_samples,))
+        if nan_flag is not None:
+            _want_numel(who, "nan_flag", nan_flag, 1, torch.int32)
+        if image is not None and (not isinstance(image, torch.Tensor) or image.dim() < 1
+                                  or image.shape[-1] != 3):
+            raise ValueError("%s: image must be a (H,W,3) torch.uint8 frame" % who)
+        if image is not None and ray_index is None:
+            # a contiguous range of rays writes the pixels first id - pixel_offset .. + count
+            first = base - int(pixel_offset)
+            if first < 0 or first + rays > image.numel() // 3:
+                raise ValueError("%s: image holds %d pixels; ray_index = (first id %d, count %d) "
+                                 "with pixel_offset %d writes the pixels %d .. %d"
+                                 % (who, image.numel() // 3, base, rays, pixel_offset, first,
+                                    first + rays - 1))
         # the struct fields below are raw integers, which the same-device check of ops._call
         # cannot see: a sampler / grid / output on another GPU than the model must fail HERE,
         # not as an illegal access inside the kernel
@@ -1197,6 +1254,22 @@ class MlpProgram:
         ``ffn_focus_fused``): fills ``t_io`` (R,S) in place."""
         if self.big or n_focus > 64:
             raise NotImplementedError("fused focus sampling: chains of up to 512 channels, at most 64 probe points")
+        who = "MlpProgram.focus_sample"
+        _want(who, "ray_index", ray_index, (None,), torch.int64)
+        rays = ray_index.shape[0]
+        if isinstance(num_samples, bool) or int(num_samples) != num_samples \
+                or not 1 <= num_samples <= 256:
+            raise ValueError("%s: num_samples must be an integer in 1 .. 256, got %r"
+                             % (who, num_samples))
+        if isinstance(n_focus, bool) or int(n_focus) != n_focus or not 1 <= n_focus <= num_samples:
+            raise ValueError("%s: n_focus must be an integer in 1 .. num_samples = %d, got %r"
+                             % (who, num_samples, n_focus))
+        _want(who, "starts", starts, (None, 3))
+        _want(who, "directions", directions, (starts.shape[0], 3))
+        _want(who, "near_far", near_far, (2, None))
+        _want(who, "unit_focus", unit_focus, (n_focus,))
+        _want(who, "u", u, (rays, n_focus))
+        _want(who, "t_io", t_io, (rays, num_samples))
         _call("ffn_focus_fused", ctypes.byref(self.fwd), _dev(self.packed_fwd), _dev(self.bias_buf),
               _dev(starts), _dev(directions), _dev(near_far), c_i64(near_far.shape[1]),
               _dev(ray_index, torch.int64), c_i(ray_index.shape[0]), c_i(num_samples), c_i(n_focus),
@@ -1221,7 +1294,12 @@ class MlpProgram:
         Forward / backward pairs: the same mode on both sides, or an exact-f32 forward under any
         backward (the slab, mask and save-on-consume layouts are shared and both directions are
         tested against each other); any other mix raises."""
-        n = positions.shape[0]
+        who = "MlpProgram.backward"
+        n = self._want_samples(who, positions, views)
+        _want(who, "d_logits", d_logits, (n, 4))
+        _want_numel(who, "grads", grads, self.num_grad_floats)
+        if n > 0:
+            _want_numel(who, "saved", saved, self.saved_floats(n), at_least=True)
         if n == 0:                      # an empty batch contributes no gradient
             return grads.zero_()
         record = (getattr(self, "_fwd_records", None) or {}).get(saved.data_ptr())

@@ -4,6 +4,7 @@ CUDA(HIP) float32 tensors; there is no CPU path."""
 
 import ctypes
 import math
+import numbers
 from typing import Optional
 
 import numpy as np
@@ -32,6 +33,71 @@ def _dev(t: Optional[torch.Tensor], dtype=torch.float32, name="tensor"):
     ptr = _DevPtr(t.data_ptr())
     ptr.device = t.device
     return ptr
+
+
+def _want(who, name, t, shape, dtype=torch.float32):
+    """The argument contract of a wrapper ("The argument contract"): ``t`` is a
+    contiguous ``dtype`` tensor of ``shape`` (``None`` = any extent), else ``ValueError`` (``TypeError``
+    for the dtype, as ``_dev`` raises it) naming the wrapper and the argument.  Reads the tensor's
+    metadata only: no device memory, no synchronisation."""
+    if isinstance(t, torch.Tensor) and t.dtype == dtype:
+        # the good case first, on plain ints: this runs in every launch of the training step
+        got = t.shape
+        if len(got) == len(shape):
+            for w, g in zip(shape, got):
+                if w is not None and w != g:
+                    break
+            else:
+                if t.is_contiguous():
+                    return
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be a %s tensor, got %s" % (who, name, dtype, type(t).__name__))
+    if t.dtype != dtype:
+        raise TypeError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+    got = t.shape
+    if len(got) != len(shape) or any(w is not None and w != g for w, g in zip(shape, got)):
+        raise ValueError("%s: %s must be (%s), got %s"
+                         % (who, name, ", ".join("*" if w is None else str(w) for w in shape),
+                            tuple(got)))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def _want_numel(who, name, t, numel, dtype=torch.float32, at_least=False):
+    """``_want`` for a buffer the entry point takes as a flat extent: ``numel`` elements exactly
+    (``at_least``: or more), whatever the shape."""
+    if isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous():
+        have = t.numel()
+        if have == numel or (at_least and have > numel):
+            return
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be a %s tensor, got %s" % (who, name, dtype, type(t).__name__))
+    if t.dtype != dtype:
+        raise TypeError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+    if t.numel() != numel and not (at_least and t.numel() > numel):
+        raise ValueError("%s: %s must hold %s%d elements, got %s = %d"
+                         % (who, name, "at least " if at_least else "", numel, tuple(t.shape),
+                            t.numel()))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def _want_tensors(who, **named):
+    """Every named argument is a tensor (the checks that follow read ``.shape`` and ``.dim()``)."""
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+
+
+def _want_int(who, name, value, low, high=None):
+    """An integer argument inside the bounds include/ffn_hip.h documents for it."""
+    if type(value) is int and value >= low and (high is None or value <= high):
+        return
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < low or (high is not None
+                                                                         and value > high):
+        raise ValueError("%s: %s must be an integer %s, got %r"
+                         % (who, name, ">= %d" % low if high is None else "in %d .. %d" % (low, high),
+                            value))
 
 
 def _call(name, *args):
@@ -68,7 +134,16 @@ def raygen_nearfar(unproj: torch.Tensor, cam_pos: torch.Tensor, width: int, heig
                    box_lo, box_hi, points: Optional[torch.Tensor] = None):
     """K1.  unproj (C,4,4), cam_pos (C,3) on the GPU -> starts, directions, near_far, valid.
     ``points`` (W*H,2) float32 overrides the integer pixel grid."""
+    who = "raygen_nearfar"
+    if not isinstance(unproj, torch.Tensor) or unproj.dim() not in (2, 3):
+        raise ValueError("%s: unproj must be a (C,4,4) or (C,16) tensor" % who)
     cams = unproj.shape[0]
+    _want_numel(who, "unproj", unproj, 16 * cams)
+    _want(who, "cam_pos", cam_pos, (cams, 3))
+    _want_int(who, "width", width, 1)
+    _want_int(who, "height", height, 1)
+    if points is not None:
+        _want(who, "points", points, (width * height, 2))
     total = cams * width * height
     dev = unproj.device
     starts = torch.empty((total, 3), dtype=torch.float32, device=dev)
@@ -85,7 +160,19 @@ def sample_t(near_far: torch.Tensor, ray_index: torch.Tensor, count: int, unit: 
              noise: Optional[torch.Tensor], anneal: Optional[float],
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K2a.  Returns (R, stride) t-values; the first `count` columns are filled."""
+    who = "sample_t"
+    _want(who, "near_far", near_far, (2, None))
+    _want(who, "ray_index", ray_index, (None,), torch.int64)
     rays = ray_index.shape[0]
+    _want_int(who, "count", count, 1)
+    _want(who, "unit", unit, (count,))
+    if noise is not None:
+        _want(who, "noise", noise, (rays, count))
+    if out is not None:
+        _want(who, "out", out, (rays, None))
+        if out.shape[1] < count:
+            raise ValueError("%s: out must be (%d, >= %d), got %s"
+                             % (who, rays, count, tuple(out.shape)))
     if out is None:
         out = torch.empty((rays, count), dtype=torch.float32, device=near_far.device)
     _call("ffn_sample_t", _dev(near_far), c_i64(near_far.shape[1]),
@@ -97,7 +184,12 @@ def sample_t(near_far: torch.Tensor, ray_index: torch.Tensor, count: int, unit: 
 
 def materialise_samples(starts, directions, ray_index, t_values, want_views=True):
     """K2b.  positions (R,S,3) [and view_directions (R,S,3)]."""
+    who = "materialise_samples"
+    _want(who, "t_values", t_values, (None, None))
     rays, count = t_values.shape
+    _want(who, "ray_index", ray_index, (rays,), torch.int64)
+    _want(who, "starts", starts, (None, 3))
+    _want(who, "directions", directions, (starts.shape[0], 3))
     pos = torch.empty((rays, count, 3), dtype=torch.float32, device=t_values.device)
     views = torch.empty_like(pos) if want_views else None
     _call("ffn_materialise_samples", _dev(starts), _dev(directions),
@@ -108,6 +200,23 @@ def materialise_samples(starts, directions, ray_index, t_values, want_views=True
 
 def sample_materialise(near_far, starts, directions, ray_index, count, unit, noise, anneal, want_views=True):
     """K2a + K2b in one launch: t (R,count), positions (R,count,3) [, view_directions]."""
+    who = "sample_materialise"
+    try:            # every launch of a training step comes through here: the good case on plain ints
+        good = (type(count) is int and count >= 1 and near_far.dim() == 2 and near_far.shape[0] == 2
+                and starts.dim() == 2 and starts.shape[1] == 3 and directions.shape == starts.shape
+                and ray_index.dim() == 1 and unit.shape == (count,)
+                and (noise is None or noise.shape == (ray_index.shape[0], count)))
+    except (AttributeError, TypeError):
+        good = False
+    if not good:    # (dtype and contiguity are ``_dev``'s, before the one launch)
+        _want(who, "near_far", near_far, (2, None))
+        _want(who, "starts", starts, (None, 3))
+        _want(who, "directions", directions, (starts.shape[0], 3))
+        _want(who, "ray_index", ray_index, (None,), torch.int64)
+        _want_int(who, "count", count, 1)
+        _want(who, "unit", unit, (count,))
+        if noise is not None:
+            _want(who, "noise", noise, (ray_index.shape[0], count))
     rays = ray_index.shape[0]
     t = torch.empty((rays, count), dtype=torch.float32, device=near_far.device)
     pos = torch.empty((rays, count, 3), dtype=torch.float32, device=near_far.device)
@@ -120,7 +229,10 @@ def sample_materialise(near_far, starts, directions, ray_index, count, unit, noi
 
 def cdf_build(t_probe: torch.Tensor, opacity: torch.Tensor) -> torch.Tensor:
     """K2c.  (P,n),(P,n) -> (P,n-1)."""
+    _want("cdf_build", "t_probe", t_probe, (None, None))
     rays, n = t_probe.shape
+    _want_int("cdf_build", "t_probe.shape[1]", n, 1)
+    _want("cdf_build", "opacity", opacity, (rays, n))
     cdf = torch.empty((rays, n - 1), dtype=torch.float32, device=t_probe.device)
     _call("ffn_cdf_build", _dev(t_probe), _dev(opacity), c_i64(rays), c_i(n), _dev(cdf))
     return cdf
@@ -128,7 +240,10 @@ def cdf_build(t_probe: torch.Tensor, opacity: torch.Tensor) -> torch.Tensor:
 
 def cdf_build_logits(t_probe: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
     """K2c on raw coarse-model outputs: (P,n), (P*n,4) -> (P,n-1); softplus inside."""
+    _want("cdf_build_logits", "t_probe", t_probe, (None, None))
     rays, n = t_probe.shape
+    _want_int("cdf_build_logits", "t_probe.shape[1]", n, 1)
+    _want_numel("cdf_build_logits", "logits", logits, rays * n * 4)
     cdf = torch.empty((rays, n - 1), dtype=torch.float32, device=t_probe.device)
     _call("ffn_cdf_build_logits", _dev(t_probe), _dev(logits), c_i64(rays), c_i(n), _dev(cdf))
     return cdf
@@ -136,7 +251,19 @@ def cdf_build_logits(t_probe: torch.Tensor, logits: torch.Tensor) -> torch.Tenso
 
 def focus_sample_merge(near_far, cdfs, ray_index, u, unit_focus, t_io, n_focus, rows_local=False):
     """K2d.  In-place on t_io (R,S).  ``rows_local``: cdfs holds one row per batch ray."""
+    who = "focus_sample_merge"
+    _want(who, "t_io", t_io, (None, None))
     rays, count = t_io.shape
+    _want_int(who, "t_io.shape[1]", count, 1, 256)
+    _want_int(who, "n_focus", n_focus, 1, count)
+    _want(who, "near_far", near_far, (2, None))
+    _want(who, "cdfs", cdfs, (rays if rows_local else None, n_focus - 1))
+    if not rows_local and cdfs.shape[0] < near_far.shape[1]:
+        raise ValueError("%s: cdfs holds %d rows, fewer than the %d rays of near_far that index it"
+                         % (who, cdfs.shape[0], near_far.shape[1]))
+    _want(who, "ray_index", ray_index, (rays,), torch.int64)
+    _want(who, "u", u, (rays, n_focus))
+    _want(who, "unit_focus", unit_focus, (n_focus,))
     _call("ffn_focus_sample_merge_rows" if rows_local else "ffn_focus_sample_merge", _dev(near_far), c_i64(near_far.shape[1]), _dev(cdfs),
               _dev(ray_index, torch.int64), _dev(u), _dev(unit_focus), c_i(rays), c_i(count),
               c_i(n_focus), _dev(t_io))
@@ -146,6 +273,9 @@ def focus_sample_merge(near_far, cdfs, ray_index, u, unit_focus, t_io, n_focus, 
 def to_image(colors: torch.Tensor, pixel_index: torch.Tensor, width: int, height: int):
     """K8.  (n,3) colours + (n,) pixel ids -> (H,W,3) uint8 on the GPU: the byte of a colour
     ``c`` is ``float32(c) * 255`` truncated, unlisted pixels are 0."""
+    for name, t in (("colors", colors), ("pixel_index", pixel_index)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("to_image: %s must be a tensor, got %s" % (name, type(t).__name__))
     if colors.dim() != 2 or colors.shape[1] != 3:
         raise ValueError("to_image: colors must be (n, 3), got %s" % (tuple(colors.shape),))
     if pixel_index.numel() != colors.shape[0]:
@@ -165,6 +295,12 @@ def to_image(colors: torch.Tensor, pixel_index: torch.Tensor, width: int, height
 
 def ycrcb_to_rgb_u8(image: torch.Tensor) -> torch.Tensor:
     """K8b.  (H,W,3) uint8 YCrCb frame -> RGB, in place (OpenCV's 8-bit COLOR_YCrCb2RGB)."""
+    who = "ycrcb_to_rgb_u8"
+    if not isinstance(image, torch.Tensor) or image.dim() < 1 or image.shape[-1] != 3:
+        raise ValueError("%s: image must be a (..., 3) torch.uint8 frame, got %s"
+                         % (who, tuple(image.shape) if isinstance(image, torch.Tensor)
+                            else type(image).__name__))
+    _want_numel(who, "image", image, image.numel(), torch.uint8)
     _call("ffn_ycrcb_to_rgb_u8", _dev(image, torch.uint8, "image"), c_i64(image.numel() // 3))
     return image
 
@@ -173,6 +309,8 @@ def ycrcb_to_rgb_u8(image: torch.Tensor) -> torch.Tensor:
 def fourier_encode(x: torch.Tensor, b: Optional[torch.Tensor], a: Optional[torch.Tensor],
                    scale: float, include_input: bool) -> torch.Tensor:
     """K3.  (N,3) -> (N, 2F[+3]) with the cos block first; b (3,F) or None, a (F) or None."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError("fourier_encode: x must be a tensor, got %s" % type(x).__name__)
     if x.dim() != 2 or x.shape[1] != 3:
         raise ValueError("fourier_encode: x must be (N, 3), got %s" % (tuple(x.shape),))
     if b is not None and (b.dim() != 2 or b.shape[0] != 3):
@@ -196,7 +334,11 @@ def fourier_encode(x: torch.Tensor, b: Optional[torch.Tensor], a: Optional[torch
 def composite_fwd(logits: torch.Tensor, t: torch.Tensor, include_depth: bool,
                   nan_flag: Optional[torch.Tensor] = None):
     """K5.  logits (R,S,4), t (R,S) -> color (R,3), alpha (R), depth (R)|None."""
+    _want("composite_fwd", "t", t, (None, None))
     rays, count = t.shape
+    _want_numel("composite_fwd", "logits", logits, rays * count * 4)
+    if nan_flag is not None:
+        _want_numel("composite_fwd", "nan_flag", nan_flag, 1, torch.int32)
     dev = t.device
     color = torch.empty((rays, 3), dtype=torch.float32, device=dev)
     alpha = torch.empty((rays,), dtype=torch.float32, device=dev)
@@ -208,7 +350,9 @@ def composite_fwd(logits: torch.Tensor, t: torch.Tensor, include_depth: bool,
 
 def blend_weights(t: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
     """K5w.  utils.calculate_blend_weights: (R,S),(R,S) -> (R,S)."""
+    _want("blend_weights", "t", t, (None, None))
     rays, count = t.shape
+    _want("blend_weights", "sigma", sigma, (rays, count))
     out = torch.empty_like(t)
     _call("ffn_blend_weights", _dev(t), _dev(sigma), c_i(rays), c_i(count), _dev(out))
     return out
@@ -217,7 +361,11 @@ def blend_weights(t: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
 def blend_weights_bwd(t: torch.Tensor, sigma: torch.Tensor, d_weights: torch.Tensor,
                       want_dt: bool = False):
     """K5w backward.  Returns (d_sigma (R,S), d_t (R,S) | None)."""
+    who = "blend_weights_bwd"
+    _want(who, "t", t, (None, None))
     rays, count = t.shape
+    _want(who, "sigma", sigma, (rays, count))
+    _want(who, "d_weights", d_weights, (rays, count))
     d_sigma = torch.empty_like(t)
     d_t = torch.empty_like(t) if want_dt else None
     _call("ffn_blend_weights_bwd", _dev(t), _dev(sigma), _dev(d_weights), c_i(rays), c_i(count),
@@ -227,7 +375,12 @@ def blend_weights_bwd(t: torch.Tensor, sigma: torch.Tensor, d_weights: torch.Ten
 
 def composite_bwd(logits, t, d_color, d_alpha) -> torch.Tensor:
     """K5b.  d(logits) (R,S,4)."""
+    who = "composite_bwd"
+    _want(who, "t", t, (None, None))
     rays, count = t.shape
+    _want_numel(who, "logits", logits, rays * count * 4)
+    _want(who, "d_color", d_color, (rays, 3))
+    _want(who, "d_alpha", d_alpha, (rays,))
     d_logits = torch.empty((rays, count, 4), dtype=torch.float32, device=t.device)
     _call("ffn_composite_bwd", _dev(logits), _dev(t), _dev(d_color), _dev(d_alpha),
               c_i(rays), c_i(count), _dev(d_logits))
@@ -238,7 +391,16 @@ def mse_loss(color, alpha, gt_colors, gt_alphas, ray_index, color_scale, alpha_s
              want_grad=True, sums_out=None):
     """K6.  Returns (sums (2,), d_color, d_alpha); ``sums_out`` (2 floats) receives the sums
     in place of a fresh tensor."""
+    who = "mse_loss"
+    _want(who, "color", color, (None, 3))
     rays = color.shape[0]
+    _want(who, "alpha", alpha, (rays,))
+    _want(who, "gt_colors", gt_colors, (None, 3))
+    if gt_alphas is not None:
+        _want(who, "gt_alphas", gt_alphas, (gt_colors.shape[0],))
+    _want(who, "ray_index", ray_index, (rays,), torch.int64)
+    if sums_out is not None:
+        _want_numel(who, "sums_out", sums_out, 2)
     dev = color.device
     sums = sums_out if sums_out is not None else torch.empty((2,), dtype=torch.float32, device=dev)
     scratch = torch.empty((2 * ((rays + 255) // 256),), dtype=torch.float32, device=dev)
@@ -255,7 +417,25 @@ def composite_train(logits, t, gt_colors, gt_alphas, ray_index, color_scale, alp
     """K5t: K5 + K6 + K5b of one training batch in one launch.  logits (R,S,4), t (R,S) ->
     (d_logits (R,S,4), partials (blocks,2)): d_logits bit-identical to ``composite_fwd`` ->
     ``mse_loss`` -> ``composite_bwd``; the loss sums per workgroup go to ``loss_from_partials``."""
-    rays, count = t.shape
+    who = "composite_train"
+    try:            # every launch of a training step comes through here: the good case on plain ints
+        rays, count = t.shape
+        good = (logits.numel() == rays * count * 4 and gt_colors.dim() == 2
+                and gt_colors.shape[1] == 3 and ray_index.shape == (rays,)
+                and (gt_alphas is None or gt_alphas.shape == (gt_colors.shape[0],))
+                and (nan_flag is None or nan_flag.numel() == 1))
+    except (AttributeError, TypeError, ValueError):
+        good = False
+    if not good:    # (dtype and contiguity are ``_dev``'s, before the one launch)
+        _want(who, "t", t, (None, None))
+        rays, count = t.shape
+        _want_numel(who, "logits", logits, rays * count * 4)
+        _want(who, "gt_colors", gt_colors, (None, 3))
+        if gt_alphas is not None:
+            _want(who, "gt_alphas", gt_alphas, (gt_colors.shape[0],))
+        _want(who, "ray_index", ray_index, (rays,), torch.int64)
+        if nan_flag is not None:
+            _want_numel(who, "nan_flag", nan_flag, 1, torch.int32)
     blocks = int(_lib.load().ffn_composite_train_blocks(c_i(rays)))
     d_logits = torch.empty((rays, count, 4), dtype=torch.float32, device=t.device)
     partials = torch.empty((blocks, 2), dtype=torch.float32, device=t.device)
@@ -269,6 +449,9 @@ def loss_from_partials(partials: torch.Tensor, rays: int, alpha_weight: float,
                        sums_out: Optional[torch.Tensor] = None, want_loss: bool = True):
     """Fixed-order sum of K5t's per-workgroup pairs: into ``sums_out`` (2 floats, for the
     data-parallel all-reduce) and / or the scalar loss (a fresh device scalar)."""
+    _want("loss_from_partials", "partials", partials, (None, 2))
+    if sums_out is not None:
+        _want_numel("loss_from_partials", "sums_out", sums_out, 2)
     loss = torch.empty((), dtype=torch.float32, device=partials.device) if want_loss else None
     _call("ffn_loss_from_partials", _dev(partials), c_i(partials.shape[0]), c_f(3.0 * rays),
           c_f(float(rays)), c_f(alpha_weight), _dev(sums_out), _dev(loss))
@@ -277,6 +460,7 @@ def loss_from_partials(partials: torch.Tensor, rays: int, alpha_weight: float,
 
 def loss_value(sums: torch.Tensor, rays: int, alpha_weight: float) -> torch.Tensor:
     """sums[0] / (3 rays) + alpha_weight * sums[1] / rays as a fresh device scalar (one launch)."""
+    _want_numel("loss_value", "sums", sums, 2)
     out = torch.empty((), dtype=torch.float32, device=sums.device)
     _call("ffn_loss_value", _dev(sums), c_f(3.0 * rays), c_f(float(rays)), c_f(alpha_weight), _dev(out))
     return out
@@ -288,10 +472,35 @@ def regression_blocks(n: int) -> int:
     return int(_lib.load().ffn_regression_blocks(c_i64(n)))
 
 
+def _regression_want(who, logits, target, c, d_logits, partials, partials_needed=True):
+    """What K11 and K11b share: logits (n,4), target (n,c) with 1 <= c <= 4 (``target`` None: ``c``
+    from the caller), d_logits (n,4) where there is one, ``regression_blocks(n)`` partials."""
+    if c is not None:
+        _want_int(who, "c", c, 1, 4)
+    if target is not None:
+        _want(who, "target", target, (None, c))
+        n, c = target.shape
+        _want_int(who, "target.shape[1]", c, 1, 4)
+        _want(who, "logits", logits, (n, 4))
+    else:
+        _want(who, "logits", logits, (None, 4))
+        n = logits.shape[0]
+    if d_logits is not None:
+        _want(who, "d_logits", d_logits, (n, 4))
+    if partials is not None:
+        _want_numel(who, "partials", partials, regression_blocks(n) if n > 0 else 0, at_least=True)
+    elif partials_needed:
+        raise ValueError("%s: partials must be a torch.float32 tensor, got NoneType" % who)
+    return n, c
+
+
 def regression_train(logits: torch.Tensor, target: torch.Tensor, d_logits: torch.Tensor,
                      partials: torch.Tensor):
     """K11 training: logits (n,4), target (n,c) -> d_logits (n,4) of 0.5 * mean((sigmoid - y)^2)
     (columns >= c exactly 0) and one sum of squares per workgroup in ``partials``."""
+    _want("regression_train", "target", target, (None, None))
+    _want("regression_train", "d_logits", d_logits, (None, 4))
+    _regression_want("regression_train", logits, target, None, d_logits, partials)
     n, c = target.shape
     _call("ffn_regression_train", _dev(logits, name="logits"), _dev(target, name="target"),
           c_i64(n), c_i(c), c_f(1.0 / (n * c)), _dev(d_logits, name="d_logits"),
@@ -302,14 +511,27 @@ def regression_eval(logits: torch.Tensor, target: Optional[torch.Tensor], c: int
                     partials: Optional[torch.Tensor], image: Optional[torch.Tensor] = None):
     """K11 validation: sums of (sigmoid - y)^2 per workgroup into ``partials`` and / or the
     (sigmoid * 255) u8 pixels (n,c) into ``image``."""
-    n = logits.shape[0]
+    who = "regression_eval"
+    if partials is not None and target is None:
+        raise ValueError("%s: partials need a target to compare with" % who)
+    n, c = _regression_want(who, logits, target, c, None, partials, partials_needed=False)
+    if image is not None:
+        _want_numel(who, "image", image, n * c, torch.uint8)
     _call("ffn_regression_eval", _dev(logits, name="logits"), _dev(target, name="target"),
           c_i64(n), c_i(c), _dev(partials, name="partials"), _dev(image, torch.uint8, "image"))
+
+
+def _regression_loss_want(who, partials, sse_out, loss_out):
+    _want(who, "partials", partials, (None,))
+    for name, t in (("sse_out", sse_out), ("loss_out", loss_out)):
+        if t is not None:
+            _want_numel(who, name, t, 1)
 
 
 def regression_loss(partials: torch.Tensor, count: int, sse_out: Optional[torch.Tensor] = None,
                     loss_out: Optional[torch.Tensor] = None):
     """Fixed-order sum of K11's partials: sse into ``sse_out``, 0.5 * sse / count into ``loss_out``."""
+    _regression_loss_want("regression_loss", partials, sse_out, loss_out)
     _call("ffn_regression_loss", _dev(partials), c_i(partials.shape[0]), c_f(float(count)),
           _dev(sse_out), _dev(loss_out))
 
@@ -324,6 +546,9 @@ def regression_mse_train(logits: torch.Tensor, target: torch.Tensor, d_logits: t
                          partials: torch.Tensor):
     """K11b training: logits (n,4), target (n,c) -> d_logits (n,4) of mean((z - y)^2) (columns
     >= c exactly 0) and one sum of squares per workgroup in ``partials``."""
+    _want("regression_mse_train", "target", target, (None, None))
+    _want("regression_mse_train", "d_logits", d_logits, (None, 4))
+    _regression_want("regression_mse_train", logits, target, None, d_logits, partials)
     n, c = target.shape
     _call("ffn_regression_mse_train", _dev(logits, name="logits"), _dev(target, name="target"),
           c_i64(n), c_i(c), c_f(inv_count(n * c)), _dev(d_logits, name="d_logits"),
@@ -332,6 +557,8 @@ def regression_mse_train(logits: torch.Tensor, target: torch.Tensor, d_logits: t
 
 def regression_mse_eval(logits: torch.Tensor, target: torch.Tensor, partials: torch.Tensor):
     """K11b validation: sums of (z - y)^2 per workgroup into ``partials``."""
+    _want("regression_mse_eval", "target", target, (None, None))
+    _regression_want("regression_mse_eval", logits, target, None, None, partials)
     n, c = target.shape
     _call("ffn_regression_mse_eval", _dev(logits, name="logits"), _dev(target, name="target"),
           c_i64(n), c_i(c), _dev(partials, name="partials"))
@@ -340,6 +567,7 @@ def regression_mse_eval(logits: torch.Tensor, target: torch.Tensor, partials: to
 def regression_mse_loss(partials: torch.Tensor, count: int, sse_out: Optional[torch.Tensor] = None,
                         loss_out: Optional[torch.Tensor] = None):
     """Fixed-order sum of K11b's partials: sse into ``sse_out``, sse / count into ``loss_out``."""
+    _regression_loss_want("regression_mse_loss", partials, sse_out, loss_out)
     _call("ffn_regression_mse_loss", _dev(partials), c_i(partials.shape[0]), c_f(float(count)),
           _dev(sse_out), _dev(loss_out))
 
@@ -349,7 +577,20 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, weight_d
               clip_value=0.1, max_norm=0.1, beta1=0.9, beta2=0.999, eps=1e-8,
               scratch=None, norm_out=None):
     """K7 on flat fp32 buffers; `step` is the 1-based update count."""
+    who = "clip_adam"
+    if not isinstance(params, torch.Tensor):
+        raise ValueError("%s: params must be a torch.float32 tensor, got %s"
+                         % (who, type(params).__name__))
     n = params.numel()
+    _want_numel(who, "params", params, n)
+    _want_numel(who, "grads", grads, n)
+    _want_numel(who, "exp_avg", exp_avg, n)
+    _want_numel(who, "exp_avg_sq", exp_avg_sq, n)
+    _want_int(who, "step", step, 1)
+    if scratch is not None:
+        _want_numel(who, "scratch", scratch, (n + 1023) // 1024, at_least=True)
+    if norm_out is not None:
+        _want_numel(who, "norm_out", norm_out, 1)
     if scratch is None:
         scratch = torch.empty(((n + 1023) // 1024,), dtype=torch.float32, device=params.device)
     step_size = lr / (1.0 - beta1 ** step)
@@ -364,6 +605,8 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, weight_d
 def occupancy_build(logits: torch.Tensor, resolution: int, sigma_threshold: float,
                     dilate: bool) -> torch.Tensor:
     """K9a/b.  logits (G^3,4) at the cell centres -> bit mask (ceil(G^3/32),) int32."""
+    _want_int("occupancy_build", "resolution", resolution, 1)
+    _want_numel("occupancy_build", "logits", logits, 4 * resolution ** 3)
     words = (resolution ** 3 + 31) // 32
     bits = torch.empty((words,), dtype=torch.int32, device=logits.device)
     scratch = torch.empty_like(bits) if dilate else None
@@ -376,6 +619,12 @@ def occupancy_compact(positions: torch.Tensor, views: Optional[torch.Tensor], bo
                       resolution: int, bits: torch.Tensor):
     """K9c-e.  (N,3) samples -> packed positions / views of the samples in occupied cells and
     their int32 source index.  One device-to-host sync (the packed count sizes the outputs)."""
+    who = "occupancy_compact"
+    _want(who, "positions", positions, (None, 3))
+    if views is not None:
+        _want(who, "views", views, (positions.shape[0], 3))
+    _want_int(who, "resolution", resolution, 1)
+    _want_numel(who, "bits", bits, (resolution ** 3 + 31) // 32, torch.int32)
     n = positions.shape[0]
     dev = positions.device
     blocks = (n + 255) // 256
@@ -485,6 +734,9 @@ def occupancy_from_octree(leaf_index: torch.Tensor, scale: float, center, box_mi
 def scatter_logits(packed: torch.Tensor, index: torch.Tensor, n: int,
                    empty_sigma_logit: float = -100.0) -> torch.Tensor:
     """K9f.  (M,4) logits of the evaluated samples -> (N,4), the rest (0,0,0,empty_sigma_logit)."""
+    _want("scatter_logits", "packed", packed, (None, 4))
+    _want("scatter_logits", "index", index, (packed.shape[0],), torch.int32)
+    _want_int("scatter_logits", "n", n, packed.shape[0])
     out = torch.empty((n, 4), dtype=torch.float32, device=index.device)
     _call("ffn_scatter_logits", _dev(packed), _dev(index, torch.int32), c_i64(packed.shape[0]),
               c_i64(n), c_f(empty_sigma_logit), _dev(out))
@@ -493,6 +745,8 @@ def scatter_logits(packed: torch.Tensor, index: torch.Tensor, n: int,
 
 def gather_logits(full: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     """K9g.  (N,4) rows at ``index`` (int32) -> (M,4)."""
+    _want("gather_logits", "full", full, (None, 4))
+    _want("gather_logits", "index", index, (None,), torch.int32)
     m = index.shape[0]
     out = torch.empty((m, 4), dtype=torch.float32, device=full.device)
     if m > 0:
@@ -504,6 +758,10 @@ def gather_logits(full: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
 def voxels_forward(volume: torch.Tensor, bias: torch.Tensor, positions: torch.Tensor, side: int,
                    scale: float) -> torch.Tensor:
     """K10.  volume (4,S,S,S), bias (4), positions (N,3) -> logits (N,4)."""
+    _want_int("voxels_forward", "side", side, 1)
+    _want_numel("voxels_forward", "volume", volume, 4 * side ** 3)
+    _want_numel("voxels_forward", "bias", bias, 4)
+    _want("voxels_forward", "positions", positions, (None, 3))
     n = positions.shape[0]
     out = torch.empty((n, 4), dtype=torch.float32, device=positions.device)
     _call("ffn_voxels_forward", _dev(volume), _dev(bias), _dev(positions, name="positions"),
@@ -528,9 +786,15 @@ def voxels_backward(positions: torch.Tensor, d_logits: torch.Tensor, side: int, 
     """K10b, the adjoint of K10.  positions (N,3), d_logits (N,4) -> d_volume (4,S,S,S) and
     d_bias (4), both overwritten (no zeroing needed); deterministic (no float atomics).
     ``workspace``: any float32 device tensor of at least ``voxels_backward_workspace_bytes``."""
+    who = "voxels_backward"
+    _want_int(who, "side", side, 1, 1024)
+    _want(who, "positions", positions, (None, 3))
     n = positions.shape[0]
+    _want(who, "d_logits", d_logits, (n, 4))
     dev = positions.device
     need = voxels_backward_workspace_bytes(n, side)
+    if workspace is not None:
+        _want_numel(who, "workspace", workspace, (need + 3) // 4, at_least=True)
     if workspace is None:
         workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
     if d_volume is None:
@@ -570,7 +834,15 @@ def octree_surface_points(alpha: torch.Tensor, depth: torch.Tensor, starts: torc
     positions (N,3), colors (N,C) or None, count (int32 scalar on the device): the first
     ``count`` rows hold ``starts + directions * depth`` / ``color`` of the rays with
     ``alpha > threshold``, in ray order; the other rows are zero."""
+    who = "octree_surface_points"
+    _want(who, "alpha", alpha, (None,))
     n = alpha.shape[0]
+    if color is not None:
+        _want(who, "color", color, (n, None))
+    if n > 0:
+        _want(who, "depth", depth, (n,))
+        _want(who, "starts", starts, (n, 3))
+        _want(who, "directions", directions, (n, 3))
     dev = alpha.device
     channels = 0 if color is None else color.shape[1]
     # zeros, not empty: the rows past ``count`` are returned too, and whatever an earlier tensor
@@ -593,6 +865,7 @@ def octree_surface_points(alpha: torch.Tensor, depth: torch.Tensor, starts: torc
 
 def octree_path_codes(positions: torch.Tensor, center, scale: float, depth: int) -> torch.Tensor:
     """K12e.  positions (N,3), the cube's centre (3 floats) and half side -> int32 codes (N)."""
+    _want("octree_path_codes", "positions", positions, (None, 3))
     n = positions.shape[0]
     codes = torch.empty((n,), dtype=torch.int32, device=positions.device)
     if n == 0:
@@ -607,6 +880,9 @@ def octree_structure(sorted_codes: torch.Tensor, perm: torch.Tensor, depth: int,
     """K12f-g on stably sorted codes.  -> leaf_of_point (N) int64 (leaf id or -1, in the caller's
     point order), and per leaf in code order: leaf_ids (L) int64, leaf_start (L) int64,
     leaf_count (L) int32.  Reads the leaf count back once."""
+    who = "octree_structure"
+    _want(who, "sorted_codes", sorted_codes, (None,), torch.int32)
+    _want(who, "perm", perm, (sorted_codes.shape[0],), torch.int64)
     n = sorted_codes.shape[0]
     dev = sorted_codes.device
     leaf_sorted = torch.empty((n,), dtype=torch.int64, device=dev)
@@ -631,6 +907,7 @@ def octree_structure(sorted_codes: torch.Tensor, perm: torch.Tensor, depth: int,
 
 def octree_interior_nodes(leaf_ids: torch.Tensor, depth: int) -> torch.Tensor:
     """K12h.  leaf ids in code order -> the ids of the interior nodes (int64, unsorted)."""
+    _want("octree_interior_nodes", "leaf_ids", leaf_ids, (None,), torch.int64)
     k = leaf_ids.shape[0]
     dev = leaf_ids.device
     if depth < 2 or k == 0:
@@ -648,6 +925,11 @@ def octree_interior_nodes(leaf_ids: torch.Tensor, depth: int) -> torch.Tensor:
 def octree_leaf_means(data: torch.Tensor, perm: torch.Tensor, leaf_start: torch.Tensor,
                       leaf_count: torch.Tensor) -> torch.Tensor:
     """K12i.  data (N,C), perm (N) int64, per leaf start / count into perm -> (L,C) means."""
+    who = "octree_leaf_means"
+    _want(who, "data", data, (None, None))
+    _want(who, "perm", perm, (data.shape[0],), torch.int64)
+    _want(who, "leaf_start", leaf_start, (None,), torch.int64)
+    _want(who, "leaf_count", leaf_count, (leaf_start.shape[0],), torch.int32)
     k = leaf_start.shape[0]
     n, channels = data.shape
     out = torch.empty((k, channels), dtype=torch.float32, device=data.device)
@@ -661,6 +943,9 @@ def octree_leaf_means(data: torch.Tensor, perm: torch.Tensor, leaf_start: torch.
 def octree_query(positions: torch.Tensor, scale: float, node_index: torch.Tensor,
                  leaf_index: torch.Tensor) -> torch.Tensor:
     """K12j.  positions (N,3), sorted int64 id arrays -> (N) int64 index into leaf_index or -1."""
+    _want("octree_query", "positions", positions, (None, 3))
+    _want("octree_query", "node_index", node_index, (None,), torch.int64)
+    _want("octree_query", "leaf_index", leaf_index, (None,), torch.int64)
     n = positions.shape[0]
     out = torch.empty((n,), dtype=torch.int64, device=positions.device)
     if n > 0:
@@ -673,6 +958,7 @@ def octree_query(positions: torch.Tensor, scale: float, node_index: torch.Tensor
 
 def octree_leaf_geometry(leaf_index: torch.Tensor, scale: float):
     """K12k.  sorted leaf ids -> centres (L,3) float32 and depths (L) int32."""
+    _want("octree_leaf_geometry", "leaf_index", leaf_index, (None,), torch.int64)
     k = leaf_index.shape[0]
     centers = torch.empty((k, 3), dtype=torch.float32, device=leaf_index.device)
     depths = torch.empty((k,), dtype=torch.int32, device=leaf_index.device)
@@ -682,10 +968,23 @@ def octree_leaf_geometry(leaf_index: torch.Tensor, scale: float):
     return centers, depths
 
 
-def _walk_args(starts, directions, scale, depth, node_index, leaf_index):
+def _walk_check(starts, directions, scale, depth, node_index, leaf_index):
+    """What every walk refuses: rays that are not (N,3) twice, id arrays that are not (n,) int64, a
+    depth outside 1 .. 11 (include/ffn_hip.h, K13)."""
+    if not isinstance(starts, torch.Tensor) or not isinstance(directions, torch.Tensor) \
+            or starts.dim() != 2:
+        raise ValueError("octree walk: starts and directions must both be (N,3)")
     n = starts.shape[0]
     if starts.shape != (n, 3) or directions.shape != (n, 3):
         raise ValueError("octree walk: starts and directions must both be (N,3)")
+    _want("octree walk", "node_index", node_index, (None,), torch.int64)
+    _want("octree walk", "leaf_index", leaf_index, (None,), torch.int64)
+    _want_int("octree walk", "depth", depth, 1, 11)
+
+
+def _walk_args(starts, directions, scale, depth, node_index, leaf_index):
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
+    n = starts.shape[0]
     return (_dev(starts, name="starts"), _dev(directions, name="directions"), c_i64(n),
             c_f(scale), c_i(depth),
             _dev(node_index if node_index.numel() else None, torch.int64, "node_index"),
@@ -697,6 +996,8 @@ def octree_walk(starts: torch.Tensor, directions: torch.Tensor, scale: float, de
                 node_index: torch.Tensor, leaf_index: torch.Tensor, max_length: int):
     """K13.  starts, directions (N,3) in the tree's frame, sorted int64 id arrays, depth = 1 + the
     deepest leaf's level -> t_stops (N,max_length) float32, leaves (N,max_length) int64."""
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
+    _want_int("octree walk", "max_length", max_length, 2)
     n = starts.shape[0]
     t_stops = torch.empty((n, max_length), dtype=torch.float32, device=starts.device)
     leaves = torch.empty((n, max_length), dtype=torch.int64, device=starts.device)
@@ -712,6 +1013,7 @@ def octree_spans(starts: torch.Tensor, directions: torch.Tensor, scale: float, d
                  pad: float = 1.0):
     """K13, span form.  -> t_in (N), t_out (N) float32 and hit (N) uint8: the span of the leaves
     that end after ``t_min``, widened by ``pad`` finest-cell sides along the ray."""
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
     n = starts.shape[0]
     t_in = torch.empty((n,), dtype=torch.float32, device=starts.device)
     t_out = torch.empty((n,), dtype=torch.float32, device=starts.device)
@@ -741,6 +1043,7 @@ def octree_first_hit(starts: torch.Tensor, directions: torch.Tensor, scale: floa
     """K14.  Arguments as for ``octree_spans`` -> per ray the first leaf that ends after ``t_min``:
     leaf (N) int64 index into leaf_index or -1, t_hit (N) float32 = max(entry t, t_min) or 0,
     face (N) int8: the entry face 0 .. 5, 6 for an entry before ``t_min``, -1 for a miss."""
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
     n = starts.shape[0]
     leaf = torch.empty((n,), dtype=torch.int64, device=starts.device)
     t_hit = torch.empty((n,), dtype=torch.float32, device=starts.device)
@@ -762,6 +1065,10 @@ def octree_render(starts: torch.Tensor, directions: torch.Tensor, scale: float, 
     ``octree_first_hit``."""
     if shading not in OCTREE_SHADING:
         raise ValueError("octree render: shading is 'flat' or 'faces', got %r" % (shading,))
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
+    if not isinstance(leaf_data, torch.Tensor):
+        raise ValueError("octree render: leaf_data must be a tensor, got %s"
+                         % type(leaf_data).__name__)
     if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 3:
         raise ValueError("octree render: leaf_data must be (num_leaves, C >= 3), got %s for %d "
                          "leaves" % (tuple(leaf_data.shape), leaf_index.numel()))
@@ -789,6 +1096,9 @@ def octree_render(starts: torch.Tensor, directions: torch.Tensor, scale: float, 
 
 
 def _check_leaf_data(who, leaf_data, leaf_index):
+    for name, t in (("leaf_index", leaf_index), ("leaf_data", leaf_data)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
     if leaf_data.dim() != 2 or leaf_data.shape[0] != leaf_index.numel() or leaf_data.shape[1] < 4:
         raise ValueError("%s: leaf_data must be (num_leaves, C >= 4), got %s for %d leaves"
                          % (who, tuple(leaf_data.shape), leaf_index.numel()))
@@ -804,6 +1114,7 @@ def _render_volume(name, walk, t_min, leaf_block, background, min_transmittance,
     """A volume render through entry point ``name`` -> color (N,3), alpha (N), depth (N).
     ``walk``: the arguments of ``_walk_args``; ``leaf_block()``: the leaf arguments after
     ``t_min``; ``tail``: those after the outputs."""
+    _walk_check(*walk)
     n, dev = walk[0].shape[0], walk[0].device
     color = torch.empty((n, 3), dtype=torch.float32, device=dev)
     alpha = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -855,6 +1166,9 @@ def octree_sh_device_layout(leaf_data: np.ndarray, degree: int) -> np.ndarray:
 def _check_leaf_rows(who, leaf_rows, leaf_index, degree) -> int:
     """SH rows in the device layout, one per leaf -> the channels of ``degree``."""
     channels = octree_sh_channels(degree)
+    for name, t in (("leaf_index", leaf_index), ("leaf_rows", leaf_rows)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
     if (leaf_rows.dim() != 2 or leaf_rows.shape[0] != leaf_index.numel()
             or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0):
         raise ValueError("%s: leaf_rows must be (num_leaves, stride) with stride a multiple of 4 "
@@ -885,6 +1199,10 @@ def octree_sh_accumulate(logits: torch.Tensor, leaf_data: torch.Tensor, weights,
     inv_views into the density."""
     channels = octree_sh_channels(degree)
     basis = (channels - 1) // 3
+    for name, t in (("logits", logits), ("leaf_data", leaf_data)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("octree sh_accumulate: %s must be a tensor, got %s"
+                             % (name, type(t).__name__))
     if logits.dim() != 2 or logits.shape[1] != 4:
         raise ValueError("octree sh_accumulate: logits must be (L,4), got %s"
                          % (tuple(logits.shape),))
@@ -982,8 +1300,12 @@ def _render_volume_backward(name, walk, t_min, leaf_block, background, min_trans
     ``dist = (dist_scale, ray_distortion)`` (K29b) calls entry point ``name + "_dist"`` with the two
     behind ``tail``; ``None`` calls ``name`` as ever."""
     who = "octree " + name[len("ffn_octree_"):]
+    _walk_check(*walk)
     starts, leaf_index = walk[0], walk[5]
     d_color, d_alpha = grads
+    for label, t in (("d_color", d_color), ("d_alpha", d_alpha)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, label, type(t).__name__))
     n, leaves = starts.shape[0], leaf_index.numel()
     if d_color.shape != (n, 3) or d_alpha.shape != (n,):
         raise ValueError("%s: d_color must be (N,3) and d_alpha (N,)" % who)
@@ -1060,6 +1382,7 @@ def octree_render_volume_backward(starts: torch.Tensor, directions: torch.Tensor
 
 def octree_project(leaf_data: torch.Tensor) -> torch.Tensor:
     """K17c, in place on leaf_data (L,4): rgb clamped to [0, 1], sigma to [0, inf), NaN -> 0."""
+    _want_tensors("octree project", leaf_data=leaf_data)
     if leaf_data.dim() != 2 or leaf_data.shape[1] != 4:
         raise ValueError("octree project: leaf_data must be (L,4), got %s" % (tuple(leaf_data.shape),))
     if leaf_data.shape[0] > 0:
@@ -1136,6 +1459,7 @@ def octree_project_sh(leaf_rows: torch.Tensor, degree: int) -> torch.Tensor:
     """K19c, in place on leaf_rows (L, stride) in the device layout: density to [0, inf), NaN -> 0
     for density and coefficients; the coefficients are otherwise untouched, the padding too."""
     channels = octree_sh_channels(degree)
+    _want_tensors("octree project_sh", leaf_rows=leaf_rows)
     if leaf_rows.dim() != 2 or leaf_rows.shape[1] < channels or leaf_rows.shape[1] % 4 != 0:
         raise ValueError("octree project_sh: leaf_rows must be (L, stride) with stride a multiple "
                          "of 4 and >= %d, got %s" % (channels, tuple(leaf_rows.shape),))
@@ -1149,6 +1473,8 @@ def octree_neighbors(node_index: torch.Tensor, leaf_index: torch.Tensor) -> torc
     """K20a.  Sorted int64 id arrays -> (L,6) int32: per leaf and direction (-x, +x, -y, +y, -z, +z)
     the number of the leaf of equal size or coarser across that face, -1 for the cube's boundary,
     empty space or finer leaves (which hold the adjacency from their side)."""
+    _want("octree_neighbors", "node_index", node_index, (None,), torch.int64)
+    _want("octree_neighbors", "leaf_index", leaf_index, (None,), torch.int64)
     leaves = leaf_index.numel()
     out = torch.empty((leaves, 6), dtype=torch.int32, device=leaf_index.device)
     if leaves > 0:
@@ -1299,6 +1625,7 @@ def octree_tv(rows: torch.Tensor, plan: OctreeTVPlan, weights, eps: float,
     if not isinstance(plan, OctreeTVPlan):
         raise TypeError("octree tv: plan must be an OctreeTVPlan (ops.octree_tv_plan)")
     eps = octree_tv_check_eps(eps)
+    _want_tensors("octree tv", rows=rows)
     if rows.dim() != 2 or rows.shape[1] % 4 != 0 or not 4 <= rows.shape[1] <= 64:
         raise ValueError("octree tv: rows must be (num_leaves, stride) with stride a multiple of 4 "
                          "in 4 .. 64, got %s" % (tuple(rows.shape),))
@@ -1340,6 +1667,7 @@ def octree_tv(rows: torch.Tensor, plan: OctreeTVPlan, weights, eps: float,
 def octree_bake(logits: torch.Tensor) -> torch.Tensor:
     """Raw model logits (L,4) [r, g, b, sigma] -> (L,4) float32 [sigmoid(r), sigmoid(g),
     sigmoid(b), softplus(sigma)], the activations of the compositing kernels bit for bit."""
+    _want_tensors("octree bake", logits=logits)
     if logits.dim() != 2 or logits.shape[1] != 4:
         raise ValueError("octree bake: logits must be (L,4), got %s" % (tuple(logits.shape),))
     out = torch.empty_like(logits)
@@ -1353,6 +1681,9 @@ def octree_cell_centers(first_code: int, count: int, center, scale: float, depth
     """K16a.  -> (count,3) float32 on ``device``: the centres of the finest cells (level
     ``depth - 1``) with the path codes ``first_code .. first_code + count - 1``, shifted by the
     cube's ``center``."""
+    _want_int("octree_cell_centers", "depth", depth, 1, octree_max_depth())
+    _want_int("octree_cell_centers", "count", count, 0, 8 ** (depth - 1))
+    _want_int("octree_cell_centers", "first_code", first_code, 0, 8 ** (depth - 1) - count)
     out = torch.empty((count, 3), dtype=torch.float32, device=device)
     _call("ffn_octree_cell_centers", c_i64(first_code), c_i64(count), c_f(center[0]),
           c_f(center[1]), c_f(center[2]), c_f(scale), c_i(depth), _dev(out))
@@ -1364,6 +1695,8 @@ def octree_density_select(logits: torch.Tensor, first_code: int, tau: float, sid
     """K16b.  logits (N,4) of the cells ``first_code .. first_code + N - 1`` -> codes (K) int32 and
     data (K,4) float32 of the cells with ``softplus(sigma) * side > tau``, in code order; data is
     what ``octree_bake`` makes of the kept rows.  Reads the count back once."""
+    _want_tensors("octree density select", logits=logits)
+    _want_int("octree density select", "depth", depth, 1, octree_max_depth())
     if logits.dim() != 2 or logits.shape[1] != 4:
         raise ValueError("octree density select: logits must be (N,4), got %s"
                          % (tuple(logits.shape),))
@@ -1388,6 +1721,9 @@ def octree_merge_level(codes: torch.Tensor, levels: torch.Tensor, data: torch.Te
     the finest level, levels (N) int32, data (N,4) float32): eight sibling leaves of ``level``
     within the tolerances of their mean become their parent.  -> the new (codes, levels, data).
     Reads the count back once."""
+    _want_tensors("octree merge level", codes=codes, levels=levels, data=data)
+    _want_int("octree merge level", "depth", depth, 2, octree_max_depth())
+    _want_int("octree merge level", "level", level, 1, depth - 1)
     n = codes.shape[0]
     dev = codes.device
     if levels.shape != (n,) or data.shape != (n, 4):
@@ -1419,6 +1755,8 @@ def octree_leaf_weights(starts: torch.Tensor, directions: torch.Tensor, scale: f
     the stride of ``octree_sh_device_layout`` and offset 0 for SH rows.  With ``out`` (L,) float32
     given the maxima fold into it (and it is returned): cameras or chunks of rays, in any order,
     give the bits of one call over all of them.  ``out`` holds weights, that is values >= 0."""
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
+    _want_tensors("octree leaf_weights", rows=rows)
     stride, sigma_offset = int(stride), int(sigma_offset)
     if (rows.dim() != 2 or rows.shape[0] != leaf_index.numel() or rows.shape[1] != stride
             or stride < 1 or not 0 <= sigma_offset < stride):
@@ -1449,6 +1787,8 @@ def octree_distortion(starts: torch.Tensor, directions: torch.Tensor, scale: flo
     ``m`` a chord's midpoint and ``L`` its length, both as world lengths along the ray -> (N,)
     float32, +0 for a ray that takes no leaf.  ``rows``, ``stride`` and ``sigma_offset`` as for
     ``octree_leaf_weights`` (only the density is read).  No atomics: the same bits on every call."""
+    _walk_check(starts, directions, scale, depth, node_index, leaf_index)
+    _want_tensors("octree distortion", rows=rows)
     stride, sigma_offset = int(stride), int(sigma_offset)
     if (rows.dim() != 2 or rows.shape[0] != leaf_index.numel() or rows.shape[1] != stride
             or stride < 1 or not 0 <= sigma_offset < stride):
@@ -1484,6 +1824,10 @@ def octree_focus_sample(starts: torch.Tensor, directions: torch.Tensor, near_far
     whose M is not positive or below ``min_mass``, that misses the cube or has no near < far gets
     ``near + u * (far - near)``."""
     who = "octree focus_sample"
+    _want_tensors(who, starts=starts, directions=directions, near_far=near_far,
+                  ray_index=ray_index, leaf_index=leaf_index, rows=rows, u=u)
+    _want(who, "node_index", node_index, (None,), torch.int64)
+    _want_int(who, "depth", depth, 1, 11)
     n = starts.shape[0]
     if starts.shape != (n, 3) or directions.shape != (n, 3) or near_far.shape != (2, n):
         raise ValueError("%s: starts and directions must be (N,3) and near_far (2,N)" % who)
@@ -1590,6 +1934,7 @@ def octree_refine(leaf_ids: torch.Tensor, rows: Optional[torch.Tensor], action: 
     at level ``octree_max_depth() - 1`` (the tree would pass the ray walk's depth limit of 11) and
     when the new leaf count could reach 2^31.  Reads one small block of counts back; the sort to code
     order and back to id order, the interior nodes (K12h) and the permutations are plumbing."""
+    _want_tensors("octree refine", leaf_ids=leaf_ids, action=action)
     num = leaf_ids.shape[0]
     dev = leaf_ids.device
     depth = int(depth)
@@ -2051,6 +2396,8 @@ def _octree_visible_pairs(entry, moments, leaf_centers, scale, depth, node_index
     leaves, cameras, height, width = octree_visible_check(
         leaf_centers, leaf_index, rows, stride, sigma_offset, images_u8, proj, eyes, depth,
         alpha_u8, min_transmittance, out, moments)
+    _want("octree_visible_moments" if moments else "octree_visible_votes", "node_index",
+          node_index, (None,), torch.int64)
     dev = leaf_index.device
     if out is None:
         out = torch.zeros((leaves, 8 if moments else 4), dtype=torch.uint32, device=dev)
@@ -2102,6 +2449,9 @@ def octree_mesh_solid(rows: Optional[torch.Tensor], sigma_offset: int,
     if rows is not None and (rows.dim() != 2 or rows.shape[0] != num_leaves):
         raise ValueError("octree mesh: rows must be (num_leaves, stride) = (%d, stride), got %s"
                          % (num_leaves, tuple(rows.shape)))
+    if rows is not None and not 0 <= int(sigma_offset) < rows.shape[1]:
+        raise ValueError("octree mesh: sigma_offset %r is outside the %d columns of rows"
+                         % (sigma_offset, rows.shape[1]))
     if solid is not None and tuple(solid.shape) != (num_leaves,):
         raise ValueError("octree mesh: solid must be (num_leaves,) = (%d,), got %s"
                          % (num_leaves, tuple(solid.shape)))
@@ -2136,6 +2486,9 @@ def octree_mesh_candidates(node_index: torch.Tensor, leaf_index: torch.Tensor,
                            count: int, depth: int):
     """K30b on the candidates ``first .. first + count - 1`` -> (keys (K,) int64, masks (K,) uint8,
     samples (K,8) int32) of the corners kept, in candidate order.  Reads the count back once."""
+    _want_tensors("octree mesh", leaf_index=leaf_index, solid=solid, cand_offsets=cand_offsets)
+    _want("octree mesh", "node_index", node_index, (None,), torch.int64)
+    _want_int("octree mesh", "depth", depth, 1, octree_mesh_max_depth())
     dev = leaf_index.device
     num_leaves = leaf_index.numel()
     if tuple(solid.shape) != (num_leaves,) or tuple(cand_offsets.shape) != (num_leaves + 1,):
@@ -2170,6 +2523,9 @@ def octree_mesh_vertices(keys: torch.Tensor, masks: torch.Tensor, samples: torch
     int32; ``alpha`` (L,) of K30a; ``rows`` (L, stride) and ``color = (offset, step, sh)`` name the
     three colour columns (``sh``: band-0 SH logits), or ``rows`` None for no colours.
     -> vertices (V,3) f32, colors (V,3) f32 or None, normals (V,3) f32, corners (V,3) int32."""
+    _want("octree mesh", "keys", keys, (None,), torch.int64)
+    _want_tensors("octree mesh", masks=masks, samples=samples)
+    _want("octree mesh", "alpha", alpha, (None,))
     dev = keys.device
     count = keys.numel()
     num_leaves = alpha.numel()
@@ -2200,6 +2556,8 @@ def octree_mesh_faces(keys: torch.Tensor, masks: torch.Tensor, depth: int) -> to
     """K30d.  ``keys`` (V,) int64 ascending and their ``masks`` -> triangles (F,3) int32, two per
     owned quad, ordered by owner vertex, then axis, wound so that the normal points from solid to
     empty.  Reads the quad count back once; a quad whose corner is not among the keys raises."""
+    _want("octree mesh", "keys", keys, (None,), torch.int64)
+    _want_tensors("octree mesh", masks=masks)
     dev = keys.device
     count = keys.numel()
     if tuple(masks.shape) != (count,):

@@ -21,6 +21,9 @@
  *     success it writes every output word that the comment does not call undefined; it
  *     reads its inputs only within their extents.  tests/test_memory_bounds_gpu.py holds
  *     every entry point that takes a `stream` to this, between red zones
+ *   - arguments: the entry points trust the extents they are given.  The Python wrappers refuse a
+ *     tensor whose shape does not give a pointer its documented extent before anything is
+ *     launched; tests/test_wrapper_refusals_cpu.py holds every wrapper to that
  *   - functions are re-entrant and keep no mutable global state
  *   - one device per call: the device that is current on the calling thread
  */
