@@ -70,6 +70,9 @@ SOURCES = {
     # the edge crossing alpha = E(a) / (E(a) - E(b)), the blends out + m * (in[s] - in[p]) and the
     # sums of the vertex entries in a fixed order, every product, add and quotient rounded
     "mesh_aa.hip": ["-ffp-contract=off"],
+    # lambda_i = E_i / |A|, r_i = (a_i depth_w) / w_i, G = (r0 n0 + r1 n1) + r2 n2 and the sums of
+    # -(lambda_j G) over pixels and corners in a fixed order, every operation rounded on its own
+    "mesh_interp_grad.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

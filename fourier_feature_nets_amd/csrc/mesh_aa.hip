@@ -39,7 +39,8 @@
 // gfx950 disassemblies before and after this file was added are the same.
 //
 // Not done: a work split for a vertex on a long silhouette (K34c's loop is linear in the run, as
-// K33c's), interior gradients (colour through the barycentric weights), several cameras per launch.
+// K33c's), several cameras per launch.  The interior gradients (colour through the barycentric
+// weights) are K35's, in mesh_interp_grad.hip.
 #include "common.h"
 #include "mesh_raster_terms.h"
 

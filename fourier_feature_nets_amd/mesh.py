@@ -38,7 +38,9 @@ and ``texture_to_uint8`` + ``save_obj(uvs=, texture=)`` write the result out.
 ``csrc/mesh_aa.hip``, nvdiffrast's edge antialiasing), which makes the picture a smooth function of
 the vertex positions; ``render_mesh_geometry_backward`` is its transpose in the positions,
 ``fit_mesh_geometry`` optimises them against a dataset's images, and ``edge_opposites`` and
-``vertex_neighbors`` make the edge and neighbour lists they need.
+``vertex_neighbors`` make the edge and neighbour lists they need.  With ``interior=True`` both add
+the other half of the geometry gradient, colour through the barycentric weights (K35,
+``csrc/mesh_interp_grad.hip``): it moves the vertices that lie on no outline.
 """
 
 import os
@@ -1469,9 +1471,20 @@ def _geometry_backward(frame, opposites, vertices, triangles, proj, width, heigh
     return grad, d_color, d_alpha
 
 
+def _interior_backward(frame, adjacency, vertices, triangles, colors, proj, width, height,
+                       d_color, grad):
+    """K35a on K34b's ``d_color`` (the gradient in K31's plain colour) and K35b added into ``grad``,
+    which already holds K34c's result for this frame.  No read-back."""
+    record, _, _, ids, _ = frame
+    face_grads = ops.mesh_interp_face_grads(record, ids, d_color, colors, triangles, width, height)
+    return ops.mesh_interp_vertex_grad(face_grads, adjacency[0], adjacency[1], vertices, proj,
+                                       grad, accumulate=True)
+
+
 def render_mesh_geometry_backward(vertices, triangles, camera, colors, d_color, d_alpha,
                                   opposites=None, grad=None, accumulate: bool = False,
-                                  background=(0, 0, 0), batch_size: int = 1 << 22):
+                                  background=(0, 0, 0), batch_size: int = 1 << 22,
+                                  interior: bool = False, adjacency=None):
     """The transpose of ``render_mesh(..., colors=colors, antialias=True)`` in the vertex
     POSITIONS (K34, ``csrc/mesh_aa.hip``) -> ``(grad (V,3), d_color_plain (H W,3))`` float32.
     ``d_color`` (H W,3) and ``d_alpha`` (H W,) are the gradient of a loss in the antialiased colour
@@ -1485,11 +1498,21 @@ def render_mesh_geometry_backward(vertices, triangles, camera, colors, d_color, 
     returns for these triangles (made here when None).  ``grad`` (a GPU tensor) is written in
     place when given, and added to with ``accumulate``.
 
-    The limits: only silhouette and fold edges (and boundary and non-manifold ones) carry a
-    gradient -- the interior term, colour through the barycentric weights, is not built; the
-    topology never changes; the snap to 1/256 pixel is passed straight through; a silhouette that
-    falls between two pixel centres of the same id is not seen; self-intersections are not
-    prevented."""
+    ``interior=True`` adds the other half of the gradient (K35, ``csrc/mesh_interp_grad.hip``):
+    colour through the barycentric weights.  After K34b, the sort and K34c it runs K35a on K34b's
+    ``d_color_plain`` and K35b with ``accumulate`` into the same ``grad``, so a vertex that lies
+    on no outline is moved by the colours sliding over its triangles.  ``adjacency``: what
+    ``vertex_adjacency`` returns for these triangles (made here when None; not used without
+    ``interior``).  With the default ``False`` none of K35 is reached and the result is
+    unchanged bit for bit.
+
+    The limits: without ``interior`` only silhouette and fold edges (and boundary and
+    non-manifold ones) carry a gradient.  With it: which triangle wins a pixel is held fixed (a
+    change of visibility is seen at silhouettes only, by K34); the snap to 1/256 pixel is passed
+    straight through; the topology never changes; a silhouette that falls between two pixel
+    centres of the same id is not seen; self-intersections are not prevented.  The interior term
+    has no textured path (the derivative of the bilinear lookup in the UVs is not built), and a
+    screen-filling triangle is one wavefront's loop, as in K32a."""
     who = "render_mesh_geometry_backward"
     num_vertices = _mesh_colors_check(who, vertices, colors, batch_size=batch_size)
     if colors is None:
@@ -1512,13 +1535,20 @@ def render_mesh_geometry_backward(vertices, triangles, camera, colors, d_color, 
     as_numpy, device, vertices, triangles = _mesh_on(vertices, triangles)
     if opposites is None:
         opposites = edge_opposites(triangles, num_vertices, device)
+    if interior and adjacency is None:
+        adjacency = vertex_adjacency(triangles, num_vertices, device)
     proj = supersample_projection(camera, 1)
+    colors = _on(colors, "float32", device)
     record, color, alpha, _, ids, _, _, zbuf = _rasterize_z(
         vertices, triangles, proj, eye_positions([camera], (0.0, 0.0, 0.0))[0], width, height,
-        _on(colors, "float32", device), background=background, batch_size=batch_size)
+        colors, background=background, batch_size=batch_size)
+    frame = (record, color, alpha, ids, zbuf)
     grad, plain, _ = _geometry_backward(
-        (record, color, alpha, ids, zbuf), opposites, vertices, triangles, proj, width, height,
+        frame, opposites, vertices, triangles, proj, width, height,
         _on(d_color, "float32", device), _on(d_alpha, "float32", device), grad, accumulate)
+    if interior:
+        _interior_backward(frame, adjacency, vertices, triangles, colors, proj, width, height,
+                           plain, grad)
     if as_numpy:
         return grad.cpu().numpy(), plain.cpu().numpy()
     return grad, plain
@@ -1529,7 +1559,7 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
                       cameras_per_step: int = 1, report_interval: int = 100, alpha_weight=None,
                       laplacian_weight: float = 0.0, max_displacement=None,
                       clip_value: float = CLIP_VALUE, max_norm: float = MAX_NORM,
-                      seed: int = 20080524, verbose: bool = True):
+                      seed: int = 20080524, verbose: bool = True, interior: bool = False):
     """Optimises the vertex POSITIONS (V,3) of a mesh against the images of ``train_dataset`` (an
     ``ImageDataset``) through ``render_mesh(..., antialias=True)`` with a black background ->
     ``(vertices, log)``; the per-vertex ``colors`` and the triangles are held fixed.  numpy in gives
@@ -1539,7 +1569,11 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
     K31 frame, K34a, K6 (``ops.mse_loss``) on colour and alpha with ``color_scale = 1 / (3 count)``
     and ``alpha_scale = alpha_weight / count`` (``count`` the pixels of the step; ``alpha_weight``
     None takes the dataset's, as ``fit_octree`` does, and 0 for a dataset without alpha), K34b, the
-    stable sort of its entries and K34c accumulated over the step's cameras.  Then, with
+    stable sort of its entries and K34c accumulated over the step's cameras; with ``interior``
+    (default off) two more launches per camera, K35a on K34b's gradient in the plain colour and
+    K35b accumulated into the same buffer (``csrc/mesh_interp_grad.hip``: colour through the
+    barycentric weights; the adjacency is made once, a step gains no host synchronisation, and
+    without it none of K35 is reached: results and logs are unchanged bit for bit).  Then, with
     ``laplacian_weight > 0``, K34d on the displacement ``d = v - v0`` adds the gradient of
     ``laplacian_weight * (1 / V) * 1/2 sum_edges |d_i - d_j|^2`` (report lines gain ``lap:``, the
     value of that term; with 0 the kernel is not entered); then K7 (``ops.clip_adam``) and, with
@@ -1552,11 +1586,15 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
     camera.  ``learning_rate``, ``laplacian_weight`` and ``max_displacement`` have NO tuned
     defaults: 1e-3 is a guess in scene units per step, 0 and None switch the two off.
 
-    The limits: only silhouette and fold edges (and boundary and non-manifold ones) carry a
-    gradient -- the interior term, colour through the barycentric weights, is not built, so a
-    vertex that no camera sees on an outline does not move; the topology never changes; the snap
-    to 1/256 pixel is passed straight through; a silhouette that falls between two pixel centres
-    of the same id is not seen; self-intersections are not prevented."""
+    The limits: without ``interior`` only silhouette and fold edges (and boundary and
+    non-manifold ones) carry a gradient, so a vertex that no camera sees on an outline does not
+    move.  With it every vertex of a triangle that wins a pixel does, and may slide along the
+    surface: thin triangles can fold when nothing smooths them.  In both: which triangle wins a
+    pixel is held fixed away from silhouettes; the topology never changes; the snap to 1/256
+    pixel is passed straight through; a silhouette that falls between two pixel centres of the
+    same id is not seen; self-intersections are not prevented.  The interior term has no textured
+    path (``fit_mesh_texture`` does not move geometry), there is no joint colour-and-geometry
+    step, and a screen-filling triangle is one wavefront's loop, as in K32a."""
     who = "fit_mesh_geometry"
     num_vertices = _mesh_colors_check(who, vertices, colors)
     if colors is None:
@@ -1583,6 +1621,7 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
     colors = _on(colors, "float32", device)
     data = start.clone()
     opposites = edge_opposites(triangles, num_vertices, device)
+    adjacency = vertex_adjacency(triangles, num_vertices, device) if interior else None
     per = width * height
     pixels = torch.arange(per, dtype=torch.int64, device=device)
     alphas = train_dataset._gt_alphas()
@@ -1627,8 +1666,11 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
             sums, g_color, g_alpha = ops.mse_loss(color, alpha, train_dataset.colors, alphas,
                                                   pixels + camera * per, 1.0 / (3 * count),
                                                   aw / count)
-            _geometry_backward(plain, opposites, data, triangles, proj, width, height, g_color,
-                               g_alpha, grads, number > 0)
+            _, d_plain, _ = _geometry_backward(plain, opposites, data, triangles, proj, width,
+                                               height, g_color, g_alpha, grads, number > 0)
+            if interior:
+                _interior_backward(plain, adjacency, data, triangles, colors, proj, width, height,
+                                   d_plain, grads)
             total = sums if total is None else total + sums
         if laplacian_weight > 0:
             torch.sub(data, start, out=displacement)

@@ -3141,3 +3141,91 @@ def mesh_laplacian(values: torch.Tensor, neighbor_starts: torch.Tensor, neighbor
           c_i64(values.shape[0]), c_i64(neighbors.shape[0]), c_f(scale), _dev(out, name="out"),
           c_i(1 if accumulate else 0))
     return out
+
+
+# --------------------------------------------------------------------------------- K35
+def mesh_interp_face_grads_check(record, ids, d_color, colors, triangles, width: int,
+                                 height: int) -> None:
+    """The refusals of ``mesh_interp_face_grads`` that need no device."""
+    who = "mesh_interp_face_grads"
+    _raster_want(who, "triangles", triangles, torch.int32, (None, 3))
+    _raster_want(who, "colors", colors, torch.float32, (None, 3))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= triangles.shape[0] <= most:
+        raise ValueError("%s: triangles holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, triangles.shape[0]))
+    if not 1 <= colors.shape[0] <= most:
+        raise ValueError("%s: colors holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, colors.shape[0]))
+    _raster_want(who, "record", record, torch.int32, (triangles.shape[0], 16))
+    _raster_check_image(who, width, height)
+    _raster_want(who, "ids", ids, torch.int32, (width * height,))
+    _raster_want(who, "d_color", d_color, torch.float32, (width * height, 3))
+
+
+def mesh_interp_face_grads(record: torch.Tensor, ids: torch.Tensor, d_color: torch.Tensor,
+                           colors: torch.Tensor, triangles: torch.Tensor, width: int,
+                           height: int) -> torch.Tensor:
+    """K35a.  record (F,16) int32 of K31a, ids (H W,) int32 of K31c, d_color (H W,3) f32 (the
+    gradient in K31c's colour; under antialiasing K34b's ``d_color``), colors (V,3) f32 and
+    triangles (F,3) int32 -> ``face_grads`` (F,9) f32: per triangle, over the pixels ``ids`` gives
+    it, the sums of the gradient in the screen position ``(sx, sy)`` of corner ``j`` (columns
+    ``3 j``, ``3 j + 1``, in pixels) and in its ``w`` (column ``3 j + 2``) that the colour carries
+    through the barycentric weights, the winner of every pixel held fixed.  K32a's organisation:
+    one wavefront per triangle, a fixed order, no atomics.  A pixel whose id is another
+    triangle's (or -1) is not read: a NaN there reaches nothing."""
+    width, height = int(width), int(height)
+    mesh_interp_face_grads_check(record, ids, d_color, colors, triangles, width, height)
+    face_grads = torch.empty((record.shape[0], 9), dtype=torch.float32, device=record.device)
+    _call("ffn_mesh_interp_face_grads", _dev(record, torch.int32, "record"),
+          _dev(ids, torch.int32, "ids"), _dev(d_color, name="d_color"),
+          _dev(colors, name="colors"), c_i64(colors.shape[0]),
+          _dev(triangles, torch.int32, "triangles"), c_i64(triangles.shape[0]), c_i(width),
+          c_i(height), _dev(face_grads))
+    return face_grads
+
+
+def mesh_interp_vertex_grad_check(face_grads, corner_order, vertex_starts, vertices, proj,
+                                  grad=None, accumulate: bool = False):
+    """The refusals of ``mesh_interp_vertex_grad`` that need no device -> ``proj`` as 12 host
+    floats."""
+    who = "mesh_interp_vertex_grad"
+    _raster_want(who, "face_grads", face_grads, torch.float32, (None, 9))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= face_grads.shape[0] <= most:
+        raise ValueError("%s: face_grads holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, face_grads.shape[0]))
+    _raster_want(who, "corner_order", corner_order, torch.int32, (3 * face_grads.shape[0],))
+    _raster_want(who, "vertices", vertices, torch.float32, (None, 3))
+    if not 1 <= vertices.shape[0] <= most:
+        raise ValueError("%s: vertices holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, vertices.shape[0]))
+    _raster_want(who, "vertex_starts", vertex_starts, torch.int32, (vertices.shape[0] + 1,))
+    if accumulate and grad is None:
+        raise ValueError("%s: accumulate needs grad to add to" % who)
+    if grad is not None:
+        _raster_want(who, "grad", grad, torch.float32, (vertices.shape[0], 3))
+    if np.shape(proj) != (3, 4):
+        raise ValueError("%s: proj must be (3, 4), got %s" % (who, np.shape(proj)))
+    return _raster_host(who, "proj", proj, 12)
+
+
+def mesh_interp_vertex_grad(face_grads: torch.Tensor, corner_order: torch.Tensor,
+                            vertex_starts: torch.Tensor, vertices: torch.Tensor, proj,
+                            grad: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """K35b.  face_grads (F,9) of K35a, ``corner_order`` (3F,) and ``vertex_starts`` (V+1,) int32
+    of ``mesh.vertex_adjacency``, vertices (V,3) f32 and ``proj`` (3,4) on the host -> ``grad``
+    (V,3) f32: per vertex the sums of its corners' three columns in CSR order, put through the
+    Jacobian of K31a's projection (``sx``, ``sy`` and ``w``), a zero row when ``!(w > 0)``.  One
+    thread per vertex, no atomics; the loop is linear in the valence.  ``grad`` is written in
+    place when given, and with ``accumulate`` added to: this is how it joins K34c's result."""
+    matrix = mesh_interp_vertex_grad_check(face_grads, corner_order, vertex_starts, vertices, proj,
+                                           grad, accumulate)
+    if grad is None:
+        grad = torch.empty((vertices.shape[0], 3), dtype=torch.float32, device=vertices.device)
+    _call("ffn_mesh_interp_vertex_grad", _dev(face_grads, name="face_grads"),
+          _dev(corner_order, torch.int32, "corner_order"),
+          _dev(vertex_starts, torch.int32, "vertex_starts"), c_i64(face_grads.shape[0]),
+          _dev(vertices, name="vertices"), c_i64(vertices.shape[0]), matrix,
+          _dev(grad, name="grad"), c_i(1 if accumulate else 0))
+    return grad

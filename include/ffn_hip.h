@@ -1859,6 +1859,61 @@ int ffn_mesh_laplacian(const float* values, const int32_t* neighbor_starts,
                        const int32_t* neighbors, int64_t num_vertices, int64_t num_neighbors,
                        float scale, float* out, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K35  the interior half of the geometry gradient behind K31: colour through the barycentric
+ * weights (csrc/mesh_interp_grad.hip).  No counterpart in the reference; the method is nvdiffrast's
+ * (Laine et al. 2020).  K34 gives a gradient to the vertices of silhouette edges; here every pixel a
+ * triangle wins gives one to the triangle's three corners, for the per-vertex colours only (the
+ * textured path has none).  Which triangle wins a pixel is held fixed and the snap to 1/256 pixel is
+ * passed straight through.  The edge functions are int64; every float operation is one rounded f32
+ * operation in the order written (no fma; / is the IEEE division; -x is the sign flip); no float
+ * atomics and no LDS: the same inputs give the same bits on every call.  Every index read from an
+ * input array is held against its range before it is used.  Limits as in K31: 1 <= width, height <=
+ * 16384; 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; bad shapes and null pointers are refused
+ * by name before any launch.  record is 16-byte aligned.
+ *
+ * K35a, one wavefront (64 lanes) per triangle f, K32a's organisation.  record (num_triangles,16)
+ * int32 from K31a; ids (height width) int32 from K31c; d_color (height width,3) f32: the gradient of
+ * a loss in K31c's colour (under antialiasing, K34b's d_color); colors (num_vertices,3) f32;
+ * triangles (num_triangles,3) int32, ids clamped into 0 .. num_vertices - 1 as in K31.
+ *   the box, n, the box pixels k and the SELECTED ones (ids[p] == f) exactly as in K32a: a box that
+ *   is empty, not inside the image, or has n > 2^28 contributes nothing; a pixel that is not selected
+ *   is skipped by selection, d_color[p] is not read
+ *   per triangle: X, Y, A, sgn = sign(A), w_i from record[f]; c_i = colors[triangles[f][i]];
+ *     for edge i with j = (i+1) mod 3, k = (i+2) mod 3:  dx_i = sgn (-(Y_k - Y_j)), dy_i = sgn (X_k - X_j)
+ *     (int64);  n_i = ((256.0f * (float)dx_i) / (float)|A|, (256.0f * (float)dy_i) / (float)|A|): the
+ *     gradient of lambda_i per pixel
+ *   a selected pixel: E_i as in K31b (int64, sgn applied); lambda_i = (float)E_i / (float)|A|;
+ *     q_i = lambda_i / w_i;  depth_w = 1.0f / ((q0 + q1) + q2);  b_i = q_i * depth_w (the bits of K31c);
+ *     C_ch = (c0_ch b0 + c1_ch b1) + c2_ch b2;  g = d_color[p];
+ *     a_i = (g_r * (ci_r - C_r) + g_g * (ci_g - C_g)) + g_b * (ci_b - C_b);
+ *     r_i = (a_i * depth_w) / w_i: d loss / d lambda_i;
+ *     G = ((r0 * n0.x + r1 * n1.x) + r2 * n2.x, likewise y): d loss / d (the sample point, in pixels);
+ *     t[3 j] = -(lambda_j * G.x), t[3 j + 1] = -(lambda_j * G.y): d loss / d (sx, sy) of corner j;
+ *     t[3 j + 2] = -(r_j * q_j): d loss / d w_j
+ *   segments of 64 box pixels, the fold x += shfl_xor(x, off), off = 32 .. 1, and acc = acc + segment_s
+ *   from 0.0f in the order of s, as in K32a
+ * face_grads (num_triangles,9) f32 = the nine acc.  Every row is written; the row of a triangle that
+ * is not drawn, or wins no pixel, is +0.
+ *
+ * K35b, one thread per vertex v.  corner_order (3 num_triangles) and vertex_starts (num_vertices + 1)
+ * int32: K32b's CSR, the range of a row clamped into the array.  From 0.0f and in that order, for the
+ * corner 3 f + i:  gx = gx + face_grads[f][3 i], gy = gy + face_grads[f][3 i + 1],
+ * gw = gw + face_grads[f][3 i + 2]; a corner outside 0 .. 3 num_triangles - 1 is skipped.  v projected
+ * as in K31a to x, y, w, sx = x / w, sy = y / w (proj: 12 floats in HOST memory).  !(w > 0): the row
+ * is +0.  Else, per component c of the position, with P the rows of proj:
+ *   grad[v][c] = ((gx * (P0c - sx * P2c)) + (gy * (P1c - sy * P2c))) / w + gw * P2c
+ * grad (num_vertices,3) = the row, or with accumulate != 0 out = out + row, one add each: this is how
+ * it joins K34c's result in one buffer.  The loop is linear in the valence. */
+int ffn_mesh_interp_face_grads(const int32_t* record, const int32_t* ids, const float* d_color,
+                               const float* colors, int64_t num_vertices, const int32_t* triangles,
+                               int64_t num_triangles, int width, int height, float* face_grads,
+                               void* stream);
+int ffn_mesh_interp_vertex_grad(const float* face_grads, const int32_t* corner_order,
+                                const int32_t* vertex_starts, int64_t num_triangles,
+                                const float* vertices, int64_t num_vertices, const float* proj,
+                                float* grad, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

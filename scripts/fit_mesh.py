@@ -6,10 +6,13 @@ after, the mean PSNR of ``render_mesh_image`` over the fitted cameras and over t
 and the mean intersection over union of the drawn silhouette with the images' own alpha, and writes
 the mesh with its new positions and colours.  No counterpart in the reference.
 
-``--learning-rate``, ``--laplacian-weight`` and ``--max-displacement`` are untuned.
+``--learning-rate``, ``--laplacian-weight`` and ``--max-displacement`` are untuned.  ``--interior``
+adds the interior half of the geometry gradient (kernel K35: colour through the barycentric
+weights); it is off by default.
 
     python scripts/fit_mesh.py mesh.obj data.npz out.obj [--steps N] [--learning-rate R]
-        [--laplacian-weight W] [--max-displacement D] [--color-steps N] [--split train]
+        [--laplacian-weight W] [--max-displacement D] [--interior] [--color-steps N]
+        [--split train]
 """
 
 import os
@@ -33,6 +36,9 @@ FIT_MESH = [
                                 help="weight of the displacement's smoothness term (untuned)")),
     ("--max-displacement", dict(type=float, default=None,
                                 help="clamp on every component of the displacement (untuned)")),
+    ("--interior", dict(action="store_true",
+                        help="also move vertices by the colours sliding over their triangles "
+                             "(K35); off by default")),
     ("--color-steps", dict(type=int, default=0,
                            help="steps of fit_mesh_colors after the colours are taken")),
     ("--split", dict(choices=["train", "val", "test"], default="train")),
@@ -121,7 +127,7 @@ def main():
             vertices, triangles, colors, dataset, None, num_steps=args.steps,
             learning_rate=args.learning_rate, cameras_per_step=args.cameras_per_step,
             laplacian_weight=args.laplacian_weight, max_displacement=args.max_displacement,
-            seed=args.seed, verbose=False)
+            seed=args.seed, verbose=False, interior=args.interior)
         moved = np.linalg.norm(fitted - vertices, axis=1)
         print("fit: %d steps, loss %.6f -> %.6f, mean displacement %.5f, largest %.5f"
               % (len(log), log[0].loss, log[-1].loss, moved.mean(), moved.max()))
