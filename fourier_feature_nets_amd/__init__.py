@@ -17,11 +17,12 @@ from .octree_fit import (FitLogEntry, OctreeField, OctreeSHField, RefineReport, 
 from .pixel_dataset import PixelData, PixelDataset
 from .regression import RegressionEngine
 from .signal_dataset import SignalData, SignalDataset
-from .mesh import (MeshTaps, bake_vertex_colors, color_mesh_from_images, edge_opposites,
+from .mesh import (MeshBVH, MeshHit, MeshTaps, bake_vertex_colors, build_mesh_bvh, cast_rays,
+                   color_mesh_from_images, edge_opposites,
                    fit_mesh_colors, fit_mesh_geometry, fit_mesh_texture, load_obj,
-                   mesh_texture_taps, normalize_points, procedural_torus, render_mesh,
+                   mesh_spans, mesh_texture_taps, normalize_points, procedural_torus, render_mesh,
                    render_mesh_backward, render_mesh_geometry_backward, render_mesh_image,
-                   render_mesh_texture, render_mesh_texture_backward, sample_mesh, save_obj,
+                   render_mesh_rays, render_mesh_texture, render_mesh_texture_backward, sample_mesh, save_obj,
                    texture_mesh_from_images, texture_to_uint8, triangle_counts, unwrap_mesh,
                    vertex_adjacency, vertex_neighbors)
 from .models import (
@@ -47,10 +48,10 @@ from .voxels import VoxelProgram, Voxels
 __version__ = "0.1.0"
 
 __all__ = ["__version__", "ActivationVisualizer", "BasicFourierMLP", "CameraInfo", "ETABar", "EvaluationVisualizer", "FitLogEntry", "FourierFeatureMLP", "FrameSink",
-           "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "MeshTaps", "NeRF",
+           "GaussianFourierMLP", "ImageDataset", "LogEntry", "MLP", "MeshBVH", "MeshHit", "MeshTaps", "NeRF",
            "OcTree", "OccupancyGrid", "OctreeField", "OctreeSHField", "OrbitVideoVisualizer", "PhotoReport", "PhotoSweep", "PixelData", "PixelDataset", "PositionalFourierMLP", "RayDataset", "RaySampler", "RaySamples", "Raycaster", "RefineReport", "RegressionEngine",
-           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "bake_vertex_colors", "calculate_blend_weights", "color_mesh_from_images", "edge_opposites",
+           "RenderResult", "Resolution", "SignalData", "SignalDataset", "SurfaceMesh", "TrainEngine", "Visualizer", "VoxelProgram", "Voxels", "bake_vertex_colors", "build_mesh_bvh", "calculate_blend_weights", "cast_rays", "color_mesh_from_images", "edge_opposites",
            "exponential_lr_decay", "eye_positions", "fit_mesh_colors", "fit_mesh_geometry", "fit_mesh_texture", "fit_octree", "fit_octree_adaptive", "fit_octree_sh", "leaf_weights_over",
-           "linspace", "load_model", "load_obj", "mesh_texture_taps", "normalize_points", "orbit", "photo_actions", "procedural_torus",
-           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_geometry_backward", "render_mesh_image", "render_mesh_texture", "render_mesh_texture_backward", "sample_mesh", "save_obj",
+           "linspace", "load_model", "load_obj", "mesh_spans", "mesh_texture_taps", "normalize_points", "orbit", "photo_actions", "procedural_torus",
+           "projection_matrices", "refine_actions", "render_mesh", "render_mesh_backward", "render_mesh_geometry_backward", "render_mesh_image", "render_mesh_rays", "render_mesh_texture", "render_mesh_texture_backward", "sample_mesh", "save_obj",
            "texture_mesh_from_images", "texture_to_uint8", "triangle_counts", "unwrap_mesh", "vertex_adjacency", "vertex_neighbors"]

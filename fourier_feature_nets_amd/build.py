@@ -73,6 +73,9 @@ SOURCES = {
     # lambda_i = E_i / |A|, r_i = (a_i depth_w) / w_i, G = (r0 n0 + r1 n1) + r2 n2 and the sums of
     # -(lambda_j G) over pixels and corners in a fixed order, every operation rounded on its own
     "mesh_interp_grad.hip": ["-ffp-contract=off"],
+    # the slab test (lo - o) * inv and Moeller-Trumbore's cross and dot products, K36d's
+    # (c0 b0 + c1 b1) + c2 b2: every product, sum and quotient rounded on its own
+    "mesh_cast.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]

@@ -43,6 +43,7 @@ the other half of the geometry gradient, colour through the barycentric weights 
 ``csrc/mesh_interp_grad.hip``): it moves the vertices that lie on no outline.
 """
 
+import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -1702,3 +1703,187 @@ def fit_mesh_geometry(vertices, triangles, colors, train_dataset, val_dataset=No
                        validate if val_dataset is not None else None, int(num_steps),
                        learning_rate, report_interval, clip_value, max_norm, verbose, fields)
     return (data if torch.is_tensor(vertices) else data.cpu().numpy()), log
+
+
+# ------------------------------------------------------------------------------------ K36
+class MeshBVH(NamedTuple("MeshBVH", [("nodes", torch.Tensor), ("boxes", torch.Tensor),
+                                     ("order", torch.Tensor), ("vertices", torch.Tensor),
+                                     ("triangles", torch.Tensor), ("levels", int),
+                                     ("leaf_size", int), ("pad", float)])):
+    """The tree K36 casts rays through (``build_mesh_bvh``): ``nodes`` (2^levels - 1, 6) f32, the
+    boxes of a complete binary tree stored level by level; ``boxes`` (F,6) f32, the padded box of
+    every triangle; ``order`` (F,) int32, the triangles in Morton order, ``leaf_size`` to a leaf;
+    and the ``vertices`` (V,3) f32 and ``triangles`` (F,3) int32 it was built from, on the device.
+    It is a snapshot: after the vertices move, build another."""
+
+    @property
+    def num_triangles(self) -> int:
+        return int(self.triangles.shape[0])
+
+
+MeshHit = NamedTuple("MeshHit", [("triangles", torch.Tensor), ("t", torch.Tensor),
+                                 ("u", torch.Tensor), ("v", torch.Tensor)])
+
+
+def _finite_extent(vertices: torch.Tensor):
+    """(lowest corner (3,), longest side, largest |coordinate|) of the finite vertices, on the
+    host; one read-back."""
+    finite = torch.isfinite(vertices).all(1, keepdim=True)
+    high = torch.where(finite, vertices, torch.full_like(vertices, -math.inf)).amax(0)
+    low = torch.where(finite, vertices, torch.full_like(vertices, math.inf)).amin(0)
+    largest = torch.where(torch.isfinite(vertices), vertices.abs(),
+                          torch.zeros_like(vertices)).amax().reshape(1)
+    found = torch.cat([low, high, largest]).cpu().numpy()
+    return found[0:3], found[3:6], found[6]
+
+
+def build_mesh_bvh(vertices, triangles, leaf_size: int = 4, pad=None, device=None) -> MeshBVH:
+    """The tree over a mesh that ``cast_rays``, ``mesh_spans``, ``render_mesh_rays`` and
+    ``RaySampler.clip_to_mesh`` walk (K36a/b, ``csrc/mesh_cast.hip``): the triangles sorted by the
+    30-bit Morton code of their box centres (``torch.sort``: plumbing), ``leaf_size`` (1 .. 64) to a
+    leaf of an implicit balanced binary tree.  vertices (V,3), triangles (F,3) integers (ids are
+    clamped into the vertices, as K22 and K31 do), numpy or tensors.
+
+    ``pad`` >= 0 widens every triangle's box on all sides; None, the default, takes ``2^-16`` times
+    the largest finite |coordinate|.  A hit has to lie inside its triangle's padded box, which
+    makes the tree exact (a culled node never hides a hit) and discards the garbage ``t`` of
+    grazing rays; ``pad`` only has to cover the rounding of ``t`` against the box planes.  A
+    triangle with a non-finite coordinate is never hit.
+
+    The result does not depend on the order of the sort or on ``leaf_size``, only the time does.
+    Not done: a refit when the vertices move (build again), a surface-area or LBVH build."""
+    who = "build_mesh_bvh"
+    shape = _shape_of(vertices)
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= _MOST:
+        raise ValueError("%s: vertices must be (V,3) with 1 <= V <= (2^31 - 1) / 3, got %s"
+                         % (who, shape))
+    shape = _shape_of(triangles)
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= _MOST:
+        raise ValueError("%s: triangles must be (F,3) with 1 <= F <= (2^31 - 1) / 3, got %s"
+                         % (who, shape))
+    if isinstance(leaf_size, bool) or int(leaf_size) != leaf_size \
+            or not 1 <= leaf_size <= ops.MESH_CAST_MAX_LEAF:
+        raise ValueError("%s: leaf_size must be an integer in 1 .. %d, got %r"
+                         % (who, ops.MESH_CAST_MAX_LEAF, leaf_size))
+    leaf_size = int(leaf_size)
+    if pad is not None and not (float(pad) >= 0.0 and math.isfinite(float(pad))):
+        raise ValueError("%s: pad must be a finite number >= 0, got %r" % (who, pad))
+    _, device, vertices, triangles = _mesh_on(vertices, triangles, device)
+    low, high, largest = _finite_extent(vertices)
+    if pad is None:
+        pad = np.float32(2.0 ** -16) * np.float32(largest)
+    pad = float(np.float32(pad))
+    extent = np.float32((high - low).max()) if np.isfinite(high - low).all() else np.float32(0.0)
+    with np.errstate(all="ignore"):
+        scale = np.float32(1024.0) / extent if extent > 0 else np.float32(0.0)
+    if not np.isfinite(scale):
+        scale = np.float32(0.0)
+    corner = low if np.isfinite(low).all() else np.zeros(3, dtype=np.float32)
+    boxes, keys = ops.mesh_cast_boxes(vertices, triangles, pad, corner, float(scale))
+    number = torch.arange(keys.shape[0], dtype=torch.int64, device=device)
+    order = torch.sort((keys.to(torch.int64) << 32) | number).values.bitwise_and_(0xFFFFFFFF) \
+        .to(torch.int32)
+    nodes = ops.mesh_cast_tree(boxes, order, leaf_size)
+    return MeshBVH(nodes, boxes, order, vertices, triangles,
+                   ops.mesh_cast_levels(triangles.shape[0], leaf_size), leaf_size, pad)
+
+
+def _cast_rays_on(who, bvh, starts, directions):
+    """-> (whether the rays came as numpy, starts, directions (R,3) f32 on the tree's device)."""
+    if not isinstance(bvh, MeshBVH):
+        raise ValueError("%s: bvh must be a MeshBVH (build_mesh_bvh), got %s"
+                         % (who, type(bvh).__name__))
+    for name, value in (("starts", starts), ("directions", directions)):
+        shape = _shape_of(value)
+        if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+            raise ValueError("%s: %s must be (R,3) with R >= 1, got %s" % (who, name, shape))
+    if _shape_of(starts) != _shape_of(directions):
+        raise ValueError("%s: starts %s and directions %s must have one shape"
+                         % (who, _shape_of(starts), _shape_of(directions)))
+    device = bvh.nodes.device
+    return (not torch.is_tensor(starts), _on(starts, "float32", device),
+            _on(directions, "float32", device))
+
+
+def _cast(bvh, starts, directions, t_min, farthest):
+    return ops.mesh_cast(bvh.nodes, bvh.boxes, bvh.order, bvh.vertices, bvh.triangles, starts,
+                         directions, bvh.leaf_size, float(t_min), farthest)
+
+
+def cast_rays(bvh: MeshBVH, starts, directions, t_min: float = 0.0,
+              which: str = "nearest") -> MeshHit:
+    """Per ray ``o + t d`` the triangle of the mesh it hits first after ``t_min`` (K36c), or with
+    ``which="farthest"`` last: the mesh counterpart of ``OcTree.first_hit``.  starts, directions
+    (R,3), numpy or tensors (numpy in gives numpy out); the directions need not be unit vectors,
+    ``t`` is in their units.  -> ``MeshHit``: ``triangles`` (R,) int32, -1 for a miss; ``t`` and the
+    barycentric ``u``, ``v`` (R,) float32 of the hit (the point is ``(1 - u - v) a + u b + v c``), 0
+    on a miss.  Both sides of a triangle are hit; a ray in a triangle's plane misses it; of two
+    triangles hit at the same ``t`` (a shared edge or vertex) the lower id is returned; a NaN or
+    infinite ray misses.  The answer is bit for bit that of testing every triangle.  No gradient
+    flows through the cast."""
+    who = "cast_rays"
+    if which not in ("nearest", "farthest"):
+        raise ValueError("%s: which must be 'nearest' or 'farthest', got %r" % (who, which))
+    as_numpy, starts, directions = _cast_rays_on(who, bvh, starts, directions)
+    hit = MeshHit(*_cast(bvh, starts, directions, t_min, which == "farthest"))
+    return MeshHit(*[x.cpu().numpy() for x in hit]) if as_numpy else hit
+
+
+def mesh_spans(bvh: MeshBVH, starts, directions, t_min: float = 0.0, margin: float = 0.0):
+    """Per ray the span ``[t_in, t_out]`` between its first and its last hit of the mesh after
+    ``t_min`` (two casts of K36c), widened by ``margin`` (in units of ``t``) at both ends but not
+    below ``t_min``, and ``hit``: whether it meets the mesh at all.  -> ``(t_in, t_out`` float32,
+    ``hit`` bool), each (R,); 0, 0, False for a miss.  The mesh counterpart of ``OcTree.spans``."""
+    who = "mesh_spans"
+    if not (float(margin) >= 0.0 and math.isfinite(float(margin))):
+        raise ValueError("%s: margin must be a finite number >= 0, got %r" % (who, margin))
+    as_numpy, starts, directions = _cast_rays_on(who, bvh, starts, directions)
+    near, t_near, _, _ = _cast(bvh, starts, directions, t_min, False)
+    _, t_far, _, _ = _cast(bvh, starts, directions, t_min, True)
+    hit = near >= 0
+    zero = torch.zeros_like(t_near)
+    t_in = torch.where(hit, torch.clamp_min(t_near - float(margin), float(t_min)), zero)
+    t_out = torch.where(hit, t_far + float(margin), zero)
+    if as_numpy:
+        return t_in.cpu().numpy(), t_out.cpu().numpy(), hit.cpu().numpy()
+    return t_in, t_out, hit
+
+
+def render_mesh_rays(bvh: MeshBVH, starts, directions, colors=None, uvs=None, texture=None,
+                     background=(0, 0, 0), t_min: float = 0.0):
+    """The mesh as a batch of rays sees it (K36c and K36d) -> ``RenderResult``: ``color`` (R,3) of
+    the first hit, ``alpha`` (R,) 1 on a hit and 0 on a miss, ``depth`` (R,) the hit's ``t`` (the
+    distance for unit directions).  Exactly one of ``colors`` (V,3), interpolated with the hit's
+    barycentric weights, and ``uvs`` (V,2) + ``texture`` (h,w,C) uint8 with row 0 at the top (as
+    ``render_mesh`` takes it).  A miss gets ``background``.  numpy in gives numpy out.  There is no
+    camera plane: the rays may start inside the mesh or next to it, where ``render_mesh`` reports
+    triangles ``clipped``."""
+    who = "render_mesh_rays"
+    from .utils import RenderResult
+    as_numpy, starts, directions = _cast_rays_on(who, bvh, starts, directions)
+    if colors is not None and (uvs is not None or texture is not None):
+        raise ValueError("%s: give either colors, or uvs and texture, not both" % who)
+    if colors is None and (uvs is None or texture is None):
+        raise ValueError("%s: give colors, or both uvs and texture" % who)
+    num_vertices = bvh.vertices.shape[0]
+    for name, value, last in (("colors", colors, 3), ("uvs", uvs, 2)):
+        if value is not None and _shape_of(value) != (num_vertices, last):
+            raise ValueError("%s: %s must be (V,%d) = (%d,%d), got %s"
+                             % (who, name, last, num_vertices, last, _shape_of(value)))
+    if texture is not None:
+        tex = _shape_of(texture)
+        if len(tex) != 3 or tex[2] < 3 or min(tex) < 1:
+            raise ValueError("%s: texture must be (H,W,C) with C >= 3, got %s" % (who, tex))
+        texture = texture.flip(0) if torch.is_tensor(texture) else np.asarray(texture)[::-1]
+    ground = np.asarray(background, dtype=np.float64).reshape(-1)
+    if ground.shape != (3,) or not np.isfinite(ground).all():
+        raise ValueError("%s: background must be three finite numbers, got %r"
+                         % (who, background))
+    device = bvh.nodes.device
+    hit, t, u, v = _cast(bvh, starts, directions, t_min, False)
+    out = RenderResult(*ops.mesh_cast_shade(
+        hit, t, u, v, bvh.triangles,
+        None if colors is None else _on(colors, "float32", device),
+        None if uvs is None else _on(uvs, "float32", device),
+        None if texture is None else _on(texture, "uint8", device), ground))
+    return out.numpy() if as_numpy else out

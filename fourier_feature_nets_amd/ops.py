@@ -3229,3 +3229,197 @@ def mesh_interp_vertex_grad(face_grads: torch.Tensor, corner_order: torch.Tensor
           _dev(vertices, name="vertices"), c_i64(vertices.shape[0]), matrix,
           _dev(grad, name="grad"), c_i(1 if accumulate else 0))
     return grad
+
+
+# --------------------------------------------------------------------------------- K36
+MESH_CAST_MAX_LEAF = 64
+MESH_CAST_MAX_LEVELS = 31
+MESH_CAST_MAX_RAYS = 2 ** 31 - 1
+MESH_CAST_EMPTY_KEY = 1 << 30       # K36a's key of a triangle with a non-finite vertex
+
+
+def mesh_cast_levels(num_triangles: int, leaf_size: int) -> int:
+    """The levels of K36's tree: the smallest count whose ``2^(levels - 1)`` leaves of
+    ``leaf_size`` triangles hold every triangle."""
+    levels = 1
+    while (leaf_size << (levels - 1)) < num_triangles:
+        levels += 1
+    return levels
+
+
+def _cast_number(who, name, value, low=None):
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) \
+            or not math.isfinite(value) or (low is not None and value < low):
+        raise ValueError("%s: %s must be a finite number%s, got %r"
+                         % (who, name, "" if low is None else " >= %g" % low, value))
+    return float(value)
+
+
+def _cast_check_tree(who, boxes, order, leaf_size, nodes=None, with_nodes=False) -> int:
+    """boxes (F,6), order (F,), ``leaf_size`` and, ``with_nodes``, nodes (2^levels - 1, 6) ->
+    levels."""
+    _raster_want(who, "boxes", boxes, torch.float32, (None, 6))
+    num = boxes.shape[0]
+    if not 1 <= num <= (2 ** 31 - 1) // 3:
+        raise ValueError("%s: boxes holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, num))
+    _raster_want(who, "order", order, torch.int32, (num,))
+    _want_int(who, "leaf_size", leaf_size, 1, MESH_CAST_MAX_LEAF)
+    levels = mesh_cast_levels(num, leaf_size)
+    if levels > MESH_CAST_MAX_LEVELS:
+        raise ValueError("%s: boxes and leaf_size need %d levels; at most %d are supported"
+                         % (who, levels, MESH_CAST_MAX_LEVELS))
+    if with_nodes:
+        _raster_want(who, "nodes", nodes, torch.float32, ((1 << levels) - 1, 6))
+    return levels
+
+
+def mesh_cast_boxes_check(vertices, triangles, pad, grid_lo, grid_scale):
+    """The refusals of ``mesh_cast_boxes`` that need no device -> (pad, grid_lo, grid_scale) as
+    host floats."""
+    who = "mesh_cast_boxes"
+    _raster_check_mesh(who, vertices, triangles)
+    pad = _cast_number(who, "pad", pad, 0.0)
+    scale = _cast_number(who, "grid_scale", grid_scale, 0.0)
+    corner = np.asarray(grid_lo, dtype=np.float64).reshape(-1)
+    if corner.shape != (3,) or not np.isfinite(corner).all():
+        raise ValueError("%s: grid_lo must be three finite numbers, got %r" % (who, grid_lo))
+    return pad, [float(c) for c in corner], scale
+
+
+def mesh_cast_boxes(vertices: torch.Tensor, triangles: torch.Tensor, pad: float, grid_lo,
+                    grid_scale: float):
+    """K36a.  vertices (V,3) f32, triangles (F,3) int32 (ids clamped into the vertices) ->
+    ``(boxes (F,6) f32, keys (F,) int32)``: per triangle ``min(a,b,c) - pad`` and ``max(a,b,c) +
+    pad`` (the empty box ``+inf, -inf`` when a coordinate is not finite) and the 30-bit Morton code
+    of the box centre on the grid of 1024 cells a side that starts at ``grid_lo`` with
+    ``grid_scale`` cells per unit (``MESH_CAST_EMPTY_KEY`` for an empty box)."""
+    pad, corner, scale = mesh_cast_boxes_check(vertices, triangles, pad, grid_lo, grid_scale)
+    num = triangles.shape[0]
+    boxes = torch.empty((num, 6), dtype=torch.float32, device=vertices.device)
+    keys = torch.empty((num,), dtype=torch.int32, device=vertices.device)
+    _call("ffn_mesh_cast_boxes", _dev(vertices, name="vertices"), c_i64(vertices.shape[0]),
+          _dev(triangles, torch.int32, "triangles"), c_i64(num), c_f(pad), c_f(corner[0]),
+          c_f(corner[1]), c_f(corner[2]), c_f(scale), _dev(boxes), _dev(keys, torch.int32))
+    return boxes, keys
+
+
+def mesh_cast_tree_check(boxes, order, leaf_size) -> int:
+    """The refusals of ``mesh_cast_tree`` that need no device -> the number of levels."""
+    return _cast_check_tree("mesh_cast_tree", boxes, order, leaf_size)
+
+
+def mesh_cast_tree(boxes: torch.Tensor, order: torch.Tensor, leaf_size: int) -> torch.Tensor:
+    """K36b.  boxes (F,6) f32 of K36a, order (F,) int32 (a permutation of the triangles; entries
+    are clamped) -> ``nodes`` (2^levels - 1, 6) f32, ``levels = mesh_cast_levels(F, leaf_size)``:
+    the boxes of the complete binary tree whose leaf ``j`` holds the triangles
+    ``order[j leaf_size : (j + 1) leaf_size]``, level ``l`` from row ``2^l - 1``; the empty box for
+    a node over no triangle."""
+    levels = mesh_cast_tree_check(boxes, order, leaf_size)
+    nodes = torch.empty(((1 << levels) - 1, 6), dtype=torch.float32, device=boxes.device)
+    _call("ffn_mesh_cast_tree", _dev(boxes, name="boxes"), _dev(order, torch.int32, "order"),
+          c_i64(boxes.shape[0]), c_i(leaf_size), c_i(levels), _dev(nodes))
+    return nodes
+
+
+def mesh_cast_check(nodes, boxes, order, vertices, triangles, starts, directions, leaf_size,
+                    t_min=0.0, farthest: bool = False):
+    """The refusals of ``mesh_cast`` that need no device -> (levels, t_min)."""
+    who = "mesh_cast"
+    _raster_check_mesh(who, vertices, triangles)
+    _raster_want(who, "boxes", boxes, torch.float32, (triangles.shape[0], 6))
+    levels = _cast_check_tree(who, boxes, order, leaf_size, nodes, True)
+    _raster_want(who, "starts", starts, torch.float32, (None, 3))
+    if not 1 <= starts.shape[0] <= MESH_CAST_MAX_RAYS:
+        raise ValueError("%s: starts holds %d rays; 1 .. 2^31 - 1 are supported"
+                         % (who, starts.shape[0]))
+    _raster_want(who, "directions", directions, torch.float32, (starts.shape[0], 3))
+    if isinstance(t_min, bool) or not isinstance(t_min, numbers.Real) or math.isnan(t_min):
+        raise ValueError("%s: t_min must be a number, not NaN, got %r" % (who, t_min))
+    return levels, float(t_min)
+
+
+def mesh_cast(nodes: torch.Tensor, boxes: torch.Tensor, order: torch.Tensor,
+              vertices: torch.Tensor, triangles: torch.Tensor, starts: torch.Tensor,
+              directions: torch.Tensor, leaf_size: int, t_min: float = 0.0,
+              farthest: bool = False):
+    """K36c.  nodes, boxes, order of K36a/b, the mesh they were built from, starts and directions
+    (R,3) f32 -> ``(hit (R,) int32, t, u, v (R,) f32)``: per ray the triangle with the least
+    ``(t, id)`` among those it hits beyond ``t_min`` (with ``farthest`` the greatest ``t``, ties to
+    the lower id) and Moeller-Trumbore's ``t, u, v`` of that hit; -1 and zeros for a miss.  Two-sided;
+    a ray in a triangle's plane, and a NaN or infinite ray, misses.  One lane per ray, a stackless
+    walk with a trip bound; no atomics, no LDS, no scratch."""
+    levels, t_min = mesh_cast_check(nodes, boxes, order, vertices, triangles, starts, directions,
+                                    leaf_size, t_min, farthest)
+    dev, num = starts.device, starts.shape[0]
+    hit = torch.empty((num,), dtype=torch.int32, device=dev)
+    t, u, v = (torch.empty((num,), dtype=torch.float32, device=dev) for _ in range(3))
+    _call("ffn_mesh_cast", _dev(nodes, name="nodes"), _dev(boxes, name="boxes"),
+          _dev(order, torch.int32, "order"), _dev(vertices, name="vertices"),
+          c_i64(vertices.shape[0]), _dev(triangles, torch.int32, "triangles"),
+          c_i64(triangles.shape[0]), c_i(leaf_size), c_i(levels), _dev(starts, name="starts"),
+          _dev(directions, name="directions"), c_i64(num), c_f(t_min), c_i(1 if farthest else 0),
+          _dev(hit, torch.int32), _dev(t), _dev(u), _dev(v))
+    return hit, t, u, v
+
+
+def mesh_cast_shade_check(hit, t, u, v, triangles, colors, uvs, texture, background):
+    """The refusals of ``mesh_cast_shade`` that need no device -> (number of vertices, background
+    as three host floats).  Exactly one of ``colors`` and ``uvs`` + ``texture`` is given."""
+    who = "mesh_cast_shade"
+    _raster_want(who, "hit", hit, torch.int32, (None,))
+    num = hit.shape[0]
+    if not 1 <= num <= MESH_CAST_MAX_RAYS:
+        raise ValueError("%s: hit holds %d rays; 1 .. 2^31 - 1 are supported" % (who, num))
+    for name, value in (("t", t), ("u", u), ("v", v)):
+        _raster_want(who, name, value, torch.float32, (num,))
+    _raster_want(who, "triangles", triangles, torch.int32, (None, 3))
+    most = (2 ** 31 - 1) // 3
+    if not 1 <= triangles.shape[0] <= most:
+        raise ValueError("%s: triangles holds %d triangles; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, triangles.shape[0]))
+    if (colors is None) == (uvs is None and texture is None) or (uvs is None) != (texture is None):
+        raise ValueError("%s: give either colors, or uvs and texture" % who)
+    if colors is not None:
+        _raster_want(who, "colors", colors, torch.float32, (None, 3))
+        vertices = colors.shape[0]
+    else:
+        _raster_want(who, "uvs", uvs, torch.float32, (None, 2))
+        vertices = uvs.shape[0]
+        _raster_want(who, "texture", texture, torch.uint8, (None, None, None))
+        tex_h, tex_w, channels = texture.shape
+        if (channels < 3 or not 1 <= tex_h <= MESH_MAX_TEXTURE_SIDE
+                or not 1 <= tex_w <= MESH_MAX_TEXTURE_SIDE or tex_h * tex_w * channels >= 2 ** 31):
+            raise ValueError("%s: texture must be (H, W, C) with C >= 3, 1 <= H, W <= 2^24 and "
+                             "fewer than 2^31 bytes, got %s" % (who, tuple(texture.shape)))
+    if not 1 <= vertices <= most:
+        raise ValueError("%s: %s holds %d vertices; 1 .. (2^31 - 1) / 3 are supported"
+                         % (who, "colors" if colors is not None else "uvs", vertices))
+    ground = np.asarray(background, dtype=np.float32).reshape(-1)
+    if ground.shape != (3,) or not np.isfinite(ground).all():
+        raise ValueError("%s: background must be 3 finite numbers, got %r" % (who, background))
+    return vertices, [float(c) for c in ground]
+
+
+def mesh_cast_shade(hit: torch.Tensor, t: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                    triangles: torch.Tensor, colors: Optional[torch.Tensor],
+                    uvs: Optional[torch.Tensor], texture: Optional[torch.Tensor],
+                    background=(0.0, 0.0, 0.0)):
+    """K36d.  hit, t, u, v (R,) of K36c and the mesh's triangles (F,3) int32 -> ``(color (R,3),
+    alpha (R,), depth (R,))`` f32: the hit triangle's ``colors`` (V,3) under the weights ``(1 - u)
+    - v, u, v``, or its ``uvs`` (V,2) under them through ``texture`` (h,w,C) uint8 with the row
+    index growing with ``v`` (K22's lookup); 1; ``t``.  A miss gets ``background``, 0 and 0."""
+    vertices, ground = mesh_cast_shade_check(hit, t, u, v, triangles, colors, uvs, texture,
+                                             background)
+    dev, num = hit.device, hit.shape[0]
+    color = torch.empty((num, 3), dtype=torch.float32, device=dev)
+    alpha = torch.empty((num,), dtype=torch.float32, device=dev)
+    depth = torch.empty((num,), dtype=torch.float32, device=dev)
+    tex_h, tex_w, channels = (0, 0, 0) if texture is None else texture.shape
+    _call("ffn_mesh_cast_shade", _dev(hit, torch.int32, "hit"), _dev(t, name="t"),
+          _dev(u, name="u"), _dev(v, name="v"), c_i64(num),
+          _dev(triangles, torch.int32, "triangles"), c_i64(triangles.shape[0]),
+          _dev(colors, name="colors"), _dev(uvs, name="uvs"), c_i64(vertices),
+          _dev(texture, torch.uint8, "texture"), c_i(tex_h), c_i(tex_w), c_i(channels),
+          c_f(ground[0]), c_f(ground[1]), c_f(ground[2]), _dev(color), _dev(alpha), _dev(depth))
+    return color, alpha, depth

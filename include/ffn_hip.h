@@ -1914,6 +1914,81 @@ int ffn_mesh_interp_vertex_grad(const float* face_grads, const int32_t* corner_o
                                 const float* vertices, int64_t num_vertices, const float* proj,
                                 float* grad, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K36  rays against a triangle mesh: a tree over the triangles, the nearest or farthest hit of every
+ * ray, the shading of the hits (csrc/mesh_cast.hip).  No counterpart in the reference.  What K13/K14
+ * are for octrees: K31 needs a pinhole camera and refuses every triangle that reaches w <= 0; a cast
+ * has no camera plane and answers for any ray.  Every float operation is one rounded f32 operation in
+ * the order written (no fma; / is the IEEE division); no atomics, no LDS, no scratch: the same inputs
+ * give the same bits on every call.  tests/mesh_cast_reference.py restates all of it in numpy f32.
+ * Every index read from an input array is held against its range before it is used: vertex ids are
+ * clamped into 0 .. num_vertices - 1 as in K22/K31, the entries of order into 0 .. num_triangles - 1.
+ * Limits: 1 <= num_vertices, num_triangles <= (2^31 - 1) / 3; 1 <= num_rays < 2^31; 1 <= leaf_size
+ * <= 64; levels is the smallest number with leaf_size 2^(levels - 1) >= num_triangles (at most 31) and
+ * is refused when it is not; bad shapes and null pointers are refused by name before any launch.
+ * nodes and boxes are 8-byte aligned.
+ *
+ * Conventions: dot(a,b) = (a.x b.x + a.y b.y) + a.z b.z;  cross(a,b).x = a.y b.z - a.z b.y, cyclically.
+ *
+ * The box of a triangle with the (clamped) vertices a, b, c: lo = min(a,b,c) - pad, hi = max(a,b,c) +
+ * pad per axis, pad >= 0 one finite f32.  A triangle with a non-finite coordinate gets the EMPTY box
+ * lo = +inf, hi = -inf.  A box is empty iff lo.x > hi.x; an empty box is never entered and its triangle
+ * never hit (the slab test below would take it for the whole line, hence the explicit clause).
+ *
+ * The slab test of a box and a ray (o, d): inv = 1.0f / d per axis; t0 = (lo - o) inv, t1 = (hi - o)
+ * inv; near_a = fminf(t0, t1), far_a = fmaxf(t0, t1) (a NaN operand is dropped, numpy's fmin / fmax);
+ * tn = fmaxf(fmaxf(near_x, near_y), near_z), tf = fminf(fminf(far_x, far_y), far_z).
+ *
+ * The triangle test (Moeller-Trumbore, two-sided): e1 = b - a, e2 = c - a, p = cross(d, e2), det =
+ * dot(p, e1), k = 1.0f / det, s = o - a, u = dot(p, s) k, q = cross(s, e1), v = dot(d, q) k, t = dot(q,
+ * e2) k.  Triangle f is HIT iff det != 0, u >= 0, v >= 0, u + v <= 1, t is finite, t > t_min, its box is
+ * not empty and tn <= t <= tf for its own box.  The last clause makes a tree exact: every operation of
+ * the slab test is monotone, so a box built by min / max alone over other boxes has a [tn, tf] that
+ * contains theirs bit for bit, and a culled node cannot hide a hit.  The answer for a ray is the
+ * minimum of (t, f) over the hit triangles, lexicographically; in farthest mode the maximum t, ties to
+ * the lower f.  It does not depend on order (any permutation), leaf_size or the keys.
+ *
+ * K36a, one thread per triangle.  boxes (num_triangles,6) f32 = lo, hi.  keys (num_triangles) int32:
+ * per axis centre = (lo + hi) 0.5f, cell = (centre - grid) grid_scale, q = (int)fminf(fmaxf(cell,
+ * 0.0f), 1023.0f); key = the bits of q.x, q.y, q.z interleaved, x lowest (30 bits); 2^30 for an empty
+ * box.  The caller sorts key << 32 | f (torch.sort: plumbing, as in K12 and K30) into order.
+ *
+ * K36b, one thread per node of a level, `levels` launches from the leaves up.  nodes (2^levels - 1, 6)
+ * f32, level l (2^l nodes) from row 2^l - 1: no pointers.  Leaf j of the last level: fminf / fmaxf
+ * from the empty box over boxes[order[p]], j leaf_size <= p < min((j + 1) leaf_size, num_triangles).
+ * Node j of a level above: fminf of the lo, fmaxf of the hi of nodes 2 j and 2 j + 1 of the next level.
+ * Every row is written.
+ *
+ * K36c, one lane per ray; starts, directions (num_rays,3) f32.  The walk is depth first, left child
+ * first, on (level, index) alone, every node visited at most once, the loop bounded by 2^levels - 1
+ * trips.  A node is entered iff its box is not empty, tn <= tf, tf > t_min and (nearest) tn <= t_best,
+ * (farthest) tf >= t_best; t_best is +inf (-inf) until a triangle is hit.  Per ray: hit (num_rays)
+ * int32 = f, or -1; t, u, v (num_rays) f32 of that triangle, all 0 for a miss.  A NaN or infinite
+ * ray misses.  t_min is not NaN; farthest is 0 or 1.
+ *
+ * K36d, one thread per ray, hit, t, u, v as K36c writes them (a hit outside 0 .. num_triangles - 1 is
+ * a miss).  b0 = (1.0f - u) - v, b1 = u, b2 = v.  Either vertex_colors (num_vertices,3): colour =
+ * (c0 b0 + c1 b1) + c2 b2 per channel; or uvs (num_vertices,2) and texture (tex_height, tex_width,
+ * tex_channels) uint8, the row index growing with v: the UV interpolated the same way and put through
+ * K22's lookup.  color (num_rays,3), alpha (num_rays) = 1, depth (num_rays) = t; a miss gets the
+ * background, 0 and 0. */
+int ffn_mesh_cast_boxes(const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                        int64_t num_triangles, float pad, float grid_x, float grid_y, float grid_z,
+                        float grid_scale, float* boxes, int32_t* keys, void* stream);
+int ffn_mesh_cast_tree(const float* boxes, const int32_t* order, int64_t num_triangles,
+                       int leaf_size, int levels, float* nodes, void* stream);
+int ffn_mesh_cast(const float* nodes, const float* boxes, const int32_t* order,
+                  const float* vertices, int64_t num_vertices, const int32_t* triangles,
+                  int64_t num_triangles, int leaf_size, int levels, const float* starts,
+                  const float* directions, int64_t num_rays, float t_min, int farthest,
+                  int32_t* hit, float* t, float* u, float* v, void* stream);
+int ffn_mesh_cast_shade(const int32_t* hit, const float* t, const float* u, const float* v,
+                        int64_t num_rays, const int32_t* triangles, int64_t num_triangles,
+                        const float* vertex_colors, const float* uvs, int64_t num_vertices,
+                        const uint8_t* texture, int tex_height, int tex_width, int tex_channels,
+                        float background_r, float background_g, float background_b, float* color,
+                        float* alpha, float* depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

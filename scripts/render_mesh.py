@@ -2,12 +2,18 @@
 (kernel K31): one PNG per camera and its PSNR against the camera's ground-truth image, in the
 output format of ``scripts/render_octree.py``.  No counterpart in the reference.
 
+``--method rays`` casts the dataset sampler's own rays at the mesh instead (kernel K36, a tree over
+the triangles and the first hit of every ray) and prints the same lines: it has no camera plane, so
+it also draws what the rasteriser reports ``clipped``.  ``--supersample`` and ``--antialias`` are the
+rasteriser's.
+
 An OBJ whose vertices read ``v x y z r g b`` (what ``scripts/octree_to_mesh.py`` writes) is drawn
 with its vertex colours, any other with its texture (``--texture``, or the ``map_Kd`` of its
 ``mtllib``; white without one).  ``--normalize`` puts the mesh where
 ``scripts/make_mesh_npz.py`` put it when it made the dataset from the same file.
 
     python scripts/render_mesh.py mesh.obj data.npz out_dir [--normalize] [--supersample 4] [--antialias]
+    python scripts/render_mesh.py mesh.obj data.npz out_dir --method rays
 """
 
 import os
@@ -35,6 +41,8 @@ RENDER_MESH = [
                            help="sub-pixels a side that every pixel averages")),
     ("--antialias", dict(action="store_true",
                          help="blend the silhouette edges analytically (kernel K34a)")),
+    ("--method", dict(choices=["raster", "rays"], default="raster",
+                      help="the z-buffer rasteriser (K31), or a cast of the sampler's rays (K36)")),
     ("--device", dict(default="cuda", help="Pytorch compute device")),
 ]
 
@@ -43,8 +51,23 @@ def build_parser():
     return _cli.build_parser("Mesh Renderer", RENDER_MESH)
 
 
+def cast_image(ffn, bvh, sampler, camera, paint, background):
+    """The frame of ``camera`` from the sampler's own rays -> (H,W,3) uint8, K8's bytes."""
+    import torch
+    first = camera * sampler.rays_per_camera
+    rays = slice(first, first + sampler.rays_per_camera)
+    out = ffn.render_mesh_rays(bvh, sampler.starts[rays].contiguous(),
+                               sampler.directions[rays].contiguous(), background=background, **paint)
+    pixels = torch.arange(sampler.rays_per_camera, dtype=torch.int64, device=out.color.device)
+    return ffn.ops.to_image(out.color.contiguous(), pixels, sampler.image_width,
+                            sampler.image_height).cpu().numpy()
+
+
 def main():
     args = build_parser().parse_args()
+    if args.method == "rays" and (args.supersample != 1 or args.antialias):
+        print("--supersample and --antialias belong to --method raster", file=sys.stderr)
+        return 1
     device, _, _, _ = _cli.setup_device(args.device, False)
     import fourier_feature_nets_amd as ffn
     vertices, triangles, uvs, texture, colors = ffn.load_obj(args.mesh_path, args.texture,
@@ -64,10 +87,15 @@ def main():
     print("%d vertices, %d triangles, %s" % (len(vertices), len(triangles),
                                              "vertex colours" if colors is not None else "texture"))
     values = []
+    bvh = ffn.build_mesh_bvh(vertices, triangles, device=device) if args.method == "rays" else None
     for camera in range(sampler.num_cameras):
-        image = ffn.render_mesh_image(vertices, triangles, sampler.cameras[camera],
-                                      background=args.background, supersample=args.supersample,
-                                      device=device, antialias=args.antialias, **paint)
+        if bvh is not None:
+            image = cast_image(ffn, bvh, sampler, camera, paint, args.background)
+        else:
+            image = ffn.render_mesh_image(vertices, triangles, sampler.cameras[camera],
+                                          background=args.background,
+                                          supersample=args.supersample, device=device,
+                                          antialias=args.antialias, **paint)
         _cli.save_png(os.path.join(args.output_dir, "frame_{:05d}.png".format(camera)), image)
         truth = ground_truth(dataset.images[camera], resolution, args.background)
         values.append(psnr(image, truth))
